@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: frame-pairs/s of one Siamese train step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -18,6 +18,11 @@ exact-fp32 MFMA mode and the plain bf16 mode (outside the parity bar) of the sam
 are timed beside it.  One step = what TrainerSiamese.train_step runs:
 forward of both towers, pair loss, backward, [RCCL all-reduce of the flat gradient
 bucket], optimizer.  Inputs are resident in HBM before the timed region.
+
+--steps K times exactly K steps (ms_per_step = their time / K).  --dump-outputs DIR writes
+what the last timed step handed its caller -- the loss and the parameters after the update
+-- as DIR/<name>.npy (float32, rank 0): the inputs, the initial weights and the number of
+steps before it depend only on the arguments, so two builds can be compared array by array.
 
 Prints ONE JSON line (rank 0) with the contract fields plus
   roofline     fp32-MFMA roofline of the dominant kernel, timed live with
@@ -459,6 +464,33 @@ def make_stepper(trainer, pool, use_graph):
     return lambda i: stepper(packed[i % POOL])
 
 
+def training_state(trainer):
+    """Copies of what a train step carries over to the next: the flat parameters and the optimizer's state."""
+    opt = trainer.optimizer
+    return [t.clone() for t in (trainer.network.flat_parameters(), opt._s1, opt._s2)], opt.step_count
+
+
+def restore_training_state(trainer, saved):
+    """Writes training_state()'s copies back in place (a captured step graph keeps its pointers)."""
+    opt = trainer.optimizer
+    tensors, opt.step_count = saved
+    for t, s in zip((trainer.network.flat_parameters(), opt._s1, opt._s2), tensors):
+        t.copy_(s)
+    trainer.network.weights_changed_behind_torch()
+
+
+def dump_outputs(net, loss, out_dir):
+    """--dump-outputs: the last timed step's loss and the parameters its optimizer update left, DIR/<name>.npy
+    in float32 (C2: 571 k parameters, 2.3 MB).  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'loss': loss.reshape(1)}
+    arrays.update(('param.' + k, v) for k, v in net.state_dict().items())
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
+    return sorted(arrays)
+
+
 def variants_bench(torch, pool, args, rank, world):
     """SURVEY.md 8d also lists the C2 step with BatchNorm on, and with the trainer's
     class-default optimizer SGD(0.001, 0.9); the third variant is the model's class-default
@@ -830,7 +862,10 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=30)
-    ap.add_argument('--repeats', type=int, default=9, help='timed regions of --steps steps each; the median is reported')
+    ap.add_argument('--repeats', type=int, default=1,
+                    help='timed regions of --steps steps each, back to back; the median is reported')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the last timed step\'s loss and updated parameters as DIR/<name>.npy (float32)')
     ap.add_argument('--trace-run', action='store_true',
                     help='for a run under rocprofv3 --kernel-trace (tools/collect_profiles.sh): the side legs do not settle the '
                          'clock with thousands of untimed launches, so the trace\'s per-kernel averages are the timed step\'s own')
@@ -876,18 +911,22 @@ def main():
     _L.trace_paths = False
 
     # untimed, and independent of --warmup: let clocks, allocator and code caches settle
-    # (a short `--steps 20 --warmup 5` run otherwise times the first 8 ms after start-up)
+    # (a short `--steps 20 --warmup 5` run otherwise times the first 8 ms after start-up).  The loop runs as many
+    # steps as fit in its half second: the parameters and optimizer state it found are put back afterwards, so
+    # the warm-up and the timed steps start from the same state in every run (--dump-outputs)
+    saved = training_state(trainer)
     t_settle, i = time.perf_counter(), 0
     while time.perf_counter() - t_settle < 0.5:
         for _ in range(32):
             step(i)
             i += 1
         torch.cuda.synchronize()
+    restore_training_state(trainer, saved)
     for i in range(args.warmup):
         step(i)
     # EXACTLY --steps steps between barrier + synchronize on both sides, MAX over ranks -- repeated --repeats
-    # times back to back; the line's value is the MEDIAN repeat (a 20-step region is a 4 ms sample: one
-    # repeat alone reads +-5 % from run to run), min / max beside it
+    # times back to back (once by default); the line's value is the MEDIAN repeat (a 20-step region is a 4 ms
+    # sample: one repeat alone reads +-5 % from run to run -- ask for more steps or repeats), min / max beside it
     elapsed_all = []
     for rep in range(max(1, args.repeats)):
         if world > 1:
@@ -908,6 +947,7 @@ def main():
         elapsed_all.append(el)
     elapsed = sorted(elapsed_all)[len(elapsed_all) // 2]
     last_loss = float(loss)
+    dumped = dump_outputs(net, loss, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     err_default = None
     if rank == 0:
@@ -973,6 +1013,8 @@ def main():
             'tflops_whole_step': round(value * FLOP_PER_PAIR / 1e12, 2),
             'last_loss': last_loss,
         }
+        if dumped is not None:
+            out['dumped_outputs'] = dumped
         out['roofline'] = tower_roofline(torch, net) if net.precision == 'fp32' else planes_roofline(torch, net)
         # the whole step against the same roof, from the timed loop above (pack, both chains, weight gradients,
         # reduction + optimizer, every gap): the number the per-launch fractions have to be read beside

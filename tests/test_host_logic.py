@@ -243,3 +243,22 @@ def test_align_cache_compacts_its_chunks_and_keeps_every_path():
     assert early[0].numel() > 0          # (still readable: it keeps its own storage)
     cache.compact()                      # idempotent
     assert len(cache.chunks) == 1
+
+
+def test_bench_dump_outputs_writes_the_loss_and_every_parameter(tmp_path):
+    """bench.py --dump-outputs: DIR/<name>.npy in float32, the loss and every parameter of the C2 network, within 64 MB."""
+    import bench
+    from abnet3_amd.model import SiameseNetwork
+    torch.manual_seed(0)
+    net = SiameseNetwork(**bench.C2)
+    names = bench.dump_outputs(net, torch.tensor(2.5, dtype=torch.float64), str(tmp_path / 'out'))
+    assert names == sorted(['loss'] + ['param.' + k for k in net.state_dict()])
+    assert np.load(tmp_path / 'out' / 'loss.npy').tolist() == [2.5]
+    total = 0
+    for n in names:
+        a = np.load(tmp_path / 'out' / (n + '.npy'))
+        assert a.dtype == np.float32
+        total += a.nbytes
+    assert np.array_equal(np.load(tmp_path / 'out' / 'param.output_layer.0.weight.npy'),
+                          net.state_dict()['output_layer.0.weight'].numpy())
+    assert total <= 64 << 20
