@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the CDLL: see module docstring)
 HERE = os.path.dirname(os.path.abspath(__file__))
 # ABNET3_HIP_LIB points at another build of the same library (kernel experiments)
 LIB_PATH = os.environ.get('ABNET3_HIP_LIB') or os.path.join(HERE, 'lib', 'libabnet3_hip.so')
-ABI_VERSION = 19
+ABI_VERSION = 20
 MAX_LAYERS = 16
 
 ACT = {'none': 0, None: 0, 'sigmoid': 1, 'relu': 2, 'tanh': 3}
@@ -87,6 +87,12 @@ SYMBOLS = {
     'abn_fbank_batched': (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _i32, C.c_double, _i32, _i32,
                                      _f32, _vp, _vp, _vp, _i64, _vp, _vp]),
     'abn_deltas': (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    'abn_deltas_batched': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),
+    'abn_mfcc': (C.c_int, [_vp, C.c_int, _i64, _i32, C.c_double, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp,
+                            _i64, _vp, _i64, _vp]),
+    'abn_mfcc_batched': (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _i32, C.c_double, _i32, _i32, _i32, _f32, _vp, _vp,
+                                    _vp, _vp, _i64, _vp, _i64, _vp]),
+    'abn_mfcc_path': (C.c_int, [_i32, _i32, _i32]),
 }
 
 
@@ -164,6 +170,8 @@ E_UNSUPPORTED = -4
 # abn_tower_path's answers (include/abnet3_hip.h)
 PATH_PER_LAYER, PATH_FUSED_F32, PATH_PLANES, PATH_PLANES_INFER, PATH_PLANES_INFER_BN, PATH_BN_LAYERS, PATH_WIDE, PATH_BN_TOWER = range(8)
 PRECISION_NAMES = {0: 'fp32', 1: 'bf16', 2: 'bf16x3', 3: 'f16x2'}
+# abn_mfcc_path's answers
+MFCC_GENERAL, MFCC_WAVE512 = 0, 1
 
 # Which kernels the tower calls of this process took: filled in by model.py from abn_tower_path (a pure
 # query with the call's own arguments) while `trace_paths` is on -- tests, bench.py and the trainer's log

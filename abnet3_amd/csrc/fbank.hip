@@ -3,6 +3,8 @@
 // Replaces FeaturesGenerator.do_fbank, abnet3/features.py:99-114, i.e.
 //   Spectral(nfilt=40, alpha=0.97, do_dct=False, fs, frate=100, wlen=0.025,
 //            nfft=1024, ...).transform(sound)  -> float32 [T, 40]
+// and FeaturesGenerator.do_mfccs, abnet3/features.py:116-133 (nfft=512, ncep=13, lowerf=100, the DCT on;
+// mfcc512_kernel / mfcc_kernel below).
 // The arithmetic of the third-party `spectral` package is not in the
 // reference; the definition implemented here is oracle/features_np.py (parity
 // unpinned, see its header): per frame pre-emphasis -> Hamming window ->
@@ -403,6 +405,341 @@ __global__ void deltas_kernel(const float* __restrict__ x, int64_t T, int D, flo
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// MFCC (FeaturesGenerator.do_mfccs, the reference's features.py:116-133: nfft = 512, ncep = 13, lowerf = 100):
+// the filterbank's log mel energies, then the Sphinx-III "legacy" DCT of the lineage (s2dctmat / logspec2s2mfc),
+// mfcc[i] = sum_f C[i][f] logspec[f], with C = cos(pi i (f + 1/2) / nfilt), column 0 halved, divided by nfilt --
+// the host builds C (abnet3_amd/features.py, dct_table) and hands it over as fp32 [ncep][nfilt].
+// A window longer than the FFT (fs > 20480 Hz at 25 ms) is CROPPED to its first nfft samples, as rfft(frame, nfft)
+// does; the pre-emphasis history of the next frame is still the frame's element wlen - 1.
+//
+// nfft = 512: ONE WAVEFRONT per frame, persistent, in the manner of fbank1024_kernel:
+//   * the real frame x[0..511] as 256 complex points z[m] = x[2m] + i x[2m+1]; lane j holds m = j + 64 r, r < 4;
+//   * 256 = 4^4: four radix-4 Stockham passes, one 4-point DFT per lane and pass in registers, the passes exchange
+//     data through a wave-private 2 KB strip of LDS (no workgroup barrier); the 9 + 2 twiddles a lane needs depend on
+//     the lane only and stay in registers;
+//   * one split pass gives the 257 bins of rfft(x, 512); the sparse mel projection (lane f sums filter f's band);
+//   * epilogue: the nfilt log energies go through LDS, lane i < ncep takes one dot product against the DCT table
+//     (in LDS, transposed: the lanes read consecutive words).  13 floats (52 B) per frame leave the chip, not 160.
+// ---------------------------------------------------------------------------------------
+constexpr int MF_WAVES = 4;            // wavefronts (frames in flight) per workgroup
+constexpr int MF_SPARSE_Q = 20;        // 16-byte pieces of a filter's band in LDS (257 bins)
+constexpr int MF_MAX_WAVE_FILT = 64;   // the wavefront kernel: a lane per filter
+
+// forward 4-point DFT in place (natural order in, natural order out)
+__device__ __forceinline__ void dft4(cf* v)
+{
+    const cf t0 = cadd(v[0], v[2]), t1 = csub(v[0], v[2]), t2 = cadd(v[1], v[3]), t3 = mul_mi(csub(v[1], v[3]));
+    v[0] = cadd(t0, t2); v[2] = csub(t0, t2);
+    v[1] = cadd(t1, t3); v[3] = csub(t1, t3);
+}
+
+// Where element i of the wave's 256-point strip lives in LDS.  Reads are lane-linear (z[j + 64 r]); the writes of pass 0
+// (z[4 j + r]) and pass 1 (z[16 (j >> 2) + (j & 3) + 4 r]) would put 4 of every 16 lanes of a ds_write_b64 on one bank
+// pair.  XOR-ing bits 0-1 and 2-3 with bits 4-5 makes both sets distinct modulo 16 and keeps every aligned block of 16 a
+// permutation of itself (the reads stay conflict free).
+__device__ __forceinline__ int msw(int i) { return i ^ (((i >> 4) & 3) * 5); }
+
+__global__ __launch_bounds__(64 * MF_WAVES) void mfcc512_kernel(const void* __restrict__ samples, int is_i16, int64_t nsamples,
+                                                                int wlen, double fshift, int nfilt, int ncep, float alpha,
+                                                                const float* __restrict__ window,
+                                                                const float* __restrict__ melbank,
+                                                                const int32_t* __restrict__ band,
+                                                                const float* __restrict__ dct, int64_t nframes,
+                                                                float* __restrict__ out, int64_t ld_out,
+                                                                const int64_t* __restrict__ utt_soff,
+                                                                const int64_t* __restrict__ utt_foff, int n_utts)
+{
+    __shared__ cf zbuf[MF_WAVES][256];
+    __shared__ __attribute__((aligned(16))) float pw[MF_WAVES][260];
+    __shared__ __attribute__((aligned(16))) float sw4[MF_SPARSE_Q][64][4];
+    __shared__ float dct_s[MF_MAX_WAVE_FILT * MF_MAX_WAVE_FILT];          // [filter][cepstrum]
+    __shared__ float lg[MF_WAVES][64];
+    const int wave = threadIdx.x >> 6, j = threadIdx.x & 63;
+    cf* const z = zbuf[wave];
+    float* const power = pw[wave];
+
+    for (int i = threadIdx.x; i < ncep * nfilt; i += 64 * MF_WAVES) {
+        const int c = i / nfilt, f = i - c * nfilt;
+        dct_s[f * ncep + c] = dct[i];
+    }
+    // this lane's filter: its band of bins; the band's weights go to LDS once per workgroup
+    const int blo = j < nfilt ? band[2 * j] : 1, bhi = j < nfilt ? band[2 * j + 1] : 0;
+    const int a0 = blo & ~3;
+    const int nq = bhi >= blo ? (bhi - a0) / 4 + 1 : 0;
+    const bool sparse_ok = __all(nq <= MF_SPARSE_Q && bhi <= 256);
+    const int nq_max = __builtin_amdgcn_readfirstlane(__reduce_max_sync(~0ull, nq));
+    if (wave == 0 && sparse_ok) {
+        for (int q = 0; q < nq_max; ++q)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int k = a0 + 4 * q + e;
+                sw4[q][j][e] = (q < nq && k >= blo && k <= bhi) ? melbank[(int64_t)k * nfilt + j] : 0.0f;
+            }
+    }
+    if (j < 3) power[257 + j] = 0.0f;                              // (bins 257 .. 259: read under zero weights only)
+    __syncthreads();
+    // lane constants: window taps of the samples this lane touches (elements m = j + 64 r, samples 2m, 2m+1; the crop:
+    // samples past min(wlen, 512) are not part of the transform) and the twiddles of passes 1 .. 3 and of the split
+    const int wl = wlen < 512 ? wlen : 512;
+    float w0[4], w1[4];
+    cf tw1[4], tw2[4], tw3[4], tws[2];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int n0 = 2 * (j + 64 * r);
+        w0[r] = n0 < wl ? window[n0] : 0.0f;
+        w1[r] = n0 + 1 < wl ? window[n0 + 1] : 0.0f;
+        float sn, cs;
+        sincospif(-2.0f * (float)(r * (j & 3)) / 16.0f, &sn, &cs);
+        tw1[r] = {cs, sn};
+        sincospif(-2.0f * (float)(r * (j & 15)) / 64.0f, &sn, &cs);
+        tw2[r] = {cs, sn};
+        sincospif(-2.0f * (float)(r * j) / 256.0f, &sn, &cs);
+        tw3[r] = {cs, sn};
+    }
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        float sn, cs;
+        sincospif(-2.0f * (float)(j + 64 * q) / 512.0f, &sn, &cs);
+        tws[q] = {cs, sn};
+    }
+    const int nwaves = gridDim.x * MF_WAVES;
+    for (int64_t frame = (int64_t)blockIdx.x * MF_WAVES + wave; frame < nframes; frame += nwaves) {
+        int64_t fr = frame, len = nsamples;
+        const char* base = (const char*)samples;
+        if (n_utts > 0) {                                          // (wave-uniform: one frame per wavefront)
+            const int u = find_utt(utt_foff, n_utts, frame);
+            fr = frame - utt_foff[u];
+            len = utt_soff[u + 1] - utt_soff[u];
+            base += utt_soff[u] * (is_i16 ? 2 : 4);
+        }
+        const FrameSrc cur = frame_src(base, is_i16, len, fr, fshift, wlen);
+        cf v[4];
+        if (cur.avail >= wlen) {
+            // element 0's history: the previous frame (whole too: it starts earlier) ends at sample prev_start + wlen - 1
+            const int64_t i_prior = fr > 0 ? (int64_t)rint((double)(fr - 1) * fshift) + wlen - 1 : -1;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int n0 = 2 * (j + 64 * r);
+                float a = 0.0f, b = 0.0f, c = 0.0f;                  // x[n0 - 1], x[n0], x[n0 + 1]
+                if (n0 < wl) {
+                    const int64_t i = cur.start + n0;
+                    const int64_t ia = n0 > 0 ? i - 1 : i_prior;
+                    a = ia >= 0 ? cur.raw(ia) : 0.0f;
+                    b = cur.raw(i);
+                    c = n0 + 1 < wl ? cur.raw(i + 1) : 0.0f;
+                }
+                v[r] = {(b - alpha * a) * w0[r], (c - alpha * b) * w1[r]};
+            }
+        } else {
+            const FrameSrc prv = frame_src(base, is_i16, len, fr > 0 ? fr - 1 : 0, fshift, wlen);
+            const float prior = fr > 0 ? prv.at(wlen - 1) : 0.0f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int n0 = 2 * (j + 64 * r);
+                float a = 0.0f, b = 0.0f, c = 0.0f;
+                if (n0 < wl) {
+                    a = n0 > 0 ? cur.at(n0 - 1) : prior;
+                    b = cur.at(n0);
+                    c = n0 + 1 < wl ? cur.at(n0 + 1) : 0.0f;
+                }
+                v[r] = {(b - alpha * a) * w0[r], (c - alpha * b) * w1[r]};
+            }
+        }
+        // pass 0 (sub-transform size 1): no twiddles; outputs to 4 j + r
+        dft4(v);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) z[msw(4 * j + r)] = v[r];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        // pass 1 (size 4): k = j & 3; outputs to 16 (j >> 2) + k + 4 r
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = z[msw(j + 64 * r)];
+#pragma unroll
+        for (int r = 1; r < 4; ++r) v[r] = cmul(v[r], tw1[r]);
+        dft4(v);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) z[msw(16 * (j >> 2) + (j & 3) + 4 * r)] = v[r];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        // pass 2 (size 16): k = j & 15; outputs to 64 (j >> 4) + k + 16 r
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = z[msw(j + 64 * r)];
+#pragma unroll
+        for (int r = 1; r < 4; ++r) v[r] = cmul(v[r], tw2[r]);
+        dft4(v);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) z[msw(64 * (j >> 4) + (j & 15) + 16 * r)] = v[r];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        // pass 3 (size 64): k = j; outputs to j + 64 r: natural order
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = z[msw(j + 64 * r)];
+#pragma unroll
+        for (int r = 1; r < 4; ++r) v[r] = cmul(v[r], tw3[r]);
+        dft4(v);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) z[msw(j + 64 * r)] = v[r];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        // split: X[k] = (Z[k] + conj Z[256-k]) / 2 - i e^{-2 pi i k / 512} (Z[k] - conj Z[256-k]) / 2, and its mirror
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int k = j + 64 * q;                              // 0 .. 127
+            const cf a = z[msw(k)], b = z[msw((256 - k) & 255)];
+            const cf s = {0.5f * (a.x + b.x), 0.5f * (a.y - b.y)};
+            const cf d = {0.5f * (a.x - b.x), 0.5f * (a.y + b.y)};
+            const cf t = cmul(tws[q], d);
+            const cf xk = {s.x + t.y, s.y - t.x};
+            const cf xm = {s.x - t.y, -s.y - t.x};                 // bin 256 - k (k = 0: bin 256)
+            power[k] = xk.x * xk.x + xk.y * xk.y;
+            power[256 - k] = xm.x * xm.x + xm.y * xm.y;
+        }
+        if (j == 0) {                                              // bin 128: its own mirror, w = -i
+            const cf a = z[msw(128)];
+            power[128] = a.x * a.x + a.y * a.y;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        // mel projection + log, to LDS
+        float e = 0.0f;
+        if (sparse_ok) {
+            typedef float fb4 __attribute__((ext_vector_type(4)));
+            float e0 = 0.f, e1 = 0.f, e2 = 0.f, e3 = 0.f;
+            for (int q = 0; q < nq_max; ++q) {         // (every lane walks the widest band: past its own end the weights are zeros)
+                const fb4 pk = *reinterpret_cast<const fb4*>(power + min(a0 + 4 * q, 256));
+                const fb4 wk = *reinterpret_cast<const fb4*>(&sw4[q][j][0]);
+                e0 = fmaf(pk[0], wk[0], e0); e1 = fmaf(pk[1], wk[1], e1);
+                e2 = fmaf(pk[2], wk[2], e2); e3 = fmaf(pk[3], wk[3], e3);
+            }
+            e = (e0 + e1) + (e2 + e3);
+        } else {
+            for (int k = blo; k <= bhi; ++k) e = fmaf(power[k], melbank[(int64_t)k * nfilt + j], e);
+        }
+        if (j < nfilt) lg[wave][j] = logf(fmaxf(e, FB_FLOOR));
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        // the DCT: lane i < ncep, one dot product over the filters (the log energies are broadcast reads)
+        if (j < ncep) {
+            float c = 0.0f;
+            for (int f = 0; f < nfilt; ++f) c = fmaf(dct_s[f * ncep + j], lg[wave][f], c);
+            out[frame * ld_out + j] = c;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// Any other power-of-two nfft, or more than 64 filters: one workgroup per frame, fbank_kernel's radix-2 FFT and dense
+// projection, with the crop and the DCT epilogue of mfcc512_kernel.
+__global__ __launch_bounds__(256) void mfcc_kernel(const void* __restrict__ samples, int is_i16, int64_t nsamples, int wlen,
+                                                   double fshift, int nfft, int log2n, int nfilt, int ncep, float alpha,
+                                                   const float* __restrict__ window, const float* __restrict__ melbank,
+                                                   const float* __restrict__ dct, float* __restrict__ out, int64_t ld_out,
+                                                   const int64_t* __restrict__ utt_soff, const int64_t* __restrict__ utt_foff,
+                                                   int n_utts)
+{
+    __shared__ float re[FB_MAX_NFFT], im[FB_MAX_NFFT];
+    __shared__ float twr[FB_MAX_NFFT / 2], twi[FB_MAX_NFFT / 2];
+    __shared__ float part[256];
+    __shared__ float lgs[FB_MAX_FILT];
+    const int tid = threadIdx.x;
+    const int64_t frame = blockIdx.x;
+    int64_t fr = frame, len = nsamples;
+    const char* base = (const char*)samples;
+    if (n_utts > 0) {
+        const int u = find_utt(utt_foff, n_utts, frame);
+        fr = frame - utt_foff[u];
+        len = utt_soff[u + 1] - utt_soff[u];
+        base += utt_soff[u] * (is_i16 ? 2 : 4);
+    }
+    const FrameSrc cur = frame_src(base, is_i16, len, fr, fshift, wlen);
+    const FrameSrc prv = frame_src(base, is_i16, len, fr > 0 ? fr - 1 : 0, fshift, wlen);
+    const float prior = fr > 0 ? prv.at(wlen - 1) : 0.0f;
+    const int wl = wlen < nfft ? wlen : nfft;
+    for (int n = tid; n < nfft; n += 256) {
+        float v = 0.0f;
+        if (n < wl) v = (cur.at(n) - alpha * (n > 0 ? cur.at(n - 1) : prior)) * window[n];
+        const unsigned r = bitrev((unsigned)n, log2n);
+        re[r] = v;
+        im[r] = 0.0f;
+    }
+    for (int k = tid; k < nfft / 2; k += 256) {
+        float s, c;
+        sincospif(-2.0f * (float)k / (float)nfft, &s, &c);
+        twr[k] = c;
+        twi[k] = s;
+    }
+    __syncthreads();
+    for (int s = 1; s <= log2n; ++s) {
+        const int half = 1 << (s - 1), tstep = nfft >> s;
+        for (int b = tid; b < nfft / 2; b += 256) {
+            const int grp = b >> (s - 1), pos = b & (half - 1);
+            const int i0 = (grp << s) + pos, i1 = i0 + half;
+            const float wr = twr[pos * tstep], wi = twi[pos * tstep];
+            const float xr = re[i1], xi = im[i1];
+            const float tr = wr * xr - wi * xi, ti = wr * xi + wi * xr;
+            const float ur = re[i0], ui = im[i0];
+            re[i0] = ur + tr; im[i0] = ui + ti;
+            re[i1] = ur - tr; im[i1] = ui - ti;
+        }
+        __syncthreads();
+    }
+    const int nbins = nfft / 2 + 1;
+    for (int k = tid; k < nbins; k += 256) re[k] = re[k] * re[k] + im[k] * im[k];
+    __syncthreads();
+    const int groups = 256 / nfilt;
+    const int f = tid % nfilt, g = tid / nfilt;
+    float acc = 0.0f;
+    if (g < groups)
+        for (int k = g; k < nbins; k += groups) acc = fmaf(re[k], melbank[(int64_t)k * nfilt + f], acc);
+    part[tid] = (g < groups) ? acc : 0.0f;
+    __syncthreads();
+    if (tid < nfilt) {
+        float e = 0.0f;
+        for (int q = 0; q < groups; ++q) e += part[q * nfilt + tid];
+        lgs[tid] = logf(fmaxf(e, FB_FLOOR));
+    }
+    __syncthreads();
+    if (tid < ncep) {
+        float c = 0.0f;
+        for (int k = 0; k < nfilt; ++k) c = fmaf(dct[(int64_t)tid * nfilt + k], lgs[k], c);
+        out[frame * ld_out + tid] = c;
+    }
+}
+
+// deltas_kernel for a batch of utterances laid end to end, in one launch: row t belongs to the utterance u with
+// utt_foff[u] <= t < utt_foff[u + 1] and its slope never reads outside it.  Input and output are column slices of wider
+// tables (row strides ldx / ldo), so the slopes land in their columns of the final table.  Same taps, same order of
+// summation as deltas_kernel: bit for bit what abn_deltas gives on each utterance alone.
+__global__ void deltas_batched_kernel(const float* __restrict__ x, int64_t ldx, const int64_t* __restrict__ utt_foff, int n_utts,
+                                      int64_t T, int D, float* __restrict__ out, int64_t ldo)
+{
+    const int64_t n = T * D;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t t = i / D;
+        const int c = (int)(i - t * D);
+        const int u = find_utt(utt_foff, n_utts, t);
+        const int64_t t0 = utt_foff[u], Tu = utt_foff[u + 1] - t0, tl = t - t0;
+        const float* xu = x + t0 * ldx + c;
+        float acc = 0.0f;
+#pragma unroll
+        for (int k = 1; k <= 4; ++k) {
+            int64_t tp = tl + k, tm = tl - k;
+            tp = tp >= Tu ? (Tu >= 2 ? Tu - 2 : 0) : tp;
+            tm = tm < 0 ? (Tu >= 2 ? 1 : 0) : tm;
+            acc += (float)k * (xu[tp * ldx] - xu[tm * ldx]);
+        }
+        out[t * ldo + c] = acc / 60.0f;
+    }
+}
+
 }  // namespace abn
 
 using namespace abn;
@@ -467,5 +804,89 @@ extern "C" int abn_deltas(const float* feats, int64_t T, int64_t D, float* out, 
     hipLaunchKernelGGL(deltas_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, (hipStream_t)stream, feats,
                        T, (int)D, out);
     ABN_CHECK_LAUNCH("deltas");
+    return ABN_OK;
+}
+
+// Which kernel an MFCC call with these arguments takes (a pure query; -1 = the call is refused)
+static int mfcc_path(int32_t nfft, int32_t nfilt, int32_t ncep)
+{
+    if (nfft < 64 || nfft > FB_MAX_NFFT || (nfft & (nfft - 1)) != 0) return -1;
+    if (nfilt < 1 || nfilt > FB_MAX_FILT || ncep < 1 || ncep > nfilt) return -1;
+    return nfft == 512 && nfilt <= MF_MAX_WAVE_FILT ? ABN_MFCC_WAVE512 : ABN_MFCC_GENERAL;
+}
+
+static int mfcc_launch(const void* samples, int sample_is_i16, int64_t nsamples, const int64_t* utt_soff, const int64_t* utt_foff,
+                       int64_t n_utts, int32_t wlen, double fshift, int32_t nfft, int32_t nfilt, int32_t ncep, float alpha,
+                       const float* window, const float* melbank, const int32_t* band, const float* dct, int64_t nframes, float* out,
+                       int64_t ld_out, void* stream)
+{
+    ABN_REQUIRE(nframes >= 0 && nsamples >= 0, "mfcc: negative sizes");
+    ABN_REQUIRE(nfft >= 64 && nfft <= FB_MAX_NFFT && (nfft & (nfft - 1)) == 0, "mfcc: nfft=%d must be a power of two in [64, %d]", nfft, FB_MAX_NFFT);
+    ABN_REQUIRE(nfilt >= 1 && nfilt <= FB_MAX_FILT, "mfcc: nfilt=%d out of range [1, %d]", nfilt, FB_MAX_FILT);
+    ABN_REQUIRE(ncep >= 1 && ncep <= nfilt, "mfcc: ncep=%d must be in [1, nfilt=%d]", ncep, nfilt);
+    ABN_REQUIRE(wlen >= 1 && wlen <= (1 << 24), "mfcc: wlen=%d out of range", wlen);
+    ABN_REQUIRE(ld_out >= ncep, "mfcc: row stride %lld below ncep=%d", (long long)ld_out, ncep);
+    ABN_REQUIRE(fshift > 0.0, "mfcc: frame shift must be positive");
+    ABN_REQUIRE(n_utts >= 0 && n_utts < (1LL << 30) && nframes < (1LL << 31), "mfcc: too many utterances / frames");
+    if (nframes == 0) return ABN_OK;
+    ABN_REQUIRE(samples && window && melbank && band && dct && out, "mfcc: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (mfcc_path(nfft, nfilt, ncep) == ABN_MFCC_WAVE512) {
+        int64_t wgs = (nframes + MF_WAVES - 1) / MF_WAVES;
+        if (wgs > 256 * 6) wgs = 256 * 6;
+        hipLaunchKernelGGL(mfcc512_kernel, dim3((unsigned)wgs), dim3(64 * MF_WAVES), 0, st, samples, sample_is_i16, nsamples, (int)wlen,
+                           fshift, (int)nfilt, (int)ncep, alpha, window, melbank, band, dct, nframes, out, ld_out, utt_soff, utt_foff,
+                           (int)n_utts);
+        ABN_CHECK_LAUNCH("mfcc512");
+        return ABN_OK;
+    }
+    int log2n = 0;
+    while ((1 << log2n) < nfft) ++log2n;
+    hipLaunchKernelGGL(mfcc_kernel, dim3((unsigned)nframes), dim3(256), 0, st, samples, sample_is_i16, nsamples, (int)wlen, fshift,
+                       (int)nfft, log2n, (int)nfilt, (int)ncep, alpha, window, melbank, dct, out, ld_out, utt_soff, utt_foff, (int)n_utts);
+    ABN_CHECK_LAUNCH("mfcc");
+    return ABN_OK;
+}
+
+extern "C" int abn_mfcc_path(int32_t nfft, int32_t nfilt, int32_t ncep)
+{
+    return mfcc_path(nfft, nfilt, ncep);
+}
+
+extern "C" int abn_mfcc(const void* samples, int sample_is_i16, int64_t nsamples, int32_t wlen, double fshift, int32_t nfft,
+                        int32_t nfilt, int32_t ncep, float alpha, const float* window, const float* melbank, const int32_t* band,
+                        const float* dct, int64_t nframes, float* out, int64_t ld_out, void* stream)
+{
+    return mfcc_launch(samples, sample_is_i16, nsamples, nullptr, nullptr, 0, wlen, fshift, nfft, nfilt, ncep, alpha, window, melbank,
+                       band, dct, nframes, out, ld_out, stream);
+}
+
+extern "C" int abn_mfcc_batched(const void* samples, int sample_is_i16, const int64_t* utt_sample_off, const int64_t* utt_frame_off,
+                                int64_t n_utts, int32_t wlen, double fshift, int32_t nfft, int32_t nfilt, int32_t ncep, float alpha,
+                                const float* window, const float* melbank, const int32_t* band, const float* dct, int64_t nframes,
+                                float* out, int64_t ld_out, void* stream)
+{
+    ABN_REQUIRE(n_utts >= 1 && utt_sample_off && utt_frame_off, "mfcc_batched: utterance tables missing");
+    return mfcc_launch(samples, sample_is_i16, 0, utt_sample_off, utt_frame_off, n_utts, wlen, fshift, nfft, nfilt, ncep, alpha, window,
+                       melbank, band, dct, nframes, out, ld_out, stream);
+}
+
+extern "C" int abn_deltas_batched(const float* feats, int64_t ld_in, const int64_t* utt_frame_off, int64_t n_utts, int64_t T,
+                                  int64_t D, float* out, int64_t ld_out, void* stream)
+{
+    ABN_REQUIRE(T >= 0 && D >= 1 && D < (1 << 24), "deltas_batched: bad shape");
+    ABN_REQUIRE(ld_in >= D && ld_out >= D, "deltas_batched: row strides (%lld, %lld) below D=%lld", (long long)ld_in,
+                (long long)ld_out, (long long)D);
+    ABN_REQUIRE(n_utts >= 1 && n_utts < (1LL << 30), "deltas_batched: n_utts=%lld out of range", (long long)n_utts);
+    if (T == 0) return ABN_OK;
+    ABN_REQUIRE(feats && out && utt_frame_off, "deltas_batched: null pointer");
+    // the output slice may share rows with the input (other columns of one table), never its elements
+    const int64_t gap = out > feats ? (int64_t)(out - feats) : (int64_t)(feats - out);
+    ABN_REQUIRE(!(ld_in == ld_out && gap < D), "deltas_batched: output columns overlap the input's");
+    const int64_t n = T * D;
+    const int64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(deltas_batched_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, (hipStream_t)stream, feats,
+                       ld_in, utt_frame_off, (int)n_utts, T, (int)D, out, ld_out);
+    ABN_CHECK_LAUNCH("deltas_batched");
     return ABN_OK;
 }

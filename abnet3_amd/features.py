@@ -2,10 +2,11 @@
 
 Mirrors (file:line relative to the reference checkout)
   FeaturesGenerator.do_fbank      abnet3/features.py:99-114   -> abn_fbank
+  FeaturesGenerator.do_mfccs      abnet3/features.py:116-133  -> abn_mfcc
   FeaturesGenerator.stack_fbanks  abnet3/features.py:135-159  -> abn_stack_frames
 The reference delegates the filterbank arithmetic to the third-party
 spectral.Spectral (absent, unpinned); the definition implemented by the kernel
-is written down in oracle/features_np.py.  The h5features file pipeline
+is written down in oracle/features_np.py (the cepstra: dct_table below).  The h5features file pipeline
 (features.py:161-203, :299-404) is I/O orchestration and out of scope.
 """
 import numpy as np
@@ -15,6 +16,12 @@ from . import _lib
 
 LOWERF = 133.3333
 UPPERF = 6855.4976
+# do_mfccs' Spectral call (abnet3/features.py:116-133)
+MFCC_NFFT = 512
+MFCC_LOWERF = 100.0
+MFCC_UPPERF = 6855.4976
+NCEP = 13
+METHODS = ('fbanks', 'mfcc')
 
 
 def _mel(f):
@@ -48,8 +55,50 @@ def mel_filterbank(fs, nfft=1024, nfilt=40, lowerf=LOWERF, upperf=UPPERF):
     return bank
 
 
+def dct_table(nfilt, ncep=NCEP):
+    """The cepstral transform of spectral's Sphinx-III lineage (s2dctmat, the "legacy" not-quite-DCT), float64
+    [ncep, nfilt]: C[i, j] = cos(pi i (j + 1/2) / nfilt), column 0 halved; mfcc = logspec . C^T / nfilt (c0 included).
+    PARITY UNPINNED like the rest of the filterbank arithmetic."""
+    C = np.cos(np.pi * np.arange(ncep, dtype=np.float64)[:, None] * (np.arange(nfilt, dtype=np.float64)[None, :] + 0.5) / nfilt)
+    C[:, 0] *= 0.5
+    return C
+
+
+def _samples_batch(waves):
+    """A corpus as one device tensor of samples end to end + per-utterance sample counts: `waves` = int16 (or float) numpy
+    arrays, or one device tensor per utterance, or (device tensor of all samples, sample counts)."""
+    if isinstance(waves, tuple):             # (all samples end to end on the device, sample counts)
+        s, lens = waves[0], np.asarray(waves[1], dtype=np.int64)
+        assert int(lens.sum()) == s.numel()
+    else:
+        lens = np.array([len(w) for w in waves], dtype=np.int64)
+        if isinstance(waves[0], torch.Tensor):
+            s = torch.cat([w.reshape(-1) for w in waves]).cuda()
+        else:
+            dt = np.int16 if all(w.dtype == np.int16 for w in waves) else np.float32
+            s = torch.from_numpy(np.concatenate([np.asarray(w, dtype=dt).reshape(-1) for w in waves])).cuda()
+    if s.dtype not in (torch.int16, torch.float32):
+        s = s.float()
+    return s.contiguous(), lens
+
+
+def _samples_one(sound):
+    """One utterance as a contiguous int16 or float32 device tensor."""
+    if isinstance(sound, torch.Tensor):
+        s = sound
+    else:
+        sound = np.ascontiguousarray(sound)
+        if sound.dtype != np.int16:
+            sound = sound.astype(np.float32)
+        s = torch.from_numpy(sound)
+    s = s.cuda().contiguous()
+    if s.dtype not in (torch.int16, torch.float32):
+        s = s.float()
+    return s
+
+
 class FeaturesGenerator:
-    """Filterbank front end (abnet3/features.py:18-98 constructor surface kept
+    """Filterbank / MFCC front end (abnet3/features.py:18-98 constructor surface kept
     for the hot-path arguments)."""
 
     def __init__(self, files=None, output_path=None, method='fbanks', n_filters=40,
@@ -77,19 +126,42 @@ class FeaturesGenerator:
     def whoami(self):
         return {'params': self.__dict__, 'class_name': self.__class__.__name__}
 
-    def _table(self, fs, wlen, nfft, device):
-        key = (fs, wlen, nfft, self.n_filters, str(device))
+    def _table(self, fs, wlen, nfft, device, lowerf=LOWERF, upperf=UPPERF, ncep=0):
+        """(window [wlen], mel bank [nfft/2+1, n_filters], bands [n_filters, 2], DCT table [ncep, n_filters] with the
+        1/n_filters folded in, or None for ncep = 0) on `device`, built once per set of arguments."""
+        key = (fs, wlen, nfft, lowerf, upperf, ncep, self.n_filters, str(device))
         if key not in self._tables:
             win = torch.from_numpy(np.hamming(wlen).astype(np.float32)).to(device)
-            bank64 = mel_filterbank(fs, nfft, self.n_filters)
+            bank64 = mel_filterbank(fs, nfft, self.n_filters, lowerf, upperf)
             bank = torch.from_numpy(bank64.astype(np.float32)).to(device)
             # first / last bin with a non-zero weight of every filter (the sparse projection)
             band = np.zeros((self.n_filters, 2), dtype=np.int32)
             for f in range(self.n_filters):
                 nz = np.nonzero(bank64[:, f])[0]
                 band[f] = (nz[0], nz[-1]) if len(nz) else (1, 0)
-            self._tables[key] = (win, bank, torch.from_numpy(band).to(device))
+            dct = None
+            if ncep:
+                dct = torch.from_numpy((dct_table(self.n_filters, ncep) / self.n_filters).astype(np.float32)).to(device)
+            self._tables[key] = (win, bank, torch.from_numpy(band).to(device), dct)
         return self._tables[key]
+
+    def _append_deltas(self, table, D, foff, n_utts):
+        """Writes the slopes of table[:, :D] into the columns after it (deltas, then deltasdeltas), one abn_deltas_batched
+        launch per order; `foff` = cumulative frame counts on the device (slopes stay inside each utterance)."""
+        lib = _lib.load()
+        T, W = table.shape
+        if T == 0:
+            return
+        d1 = table[:, D:2 * D] if self.deltas else torch.empty(T, D, dtype=torch.float32, device=table.device)
+        _lib.check(lib.abn_deltas_batched(_lib.ptr(table), W, _lib.ptr(foff), n_utts, T, D, _lib.ptr(d1), d1.stride(0),
+                                          _lib.stream()), 'abn_deltas_batched')
+        if self.deltasdeltas:
+            c = D * (1 + int(bool(self.deltas)))
+            _lib.check(lib.abn_deltas_batched(_lib.ptr(d1), d1.stride(0), _lib.ptr(foff), n_utts, T, D, _lib.ptr(table[:, c:c + D]),
+                                              W, _lib.stream()), 'abn_deltas_batched')
+
+    def _width(self, D):
+        return D * (1 + int(bool(self.deltas)) + int(bool(self.deltasdeltas)))
 
     def deltas_of(self, feats):
         """Regression deltas of a [T, D] device tensor (spectral's do_deltas): slope over +-4
@@ -108,20 +180,11 @@ class FeaturesGenerator:
         (features.py:110-111) the slopes are appended as further columns:
         [T, n_filters * (1 + deltas + deltasdeltas)]."""
         lib = _lib.load()
-        if isinstance(sound, torch.Tensor):
-            s = sound
-        else:
-            sound = np.ascontiguousarray(sound)
-            if sound.dtype != np.int16:
-                sound = sound.astype(np.float32)
-            s = torch.from_numpy(sound)
-        s = s.cuda().contiguous()
-        if s.dtype not in (torch.int16, torch.float32):
-            s = s.float()
+        s = _samples_one(sound)
         wl = int(wlen * srate)
         fshift = float(srate) / frate
         nfr = int(s.numel() / fshift + 1)
-        win, bank, band = self._table(srate, wl, nfft, s.device)
+        win, bank, band, _ = self._table(srate, wl, nfft, s.device)
         out = torch.empty(nfr, self.n_filters, dtype=torch.float32, device=s.device)
         _lib.check(lib.abn_fbank(_lib.ptr(s), int(s.dtype == torch.int16), s.numel(), wl,
                                  fshift, nfft, self.n_filters, alpha, _lib.ptr(win),
@@ -142,21 +205,7 @@ class FeaturesGenerator:
         deltasdeltas)] float32 on the device, frame counts [T_u]); utterance u is framed on its own, exactly as
         fbank_from_samples(waves[u]) frames it."""
         lib = _lib.load()
-        if isinstance(waves, tuple):             # (all samples end to end on the device, sample counts)
-            s, lens = waves[0], np.asarray(waves[1], dtype=np.int64)
-            assert int(lens.sum()) == s.numel()
-        else:
-            lens = np.array([len(w) for w in waves], dtype=np.int64)
-        if isinstance(waves, tuple):
-            pass
-        elif isinstance(waves[0], torch.Tensor):
-            s = torch.cat([w.reshape(-1) for w in waves]).cuda()
-        else:
-            dt = np.int16 if all(w.dtype == np.int16 for w in waves) else np.float32
-            s = torch.from_numpy(np.concatenate([np.asarray(w, dtype=dt).reshape(-1) for w in waves])).cuda()
-        if s.dtype not in (torch.int16, torch.float32):
-            s = s.float()
-        s = s.contiguous()
+        s, lens = _samples_batch(waves)
         wl = int(wlen * srate)
         fshift = float(srate) / frate
         nfr = (lens / fshift + 1).astype(np.int64)           # int(len / fshift + 1) per utterance
@@ -164,21 +213,72 @@ class FeaturesGenerator:
         foff = np.concatenate(([0], np.cumsum(nfr))).astype(np.int64)
         total = int(foff[-1])
         tables = torch.from_numpy(np.concatenate((soff, foff))).cuda()
-        win, bank, band = self._table(srate, wl, nfft, s.device)
+        win, bank, band, _ = self._table(srate, wl, nfft, s.device)
         out = torch.empty(total, self.n_filters, dtype=torch.float32, device=s.device)
         _lib.check(lib.abn_fbank_batched(_lib.ptr(s), int(s.dtype == torch.int16), _lib.ptr(tables[:len(soff)]),
                                          _lib.ptr(tables[len(soff):]), len(lens), wl, fshift, nfft, self.n_filters, alpha,
                                          _lib.ptr(win), _lib.ptr(bank), _lib.ptr(band), total, _lib.ptr(out), _lib.stream()),
                    'abn_fbank_batched')
-        if self.deltas or self.deltasdeltas:               # slopes never cross an utterance boundary: per utterance
-            cols = [out]
-            d1 = torch.cat([self.deltas_of(out[foff[u]:foff[u + 1]]) for u in range(len(lens))])
-            if self.deltas:
-                cols.append(d1)
-            if self.deltasdeltas:
-                cols.append(torch.cat([self.deltas_of(d1[foff[u]:foff[u + 1]]) for u in range(len(lens))]))
-            out = torch.cat(cols, dim=1)
+        if self.deltas or self.deltasdeltas:               # one launch per order, slopes stay inside each utterance
+            full = torch.empty(total, self._width(self.n_filters), dtype=torch.float32, device=s.device)
+            full[:, :self.n_filters].copy_(out)
+            self._append_deltas(full, self.n_filters, tables[len(soff):], len(lens))
+            out = full
         return out, nfr
+
+    # -- MFCC (abnet3/features.py:116-133) ------------------------------------------------------------------------------
+    def mfcc_from_samples(self, sound, srate, alpha=0.97, frate=100, wlen=0.025, nfft=MFCC_NFFT, ncep=NCEP,
+                          lowerf=MFCC_LOWERF, upperf=MFCC_UPPERF):
+        """Cepstra [T, ncep] float32 (device tensor) of do_mfccs' Spectral call from int16 or float mono samples (numpy
+        array or device tensor): the filterbank's log mel energies between lowerf and upperf on an nfft-point spectrum (a
+        window longer than nfft is cropped to its first nfft samples), then dct_table's transform.  With deltas /
+        deltasdeltas the slopes follow as further columns: [T, ncep * (1 + deltas + deltasdeltas)]."""
+        lib = _lib.load()
+        s = _samples_one(sound)
+        wl = int(wlen * srate)
+        fshift = float(srate) / frate
+        nfr = int(s.numel() / fshift + 1)
+        win, bank, band, dct = self._table(srate, wl, nfft, s.device, lowerf, upperf, ncep)
+        out = torch.empty(nfr, self._width(ncep), dtype=torch.float32, device=s.device)
+        _lib.check(lib.abn_mfcc(_lib.ptr(s), int(s.dtype == torch.int16), s.numel(), wl, fshift, nfft, self.n_filters, ncep, alpha,
+                                _lib.ptr(win), _lib.ptr(bank), _lib.ptr(band), _lib.ptr(dct), nfr, _lib.ptr(out), out.shape[1],
+                                _lib.stream()), 'abn_mfcc')
+        if self.deltas or self.deltasdeltas:
+            foff = torch.tensor([0, nfr], dtype=torch.int64, device=s.device)
+            self._append_deltas(out, ncep, foff, 1)
+        return out
+
+    def mfcc_batch(self, waves, srate, alpha=0.97, frate=100, wlen=0.025, nfft=MFCC_NFFT, ncep=NCEP, lowerf=MFCC_LOWERF,
+                   upperf=MFCC_UPPERF):
+        """do_mfccs for a list of utterances in ONE launch (abn_mfcc_batched; `waves` as fbank_batch takes them), the deltas
+        in one more launch per order, written into their columns.  Returns (table [sum T_u, ncep * (1 + deltas +
+        deltasdeltas)] float32 on the device, frame counts [T_u]); utterance u is exactly mfcc_from_samples(waves[u])."""
+        lib = _lib.load()
+        s, lens = _samples_batch(waves)
+        wl = int(wlen * srate)
+        fshift = float(srate) / frate
+        nfr = (lens / fshift + 1).astype(np.int64)           # int(len / fshift + 1) per utterance
+        soff = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
+        foff = np.concatenate(([0], np.cumsum(nfr))).astype(np.int64)
+        total = int(foff[-1])
+        tables = torch.from_numpy(np.concatenate((soff, foff))).cuda()
+        win, bank, band, dct = self._table(srate, wl, nfft, s.device, lowerf, upperf, ncep)
+        out = torch.empty(total, self._width(ncep), dtype=torch.float32, device=s.device)
+        _lib.check(lib.abn_mfcc_batched(_lib.ptr(s), int(s.dtype == torch.int16), _lib.ptr(tables[:len(soff)]),
+                                        _lib.ptr(tables[len(soff):]), len(lens), wl, fshift, nfft, self.n_filters, ncep, alpha,
+                                        _lib.ptr(win), _lib.ptr(bank), _lib.ptr(band), _lib.ptr(dct), total, _lib.ptr(out),
+                                        out.shape[1], _lib.stream()), 'abn_mfcc_batched')
+        if self.deltas or self.deltasdeltas:
+            self._append_deltas(out, ncep, tables[len(soff):], len(lens))
+        return out, nfr
+
+    def features_batch(self, waves, srate):
+        """The front end `self.method` names, for a corpus in one launch: fbank_batch or mfcc_batch."""
+        if self.method == 'fbanks':
+            return self.fbank_batch(waves, srate)
+        if self.method == 'mfcc':
+            return self.mfcc_batch(waves, srate)
+        raise ValueError("Method %s not authorized." % self.method)
 
     def normalize_table(self, table, lengths):
         """mean_variance_normalisation / mean_var_norm_per_file (features.py:205-297) on a device table of
@@ -208,14 +308,14 @@ class FeaturesGenerator:
         return out
 
     def features_from_waves(self, waves, srate, names=None):
-        """generate() (features.py:365-404) for in-memory audio, everything staying in HBM: filterbanks ->
+        """generate() (features.py:365-404) for in-memory audio, everything staying in HBM: filterbanks or MFCCs ->
         [normalisation] -> [stacking], one launch per stage for the whole corpus.  Returns
         (table [frames, dim], names, frame counts, {name: frame times}) -- DeviceCorpus.from_table's arguments;
         times as h5features_compute writes them (features.py:195)."""
         if isinstance(waves, dict):
             names, waves = list(waves.keys()), list(waves.values())
         names = list(names) if names is not None else ['utt%06d' % i for i in range(len(waves))]
-        table, nfr = self.fbank_batch(waves, srate)
+        table, nfr = self.features_batch(waves, srate)
         if self.normalization:
             table, _ = self.normalize_table(table, nfr)
         if self.stack:
@@ -225,7 +325,7 @@ class FeaturesGenerator:
 
     def generate(self):
         """The file-level entry point the gridsearch calls (abnet3/features.py:365-404, gridsearch.py:206-215): the wav
-        files of `self.files` (a directory or a list) -> filterbanks -> [normalisation] -> [stacking] ->
+        files of `self.files` (a directory or a list) -> filterbanks or MFCCs (`method`) -> [normalisation] -> [stacking] ->
         `self.output_path`, an h5features file with one item per wav (its basename), frame times
         0.0025 + 0.01 k (features.py:195) and float32 features.  The stages run on the whole corpus in HBM
         (features_from_waves: one launch per stage; the reference's two temporary h5features files do not exist);
@@ -234,9 +334,8 @@ class FeaturesGenerator:
         (absent from the build image: features_from_waves is the in-memory form)."""
         import os
         from scipy.io import wavfile
-        if self.method != 'fbanks':
-            raise ValueError("Method %s not authorized." % self.method if self.method != 'mfcc' else
-                             "abnet3_amd: method 'mfcc' is not on the accelerated path (filterbanks only)")
+        if self.method not in METHODS:
+            raise ValueError("Method %s not authorized." % self.method)
         files = self.files
         if isinstance(files, str):
             if not os.path.isdir(files):
@@ -258,7 +357,7 @@ class FeaturesGenerator:
         special = self.normalization and (self.vad_file is not None or self.load_mean_variance_path is not None)
         keep_norm, keep_stack = self.normalization, self.stack
         if special or (self.normalization and self.save_mean_variance_path):
-            self.normalization = self.stack = False          # filterbanks only; the other stages follow below
+            self.normalization = self.stack = False          # features only; the other stages follow below
         try:
             table, names, nfr, times = self.features_from_waves(waves, rate, names)
         finally:
@@ -287,6 +386,12 @@ class FeaturesGenerator:
         from scipy.io import wavfile
         srate, sound = wavfile.read(fname)
         return self.fbank_from_samples(sound, srate).cpu().numpy()
+
+    def do_mfccs(self, fname):
+        """Compute standard mfccs from a wav file (features.py:116-133)."""
+        from scipy.io import wavfile
+        srate, sound = wavfile.read(fname)
+        return self.mfcc_from_samples(sound, srate).cpu().numpy()
 
     def stack_fbanks(self, features, nframes=7):
         """Each frame becomes the concatenation of its nframes//2 previous and

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define ABN_ABI_VERSION 19
+#define ABN_ABI_VERSION 20
 #define ABN_MAX_LAYERS 16
 
 enum { ABN_OK = 0, ABN_E_ARG = -1, ABN_E_LAUNCH = -2, ABN_E_WORKSPACE = -3,
@@ -599,6 +599,44 @@ int abn_fbank_batched(const void* samples, int sample_is_i16, const int64_t* utt
  * padded with copies of frame 1 in front and of frame T-2 behind.  Apply twice for the
  * second-order deltas.  feats, out: [T, D] fp32, distinct buffers. */
 int abn_deltas(const float* feats, int64_t T, int64_t D, float* out, void* stream);
+
+/* ... for a batch of utterances laid end to end in ONE launch (ABI v20): utt_frame_off = cumulative frame
+ * counts (device int64 [n_utts + 1], utt_frame_off[n_utts] = T); no slope crosses an utterance boundary, and
+ * every utterance's rows are bit for bit what abn_deltas gives on that utterance alone.  feats and out are
+ * [T, D] column slices of wider tables with row strides ld_in / ld_out (>= D, in floats): the slopes can be
+ * written straight into their columns of the final table.  out may share rows with feats, never elements. */
+int abn_deltas_batched(const float* feats, int64_t ld_in, const int64_t* utt_frame_off, int64_t n_utts,
+                       int64_t T, int64_t D, float* out, int64_t ld_out, void* stream);
+
+/* FeaturesGenerator.do_mfccs, abnet3/features.py:116-133 (-> spectral.Spectral with nfft=512, ncep=13,
+ * lowerf=100, upperf=6855.4976, do_dct on) (ABI v20): abn_fbank's log mel energies, then the cepstra
+ * out[t][i] = sum_f dct[i][f] logspec[t][f] for i < ncep.  dct: [ncep][nfilt] fp32 (device), built by the
+ * host (abnet3_amd/features.py, dct_table: the Sphinx-III "legacy" DCT of spectral's lineage, 1/nfilt folded
+ * in).  A window longer than nfft is cropped to its first nfft samples (what rfft(frame, nfft) does); the
+ * pre-emphasis history of the next frame stays the frame's element wlen - 1.  band: as abn_fbank's, required.
+ * out: [nframes, ncep] with row stride ld_out >= ncep (floats), so the cepstra can land in the first columns
+ * of a table that also holds their deltas.  Kernel: abn_mfcc_path. */
+int abn_mfcc(const void* samples, int sample_is_i16, int64_t nsamples, int32_t wlen, double fshift,
+             int32_t nfft, int32_t nfilt, int32_t ncep, float alpha, const float* window,
+             const float* melbank, const int32_t* band, const float* dct, int64_t nframes,
+             float* out, int64_t ld_out, void* stream);
+
+/* ... for a batch of utterances in ONE launch, with abn_fbank_batched's utterance tables. */
+int abn_mfcc_batched(const void* samples, int sample_is_i16, const int64_t* utt_sample_off,
+                     const int64_t* utt_frame_off, int64_t n_utts, int32_t wlen, double fshift,
+                     int32_t nfft, int32_t nfilt, int32_t ncep, float alpha, const float* window,
+                     const float* melbank, const int32_t* band, const float* dct, int64_t nframes,
+                     float* out, int64_t ld_out, void* stream);
+
+/* Which kernel abn_mfcc / abn_mfcc_batched take for these arguments (a pure query, no GPU needed);
+ * -1 when the call would be refused (nfft not a power of two in [64, 2048], nfilt not in [1, 128],
+ * ncep not in [1, nfilt]). */
+enum {
+    ABN_MFCC_GENERAL = 0,          /* one workgroup per frame, radix-2 FFT, dense mel projection */
+    ABN_MFCC_WAVE512 = 1           /* nfft = 512 (the reference's value), nfilt <= 64: one wavefront per frame,
+                                      radix-4 FFT, sparse mel projection, the DCT in the epilogue */
+};
+int abn_mfcc_path(int32_t nfft, int32_t nfilt, int32_t ncep);
 
 #ifdef __cplusplus
 }
