@@ -2327,6 +2327,10 @@ int abn_tower_backward_loss(const abn_tower_desc* t, const float* x1, const floa
                             int64_t scratch_floats, float* loss_out, void* loss_ws, const int32_t* n_valid, double* loss_accum,
                             void* stream)
 {
+    if (loss_kind == ABN_LOSS_KL) {      // (the chain's loss phase has the cosine losses only: abn_pair_loss_dz + abn_tower_backward)
+        set_error("tower_backward_loss: ABN_LOSS_KL is not computed inside the backward: use abn_pair_loss_dz + abn_tower_backward");
+        return ABN_E_UNSUPPORTED;
+    }
     int rc = check_desc(t, rows, 2);
     if (rc != ABN_OK) return rc;
     ABN_REQUIRE(x1 && y && ws && scratch && loss_out && loss_ws, "tower_backward_loss: null pointer");

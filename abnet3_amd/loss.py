@@ -4,10 +4,11 @@ Mirrors (file:line relative to the reference checkout)
   LossBuilder   abnet3/loss.py:15-34
   coscos2       abnet3/loss.py:37-67
   cosmargin     abnet3/loss.py:70-105
+  KLLoss        abnet3/loss.py:108-137
   weighted_loss_multi  abnet3/loss.py:140-182
 forward(input1, input2, y) returns a 0-dim tensor with .backward(); the
-arithmetic (cosine similarity with eps=1e-6, per-label transform, sum, /N) and
-its gradient run fused in one kernel (abn_pair_loss).
+arithmetic (cosine similarity with eps=1e-6 or the two KL divergences, per-label
+transform, sum, /N) and its gradient run fused in one kernel (abn_pair_loss).
 """
 import torch
 import torch.nn as nn
@@ -54,7 +55,8 @@ def _pair_loss_raw(e1, e2, y, kind, margin, avg, need_grad, act=None, masks=None
     """abn_pair_loss: (0-dim loss, [2, B, D] gradient of the loss w.r.t. (e1, e2) or None).
     With `act` (the activation that produced e1 / e2) the gradient is taken w.r.t. the
     pre-activations instead (abn_pair_loss_dz; `masks` = the output layer's dropout
-    multipliers for the two towers, or None)."""
+    multipliers for the two towers, or None).  act = 'softmax' (KLLoss only): e1 / e2 are
+    the logits of a softmax head and the gradient is d loss / d logits."""
     lib = _lib.load()
     _lib.require_device(e1, e2, y)
     if e1.dtype != torch.float32 or e2.dtype != torch.float32:
@@ -72,7 +74,8 @@ def _pair_loss_raw(e1, e2, y, kind, margin, avg, need_grad, act=None, masks=None
         m1, m2 = masks if masks is not None else (None, None)
         _lib.check(lib.abn_pair_loss_dz(
             _lib.ptr(e1), _lib.ptr(e2), _lib.ptr(y), _lib.Y_DTYPE[y.dtype], B, D,
-            _lib.LOSS[kind], float(margin), int(bool(avg)), _lib.ACT[act], _lib.ptr(m1), _lib.ptr(m2),
+            _lib.LOSS[kind], float(margin), int(bool(avg)),
+            _lib.ACT_SOFTMAX if act == 'softmax' else _lib.ACT[act], _lib.ptr(m1), _lib.ptr(m2),
             _lib.ptr(loss), _lib.ptr(de[0]), _lib.ptr(de[1]), _lib.ptr(ws), _lib.stream()),
             'abn_pair_loss_dz')
         return loss, de
@@ -171,13 +174,43 @@ class cosmargin(LossBuilder):
         return _pair_loss_raw(input1, input2, y, 'cosmargin', self.margin, self.avg, True, act=act, masks=masks)
 
 
+class KLLoss(LossBuilder):
+    """The contrastive KL loss (abnet3/loss.py:108-137) of two probability rows P, Q:
+    KL(P, Q) when they embed the same phoneme, max(0, margin - KL(P, Q)) when not, for both
+    KL(P||Q) and KL(Q||P) -- nn.HingeEmbeddingLoss(margin, size_average=avg) of each, summed.
+    Labels other than +-1 take KL + max(0, margin - KL), as the hinge loss does.  The margin
+    has no range check; like the reference, forward's `avg` ARGUMENT is ignored."""
+
+    def __init__(self, margin=1, avg=True, *args, **kwargs):
+        super(KLLoss, self).__init__(*args, **kwargs)
+        self.margin = margin
+        self.avg = avg
+
+    def forward(self, input1, input2, y, avg=True):
+        return _pair_loss(input1, input2, y, 'KLLoss', self.margin, self.avg)
+
+    def value_and_grad(self, input1, input2, y):
+        """(loss, [2, B, D] gradient w.r.t. the probability rows (input1, input2))."""
+        assert input1.size() == input2.size(), 'Input not the same size'
+        return _pair_loss_raw(input1, input2, y, 'KLLoss', self.margin, self.avg, True)
+
+    def value_and_dz(self, input1, input2, y, act, masks=None):
+        """act = 'softmax': input1 / input2 are LOGITS, the loss is that of their row softmaxes
+        (nn.Softmax, a 'softmax' last_non_linearity) and the gradient is w.r.t. the logits --
+        softmax, loss and gradient in one launch.  Other acts: as coscos2.value_and_dz, on
+        probability rows act(z)."""
+        assert input1.size() == input2.size(), 'Input not the same size'
+        return _pair_loss_raw(input1, input2, y, 'KLLoss', self.margin, self.avg, True, act=act, masks=masks)
+
+
 class weighted_loss_multi(LossBuilder):
     """Weighted loss for multi-task training based on two pair losses
     (abnet3/loss.py:140-182): weight*loss_spk + (1 - weight)*loss_phn.
 
     Parameters
     ----------
-    loss_phn, loss_spk : abnet3_amd.loss functions (coscos2 / cosmargin)
+    loss_phn, loss_spk : abnet3_amd.loss functions (coscos2 / cosmargin / KLLoss; each
+        sub-loss runs through autograd, a KLLoss on its probability form)
     weight : float
         variable between 0 and 1, to weight one or the other task.
     """

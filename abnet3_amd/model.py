@@ -855,8 +855,15 @@ class SiameseNetwork(_HipNetwork):
         return out
 
     # -- autograd-free training path (TrainerSiamese.train_step) -------------------
-    def direct_ok(self):
-        return self._last_act != 'softmax'
+    def direct_ok(self, loss_type=None):
+        """Does TrainerSiamese's autograd-free step train this network (with a loss of `loss_type`): the cosine
+        losses on every head but a softmax one, KLLoss on a softmax head (its logits form, direct_logits_info)."""
+        if loss_type is None:
+            return self._last_act != 'softmax'
+        from .loss import coscos2, cosmargin, KLLoss
+        if self._last_act == 'softmax':
+            return loss_type is KLLoss
+        return loss_type in (coscos2, cosmargin)
 
     def direct_forward(self, x1, x2, forward_only=False, n_valid=None, source=None):
         """forward(x1, x2) in the current mode without building an autograd graph:
@@ -895,6 +902,23 @@ class SiameseNetwork(_HipNetwork):
             masks = (m[:half], m[half:])
         return seg.last_act, masks
 
+    def direct_logits_info(self, state):
+        """A softmax head (the segment ends linear, its output is the softmax's input): how KLLoss's logits form
+        (value_and_dz(..., 'softmax', masks)) hands its gradient to direct_backward -- (masks | None, d_out_is_dz).
+        Without BatchNorm the output layer's dropout multipliers are folded into d loss / d z; behind a BatchNorm,
+        or with masks that exist inside the tower kernels only, the same gradient goes in unmasked as d_out (the
+        backward applies its own masks).  None for every other head."""
+        if self._last_act != 'softmax':
+            return None
+        seg, sv, _ = state
+        if seg.batch_norm or isinstance(sv.masks, _DropSeed):
+            return None, False
+        if sv.masks is None:
+            return None, True
+        m = sv.masks[-1]
+        half = m.shape[0] // 2
+        return (m[:half], m[half:]), True
+
     def can_defer_reduce(self, state):
         """True when direct_backward may leave the split-K reduction to the optimizer's
         launch (abn_tower_reduce_step): one segment owns every live parameter."""
@@ -926,6 +950,8 @@ class SiameseNetwork(_HipNetwork):
         BatchNorm statistics): the caller then uses value_and_dz + direct_backward.
         n_valid (device int32 tensor): a padded batch, only the first n_valid pairs are real; loss_accum (device
         float64 tensor): the loss is also added to it (include/abnet3_hip.h)."""
+        if loss_kind not in ('coscos2', 'cosmargin'):
+            return None                          # (abn_tower_backward_loss has the cosine losses only)
         seg, sv, grad_pass = state
         rows = sv.rows
         if (sv.n_calls != 2 or os.environ.get('ABN_LOSS_IN_BACKWARD') == '0'      # (the variable: A/B runs)

@@ -331,16 +331,17 @@ class TrainerSiamese(TrainerBuilder):
 
     def _direct_ok(self):
         """The autograd-free step applies to the plain Siamese case: our network and
-        pair losses, the fused optimizer, the unmodified give_batch_to_network."""
+        pair losses (KLLoss on a softmax head only: SiameseNetwork.direct_ok), the fused
+        optimizer, the unmodified give_batch_to_network."""
         if not getattr(self, 'direct_steps', True):
             return False
         ok = getattr(self, '_direct_cache', None)
         if ok is None:
-            from .loss import coscos2, cosmargin
+            from .loss import coscos2, cosmargin, KLLoss
             from .model import SiameseNetwork
             ok = self._direct_cache = (
-                type(self.network) is SiameseNetwork and self.network.direct_ok()
-                and type(self.loss) in (coscos2, cosmargin)
+                type(self.network) is SiameseNetwork and type(self.loss) in (coscos2, cosmargin, KLLoss)
+                and self.network.direct_ok(type(self.loss))
                 and isinstance(self.optimizer, FlatOptimizer)
                 and type(self).give_batch_to_network is TrainerSiamese.give_batch_to_network)
         return ok
@@ -410,8 +411,12 @@ class TrainerSiamese(TrainerBuilder):
                 self.optimizer.grad_scale = 1.0 / self.world_size if self._loss_is_mean() else 1.0
                 self.optimizer.step()
                 return loss_value.detach()
+            logits = self.network.direct_logits_info(state)
             if loss_value is not None:
                 pass
+            elif logits is not None:  # a softmax head (KLLoss): softmax, loss and d loss / d logits in ONE launch
+                loss_value, dz = self.loss.value_and_dz(emb[:n], emb[n:], y_batch, 'softmax', logits[0])
+                self.network.direct_backward(state, dz.view(2 * n, -1), d_out_is_dz=logits[1], defer_reduce=defer)
             elif info is not None:    # loss gradient and the output layer's act' (+ dropout) in ONE launch
                 loss_value, dz = self.loss.value_and_dz(emb[:n], emb[n:], y_batch, info[0], info[1])
                 self.network.direct_backward(state, dz.view(2 * n, -1), d_out_is_dz=True, defer_reduce=defer)
@@ -581,6 +586,8 @@ class TrainerSiamese(TrainerBuilder):
             return None
         if not self._direct_ok():
             return None
+        if type(self.loss).__name__ == 'KLLoss':
+            return None                      # (a planned step's loss rides in the backward, which has the cosine losses only)
         if getattr(self.network, 'batch_norm', False) and getattr(self.network, 'bn_sync', None) is not None:
             return None                      # (cross-replica statistics: the replicas' real-row counts differ)
         if getattr(self, '_plan_refused', False):

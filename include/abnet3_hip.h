@@ -40,11 +40,14 @@ enum { ABN_OK = 0, ABN_E_ARG = -1, ABN_E_LAUNCH = -2, ABN_E_WORKSPACE = -3,
        ABN_E_UNSUPPORTED = -4 };
 
 /* activation_functions table, abnet3/model.py:19-23.  'softmax' (last_non_linearity only,
- * model.py:161-166) is not an epilogue: the tower ends with ABN_ACT_NONE and abn_softmax_rows follows. */
-enum { ABN_ACT_NONE = 0, ABN_ACT_SIGMOID = 1, ABN_ACT_RELU = 2, ABN_ACT_TANH = 3 };
+ * model.py:161-166) is not an epilogue: the tower ends with ABN_ACT_NONE and abn_softmax_rows follows.
+ * ABN_ACT_SOFTMAX is no tower activation either (abn_tower_desc takes 0-3): only abn_pair_loss_dz with
+ * ABN_LOSS_KL takes it, meaning "e1 / e2 are the softmax's inputs" (added within ABI 20, backward compatible). */
+enum { ABN_ACT_NONE = 0, ABN_ACT_SIGMOID = 1, ABN_ACT_RELU = 2, ABN_ACT_TANH = 3, ABN_ACT_SOFTMAX = 4 };
 
-/* abnet3/loss.py:37 (coscos2), :70 (cosmargin) */
-enum { ABN_LOSS_COSCOS2 = 0, ABN_LOSS_COSMARGIN = 1 };
+/* abnet3/loss.py:37 (coscos2), :70 (cosmargin), :108 (KLLoss; added within ABI 20: abn_pair_loss,
+ * abn_pair_loss_padded and abn_pair_loss_dz take it, abn_tower_backward_loss answers ABN_E_UNSUPPORTED) */
+enum { ABN_LOSS_COSCOS2 = 0, ABN_LOSS_COSMARGIN = 1, ABN_LOSS_KL = 2 };
 
 /* label element types accepted by the pair loss: the reference compares with
  * torch.eq(y, 1) / torch.eq(y, -1) on whatever dtype arrives (int64 in
@@ -422,6 +425,9 @@ int abn_linear_backward_prec(const float* dz, const float* W, const float* a_in,
  * (ONE launch: the workgroup that finishes last sums the per-workgroup partial losses in a
  * fixed order).  Calls sharing a ws buffer must be ordered on one stream. */
 int64_t abn_pair_loss_ws_bytes(int64_t B);
+/* kind = ABN_LOSS_KL (KLLoss, abnet3/loss.py:108-137): e1 / e2 are probability rows p / q, the loss is
+ * H(KL(p||q)) + H(KL(q||p)) with H = nn.HingeEmbeddingLoss(margin) (a mean over B with avg), any margin; label 1
+ * takes KL, -1 max(0, margin - KL), any other label KL + max(0, margin - KL).  Every per-row sum in fp64. */
 int abn_pair_loss(const float* e1, const float* e2, const void* y, int y_dtype,
                   int64_t B, int64_t D, int kind, float margin, int avg,
                   float* loss_out, float* de1, float* de2, void* ws,
@@ -439,7 +445,11 @@ int abn_pair_loss_padded(const float* e1, const float* e2, const void* y, int y_
  * mask2 [B, D] or NULL) folded in: e1 / e2 are the tower's outputs act(z), and dz1 / dz2
  * receive d loss / d z = d loss / d e * act'(e) [* mask] -- the first step of
  * loss.backward() (abnet3/trainer.py:239) through a tower without BatchNorm.  Hand
- * [dz1; dz2] to abn_tower_backward with abn_tower_desc.d_out_is_dz = 1. */
+ * [dz1; dz2] to abn_tower_backward with abn_tower_desc.d_out_is_dz = 1.
+ * kind = ABN_LOSS_KL with act = ABN_ACT_SOFTMAX: e1 / e2 are LOGITS z1 / z2, the loss is KLLoss of
+ * p = softmax(z1), q = softmax(z2) (nn.Softmax of a 'softmax' last_non_linearity, abnet3/model.py:161-166), and
+ * dz1 / dz2 receive d loss / d z1, d z2 [* mask] (softmax, loss and gradient in one launch).  ABN_ACT_SOFTMAX
+ * with any other kind, or in abn_pair_loss / abn_pair_loss_padded: ABN_E_UNSUPPORTED. */
 int abn_pair_loss_dz(const float* e1, const float* e2, const void* y, int y_dtype,
                      int64_t B, int64_t D, int kind, float margin, int avg, int act,
                      const float* mask1, const float* mask2, float* loss_out,

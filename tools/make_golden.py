@@ -35,6 +35,9 @@ Fixture sets:
   G11 gridsearch  the `default_params` of the reference's test/data/buckeye.yaml as a dictionary, and what
                   the reference's own classes make of it when built the way gridsearch.py:145-202 builds them
                   (which keyword arguments they accept, parameter count, state_dict keys, optimizer class)
+  G12 kl_loss    KLLoss (abnet3/loss.py:108-137): on probability rows, behind nn.Softmax() from logits (with the
+                  reference's own float64 evaluation, a near-uniform case among them), and a softmax SiameseNetwork
+                  trained 3 steps with it (BatchNorm off / on, SGD / Adadelta; the float64 run's losses beside)
   G9 frames_loader  FramesDataLoader.load_all_frames / load_batch / batch_iterator
                   (shuffles, batch slicing, max_batches_per_epoch wrap-around) and
                   OriginalDataLoader.add_tcl_to_batch / temporal_coherence_loss
@@ -805,9 +808,111 @@ def g11_gridsearch(abnet3):
         json.dump({'default_params': params, 'reference': info}, fh, indent=1, sort_keys=True)
 
 
+def _kl_rows(torch, p, q):
+    """KL(p||q), KL(q||p) per row as the reference's KLLoss.forward writes them (abnet3/loss.py:127-137)."""
+    return torch.sum(p * torch.log(p / q), 1), torch.sum(q * torch.log(q / p), 1)
+
+
+def _kl_draw(torch, B, D, scale, margin, softmax):
+    """[B, D] logits scale * randn for both sides; rows whose KL (either direction, fp32) lies within 1e-4 of the
+    margin are drawn again, so that no hinge subgradient is decided by rounding."""
+    z1, z2 = scale * torch.randn(B, D), scale * torch.randn(B, D)
+    for _ in range(100):
+        k1, k2 = _kl_rows(torch, softmax(z1), softmax(z2))
+        bad = ((k1 - margin).abs() < 1e-4) | ((k2 - margin).abs() < 1e-4)
+        if not bool(bad.any()):
+            return z1, z2
+        n = int(bad.sum())
+        z1[bad], z2[bad] = scale * torch.randn(n, D), scale * torch.randn(n, D)
+    raise RuntimeError('could not draw rows away from the margin')
+
+
+def g12_kl_loss(abnet3):
+    """G12: KLLoss (abnet3/loss.py:108-137).  (a) on probability rows (softmax of 3 randn logits): loss and the
+    gradients w.r.t. the rows; (b) behind nn.Softmax() from logits, gradients w.r.t. the logits, with the reference's
+    own float64 evaluation (the same code on float64 tensors: its losses, and for the near-uniform cases -- 0.01 randn
+    logits -- its gradients); (c) SiameseNetwork(last_non_linearity='softmax') trained 3 steps with KLLoss (C1 =
+    40->100->50, B = 32), BatchNorm off / on, SGD / Adadelta: losses, first-step gradients (the same for both
+    optimizers: stored once), parameters after 3 steps; the float64 run's losses.  The Linear layers' initial
+    parameters are stored once (BatchNorm draws nothing: the BN network's Linear layers start from the same values)."""
+    import torch
+    import torch.nn as nn
+    out = {}
+    sm = nn.Softmax()
+    # (name, B, D, logit scale, margin, avg, label dtype)
+    cases_a = [('a0', 8, 100, 3.0, 1, True, 'i64'), ('a1', 21, 39, 3.0, 1, False, 'i64'),
+               ('a2', 21, 39, 3.0, 0.5, True, 'i64'), ('a3', 29, 7, 3.0, 0.5, False, 'f32'),
+               ('a4', 29, 7, 3.0, 3, True, 'i64'), ('a5', 8, 100, 3.0, 3, False, 'i64')]
+    cases_b = [('b0', 8, 100, 3.0, 1, True, 'i64'), ('b1', 21, 39, 3.0, 0.5, False, 'i64'),
+               ('b2', 29, 7, 3.0, 3, True, 'f32'), ('b3', 33, 7, 3.0, 1, False, 'i64'),
+               ('u0', 8, 100, 0.01, 1, True, 'i64'), ('u1', 21, 39, 0.01, 0.5, False, 'i64')]
+    names = []
+    for i, (name, B, D, scale, margin, avg, ydt) in enumerate(cases_a + cases_b):
+        torch.manual_seed(1200 + i)
+        np.random.seed(1200 + i)
+        logits = name[0] != 'a'
+        z1, z2 = _kl_draw(torch, B, D, scale, margin, sm)
+        y = np.random.choice([1, -1, 0, 2], B)
+        y = y.astype(np.float32) if ydt == 'f32' else y.astype(np.int64)
+        loss_mod = abnet3.loss.KLLoss(margin=margin, avg=avg)
+        out[name + '.margin'], out[name + '.avg'] = np.float64(margin), np.int64(avg)
+        out[name + '.y'] = y
+        for dt, sfx in ((torch.float32, ''), (torch.float64, '.f64')):
+            if not logits and dt == torch.float64:
+                continue
+            if logits:
+                a = z1.to(dt).clone().requires_grad_(True)
+                b = z2.to(dt).clone().requires_grad_(True)
+                p, q = sm(a), sm(b)
+            else:
+                a = sm(z1).detach().clone().requires_grad_(True)
+                b = sm(z2).detach().clone().requires_grad_(True)
+                p, q = a, b
+            lv = loss_mod(p, q, torch.from_numpy(y))
+            lv.backward()
+            if dt == torch.float32:         # (the float64 run's inputs are these, widened)
+                out[name + '.in1'], out[name + '.in2'] = a.detach().numpy().copy(), b.detach().numpy().copy()
+            out[name + '.loss' + sfx] = np.float64(float(lv.detach()))
+            if dt == torch.float32 or name.startswith('u'):
+                out[name + '.g1' + sfx], out[name + '.g2' + sfx] = a.grad.numpy().copy(), b.grad.numpy().copy()
+        names.append(name)
+    out['cases'] = np.array(names)
+    # (c) three training steps of a softmax network with KLLoss
+    x1, x2, y = make_inputs(32, 40, 0)
+    out['c.x1'], out['c.x2'], out['c.y'] = x1.numpy(), x2.numpy(), y
+    for bn in (False, True):
+        kw = dict(input_dim=40, num_hidden_layers=0, hidden_dim=100, output_dim=50, p_dropout=0.0,
+                  type_init='xavier_uni', activation_layer='sigmoid', batch_norm=bn, last_non_linearity='softmax')
+        out['c.bn%d.kw' % bn] = np.array(repr(kw))
+        linear = {k: v for k, v in sd_to_np(build_net(abnet3, 0, **kw), 'c.p.').items()
+                  if k.endswith(('emb.0.weight', 'emb.0.bias', 'layer.0.weight', 'layer.0.bias'))}
+        for k, v in linear.items():
+            assert k not in out or np.array_equal(out[k], v), k
+        out.update(linear)
+        for oname in ('sgd', 'adadelta'):
+            for dt, sfx in ((torch.float32, ''), (torch.float64, '.f64')):
+                net = build_net(abnet3, 0, **kw).to(dt)
+                batches = [(x1.to(dt), x2.to(dt), y)]
+                run = {}
+                tag = 'c.bn%d.%s%s' % (bn, oname, sfx)
+                run_steps(abnet3, net, abnet3.loss.KLLoss(), oname, batches, 3, run, tag)
+                out[tag + '.losses'] = run[tag + '.losses']
+                if dt == torch.float64:
+                    continue
+                for k, v in run.items():
+                    if k.startswith(tag + '.after.'):
+                        out[k] = v
+                    elif k.startswith(tag + '.grad0.'):
+                        key = 'c.bn%d.grad0.' % bn + k[len(tag + '.grad0.'):]
+                        assert key not in out or np.array_equal(out[key], v), key
+                        out[key] = v
+    np.savez_compressed(os.path.join(OUT, 'kl_loss.npz'), **out)
+
+
 ALL = {'G1': g1_tower, 'G2': g2_train_c1, 'G3': g3_loss_edge,
        'G4': g4_train_mid, 'G5': g5_cosdist, 'G6': g6_stack, 'G7': g7_frames,
-       'G8': g8_multitask, 'G5L': g5l_cosdist_libm, 'G9': g9_frames_loader, 'G10': g10_mvn, 'G11': g11_gridsearch}
+       'G8': g8_multitask, 'G5L': g5l_cosdist_libm, 'G9': g9_frames_loader, 'G10': g10_mvn, 'G11': g11_gridsearch,
+       'G12': g12_kl_loss}
 
 
 def main():
