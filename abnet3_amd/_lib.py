@@ -96,7 +96,15 @@ SYMBOLS = {
     'abn_mfcc_batched': (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _i32, C.c_double, _i32, _i32, _i32, _f32, _vp, _vp,
                                     _vp, _vp, _i64, _vp, _i64, _vp]),
     'abn_mfcc_path': (C.c_int, [_i32, _i32, _i32]),
+    'abn_integrate_ws_bytes': (_i64, [_i64]),
+    'abn_integrate_forward': (C.c_int, [_vp, _i64, _vp, _i64, _i64, C.c_int, C.c_int, _f32, _f32, _vp, _vp, _vp, _i64,
+                                         C.c_int, _vp, _vp, _vp]),
+    'abn_integrate_backward': (C.c_int, [_vp, _i64, _vp, _i64, _i64, C.c_int, C.c_int, _f32, _f32, _vp, _vp, _i64,
+                                          C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# abn_integrate_forward / _backward (include/abnet3_hip.h)
+INTEGRATE_MODE = {'sum': 0, 'concat': 1}
+W_NONE, W_FIXED, W_SCALAR, W_ATTENTION = range(4)
 
 
 class TowerDesc(C.Structure):

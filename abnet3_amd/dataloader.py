@@ -863,3 +863,83 @@ class MultiTaskDataLoader(OriginalDataLoader):
         for idx in selected_batches:
             yield self.frames_from_pairs_device(group_pairs(batches[idx]), fid2spk=fid2spk)
 
+
+
+class MultimodalDataLoader(FramesDataLoader):
+    """FramesDataLoader over several frame-synchronous feature sets (abnet3/dataloader.py:794-980): the DTW
+    alignment runs on the first modality, and every modality's rows are gathered with the same frame-pair
+    indices (one DeviceCorpus table per modality, laid out like the first one; abn_gather_pairs per modality).
+    Batches are ([X1_m for m], [X2_m for m], y).  The reference's check_consistency is a TODO; here the
+    modalities must hold the same items with the same frame counts (ValueError otherwise)."""
+
+    def __init__(self, pairs_path, features_path,
+                 batch_size=500, randomize_dataset=False,
+                 max_batches_per_epoch=None):
+        super().__init__(pairs_path, features_path, batch_size,
+                         randomize_dataset, max_batches_per_epoch)
+        self.corpora = None              # [DeviceCorpus] per modality
+
+    def __getstate__(self):
+        return (self.pairs_path, self.features_path, self.statistics_training, self.seed,
+                self.num_max_minibatches, self.batch_size)
+
+    def check_consistency(self, features):
+        """features: one {item: [T, D_m]} per modality.  Raises ValueError unless every modality holds the items
+        of the first with the same number of frames."""
+        first = features[0]
+        for m, feats in enumerate(features[1:], 1):
+            if set(feats.keys()) != set(first.keys()):
+                raise ValueError('MultimodalDataLoader: modality %d does not hold the items of modality 0 '
+                                 '(%d against %d items)' % (m, len(feats), len(first)))
+            for k, f in first.items():
+                if len(feats[k]) != len(f):
+                    raise ValueError('MultimodalDataLoader: item %r has %d frames in modality 0 and %d in '
+                                     'modality %d' % (k, len(f), len(feats[k]), m))
+
+    def set_data(self, features, times, train_pairs=None, dev_pairs=None):
+        """In-memory injection: features = [{utt: [T, D_m]} per modality], times = {utt: [T]} (the first
+        modality's frame times locate the tokens of all)."""
+        features = list(features)
+        self.check_consistency(features)
+        names = list(features[0].keys())
+        self.corpora = [DeviceCorpus({k: f[k] for k in names}, times) for f in features]
+        super().set_data(features[0], times, train_pairs, dev_pairs)
+        self.features = self.corpora[0]
+
+    def load_data(self):
+        if self.corpora is None:
+            try:
+                import h5features
+            except ImportError:
+                raise ImportError('features_path lists h5features files and the h5features package is not '
+                                  'installed; use set_data() with in-memory arrays')
+            feats, times = [], None
+            for path in self.features_path:
+                with h5features.Reader(path, 'features') as fh:
+                    data = fh.read()
+                feats.append(data.dict_features())
+                if times is None:
+                    times = data.dict_labels()
+            self.check_consistency(feats)
+            names = list(feats[0].keys())
+            self.corpora = [DeviceCorpus({k: f[k] for k in names}, times) for f in feats]
+        self.features = self.corpora[0]
+        super().load_data()
+
+    def load_batch(self, sl, mode):
+        i1, i2, y = self.frame_pairs[mode]
+        first, stop, _ = sl.indices(len(y))
+        n = max(0, stop - first)
+        lib = _lib.load()
+        X1, X2 = [], []
+        for c in self.corpora:
+            x12 = torch.empty(2 * n, c.dim, dtype=torch.float32, device=c.table.device)
+            if n:
+                _lib.check(lib.abn_gather_pairs(_lib.ptr(c.table), c.total, c.dim, _lib.ptr(i1), _lib.ptr(i2), first, n, n,
+                                                None, 0, _lib.ptr(x12), None, None, _lib.stream()), 'abn_gather_pairs')
+            X1.append(x12[:n])
+            X2.append(x12[n:])
+        return X1, X2, y[sl]
+
+    def plan(self, train_mode=True):
+        return None                    # (a list of tensors per tower: the iterator)

@@ -168,3 +168,60 @@ class EmbedderSiameseMultitask(EmbedderBuilder):
         with h5features.Writer(self.output_path + '.phn') as fh:
             fh.write(data_phn, 'features')
 
+
+
+class MultimodalEmbedder(EmbedderBuilder):
+    """Embedder class for multimodal siamese network (abnet3/embedder.py:151-221): feature_path is the list of
+    the modalities' h5features files.  With a BiWeightedDeepLearnt unit an EmbeddingObserver records the attention
+    weights of every utterance (<output_path>attention_weights.features)."""
+
+    def __init__(self, *args, **kwargs):
+        super(MultimodalEmbedder, self).__init__(*args, **kwargs)
+        from .integration import BiWeightedDeepLearnt
+        from .utils import EmbeddingObserver
+        self.observers = []
+        if isinstance(self.network.integration_unit, BiWeightedDeepLearnt):
+            print("Placing observer to save learnt attention weights")
+            self.observers.append(EmbeddingObserver(
+                self.network.integration_unit.get_weights,
+                (self.output_path or '') + "attention_weights.features"))
+
+    def embed_features(self, feats_list):
+        """[[T, output] embeddings per utterance] for feats_list = [modality 0's [T, D_0] arrays, modality 1's,
+        ...] (the loop of embedder.py:193-213: one forward per utterance, which the observers look at)."""
+        self.network.eval()
+        self.network.cuda()
+        embeddings = []
+        with torch.no_grad():
+            for feats in zip(*feats_list):
+                modes = [torch.from_numpy(np.ascontiguousarray(f, dtype=np.float32)).cuda() for f in feats]
+                emb = self.network.forward_once(modes)         # network(modes, modes)[0]
+                embeddings.append(emb.cpu().numpy())
+                for observer in self.observers:
+                    observer.register_status()
+        return embeddings
+
+    def embed(self):
+        if self.network_path is not None:
+            self.network.load_network(self.network_path)
+        try:
+            import h5features
+        except ImportError:
+            raise ImportError('MultimodalEmbedder.embed() reads and writes h5features files like the reference; '
+                              'the h5features package is not installed. Use embed_features().')
+        items, times, features_list = None, None, []
+        for path in self.feature_path:
+            with h5features.Reader(path, 'features') as fh:
+                features = fh.read()
+            features_list.append(features.features())
+            if not items:
+                items = features.items()
+            if not times:
+                times = features.labels()
+        print("Done loading input feature file")
+        embeddings = self.embed_features(features_list)
+        data = h5features.Data(items, times, embeddings, check=True)
+        with h5features.Writer(self.output_path + "embedded.features") as fh:
+            fh.write(data, 'features')
+        for observer in self.observers:
+            observer.save(items, times)

@@ -1164,3 +1164,294 @@ class SiameseMultitaskNetwork(_HipNetwork):
     def save_network(self, epoch=''):
         torch.save(self.state_dict(), self.output_path + epoch + '.pth')
 
+
+
+class _WeightsHolder(object):
+    """Where abn_integrate_forward's w [rows, K] of the last forward lands (BiWeightedDeepLearnt.get_weights)."""
+    __slots__ = ('w',)
+
+    def __init__(self):
+        self.w = None
+
+
+class MultimodalSiameseNetwork(_HipNetwork):
+    """Multimodal Siamese neural network Architecture (abnet3/model.py:379-621).
+
+    Parameters: see the reference docstring; identical names and defaults.  What the reference does and this
+    class keeps on purpose ("Multimodal networks"):
+      * the pre-nets are SequentialPartialSave parameter holders that the reference never registers: they keep
+        torch's default nn.Linear initialisation (init_weight_method reaches the integration unit and the post-net
+        only) and freeze_training() leaves them alone.  Here they ARE registered, as `pre_nets.<i>.<j>.*`, so that
+        a saved network round-trips; load_network() still takes a reference file without them (and warns);
+      * parameters() returns the reference's param-group dicts (a second group at attention_lr).
+    Launches of one forward over both towers (BatchNorm statistics per tower call): per modality its pre-net (two
+    segments when the attention reads the input of Linear k >= 1 of it: autograd adds the gradients of both paths),
+    the attention nets of a BiWeightedDeepLearnt (segments with no dropout / BatchNorm, linear last layer), ONE
+    abn_integrate_forward over all rows, the post-net."""
+
+    def __init__(self, integration_unit=None,
+                 pre_integration_net_params=None,
+                 post_integration_net_params=None,
+                 attention_lr=None,
+                 asynchronous_integration_index=None,
+                 p_dropout=0, batch_norm=False,
+                 type_init='xavier_uni', activation_layer=None,
+                 output_path=None, *args, **kwargs):
+        super(MultimodalSiameseNetwork, self).__init__(*args, **kwargs)
+        assert activation_layer in ('relu', 'sigmoid', 'tanh')
+        assert type_init in ('xavier_uni', 'xavier_normal', 'orthogonal')
+        assert integration_unit is not None, 'If only using one input, use original SiameseNetwork'
+        if asynchronous_integration_index:
+            assert asynchronous_integration_index >= 0, \
+                'asynchronous integration index must be greater than 0'
+            assert asynchronous_integration_index < len(pre_integration_net_params[0]) - 1, \
+                'asynchronous integration index must be less than number of layers on the pre integration network'
+            assert pre_integration_net_params, \
+                'If asynchronous integration index provided, then there must exist pre integration networks'
+        from .utils import SequentialPartialSave
+
+        self.activation_layer = activation_layer
+        self.batch_norm = batch_norm
+        self.type_init = type_init
+        self.p_dropout = p_dropout
+        self.output_path = output_path
+        self.integration_unit = integration_unit
+        self.attention_lr = attention_lr
+        self.asynchronous_integration_index = asynchronous_integration_index
+
+        activation = activation_functions[activation_layer]
+        if pre_integration_net_params:
+            self.pre_nets = nn.ModuleList([SequentialPartialSave(*self.build_net(p, activation))
+                                           for p in pre_integration_net_params])
+            self.pre = True
+        else:
+            self.pre = False
+        if post_integration_net_params:
+            self.post_net = nn.Sequential(*self.build_net(post_integration_net_params, activation))
+            self.post = True
+        else:
+            self.post = False
+        # self.apply(init) of the reference: the unit, then the post-net (the pre-nets are not its modules)
+        self.integration_unit.apply(self.init_weight_method)
+        if self.post:
+            self.post_net.apply(self.init_weight_method)
+        self._init_hip_state()
+
+    def build_net(self, dimensions_list, activation):
+        from .utils import expand_dimension_list
+        dimensions_list = expand_dimension_list(dimensions_list)
+        layers = []
+        for idx in range(len(dimensions_list) - 1):
+            in_dim = dimensions_list[idx]
+            out_dim = dimensions_list[idx + 1]
+            layers.append(nn.Linear(in_dim, out_dim))
+            layers.append(nn.Dropout(p=self.p_dropout))
+            if self.batch_norm:
+                layers.append(nn.BatchNorm1d(out_dim))
+            layers.append(activation())
+        return layers
+
+    def init_weight_method(self, layer):
+        if isinstance(layer, nn.Linear):
+            init_func = init_functions[self.type_init]
+            init_func(layer.weight.data,
+                      gain=nn.init.calculate_gain(self.activation_layer))
+            layer.bias.data.fill_(0.0)
+            self._weights_rewritten()
+
+    def parameters(self, recurse=True):
+        """The reference's param groups (abnet3/model.py:507-522): [{'params': pre-nets + post-net (+ the unit)}]
+        or, with attention_lr, a second group {'params': the unit's, 'lr': attention_lr}."""
+        network_params = []
+        if self.pre:
+            for pre_net in self.pre_nets:
+                network_params += list(pre_net.parameters())
+        if self.post:
+            network_params += list(self.post_net.parameters())
+        if self.attention_lr:
+            return [{'params': network_params},
+                    {'params': list(self.integration_unit.parameters()), 'lr': self.attention_lr}]
+        network_params += list(self.integration_unit.parameters())
+        return [{'params': network_params}]
+
+    param_groups = parameters          # (FlatOptimizer: learning rate per range of the flat buffer)
+
+    def freeze_training(self):
+        """nn.Module.parameters() of the REFERENCE (abnet3/model.py:524-526): the integration unit and the
+        post-net -- its pre-nets were never registered."""
+        for p in self.integration_unit.parameters():
+            p.requires_grad = False
+        if self.post:
+            for p in self.post_net.parameters():
+                p.requires_grad = False
+
+    # -- HIP plumbing ------------------------------------------------------
+    def _attention_unit(self):
+        from .integration import BiWeightedDeepLearnt
+        return self.integration_unit if isinstance(self.integration_unit, BiWeightedDeepLearnt) else None
+
+    def _segments(self):
+        act, bn = self.activation_layer, self.batch_norm
+        k = self.asynchronous_integration_index or 0
+        segs, self._pre_segs, first = [], [], 0
+        if self.pre:
+            for net in self.pre_nets:
+                blocks = _blocks_of(net)
+                head = _Segment(self, blocks[:k], first, act, act, bn) if k > 0 else None
+                tail = _Segment(self, blocks[k:], first + k, act, act, bn)
+                segs += [s for s in (head, tail) if s is not None]
+                self._pre_segs.append((head, tail))
+                first += len(blocks)
+        self._post_seg = None
+        if self.post:
+            self._post_seg = _Segment(self, _blocks_of(self.post_net), first, act, act, bn)
+            segs.append(self._post_seg)
+            first += len(self._post_seg.blocks)
+        self._att_segs = None
+        unit = self._attention_unit()
+        if unit is not None:
+            self._att_segs = tuple(_Segment(self, _blocks_of(lin), first, unit.activation_type, 'none', False)
+                                   for lin in (unit.linear1, unit.linear2))
+            segs += list(self._att_segs)
+        return segs
+
+    def _extra_params(self):
+        """Live parameters outside the segments: BiWeightedScalarLearnt's weight."""
+        from .integration import BiWeightedScalarLearnt
+        unit = self.integration_unit
+        return [unit.weight] if isinstance(unit, BiWeightedScalarLearnt) else []
+
+    def live_parameters(self):
+        return [p for seg in self._segment_list() for p in seg.params] + self._extra_params()
+
+    def _grad_slot(self, gp, p):
+        """p's view of the pass's flat gradient buffer (the learnt scalar's dw is written there)."""
+        def slot():
+            self.flat_parameters()
+            if gp.buf is None:
+                gp.buf = torch.empty_like(self._flat)
+                self._last_grad_flat = gp.buf
+            i = [q is p for q in self._live_cache].index(True)
+            off = self._offsets[i]
+            return gp.buf[off:off + p.numel()].view(p.shape)
+        return slot
+
+    @staticmethod
+    def _rows_of(x1, x2):
+        return x1 if x2 is None else torch.cat((x1, x2))
+
+    def _forward(self, xs1, xs2):
+        xs1 = list(xs1)
+        xs2 = list(xs2) if xs2 is not None else None
+        self._segment_list()             # (builds _pre_segs / _post_seg / _att_segs)
+        if self.pre:
+            assert len(xs1) == len(self.pre_nets), "Number of inputs: " + \
+                "{} doesn't ".format(len(xs1)) + "match number of pre_integration " + \
+                "nets: {}".format(len(self.pre_nets))
+        n_calls = 1 if xs2 is None else 2
+        n = xs1[0].shape[0]
+        rows = n * n_calls
+        gp = _GradPass(self)
+        masks = self._draw_dropout_masks(rows, xs1[0].device) if self.training else None
+        parts, att_in = [], []
+        for m, x1 in enumerate(xs1):
+            x2 = xs2[m] if xs2 is not None else None
+            if x2 is not None and x2.shape[0] != n or x1.shape[0] != n:
+                raise ValueError('abnet3_amd: every modality must have the same number of rows')
+            if self.pre:
+                head, tail = self._pre_segs[m]
+                if head is not None:
+                    h = self._run(head, gp, masks, x1, x2, n_calls, False)
+                    att_in.append(h)
+                    parts.append(self._run(tail, gp, masks, h, None, n_calls, False))
+                else:
+                    parts.append(self._run(tail, gp, masks, x1, x2, n_calls, False))
+                    att_in.append(self._rows_of(x1, x2) if self.asynchronous_integration_index is not None else None)
+            else:
+                parts.append(self._rows_of(x1, x2))
+                att_in.append(parts[-1])
+        if self.asynchronous_integration_index is None:
+            att_in = parts
+        from .integration import integrate, integrate_list, BiWeightedFixed, BiWeightedScalarLearnt
+        unit = self.integration_unit
+        att = self._attention_unit()
+        if isinstance(unit, BiWeightedFixed):
+            assert len(parts) == 2, "BiWeighted integrators use two modalities"
+        if att is not None and not att.freezed:
+            z1 = self._run(self._att_segs[0], gp, None, att_in[0], None, n_calls, False)
+            z2 = self._run(self._att_segs[1], gp, None, att_in[1], None, n_calls, False)
+            holder = _WeightsHolder()
+            out = integrate(unit, parts[0], parts[1], z1, z2, holder=holder)
+            att._last_w = None if holder.w is None else holder.w[rows - n:].detach()
+        elif isinstance(unit, BiWeightedScalarLearnt):
+            out = integrate(unit, parts[0], parts[1], slot=self._grad_slot(gp, unit.weight))
+        else:
+            out = integrate_list(unit, parts)
+        if self.post:
+            return self._run(self._post_seg, gp, masks, out, None, n_calls, xs2 is not None)
+        return (out[:n], out[n:]) if xs2 is not None else out
+
+    # -- reference surface ---------------------------------------------------
+    def forward_once(self, x_list):
+        """Simple forward pass for one instance x_list, which contains multiple inputs (abnet3/model.py:529-560)."""
+        return self._forward(x_list, None)
+
+    def forward(self, input1, input2):
+        """(output1, output2) (abnet3/model.py:562-570): both towers in one launch sequence per segment,
+        BatchNorm statistics per tower call."""
+        return self._forward(input1, input2)
+
+    _HIP_STATE = _HipNetwork._HIP_STATE + ('_pre_segs', '_post_seg', '_att_segs')
+
+    def whoami(self):
+        d = super(MultimodalSiameseNetwork, self).whoami()
+        d['architecture'] = self.architecture_str()
+        return d
+
+    def save_network(self, epoch=''):
+        torch.save(self.state_dict(), self.output_path + str(epoch) + 'network.pth')
+        print("Saved network")
+        self.integration_unit.save()
+        print("Saved integration unit")
+
+    def load_network(self, path=None):
+        """<path>network.pth, then the unit's <path>integration.pth (abnet3/model.py:584-588).  A file written by
+        the reference holds no pre-net: the current pre-net weights stay (one warning)."""
+        state = torch.load(path + 'network.pth', map_location='cpu')
+        missing, unexpected = self.load_state_dict(state, strict=False)
+        bad = [k for k in missing if not k.startswith('pre_nets.')]
+        if bad or unexpected:
+            raise RuntimeError('abnet3_amd: %snetwork.pth does not fit this network (missing %s, unexpected %s)'
+                               % (path, bad, list(unexpected)))
+        if missing:
+            import warnings
+            warnings.warn('abnet3_amd: %snetwork.pth holds no pre-net weights (a file the reference wrote: it never '
+                          'registered them); the pre-nets keep their current weights' % path, stacklevel=2)
+        print("Done loading network")
+        self.integration_unit.load(path)
+        print("Done loading integration unit")
+        self.weights_changed_behind_torch()
+
+    def architecture_str(self):
+        from .utils import to_ordinal
+        _str = "Multimodal Siamese Architecture"
+        if self.pre:
+            net_index = 1
+            for pre_net in self.pre_nets:
+                _str += "\nPre Net {}:\n".format(net_index)
+                _str += str(pre_net)
+                _str += "\n"
+                net_index += 1
+        _str += "\nIntegration Unit:\n"
+        _str += str(self.integration_unit)
+        if self.asynchronous_integration_index is not None:
+            _str += "\nAsynchronous integration using "
+            if self.asynchronous_integration_index == 0:
+                _str += "raw features\n"
+            else:
+                _str += "{} layer output\n".format(to_ordinal(self.asynchronous_integration_index))
+        if self.post:
+            _str += "\nPost Net:\n"
+            _str += str(self.post_net)
+            _str += "\n"
+        return _str

@@ -86,10 +86,41 @@ class FlatOptimizer(object):
         self.grad_scale = 1.0
         self._flat = None
         self._s1 = self._s2 = None
+        self._steps = None          # per live parameter (ranges())
 
     def zero_grad(self, set_to_none=True):
-        for p in self.network.parameters():
+        for p in torch.nn.Module.parameters(self.network):
             p.grad = None
+
+    def ranges(self):
+        """The launches of the next step of a network with param groups (MultimodalSiameseNetwork.param_groups):
+        [(first float, floats, lr, step, [parameter indices])] over the flat buffer, one per run of contiguous live
+        parameters that take this step (a gradient: torch.optim skips the others, their state included) with the
+        same learning rate and the same step count (Adam's bias correction and SGD's first momentum step are per
+        parameter in torch).  None for every other network: one launch over the whole buffer, as ever."""
+        groups = getattr(self.network, 'param_groups', None)
+        if groups is None:
+            return None
+        lr_of = {}
+        for g in groups():
+            for p in g['params']:
+                lr_of[id(p)] = float(g.get('lr', self.lr))
+        live = self.network.live_parameters()
+        if self._steps is None or len(self._steps) != len(live):
+            self._steps = [0] * len(live)
+        offs = self.network._offsets
+        out = []
+        for i, p in enumerate(live):
+            if p.grad is None or not p.requires_grad:
+                continue
+            lr, step = lr_of.get(id(p), self.lr), self._steps[i] + 1
+            end = offs[i] + p.numel()
+            last = out[-1] if out else None
+            if last is not None and last[4][-1] == i - 1 and last[2] == lr and last[3] == step:
+                out[-1] = (last[0], end - last[0], lr, step, last[4] + [i])
+            else:
+                out.append((offs[i], p.numel(), lr, step, [i]))
+        return out
 
     def _state(self):
         if not self.network._is_flat(full=True):
@@ -128,6 +159,16 @@ class FlatOptimizer(object):
             return
         if hasattr(self.network, 'weights_changed_behind_torch'):
             self.network.weights_changed_behind_torch()
+        ranges = self.ranges()
+        if ranges is not None:
+            for first, n, lr, step, members in ranges:
+                _lib.check(lib.abn_optimizer_step(
+                    _lib.OPT[self.kind], _lib.ptr(flat[first:]), _lib.ptr(grad[first:]), _lib.ptr(self._s1[first:]),
+                    _lib.ptr(self._s2[first:]), n, lr, hp0, hp1, eps, step, float(self.grad_scale), _lib.stream()),
+                    'abn_optimizer_step')
+                for i in members:
+                    self._steps[i] = step
+            return
         _lib.check(lib.abn_optimizer_step(
             _lib.OPT[self.kind], _lib.ptr(flat), _lib.ptr(grad), _lib.ptr(self._s1),
             _lib.ptr(self._s2), flat.numel(), self.lr, hp0, hp1, eps, self.step_count,
@@ -379,7 +420,7 @@ class TrainerSiamese(TrainerBuilder):
         """The five statements of the reference's inner loop
         (abnet3/trainer.py:236-240) plus the data-parallel gradient exchange.
         Returns the (device) loss of the batch; never synchronises."""
-        if do_training and batch[0].shape[0] > 0 and self._direct_ok():
+        if do_training and self._direct_ok() and batch[0].shape[0] > 0:
             # the five statements with the trainer driving the kernels itself: forward,
             # fused loss + its gradient, backward -- no autograd graph, no engine
             X_batch1, X_batch2, y_batch = batch
@@ -1007,3 +1048,68 @@ class TrainerSiameseMultitask(TrainerSiamese):
         static = [t.cuda().clone() for t in example_batch]
         return static, lambda: self.give_batch_to_network(tuple(static))
 
+
+class MultimodalTrainer(TrainerSiamese):
+    """Multimodal Trainer class for ABnet3 (abnet3/trainer.py:281-365): batches are ([X1_m for m], [X2_m for m],
+    y) and every step goes through give_batch_to_network and autograd (no autograd-free step, planned pass or
+    captured graph; single process only).
+
+    :param headstart: None, or (epochs, keep training the network after them, weight during them): the
+                      integration unit trains from epoch `epochs` on, with the fixed weight until then; with
+                      False the post-net stops then (freeze_training) while the pre-nets and the unit go on."""
+
+    def __init__(self, headstart=None, *args, **kwargs):
+        super(MultimodalTrainer, self).__init__(*args, **kwargs)
+        from .dataloader import MultimodalDataLoader
+        from .model import MultimodalSiameseNetwork
+        assert type(self.dataloader) == MultimodalDataLoader
+        assert type(self.network) == MultimodalSiameseNetwork
+        if self.dp:
+            raise NotImplementedError('abnet3_amd: MultimodalTrainer runs in a single process (no data-parallel '
+                                      'multimodal training)')
+        self.direct_steps = False
+        self.graph_steps = False
+        self.planned_passes = False
+        if headstart:
+            self.headstart_epochs = headstart[0]
+            self.parallel_after_headstart = headstart[1]
+            # the reference catches NotImplementedError, but a unit without the method raises AttributeError
+            if not hasattr(self.network.integration_unit, 'set_headstart_weight'):
+                raise TypeError("Headstart only works with integration units" +
+                                "which have set_headstart_weight() method implemented")
+            self.network.integration_unit.set_headstart_weight(headstart[2])
+            self.headstart = True
+        else:
+            self.headstart = False
+
+    def cuda_all_modes(self, batch_list):
+        return [mode.cuda(non_blocking=True) for mode in batch_list]
+
+    def give_batch_to_network(self, batch):
+        X_list1, X_list2, y_batch = batch
+        X_list1 = self.cuda_all_modes(X_list1)
+        X_list2 = self.cuda_all_modes(X_list2)
+        y_batch = y_batch.cuda(non_blocking=True)
+        emb_batch1, emb_batch2 = self.network(X_list1, X_list2)
+        return self.loss(emb_batch1, emb_batch2, y_batch)
+
+    def train_step_auto(self, batch):
+        return self.train_step(batch, True)
+
+    def make_graphed_step(self, example_batch, warmup=3):
+        raise NotImplementedError('abnet3_amd: multimodal steps are not captured into graphs')
+
+    def optimize_model(self, do_training=True):
+        """The headstart schedule around TrainerSiamese.optimize_model (abnet3/trainer.py:344-365)."""
+        if self.headstart and self.headstart_epochs == 0:
+            if not self.parallel_after_headstart:
+                self.network.freeze_training()
+            if not hasattr(self.network.integration_unit, 'start_training'):
+                raise TypeError("Headstart only works with integration units" +
+                                "which have start_training() method implemented")
+            self.network.integration_unit.start_training()
+            print("Headstart ended")
+        dev_loss = super(MultimodalTrainer, self).optimize_model(do_training)
+        if self.headstart and self.headstart_epochs > -1:
+            self.headstart_epochs -= 1
+        return dev_loss

@@ -311,3 +311,82 @@ def get_dtw_alignment(feat1, feat2):
     path1, path2 = out
     assert len(path1) == len(path2)
     return path1, path2
+
+
+# -- multimodal helpers (abnet3/utils.py:282-379) ---------------------------------------------------------------
+
+class EmbeddingObserver(object):
+    """Keeps what `status_getter()` returns after every embedded utterance (abnet3/utils.py:282-311): the
+    multimodal embedder records the attention weights with it.  save() writes them as h5features beside the
+    embeddings when that package is importable."""
+
+    def __init__(self, status_getter, path):
+        self.status_getter = status_getter
+        self.path = path
+        self.intern_responses = []
+
+    def register_status(self):
+        response = self.status_getter()
+        if isinstance(response, torch.Tensor):
+            response = response.detach().cpu().numpy()
+        self.intern_responses.append(np.asarray(response))
+
+    def save(self, items, times):
+        import h5features
+        data = h5features.Data(items, times, self.intern_responses, check=True)
+        with h5features.Writer(self.path) as fh:
+            fh.write(data, 'features')
+
+
+class SequentialPartialSave(torch.nn.Sequential):
+    """nn.Sequential that remembers the input of each of its nn.Linear layers (abnet3/utils.py:313-352):
+    get_partial_result(0) is the raw input, get_partial_result(k) the output of block k-1.  In this package it is
+    the PARAMETER HOLDER of a multimodal pre-net (same modules, same str()); the network runs it as tower
+    segments and records the partial results itself."""
+
+    def __init__(self, *args, **kwargs):
+        super(SequentialPartialSave, self).__init__(*args, **kwargs)
+        self.partial_results = self.create_partial_dict()
+
+    def create_partial_dict(self):
+        partial_dict = {}
+        partial_index = 0
+        for layer_index in range(len(self)):
+            if isinstance(self[layer_index], torch.nn.Linear):
+                partial_dict[partial_index] = 0
+                partial_index += 1
+        return partial_dict
+
+    def get_partial_result(self, index):
+        return self.partial_results[index]
+
+    def forward(self, input):
+        raise NotImplementedError('abnet3_amd: a pre-net runs inside MultimodalSiameseNetwork (HIP tower segments)')
+
+
+def expand_dimension_list(dimensions_list):
+    """[280, (500, 2), 100] -> [280, 500, 500, 100] (abnet3/utils.py:354-365)."""
+    final_list = []
+    for x in dimensions_list:
+        if isinstance(x, int):
+            final_list.append(x)
+        elif isinstance(x, tuple) or isinstance(x, list):
+            assert len(x) == 2
+            for _ in range(x[1]):
+                final_list.append(x[0])
+        else:
+            raise TypeError("Dimension list element must be integer or tuple")
+    return final_list
+
+
+def to_ordinal(number):
+    """Returns ordinal string for the given number (abnet3/utils.py:367-379)."""
+    suffix = "th"
+    if not 10 < number < 21:
+        if number % 10 == 1:
+            suffix = "st"
+        elif number % 10 == 2:
+            suffix = "nd"
+        elif number % 10 == 3:
+            suffix = "rd"
+    return "{}{}".format(number, suffix)

@@ -543,6 +543,31 @@ int abn_softmax_rows(const float* z, int64_t rows, int64_t n, float* out, void* 
 int abn_softmax_rows_backward(const float* a, const float* da, int64_t rows, int64_t n,
                               float* dz, void* stream);
 
+/* The integration unit of MultimodalSiameseNetwork (abnet3/integration.py:71-475), one launch per direction
+ * over the rows of both towers.  x1 [rows, d1], x2 [rows, d2] (dense, fp32):
+ *   ABN_INTEGRATE_SUM     out [rows, d1] = w * x1 + (1 - w) * x2          (d1 == d2)
+ *   ABN_INTEGRATE_CONCAT  out [rows, d1 + d2] = [w * x1 | (1 - w) * x2]
+ * weight_kind: NONE (SumIntegration / ConcatenationIntegration: w = 1 - w = 1, no products); FIXED (w_fixed and
+ * w_complement as given: BiWeightedFixed, a headstart); SCALAR (w = *w_scalar, 1 - w in fp32:
+ * BiWeightedScalarLearnt); ATTENTION (w [rows, K] = act(z1 + z2), act = ABN_ACT_SIGMOID | ABN_ACT_TANH, K = 1 or
+ * K = d1 = d2: BiWeightedDeepLearnt).  Every product and sum is one fp32 operation in torch's order, no FMA
+ * contraction.  w_out (may be NULL): receives w [rows, K] (the row weight for the non-attention kinds, K = 1).
+ * The backward takes g = d loss / d out and writes dx1, dx2 (either may be NULL), for ATTENTION dz [rows, K] =
+ * d loss / d z1 = d loss / d z2 (w = the forward's w_out), for SCALAR *dw = the sum over all rows and features of
+ * g1 x1 - g2 x2 (fp64, fixed order: bit-identical from run to run; `ws` = abn_integrate_ws_bytes(rows) bytes whose
+ * first 4 are zero before the first call -- every call leaves them zero).  Both are NULL-safe at rows = 0 (*dw = 0). */
+enum { ABN_INTEGRATE_SUM = 0, ABN_INTEGRATE_CONCAT = 1 };
+enum { ABN_INTEGRATE_W_NONE = 0, ABN_INTEGRATE_W_FIXED = 1, ABN_INTEGRATE_W_SCALAR = 2, ABN_INTEGRATE_W_ATTENTION = 3 };
+int64_t abn_integrate_ws_bytes(int64_t rows);
+int abn_integrate_forward(const float* x1, int64_t d1, const float* x2, int64_t d2, int64_t rows, int mode,
+                          int weight_kind, float w_fixed, float w_complement, const float* w_scalar,
+                          const float* z1, const float* z2, int64_t K, int act, float* out, float* w_out,
+                          void* stream);
+int abn_integrate_backward(const float* x1, int64_t d1, const float* x2, int64_t d2, int64_t rows, int mode,
+                           int weight_kind, float w_fixed, float w_complement, const float* w_scalar,
+                           const float* w, int64_t K, int act, const float* g, float* dx1, float* dx2,
+                           float* dz, float* dw, void* ws, void* stream);
+
 /* X[path] gathers of abnet3/dataloader.py:204-205, :673-684: out[i] = table[idx[i]] */
 int abn_gather_rows(const float* table, const int64_t* idx, int64_t n, int64_t D,
                     float* out, void* stream);

@@ -38,6 +38,11 @@ Fixture sets:
   G12 kl_loss    KLLoss (abnet3/loss.py:108-137): on probability rows, behind nn.Softmax() from logits (with the
                   reference's own float64 evaluation, a near-uniform case among them), and a softmax SiameseNetwork
                   trained 3 steps with it (BatchNorm off / on, SGD / Adadelta; the float64 run's losses beside)
+  G13 multimodal  MultimodalSiameseNetwork (abnet3/model.py:379-621) with each integration unit of
+                  abnet3/integration.py (BiWeightedDeepLearnt with K = 1 and K = width, sum and concat, asynchronous
+                  index 0 and 1, BatchNorm, attention_lr): initial tensors (pre-nets included), e1 / e2, coscos2
+                  loss and gradients, parameters after 3 SGD and 3 Adadelta steps; the integration units alone
+                  (inputs, output, every gradient); two headstart schedules; MultimodalDataLoader batches
   G9 frames_loader  FramesDataLoader.load_all_frames / load_batch / batch_iterator
                   (shuffles, batch slicing, max_batches_per_epoch wrap-around) and
                   OriginalDataLoader.add_tcl_to_batch / temporal_coherence_loss
@@ -75,6 +80,7 @@ def import_reference():
     import abnet3.utils
     import abnet3.features
     import abnet3.dataloader
+    import abnet3.integration
     return abnet3
 
 
@@ -909,10 +915,261 @@ def g12_kl_loss(abnet3):
     np.savez_compressed(os.path.join(OUT, 'kl_loss.npz'), **out)
 
 
+# G13 network configurations: name -> (unit class, unit kwargs, pre-net params, post-net params, network kwargs)
+MM_D1, MM_D2, MM_B = 10, 6, 16
+MM_CONFIGS = {
+    'concat': ('ConcatenationIntegration', {}, [[10, 16, 12], [6, 16, 12]], [24, 8], dict(activation_layer='sigmoid')),
+    'sum': ('SumIntegration', {}, [[10, 16, 12], [6, 16, 12]], [12, 8], dict(activation_layer='tanh')),
+    'fixed_sum': ('BiWeightedFixed', dict(integration_mode='sum', weight_value=0.3), [[10, 16, 12], [6, 16, 12]],
+                  [12, 8], dict(activation_layer='relu')),
+    'fixed_concat': ('BiWeightedFixed', dict(integration_mode='concat'), [[10, 16, 12], [6, 16, 12]], [24, 8],
+                     dict(activation_layer='sigmoid')),
+    'scalar_sum': ('BiWeightedScalarLearnt', dict(integration_mode='sum'), [[10, 16, 12], [6, 16, 12]], [12, 8],
+                   dict(activation_layer='sigmoid')),
+    'scalar_concat_lr': ('BiWeightedScalarLearnt', dict(integration_mode='concat'), [[10, 16, 12], [6, 16, 12]],
+                         [24, 8], dict(activation_layer='tanh', attention_lr=0.01)),
+    'deep_k1_sum': ('BiWeightedDeepLearnt', dict(net_params=[[12, 1], [12, 1]], integration_mode='sum'),
+                    [[10, 16, 12], [6, 16, 12]], [12, 8], dict(activation_layer='sigmoid')),
+    'deep_kd_sum': ('BiWeightedDeepLearnt', dict(net_params=[[12, 12], [12, 12]], integration_mode='sum',
+                                                  activation_type='tanh'),
+                    [[10, 16, 12], [6, 16, 12]], [12, 8], dict(activation_layer='relu')),
+    'deep_k1_concat_async0': ('BiWeightedDeepLearnt', dict(net_params=[[10, 4, 1], [6, 4, 1]], integration_mode='concat'),
+                              [[10, 16, 12], [6, 16, 12]], [24, 8],
+                              dict(activation_layer='sigmoid', asynchronous_integration_index=0)),
+    'deep_kd_concat_async1_bn': ('BiWeightedDeepLearnt', dict(net_params=[[16, 12], [16, 12]], integration_mode='concat'),
+                                 [[10, 16, 12], [6, 16, 12]], [24, 8],
+                                 dict(activation_layer='tanh', asynchronous_integration_index=1, batch_norm=True,
+                                      attention_lr=0.05)),
+    'nopost_deep_k1': ('BiWeightedDeepLearnt', dict(net_params=[[12, 1], [12, 1]], integration_mode='sum'),
+                       [[10, 16, 12], [6, 16, 12]], None, dict(activation_layer='sigmoid')),
+}
+MM_SEEDS = {name: 1300 + i for i, name in enumerate(MM_CONFIGS)}
+
+
+def mm_build(abnet3, name, seed=None):
+    """The reference network of configuration `name` under its seeds (torch and numpy)."""
+    import torch
+    cls, ukw, pre, post, nkw = MM_CONFIGS[name]
+    seed = MM_SEEDS[name] if seed is None else seed
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    unit = getattr(abnet3.integration, cls)(**ukw)
+    net = abnet3.model.MultimodalSiameseNetwork(integration_unit=unit, pre_integration_net_params=pre,
+                                                post_integration_net_params=post, **nkw)
+    return net
+
+
+def mm_state(net, prefix):
+    """Every tensor of the reference network, the pre-nets under the port's key names (pre_nets.<i>.<j>.*)."""
+    out = {prefix + k: v.detach().numpy().copy() for k, v in net.state_dict().items()}
+    if net.pre:
+        for i, pn in enumerate(net.pre_nets):
+            for k, v in pn.state_dict().items():
+                out['%spre_nets.%d.%s' % (prefix, i, k)] = v.detach().numpy().copy()
+    return out
+
+
+def mm_named_params(net):
+    """(port key, parameter) of every parameter the reference trains."""
+    out = [(k, p) for k, p in net.named_parameters()]
+    if net.pre:
+        for i, pn in enumerate(net.pre_nets):
+            out += [('pre_nets.%d.%s' % (i, k), p) for k, p in pn.named_parameters()]
+    return out
+
+
+def mm_batch(torch, seed, B=MM_B):
+    torch.manual_seed(seed)
+    xa1, xa2 = torch.randn(B, MM_D1), torch.randn(B, MM_D1)
+    xb1, xb2 = torch.randn(B, MM_D2), torch.randn(B, MM_D2)
+    y = torch.from_numpy(np.random.RandomState(seed).choice([1, -1], B))
+    return [xa1, xb1], [xa2, xb2], y
+
+
+def g13_multimodal(abnet3):
+    """G13: the multimodal family (see the module docstring)."""
+    import torch
+    out = {}
+    loss_mod = abnet3.loss.coscos2(avg=False)
+    for name in MM_CONFIGS:
+        net = mm_build(abnet3, name)
+        out.update(mm_state(net, name + '.init.'))
+        out[name + '.arch'] = np.array(net.architecture_str())
+        X1, X2, y = mm_batch(torch, MM_SEEDS[name] + 50)
+        for m in range(2):
+            out['%s.X1_%d' % (name, m)], out['%s.X2_%d' % (name, m)] = X1[m].numpy(), X2[m].numpy()
+        out[name + '.y'] = y.numpy()
+        init = {k: v.detach().clone() for k, v in net.state_dict().items()}
+        init_pre = [{k: v.detach().clone() for k, v in pn.state_dict().items()} for pn in (net.pre_nets if net.pre else [])]
+        for optim_name, make in (('sgd', lambda p: torch.optim.SGD(p, lr=0.001, momentum=0.9)),
+                                 ('adadelta', lambda p: torch.optim.Adadelta(p, lr=0.1))):
+            net.load_state_dict(init)
+            for pn, sd in zip(net.pre_nets if net.pre else [], init_pre):
+                pn.load_state_dict(sd)
+            net.train()
+            opt = make(net.parameters())
+            losses = []
+            for s in range(3):
+                e1, e2 = net(X1, X2)
+                lv = loss_mod(e1, e2, y)
+                opt.zero_grad()
+                lv.backward()
+                if s == 0 and optim_name == 'sgd':
+                    out[name + '.e1'], out[name + '.e2'] = e1.detach().numpy().copy(), e2.detach().numpy().copy()
+                    out[name + '.loss'] = np.float64(float(lv))
+                    for k, p in mm_named_params(net):
+                        out['%s.grad.%s' % (name, k)] = p.grad.detach().numpy().copy()
+                    w = net.integration_unit.get_weights() if hasattr(net.integration_unit, 'get_weights') else None
+                    if isinstance(w, torch.Tensor) and w.numel() > 1:
+                        out[name + '.w_last'] = w.detach().numpy().copy()
+                opt.step()
+                losses.append(float(lv))
+            out['%s.%s.losses' % (name, optim_name)] = np.array(losses)
+            out.update(mm_state(net, '%s.%s.after.' % (name, optim_name)))
+        # the same network in float64 (the yardstick of the fp32 results: the reference's own fp32 gradients are up
+        # to 1e-3 off in these tiny towers, where the post-net's bias gradient is a heavily cancelled sum)
+        net.load_state_dict(init)
+        for pn, sd in zip(net.pre_nets if net.pre else [], init_pre):
+            pn.load_state_dict(sd)
+        net.double()
+        for pn in (net.pre_nets if net.pre else []):
+            pn.double()
+        if isinstance(getattr(net.integration_unit, 'weight', None), torch.Tensor) and \
+                not isinstance(net.integration_unit.weight, torch.nn.Parameter):
+            net.integration_unit.weight = net.integration_unit.weight.double()
+        e1, e2 = net([x.double() for x in X1], [x.double() for x in X2])
+        lv = loss_mod(e1, e2, y)
+        lv.backward()
+        out[name + '.f64.loss'] = np.float64(float(lv))
+        for k, p in mm_named_params(net):
+            out['%s.f64.grad.%s' % (name, k)] = p.grad.detach().numpy().copy()
+
+    # the integration units alone: out = unit(x) and every gradient for a random upstream gradient g
+    units = {
+        'u_sum': ('SumIntegration', {}, 9, 9, None),
+        'u_concat': ('ConcatenationIntegration', {}, 9, 5, None),
+        'u_fixed_sum': ('BiWeightedFixed', dict(integration_mode='sum', weight_value=0.3), 9, 9, None),
+        'u_fixed_concat': ('BiWeightedFixed', dict(integration_mode='concat', weight_value=0.7), 9, 5, None),
+        'u_scalar_sum': ('BiWeightedScalarLearnt', dict(integration_mode='sum', weight_value=0.4), 9, 9, None),
+        'u_scalar_concat': ('BiWeightedScalarLearnt', dict(integration_mode='concat', weight_value=0.6), 9, 5, None),
+        'u_deep_k1_sum': ('BiWeightedDeepLearnt', dict(net_params=[[9, 1], [9, 1]], integration_mode='sum'), 9, 9, 1),
+        'u_deep_kd_sum_tanh': ('BiWeightedDeepLearnt', dict(net_params=[[9, 9], [9, 9]], integration_mode='sum',
+                                                          activation_type='tanh'), 9, 9, 9),
+        'u_deep_k1_concat': ('BiWeightedDeepLearnt', dict(net_params=[[9, 1], [5, 1]], integration_mode='concat'), 9, 5, 1),
+        'u_deep_kd_concat': ('BiWeightedDeepLearnt', dict(net_params=[[9, 9], [9, 9]], integration_mode='concat'), 9, 9, 9),
+    }
+    R = 13
+    for i, (name, (cls, kw, d1, d2, K)) in enumerate(units.items()):
+        torch.manual_seed(1400 + i)
+        np.random.seed(1400 + i)
+        unit = getattr(abnet3.integration, cls)(**kw)
+        x1 = torch.randn(R, d1, requires_grad=True)
+        x2 = torch.randn(R, d2, requires_grad=True)
+        if K is not None:
+            z = (2 * torch.randn(R, K)).requires_grad_()
+            unit.compute_attention_weight = lambda i1, i2, z=z, u=unit: u.activation_layer(z)
+            o = unit([x1, x2], diff_input=[x1, x2])
+        else:
+            o = unit([x1, x2])
+        g = torch.randn(o.shape)
+        o.backward(g)
+        out[name + '.x1'], out[name + '.x2'], out[name + '.g'] = x1.detach().numpy(), x2.detach().numpy(), g.numpy()
+        out[name + '.out'] = o.detach().numpy()
+        out[name + '.dx1'], out[name + '.dx2'] = x1.grad.numpy(), x2.grad.numpy()
+        out[name + '.mode'] = np.array(getattr(unit, 'integration_mode', 'concat' if 'concat' in name else 'sum'))
+        if K is not None:
+            out[name + '.z'], out[name + '.dz'] = z.detach().numpy(), z.grad.numpy()
+            out[name + '.act'] = np.array(unit.activation_type)
+        if cls == 'BiWeightedScalarLearnt':
+            out[name + '.w'] = unit.weight.detach().numpy()
+            out[name + '.dw'] = unit.weight.grad.numpy()
+        elif cls == 'BiWeightedFixed':
+            out[name + '.w'] = np.float64(unit.weight)
+
+    # headstart schedules (trainer.py:281-365), optimize_model re-enacted by hand (its loss.data[0] fails on 0-dim
+    # tensors): 4 epochs of 2 batches, Adadelta(0.1); the parameters after every epoch
+    for tag, hs in (('hs_true', (2, True, 0.3)), ('hs_false', (2, False, 0.3))):
+        net = mm_build(abnet3, 'deep_k1_sum', seed=1500)
+        out.update(mm_state(net, tag + '.init.'))
+        batches = [mm_batch(torch, 1510 + b) for b in range(2)]
+        for b, (X1, X2, y) in enumerate(batches):
+            for m in range(2):
+                out['%s.b%d.X1_%d' % (tag, b, m)], out['%s.b%d.X2_%d' % (tag, b, m)] = X1[m].numpy(), X2[m].numpy()
+            out['%s.b%d.y' % (tag, b)] = y.numpy()
+        opt = torch.optim.Adadelta(net.parameters(), lr=0.1)
+        epochs_left = hs[0]
+        net.integration_unit.set_headstart_weight(hs[2])
+        losses = []
+        for epoch in range(4):
+            if epochs_left == 0:
+                if not hs[1]:
+                    net.freeze_training()
+                net.integration_unit.start_training()
+            net.train()
+            for X1, X2, y in batches:
+                e1, e2 = net(X1, X2)
+                lv = loss_mod(e1, e2, y)
+                opt.zero_grad()
+                lv.backward()
+                opt.step()
+                losses.append(float(lv))
+            if epochs_left > -1:
+                epochs_left -= 1
+            out.update(mm_state(net, '%s.epoch%d.' % (tag, epoch)))
+        out[tag + '.losses'] = np.array(losses)
+
+    # MultimodalDataLoader: two modalities through the G9 fake accessor and oracle DTW, two epochs
+    sys.path.insert(0, REPO)
+    from oracle import dtw_oracle
+    rng = np.random.default_rng(13)
+    lens = (60, 48, 75, 52)
+    feats0 = {'u%d' % i: rng.standard_normal((n, 12)).astype(np.float32) for i, n in enumerate(lens)}
+    feats1 = {'u%d' % i: rng.standard_normal((n, 7)).astype(np.float32) for i, n in enumerate(lens)}
+    times = {k: (np.arange(len(v)) * 0.01 + 0.0025) for k, v in feats0.items()}
+
+    def oracle_align(f1, f2):
+        d = abnet3.utils.cosine_distance(f1, f2)
+        p1, p2 = dtw_oracle.dtw_path(d)
+        return list(p1), list(p2)
+
+    abnet3.dataloader.get_dtw_alignment = oracle_align
+    train = [('u0', 0.10, 0.42, 'u1', 0.05, 0.31, 'same'),
+             ('u2', 0.20, 0.63, 'u3', 0.11, 0.37, 'same'),
+             ('u0', 0.33, 0.51, 'u2', 0.40, 0.65, 'diff'),
+             ('u1', 0.02, 0.29, 'u3', 0.21, 0.44, 'same'),
+             ('u3', 0.02, 0.30, 'u0', 0.20, 0.40, 'diff')]
+    dev = [('u0', 0.30, 0.55, 'u3', 0.20, 0.45, 'same'),
+           ('u1', 0.10, 0.35, 'u2', 0.20, 0.41, 'diff')]
+    out['dl.train_pairs'] = np.array([' '.join(map(str, p)) for p in train])
+    out['dl.dev_pairs'] = np.array([' '.join(map(str, p)) for p in dev])
+    for k in feats0:
+        out['dl.feat0.' + k], out['dl.feat1.' + k] = feats0[k], feats1[k]
+    for name, kw, seed in (('dl_rand', dict(batch_size=20, randomize_dataset=True), 21),
+                           ('dl_sub', dict(batch_size=16, randomize_dataset=True, max_batches_per_epoch=3), 22)):
+        dl = abnet3.dataloader.MultimodalDataLoader('unused', ['m0', 'm1'], **kw)
+        dl.features_dict = {'m0': abnet3.utils.Features_Accessor(dict(times), {k: v.copy() for k, v in feats0.items()}),
+                            'm1': abnet3.utils.Features_Accessor(dict(times), {k: v.copy() for k, v in feats1.items()})}
+        dl.pairs = {'train': list(train), 'dev': list(dev)}
+        np.random.seed(seed)
+        X1s, X2s, Ys, sizes = [[], []], [[], []], [], []
+        for mode in 'TDT':
+            for X1, X2, y in dl.batch_iterator(train_mode=(mode == 'T')):
+                for m in range(2):
+                    X1s[m].append(X1[m].numpy()); X2s[m].append(X2[m].numpy())
+                Ys.append(y.numpy()); sizes.append(len(y))
+        out[name + '.kw'] = np.array(repr(kw))
+        out[name + '.seed'] = np.array(seed)
+        for m in range(2):
+            out['%s.X1_%d' % (name, m)], out['%s.X2_%d' % (name, m)] = np.vstack(X1s[m]), np.vstack(X2s[m])
+        out[name + '.y'] = np.concatenate(Ys)
+        out[name + '.sizes'] = np.array(sizes)
+    np.savez_compressed(os.path.join(OUT, 'multimodal.npz'), **out)
+
+
 ALL = {'G1': g1_tower, 'G2': g2_train_c1, 'G3': g3_loss_edge,
        'G4': g4_train_mid, 'G5': g5_cosdist, 'G6': g6_stack, 'G7': g7_frames,
        'G8': g8_multitask, 'G5L': g5l_cosdist_libm, 'G9': g9_frames_loader, 'G10': g10_mvn, 'G11': g11_gridsearch,
-       'G12': g12_kl_loss}
+       'G12': g12_kl_loss, 'G13': g13_multimodal}
 
 
 def main():
