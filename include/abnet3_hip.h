@@ -514,6 +514,28 @@ int abn_dtw_batched_overlap(const float* feats1, int64_t rows1, const float* fea
                             int64_t path_stride, double* total_cost, void* ws,
                             int64_t ws_bytes, void* host_stage, int64_t host_stage_bytes,
                             void* stream, void* side_stream);
+/* DTW cost and path length without the path (ABX evaluation, abnet3_amd/abx.py), for a pair table that lives on
+ * the DEVICE: pair p aligns rows [off1[p], off1[p]+n1[p]) of feats1 with rows [off2[p], off2[p]+n2[p]) of feats2
+ * ([rows, D] fp32; off*, n*: device arrays).  total_cost[p] (f64) and path_len[p] (int32) equal, bit for bit, what
+ * abn_dtw_batched writes for the same pair: the same cell function, the same float64 recurrence and tie-break, the
+ * length of the path its traceback would walk; 0 and 0 for a pair it drops (a NaN distance, an empty token).  A pair
+ * whose token 2 has more than abn_dtw_cost_max_n2() frames, a negative length or rows outside the arrays is refused:
+ * path_len = -1, total_cost = 0, nothing is read (callers send long pairs to abn_dtw_batched).  Token 1 has no limit,
+ * any D >= 1.  One launch on `stream`, no workspace. */
+#define ABN_DTW_COST_MAX_N2 256
+int64_t abn_dtw_cost_max_n2(void);
+int abn_dtw_cost_batched(const float* feats1, int64_t rows1, const float* feats2, int64_t rows2,
+                         const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                         int64_t npairs, int64_t D, double* total_cost, int32_t* path_len, void* stream);
+/* ABX triplet scores (abnet3_amd/abx.py).  Row r is one X of ABX cell row_cell[r]: the distances d(A, X) over its A
+ * are dist[a_off[r] .. a_off[r] + a_len[r]), the d(B, X) over its B dist[b_off[r] .. b_off[r] + b_len[r]) (device
+ * arrays, dist: [ndist] f64).  For every cell c: score2[c] = the sum over its rows and their A x B triplets of 2 when
+ * d(A, X) < d(B, X), 1 when equal, 0 otherwise; count[c] = its number of triplets (both int64 [ncells] on the device,
+ * cleared by the call; integer sums: the same values in any order).  A row that reads outside dist or names no cell
+ * is skipped and counted in *refused (device int32, cleared by the call; may be NULL). */
+int abn_abx_score(const double* dist, int64_t ndist, const int64_t* a_off, const int32_t* a_len,
+                  const int64_t* b_off, const int32_t* b_len, const int32_t* row_cell, int64_t nrows,
+                  int64_t ncells, int64_t* score2, int64_t* count, int32_t* refused, void* stream);
 /* The distance matrix alone (utils.py:40-60), one pair, float64 [N, M] out.  The
  * reference computes in the precision of its inputs (utils.py:41-42: both float32 or
  * both float64): abn_cosine_distance is the float32 arithmetic of the hot path (the
