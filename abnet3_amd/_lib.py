@@ -104,6 +104,9 @@ SYMBOLS = {
                                          C.c_int, _vp, _vp, _vp]),
     'abn_integrate_backward': (C.c_int, [_vp, _i64, _vp, _i64, _i64, C.c_int, C.c_int, _f32, _f32, _vp, _vp, _i64,
                                           C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'abn_knn_ws_bytes': (_i64, [_i64, _i64, C.c_int]),
+    'abn_knn_topk': (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _i64, _vp]),
+    'abn_segment_vectors': (C.c_int, [_vp, _i64, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp]),
 }
 # abn_integrate_forward / _backward (include/abnet3_hip.h)
 INTEGRATE_MODE = {'sum': 0, 'concat': 1}
@@ -178,6 +181,7 @@ def reload_switches():
     load().abn_reload_switches()
 
 
+E_ARG = -1
 E_WORKSPACE = -3
 E_UNSUPPORTED = -4
 

@@ -52,6 +52,7 @@ struct Switches {
     bool wgrad_step;          // ABN_WGRAD_STEP=0: small batches' weight gradients as slabs + slab_reduce_step_kernel, never tower_wgrad_step.h's one launch
     bool dtw_dealt;           // ABN_DTW_SCHED=0: the gang DTW kernel on round 4's schedule (a pair per slot), not the dealt one
     int oneshot_wgs;          // ABN_ONESHOT_WGS: most workgroups of abn_allreduce_oneshot (default 32, <= 256)
+    int knn_split;            // ABN_KNN_SPLIT: workgroups that share a query block's candidates in abn_knn_topk (0 / unset / "auto": by the grid; same bits for any value)
 };
 const Switches& switches();
 void reload_switches();

@@ -63,6 +63,8 @@ static Switches read_switches()
     s.dtw_dealt = !off("ABN_DTW_SCHED");
     s.oneshot_wgs = getenv("ABN_ONESHOT_WGS") ? atoi(getenv("ABN_ONESHOT_WGS")) : 32;
     if (s.oneshot_wgs < 1 || s.oneshot_wgs > 256) s.oneshot_wgs = 32;
+    s.knn_split = getenv("ABN_KNN_SPLIT") ? atoi(getenv("ABN_KNN_SPLIT")) : 0;
+    if (s.knn_split < 0) s.knn_split = 0;
     return s;
 }
 static Switches g_switches = read_switches();       // (at library load: no call ever reads the environment)

@@ -5,6 +5,8 @@ Mirrors (file:line relative to the reference checkout)
   OriginalDataLoader    abnet3/dataloader.py:43-352  (load_frames_from_pairs,
                         batch_iterator, temporal coherence pairs)
   FramesDataLoader      abnet3/dataloader.py:580-739 (align once, frame batches)
+  PairsDataLoader       abnet3/dataloader.py:355-546 (a k-nearest-neighbour pairs file instead of the
+                        sampler's clusters: discovery.py writes one)
 What changes underneath: the whole feature corpus lives in HBM as ONE
 [frames, D] tensor (DeviceCorpus); "same" word pairs are DTW-aligned on the GPU
 in batched launches (utils.dtw_align_batch) and cached, since the alignment of a
@@ -832,6 +834,204 @@ class FramesDataLoader(OriginalDataLoader):
         num_batches = max(1, num_pairs // self.batch_size)
         offsets = np.minimum(np.arange(num_batches + 1, dtype=np.int64) * self.batch_size, num_pairs)
         return BatchPlan(self.features.table, i1, i2, y, offsets, ids)
+
+
+class PairsDataLoader(OriginalDataLoader):
+    """Takes a pairs file instead of the sampler's cluster-derived dataset (abnet3/dataloader.py:355-546): one
+    line `file1 file2 begin1 end1 begin2 end2 distance` per discovered pair, file ids as integers (mapped to names
+    through `id_to_file`, lines `id name`, when given), begin / end as FRAME indices -- a token is
+    features[file][begin:end] --, the distance ignored.  discovery.KnnPairMiner writes both files.
+
+    The pairs are split into 'train' and 'test' by whole files (SPLIT_FILES) or by position inside every file
+    (SPLIT_EACH_FILE); an epoch is drawn from Python's `random` call for call as the reference draws it, so that
+    after random.seed(s) the epoch's pair list is the reference's.  Batches are built on the device path of
+    OriginalDataLoader (all 'same' pairs of the epoch DTW-aligned in one batched call, frames gathered in HBM)
+    and arrive as device tensors.  Under torch.distributed the trainer shards the iterator's batches (every rank
+    must then have seeded `random` alike)."""
+    SPLIT_FILES = "files"
+    SPLIT_EACH_FILE = "split_each_file"
+    SPLIT_METHODS = [SPLIT_FILES, SPLIT_EACH_FILE]
+
+    shards_itself = False
+
+    def __init__(self, pairs_path, features_path, id_to_file,
+                 ratio_split_train_test=0.7,
+                 batch_size=8, train_iterations=10000, test_iterations=500,
+                 proportion_positive_pairs=0.5,
+                 align_different_words=True,
+                 split_method=SPLIT_EACH_FILE):
+        self.pairs_path = pairs_path
+        self.features_path = features_path
+        self.features = None          # DeviceCorpus
+        self.id_to_file = id_to_file
+        self.pairs = {'train': None, 'test': None}
+        self.ratio_split_train_test = ratio_split_train_test
+        self.batch_size = batch_size
+        self.align_different_words = align_different_words
+        self.iterations = {'train': train_iterations, 'test': test_iterations}
+        self.proportion_positive_pairs = proportion_positive_pairs
+        self.split_method = split_method
+        assert split_method in self.SPLIT_METHODS
+        self.tokens = {'train': [], 'test': []}
+        self.statistics_training = defaultdict(int)
+        self.files = set()
+        self.seed = 0
+        self.tcl = 0.0
+        self.train_files = None
+        self._align = AlignCache()
+
+    def __getstate__(self):
+        """For pickle: the features (and the pairs read from the file) stay out of the state."""
+        return (self.pairs_path, self.features_path, self.id_to_file, self.ratio_split_train_test,
+                self.align_different_words, self.proportion_positive_pairs)
+
+    def __setstate__(self, state):
+        """Rebuilds the loader from __getstate__'s tuple and reloads its data (dataloader.py:407-423).  What the
+        tuple does not carry (batch size, iterations, split method) takes the constructor's default, and the
+        features are only read when there is a features_path to read them from."""
+        pairs_path, features_path, id_to_file, ratio, align_different_words, proportion = state
+        self.__init__(pairs_path, features_path, id_to_file, ratio_split_train_test=ratio,
+                      proportion_positive_pairs=proportion, align_different_words=align_different_words)
+        if features_path is not None:
+            self.load_data()
+        elif pairs_path is not None:
+            self.load_pairs()
+
+    def set_data(self, features, times, train_pairs=None, test_pairs=None):
+        """In-memory injection of what load_data() reads from features_path: features {utt: [T, D]},
+        times {utt: [T]}; optionally the split pair lists ([f1, b1, e1, f2, b2, e2], frame indices)."""
+        self.features = DeviceCorpus(features, times)
+        if train_pairs is not None or test_pairs is not None:
+            self.pairs['train'] = [list(p) for p in (train_pairs or [])]
+            self.pairs['test'] = [list(p) for p in (test_pairs or [])]
+            self._set_tokens()
+
+    def load_data(self):
+        if self.pairs['train'] is None:
+            self.load_pairs()
+        if self.features is None:
+            try:
+                import h5features
+            except ImportError:
+                raise ImportError('features_path is an h5features file and the '
+                                  'h5features package is not installed; use '
+                                  'set_data() with in-memory arrays')
+            with h5features.Reader(self.features_path, 'features') as fh:
+                feats = fh.read()
+            self.features = DeviceCorpus(feats.dict_features(), feats.dict_labels())
+
+    def load_pairs(self):
+        """Reads the pairs file and splits it (dataloader.py:439-474): 7 space-separated fields per line, the
+        7th (the distance) ignored; ids mapped through id_to_file when given, kept as ints otherwise."""
+        pairs = []
+        file_mapping = {}
+        if self.id_to_file is not None:
+            with open(self.id_to_file, 'r') as f:
+                for fid, name in (l.strip().split() for l in f):
+                    file_mapping[int(fid)] = name
+        with open(self.pairs_path, 'r') as f:
+            for line in f:
+                file1, file2, begin1, end1, begin2, end2, _distance = line.split(' ')
+                file1, file2 = int(file1), int(file2)
+                file1 = file_mapping.get(file1, file1)
+                file2 = file_mapping.get(file2, file2)
+                self.files.add(file1)
+                self.files.add(file2)
+                pairs.append([file1, int(begin1), int(end1), file2, int(begin2), int(end2)])
+        if self.split_method == self.SPLIT_FILES:
+            self.pairs['train'], self.pairs['test'] = self.split_train_test(pairs)
+        elif self.split_method == self.SPLIT_EACH_FILE:
+            self.pairs['train'], self.pairs['test'] = self.split_train_test_each_file(pairs)
+        self._set_tokens()
+
+    def _set_tokens(self):
+        """tokens[mode]: every distinct (file, begin, end) of the mode's pairs, in the iteration order of a set
+        (as dataloader.py:469-474 builds them)."""
+        for mode in ('train', 'test'):
+            tokens = set()
+            for file1, begin1, end1, file2, begin2, end2 in self.pairs[mode]:
+                tokens.add((file1, begin1, end1))
+                tokens.add((file2, begin2, end2))
+            self.tokens[mode] = list(tokens)
+
+    def split_train_test(self, pairs):
+        """Train and test by splitting the FILES in two subsets; pairs across the two are dropped
+        (dataloader.py:476-494).  The test files are random.sample(sorted(self.files), n): the reference samples
+        from the set itself, which is an error from Python 3.11 on and whose order is not reproducible."""
+        num_files_test = int(len(self.files) * (1 - self.ratio_split_train_test))
+        dev_files = set(random.sample(sorted(self.files), num_files_test))
+        train_pairs, dev_pairs = [], []
+        for pair in pairs:
+            file1, file2 = pair[0], pair[3]
+            if file1 in dev_files and file2 in dev_files:
+                dev_pairs.append(pair)
+            elif file1 not in dev_files and file2 not in dev_files:
+                train_pairs.append(pair)
+        return train_pairs, dev_pairs
+
+    def split_train_test_each_file(self, pairs):
+        """Every file is cut at ratio * (the largest end seen in it): a pair trains when its first token begins
+        before its file's cut and its second at or before its own, tests when both begin after; the rest
+        straddles and is dropped (dataloader.py:496-519, comparisons as there)."""
+        len_files = defaultdict(int)
+        for file1, _, e1, file2, _, e2 in pairs:
+            len_files[file1] = max(len_files[file1], e1)
+            len_files[file2] = max(len_files[file2], e2)
+        threshold = {f: n * self.ratio_split_train_test for f, n in len_files.items()}
+        train_pairs, dev_pairs = [], []
+        for p in pairs:
+            file1, s1, _, file2, s2, _ = p
+            if s1 > threshold[file1] and s2 > threshold[file2]:
+                dev_pairs.append(p)
+            elif s1 < threshold[file1] and s2 <= threshold[file2]:
+                train_pairs.append(p)
+        return train_pairs, dev_pairs
+
+    def epoch_pairs(self, train_mode=True):
+        """One epoch's word pairs, [f1, b1, e1, f2, b2, e2, 'same' | 'diff'], drawn as dataloader.py:521-546
+        draws them: iterations * batch_size pairs of which proportion_positive_pairs are positives sampled
+        without replacement (all of them when there are not enough), the rest pairs of tokens drawn with
+        replacement and paired consecutively; then shuffled."""
+        mode = 'train' if train_mode else 'test'
+        all_positive_pairs = self.pairs[mode]
+        tokens = self.tokens[mode]
+        num_pairs = self.iterations[mode] * self.batch_size
+        num_positive_pairs = int(num_pairs * self.proportion_positive_pairs)
+        if num_positive_pairs > len(all_positive_pairs):
+            print("Not enough positive pairs to sample this number of iterations. "
+                  "There is only {}, but {} requested".format(len(all_positive_pairs), num_positive_pairs))
+            num_positive_pairs = len(all_positive_pairs)
+        num_negative_pairs = num_pairs - num_positive_pairs
+        positive_pairs = random.sample(all_positive_pairs, num_positive_pairs)
+        positive_pairs = [list(pair) + ['same'] for pair in positive_pairs]
+        tokens = random.choices(tokens, k=2 * num_negative_pairs)
+        negative_pairs = [list(tokens[i]) + list(tokens[i + 1]) + ['diff'] for i in range(0, len(tokens), 2)]
+        pairs = positive_pairs + negative_pairs
+        random.shuffle(pairs)
+        return pairs
+
+    def batch_iterator(self, train_mode=True):
+        """Iterator over the (X1, X2, y) device batches of one epoch: slices of batch_size word pairs of
+        epoch_pairs(), until the iterations are done or a slice is empty."""
+        self.load_data()
+        iterations = self.iterations['train' if train_mode else 'test']
+        pairs = self.epoch_pairs(train_mode)
+        # one batched DTW launch for every positive pair the epoch's batches will touch
+        self.align_pairs([p[:6] for p in pairs[:iterations * self.batch_size] if p[6] == 'same'], frames=True)
+        for i in range(iterations):
+            pairs_batch = pairs[i * self.batch_size: (i + 1) * self.batch_size]
+            if len(pairs_batch) == 0:
+                break
+            yield self.frames_from_pairs_device(group_pairs(pairs_batch), frames=True)
+
+    def plan(self, train_mode=True):
+        return None                    # (the epoch is drawn per pass from `random`: the iterator)
+
+    def prefetch_alignments(self):
+        self.load_data()
+        for mode in ('train', 'test'):
+            if self.pairs[mode]:
+                self.align_pairs(self.pairs[mode], frames=True)
 
 
 class MultiTaskDataLoader(OriginalDataLoader):

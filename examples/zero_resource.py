@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""The zero-resource loop, no labels at any point: a synthetic corpus -> log-mel filterbanks (HIP) -> pair discovery
+(KnnPairMiner: segment vectors + k-nearest neighbours on the matrix cores) -> PairsDataLoader -> a few epochs of
+Siamese training -> embedding -> ABX.  The corpus' word labels are used twice only, to report: the precision of the
+mined pairs, and the ABX item file ("phones" = word types).
+
+    python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr]
+"""
+import argparse
+import os
+import random
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from abnet3_amd.abx import ABXEvaluator, Items                    # noqa: E402
+from abnet3_amd.dataloader import DeviceCorpus, PairsDataLoader   # noqa: E402
+from abnet3_amd.discovery import KnnPairMiner                     # noqa: E402
+from abnet3_amd.embedder import EmbedderSiamese                   # noqa: E402
+from abnet3_amd.features import FeaturesGenerator                 # noqa: E402
+from abnet3_amd.loss import coscos2                               # noqa: E402
+from abnet3_amd.model import SiameseNetwork                       # noqa: E402
+from abnet3_amd.trainer import TrainerSiamese                     # noqa: E402
+from end_to_end import synth_corpus                               # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--utts', type=int, default=40)
+    ap.add_argument('--words', type=int, default=12)
+    ap.add_argument('--epochs', type=int, default=3)
+    ap.add_argument('--min-similarity', type=float, default=0.8)
+    ap.add_argument('--out', default='/tmp/abnet3_zr')
+    args = ap.parse_args()
+    rng = np.random.default_rng(0)
+    random.seed(0)
+    np.random.seed(0)
+    torch.manual_seed(0)
+
+    wavs, tokens = synth_corpus(args.utts, args.words, rng)
+    fg = FeaturesGenerator(norm_per_channel=True)
+    fb, _ = fg.normalize_features({k: fg.fbank_from_samples(v, 16000).cpu().numpy() for k, v in wavs.items()})
+    times = {k: np.arange(len(v)) * 0.01 + 0.0125 for k, v in fb.items()}
+
+    miner = KnnPairMiner(fb, times, min_similarity=args.min_similarity)
+    pairs_path, map_path = miner.write(args.out + '_mined')
+    a, b, sim = miner.pairs
+
+    def word_at(seg):
+        name = miner.names[miner.seg_file[seg]]
+        lo, hi = miner.seg_begin[seg] * 0.01, (miner.seg_begin[seg] + miner.seg_len[seg]) * 0.01
+        best = max((min(hi, t[2]) - max(lo, t[1]), t[3]) for t in tokens if t[0] == name)
+        return best[1] if best[0] >= 0.5 * (hi - lo) else -1
+    hits = [word_at(x) == word_at(y) != -1 for x, y in zip(a[:500], b[:500])]
+    print('%d segments, %d mined pairs; %.1f %% of the top %d join two tokens of one word'
+          % (miner.table.shape[0], len(a), 100 * np.mean(hits) if hits else 0.0, len(hits)))
+
+    dl = PairsDataLoader(pairs_path, None, map_path, batch_size=8, train_iterations=200, test_iterations=50,
+                         split_method='files')
+    dl.set_data(fb, times)
+    net = SiameseNetwork(input_dim=40, num_hidden_layers=1, hidden_dim=200, output_dim=40, p_dropout=0.0,
+                         activation_layer='sigmoid', output_path=args.out + '_network')
+    trainer = TrainerSiamese(network=net, loss=coscos2(avg=False), num_epochs=args.epochs, patience=30,
+                             optimizer_type='adadelta', lr=0.5, dataloader=dl, log_dir=args.out + '_runs')
+    trainer.train()
+    print('dev losses per epoch:', ['%.2f' % v for v in trainer.dev_losses])
+
+    names = list(fb)
+    emb = EmbedderSiamese(network=net, network_path=args.out + '_network.pth', feature_path=None,
+                          output_path=None).embed_features([fb[k] for k in names])
+    keep = [t for t in tokens if t[2] - t[1] >= 0.1]
+    items = Items([t[0] for t in keep], [t[1] for t in keep], [t[2] for t in keep], ['w%d' % t[3] for t in keep],
+                  ['-'] * len(keep), ['-'] * len(keep), ['spk'] * len(keep))
+    for label, feats in (('filterbanks', fb), ('embeddings', dict(zip(names, emb)))):
+        r = ABXEvaluator(items, DeviceCorpus({k: np.asarray(feats[k], dtype=np.float32) for k in names}, times)).run('within')
+        print('ABX error on %s: %.2f %% (%d triplets)' % (label, r.error, r.n_triplets))
+
+
+if __name__ == '__main__':
+    main()

@@ -695,6 +695,32 @@ enum {
 };
 int abn_mfcc_path(int32_t nfft, int32_t nfilt, int32_t ncep);
 
+/* k nearest neighbours by cosine similarity, for pair discovery (abnet3_amd/discovery.py writes the pairs file that
+ * PairsDataLoader, abnet3/dataloader.py:355-546, reads; the program that wrote the reference's
+ * test/data/dataloader/pairs_knn.txt is not part of it) (added within ABI 20, backward compatible).
+ * Q [nq][d], C [nc][d]: row-major fp32, rows L2-normalised by the caller, 16-byte aligned; sim(i, j) = <Q_i, C_j>,
+ * accumulated in fp32 on the matrix cores (v_mfma_f32_32x32x2_f32, k ascending).  q_meta / c_meta: int32 [n][3] =
+ * file, begin, end per row, or NULL; when BOTH are given candidate j is excluded for query i if the files are equal
+ * and the half-open intervals intersect (b_i < e_j && b_j < e_i) -- which covers i == j when Q and C are one table.
+ * idx / sim [nq][k]: the k non-excluded candidates of largest sim, by descending sim, ties by ascending j; unused
+ * places hold idx = -1, sim = -inf.  1 <= k <= 32, d a multiple of 4 in [4, 4096]: anything else is
+ * ABN_E_UNSUPPORTED (ABN_E_ARG for null pointers and sizes < 1), before any launch.  The nq x nc similarities are
+ * never written to memory; the candidates of a query block are split over several workgroups (ABN_KNN_SPLIT, or by
+ * the grid) whose partial lists go through ws (abn_knn_ws_bytes; 0 bytes when the split is 1) and are merged by the
+ * same order, so the output is bit-identical for any split. */
+int64_t abn_knn_ws_bytes(int64_t nq, int64_t nc, int k);      /* host; -1 for sizes abn_knn_topk refuses */
+int abn_knn_topk(const float* Q, int64_t nq, const float* C, int64_t nc, int d,
+                 const int32_t* q_meta, const int32_t* c_meta, int k, int32_t* idx, float* sim,
+                 void* ws, int64_t ws_bytes, void* stream);
+
+/* The segment vectors abn_knn_topk searches: segment g covers rows seg_row0[g] .. + seg_len[g] - 1 of table
+ * [rows][D]; its vector is the K rows seg_row0[g] + ((2j + 1) seg_len[g]) / (2K), j = 0 .. K - 1, concatenated to
+ * K D floats and scaled to unit L2 norm (sum of squares in float64, scale applied in fp32).  out [nseg][K D];
+ * keep [nseg] bytes: 0 where the segment is all zero (its vector is then zero and the caller leaves it out).
+ * seg_row0: device int64, seg_len: device int32; the caller guarantees that every segment lies inside the table. */
+int abn_segment_vectors(const float* table, int64_t D, const int64_t* seg_row0, const int32_t* seg_len,
+                        int64_t nseg, int K, float* out, uint8_t* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

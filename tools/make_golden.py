@@ -46,6 +46,12 @@ Fixture sets:
   G9 frames_loader  FramesDataLoader.load_all_frames / load_batch / batch_iterator
                   (shuffles, batch slicing, max_batches_per_epoch wrap-around) and
                   OriginalDataLoader.add_tcl_to_batch / temporal_coherence_loss
+  G14 pairs_loader  PairsDataLoader.load_pairs (abnet3/dataloader.py:439-474) on the reference's own test files
+                  (test/data/dataloader/pairs_knn.txt, id_to_file.txt, copied to tests/golden/pairs_loader/ as data):
+                  the train / test pair lists for both split methods at ratios 0.5 and 0.7, with and without the
+                  id_to_file map.  split_method='files' calls random.sample on a SET (dataloader.py:484), a TypeError
+                  from Python 3.11 on: for those cases only, random.sample is given sorted(set) instead (the
+                  population abnet3_amd's class samples from), after random.seed(seed); the seed is recorded
 
 usage: python tools/make_golden.py [--only G1,G3]
 """
@@ -1166,10 +1172,52 @@ def g13_multimodal(abnet3):
     np.savez_compressed(os.path.join(OUT, 'multimodal.npz'), **out)
 
 
+def g14_pairs_loader(abnet3):
+    """G14: the reference's PairsDataLoader.load_pairs on its own test data."""
+    import contextlib
+    import io
+    import json
+    import random
+    import shutil
+    src = os.path.join(REF, 'test', 'data', 'dataloader')
+    dst = os.path.join(OUT, 'pairs_loader')
+    os.makedirs(dst, exist_ok=True)
+    for f in ('pairs_knn.txt', 'id_to_file.txt'):
+        shutil.copyfile(os.path.join(src, f), os.path.join(dst, f))
+    real_sample = random.sample
+
+    def sample_sorted(population, k, **kw):
+        return real_sample(sorted(population) if isinstance(population, (set, frozenset)) else population, k, **kw)
+
+    seed, cases = 3, []
+    for method in ('files', 'split_each_file'):
+        for ratio in (0.5, 0.7):
+            for mapped in (True, False):
+                dl = abnet3.dataloader.PairsDataLoader(
+                    pairs_path=os.path.join(dst, 'pairs_knn.txt'), features_path=None,
+                    id_to_file=os.path.join(dst, 'id_to_file.txt') if mapped else None,
+                    ratio_split_train_test=ratio, split_method=method)
+                random.seed(seed)
+                random.sample = sample_sorted
+                try:
+                    with contextlib.redirect_stdout(io.StringIO()):
+                        dl.load_pairs()
+                finally:
+                    random.sample = real_sample
+                cases.append({'split_method': method, 'ratio': ratio, 'id_to_file': mapped, 'seed': seed,
+                              'train': dl.pairs['train'], 'test': dl.pairs['test'],
+                              'tokens_train': sorted(list(t) for t in dl.tokens['train']),
+                              'tokens_test': sorted(list(t) for t in dl.tokens['test']),
+                              'files': sorted(dl.files)})
+    with open(os.path.join(dst, 'load_pairs.json'), 'w') as fh:
+        json.dump({'cases': cases}, fh, indent=0)
+        fh.write('\n')
+
+
 ALL = {'G1': g1_tower, 'G2': g2_train_c1, 'G3': g3_loss_edge,
        'G4': g4_train_mid, 'G5': g5_cosdist, 'G6': g6_stack, 'G7': g7_frames,
        'G8': g8_multitask, 'G5L': g5l_cosdist_libm, 'G9': g9_frames_loader, 'G10': g10_mvn, 'G11': g11_gridsearch,
-       'G12': g12_kl_loss, 'G13': g13_multimodal}
+       'G12': g12_kl_loss, 'G13': g13_multimodal, 'G14': g14_pairs_loader}
 
 
 def main():
