@@ -77,6 +77,9 @@ SYMBOLS = {
                                            _i64, _vp, _vp]),
     'abn_dtw_cost_max_n2': (_i64, []),
     'abn_dtw_cost_batched': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    'abn_kl_tables': (C.c_int, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
+    'abn_dtw_cost_kl_batched': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
+                                           _vp]),
     'abn_abx_score': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     'abn_cosine_distance': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     'abn_cosine_distance_f64': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),

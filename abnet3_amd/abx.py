@@ -1,6 +1,6 @@
 """ABX phone discriminability of embeddings (the ZeroSpeech 2017 track-1 measure) on the MI355X.
 
-    python -m abnet3_amd.abx FEATURES ITEMS [--mode within|across|both]
+    python -m abnet3_amd.abx FEATURES ITEMS [--mode within|across|both] [--distance cosine|kl] [--floor F]
 
 The definition this module computes:
 
@@ -14,6 +14,28 @@ The definition this module computes:
   parallel frames whose cosine rounds above 1, or non-finite values) raises ValueError naming the items.  An
   all-zero frame is not dropped: it is at distance 1 from every other frame and 0 from another zero frame
   (the reference's rule, csrc/dist_ref.h).
+* Distance, ``distance='kl'`` (posteriorgrams: the rows a softmax network trained with KLLoss emits, the ZeroSpeech
+  evaluation's ``KL`` option): the same DTW over the symmetrised Kullback-Leibler divergence of the frames, by
+  ``abn_dtw_cost_kl_batched``.  The reference has no ABX code and no KL frame distance (its KLLoss is a training loss
+  over pairs of rows), so this definition is the build's own, like the DTW recurrence ("parity unpinned", DESIGN §5);
+  tests/abx_kl_np.py restates it in numpy bit for bit.
+  - Tables (``kl_tables``, ``abn_kl_tables``): for the feature table x [rows, D] float32 and a floor f (float32,
+    default 1e-6, > 0): P[r, k] = max(x[r, k], f) in float32, L[r, k] = float32(log(float64(P[r, k]))).  No
+    renormalisation.  A row with a non-finite or a negative value is BAD (flagged per row, its P / L contents
+    unspecified).  Zeros are legal (a saturated softmax) and are floored.
+  - Cell, for frames p (token 1) and q (token 2), in float32 with no fused multiply-add, in ascending k:
+    acc = 0; for k: acc = acc + ((P_p[k] - P_q[k]) * (L_p[k] - L_q[k])), each of the four operations rounded to float32
+    on its own, subnormals kept; d = 0.5f * acc.  For rows that sum to one this is half the sum of KL(p||q) and
+    KL(q||p).  The direct form is deliberate: every term is >= 0 (the rounded logarithm is monotone), so d >= 0
+    always and d == 0 exactly for identical frames; the expanded form (entropies minus cross dot products) cancels to
+    a few 1e-7 of either sign for near-identical frames, which breaks both properties and the ties the tie-break
+    relies on.
+  - Recurrence, tie-break, path length and d(P, Q) = total_cost / path_len: those of the cosine route (float64
+    cost = d + min(diag, up, left), first minimum in the order diag, up, left, the length carried along the chosen
+    predecessor).  Not symmetrised over the pair.
+  - A pair one of whose frames lies in a BAD row is dropped (path_len = 0) and raises ValueError naming the items.
+  - A token 2 of more than abn_dtw_cost_max_n2() frames (256: 2.56 s; ABX items are phones) raises ValueError: this
+    distance has no second kernel to fall back to.  Token 1 is unbounded.
 * Within speaker: A, B, X share context and speaker; phone(A) = phone(X) = p, phone(B) = q != p, A != X.  The
   cell is (p, q, context, speaker).
 * Across speaker: A, B, X share context; A and B share speaker s, X has speaker t != s; phone(A) = phone(X) = p,
@@ -29,7 +51,7 @@ order of any sum but the final float64 averages.  Memory is linear in the number
 """
 import argparse
 import sys
-from collections import defaultdict
+from collections import defaultdict, namedtuple
 
 import numpy as np
 import torch
@@ -37,6 +59,10 @@ import torch
 from . import _lib
 
 MODES = ('within', 'across')
+DISTANCES = ('cosine', 'kl')
+
+# what distance='kl' reads of one feature table (kl_tables): P and L [rows, D] float32, bad [rows] uint8, on the device
+KLTables = namedtuple('KLTables', ['P', 'L', 'bad'])
 
 
 class Items(object):
@@ -179,12 +205,51 @@ def _dev(a, dtype):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
 
 
-def dtw_cost_batch(feats1, off1, n1, feats2, off2, n2):
-    """(total_cost float64, path_len int32) device tensors of pair p = rows [off1[p], off1[p]+n1[p]) of feats1 against
-    [off2[p], off2[p]+n2[p]) of feats2, equal to dtw_align_batch's: abn_dtw_cost_batched for every pair whose token 2
-    fits its cap (abn_dtw_cost_max_n2() frames), abn_dtw_batched (utils.dtw_align_batch) for the others."""
+def kl_tables(table, floor=1e-6):
+    """KLTables (P, L, bad) of the device feature table [rows, D] float32 (abn_kl_tables): P = max(table, floor),
+    L = float32(log(float64(P))), bad[r] = 1 when row r holds a non-finite or a negative value."""
+    floor = np.float32(floor)
+    if not (floor > 0 and np.isfinite(floor)):
+        raise ValueError('kl_tables: the floor must be a positive finite float32, not %r' % (floor,))
     lib = _lib.load()
-    _lib.require_device(feats1, feats2)
+    if table.dim() != 2 or table.dtype != torch.float32:
+        raise ValueError('kl_tables: a [rows, D] float32 table is needed')
+    table = table.contiguous()
+    _lib.require_device(table)
+    P, L = torch.empty_like(table), torch.empty_like(table)
+    bad = torch.empty(table.shape[0], dtype=torch.uint8, device=table.device)
+    if table.shape[0]:
+        _lib.check(lib.abn_kl_tables(_lib.ptr(table), table.shape[0], table.shape[1], float(floor), _lib.ptr(P), _lib.ptr(L),
+                                     _lib.ptr(bad), _lib.stream()), 'abn_kl_tables')
+    return KLTables(P, L, bad)
+
+
+def dtw_cost_batch(feats1, off1, n1, feats2, off2, n2, distance='cosine'):
+    """(total_cost float64, path_len int32) device tensors of pair p = rows [off1[p], off1[p]+n1[p]) of feats1 against
+    [off2[p], off2[p]+n2[p]) of feats2.
+
+    distance='cosine': feats* are [rows, D] float32 device tables; the result equals dtw_align_batch's:
+    abn_dtw_cost_batched for every pair whose token 2 fits its cap (abn_dtw_cost_max_n2() frames), abn_dtw_batched
+    (utils.dtw_align_batch) for the others.
+    distance='kl': feats* are KLTables (or any (P, L, bad) triple) as kl_tables returns them;
+    abn_dtw_cost_kl_batched.  A token 2 beyond the cap raises ValueError (there is no second kernel); a pair with a
+    BAD row comes back with path_len = 0."""
+    if distance not in DISTANCES:
+        raise ValueError('distance must be one of %s, not %r' % (DISTANCES, distance))
+    lib = _lib.load()
+    kl = distance == 'kl'
+    if kl:
+        (feats1, L1, bad1), (feats2, L2, bad2) = feats1, feats2
+        _lib.require_device(feats1, L1, bad1, feats2, L2, bad2)
+        for P_, L_, b_ in ((feats1, L1, bad1), (feats2, L2, bad2)):
+            if (P_.dim() != 2 or L_.shape != P_.shape or b_.shape != P_.shape[:1] or P_.dtype != torch.float32 or
+                    L_.dtype != torch.float32 or b_.dtype != torch.uint8 or
+                    not (P_.is_contiguous() and L_.is_contiguous() and b_.is_contiguous())):
+                raise ValueError('dtw_cost_batch: distance=\'kl\' takes (P, L, bad) as kl_tables returns them')
+        if feats1.shape[1] != feats2.shape[1]:
+            raise ValueError('dtw_cost_batch: the two sides have different frame widths')
+    else:
+        _lib.require_device(feats1, feats2)
     off1 = np.ascontiguousarray(off1, dtype=np.int64)
     off2 = np.ascontiguousarray(off2, dtype=np.int64)
     n1 = np.ascontiguousarray(n1, dtype=np.int32)
@@ -193,16 +258,26 @@ def dtw_cost_batch(feats1, off1, n1, feats2, off2, n2):
     if P and (n1.min() < 0 or n2.min() < 0 or off1.min() < 0 or off2.min() < 0 or
               (off1 + n1).max() > feats1.shape[0] or (off2 + n2).max() > feats2.shape[0]):
         raise ValueError('dtw_cost_batch: a pair reads outside the feature tables')
+    cap = lib.abn_dtw_cost_max_n2()
+    long_ = np.flatnonzero(n2 > cap)
+    if kl and len(long_):
+        raise ValueError('dtw_cost_batch: token 2 of pair %d has %d frames; distance=\'kl\' takes at most %d '
+                         '(%d pair(s) beyond it)' % (long_[0], n2[long_[0]], cap, len(long_)))
     cost = torch.empty(P, dtype=torch.float64, device=feats1.device)
     plen = torch.empty(P, dtype=torch.int32, device=feats1.device)
     if P == 0:
         return cost, plen
     d_off1, d_n1, d_off2, d_n2 = _dev(off1, np.int64), _dev(n1, np.int32), _dev(off2, np.int64), _dev(n2, np.int32)
+    if kl:
+        _lib.check(lib.abn_dtw_cost_kl_batched(_lib.ptr(feats1), _lib.ptr(L1), feats1.shape[0], _lib.ptr(feats2), _lib.ptr(L2),
+                                               feats2.shape[0], _lib.ptr(d_off1), _lib.ptr(d_n1), _lib.ptr(d_off2),
+                                               _lib.ptr(d_n2), P, feats1.shape[1], _lib.ptr(bad1), _lib.ptr(bad2),
+                                               _lib.ptr(cost), _lib.ptr(plen), _lib.stream()), 'abn_dtw_cost_kl_batched')
+        return cost, plen
     _lib.check(lib.abn_dtw_cost_batched(_lib.ptr(feats1), feats1.shape[0], _lib.ptr(feats2), feats2.shape[0],
                                         _lib.ptr(d_off1), _lib.ptr(d_n1), _lib.ptr(d_off2), _lib.ptr(d_n2), P,
                                         feats1.shape[1], _lib.ptr(cost), _lib.ptr(plen), _lib.stream()),
                'abn_dtw_cost_batched')
-    long_ = np.flatnonzero(n2 > lib.abn_dtw_cost_max_n2())
     if len(long_):
         from .utils import dtw_align_batch
         res = dtw_align_batch(feats1, off1[long_], n1[long_], feats2, off2[long_], n2[long_])
@@ -233,15 +308,18 @@ def abx_score(dist, plan):
 class ABXResult(object):
     """error: percent.  cells: [(key, n_triplets, score)] with key = (phone p, phone q, context, speaker key) --
     speaker key = speaker (within) or (speaker of A and B, speaker of X) (across).  by_phone_pair: {(p, q): score}.
-    n_items (kept), n_pairs (DTW alignments), n_triplets, dropped: [(item index, description)]."""
+    n_items (kept), n_pairs (DTW alignments), n_triplets, dropped: [(item index, description)].  distance: the frame
+    distance of the alignments ('cosine' or 'kl')."""
 
-    def __init__(self, mode, error, cells, by_phone_pair, n_items, n_pairs, n_triplets, dropped):
+    def __init__(self, mode, error, cells, by_phone_pair, n_items, n_pairs, n_triplets, dropped, distance='cosine'):
         self.mode, self.error, self.cells, self.by_phone_pair = mode, error, cells, by_phone_pair
         self.n_items, self.n_pairs, self.n_triplets, self.dropped = n_items, n_pairs, n_triplets, dropped
+        self.distance = distance
 
     def __repr__(self):
-        return ('ABXResult(%s: error %.4f %%, %d cells, %d items, %d pairs, %d triplets, %d dropped)'
-                % (self.mode, self.error, len(self.cells), self.n_items, self.n_pairs, self.n_triplets, len(self.dropped)))
+        return ('ABXResult(%s, %s: error %.4f %%, %d cells, %d items, %d pairs, %d triplets, %d dropped)'
+                % (self.mode, self.distance, self.error, len(self.cells), self.n_items, self.n_pairs, self.n_triplets,
+                   len(self.dropped)))
 
 
 def _read_h5features(path):
@@ -261,10 +339,15 @@ class ABXEvaluator(object):
     items: an Items (read_item_file) or the path of an item file.
     corpus: a DeviceCorpus (e.g. ``DeviceCorpus.from_table(embedder.embed_table(table), names, lengths, times)``),
     a {name: [T, D]} features dict together with `times` ({name: [T] frame times in seconds}), or the path of an
-    h5features file (needs the h5features package)."""
+    h5features file (needs the h5features package).
+    distance: 'cosine' (embeddings) or 'kl' (posteriorgrams: the symmetrised Kullback-Leibler divergence over the
+    tables of kl_tables(corpus.table, floor), built here once and kept for every run)."""
 
-    def __init__(self, items, corpus, times=None):
+    def __init__(self, items, corpus, times=None, distance='cosine', floor=1e-6):
+        if distance not in DISTANCES:
+            raise ValueError('distance must be one of %s, not %r' % (DISTANCES, distance))
         from .dataloader import DeviceCorpus
+        self.distance = distance
         self.items = read_item_file(items) if isinstance(items, str) else items
         if isinstance(corpus, str):
             corpus, times = _read_h5features(corpus)
@@ -280,6 +363,7 @@ class ABXEvaluator(object):
             self.row[i], self.n[i] = r, n
         self.kept = np.flatnonzero(self.n > 0)
         self.dropped = [(int(i), self.items.describe(i)) for i in np.flatnonzero(self.n == 0)]
+        self.tables = kl_tables(corpus.table, floor) if distance == 'kl' else None
 
     def plan(self, mode):
         k = self.kept
@@ -290,15 +374,16 @@ class ABXEvaluator(object):
     def distances(self, plan):
         """d(P, Q) of every needed pair of `plan` (float64, device)."""
         P, Q = self.kept[plan.P], self.kept[plan.Q]
-        t = self.corpus.table
-        cost, plen = dtw_cost_batch(t, self.row[P], self.n[P], t, self.row[Q], self.n[Q])
+        t = self.tables if self.distance == 'kl' else self.corpus.table
+        cost, plen = dtw_cost_batch(t, self.row[P], self.n[P], t, self.row[Q], self.n[Q], distance=self.distance)
         ln = plen.cpu().numpy()
         bad = np.flatnonzero(ln <= 0)
         if len(bad):
             b = bad[0]
-            raise ValueError('ABX: the alignment of item %d (%s) with item %d (%s) was dropped (a NaN frame distance: '
-                             'identical or parallel frames, or non-finite values); %d pair(s) in all'
-                             % (P[b], self.items.describe(P[b]), Q[b], self.items.describe(Q[b]), len(bad)))
+            why = ('a frame with a non-finite or negative value' if self.distance == 'kl' else
+                   'a NaN frame distance: identical or parallel frames, or non-finite values')
+            raise ValueError('ABX: the alignment of item %d (%s) with item %d (%s) was dropped (%s); %d pair(s) in all'
+                             % (P[b], self.items.describe(P[b]), Q[b], self.items.describe(Q[b]), why, len(bad)))
         return cost / plen.to(torch.float64)
 
     def run(self, mode='within'):
@@ -310,7 +395,8 @@ class ABXEvaluator(object):
             score2 = count = np.zeros(0, dtype=np.int64)
         error, by_pair, cell_score = aggregate(plan.cells, score2, count)
         cells = [(key, int(n), sc) for key, n, sc in zip(plan.cells, count, cell_score)]
-        return ABXResult(mode, error, cells, by_pair, len(self.kept), len(plan.P), int(count.sum()), self.dropped)
+        return ABXResult(mode, error, cells, by_pair, len(self.kept), len(plan.P), int(count.sum()), self.dropped,
+                         self.distance)
 
 
 def main(argv=None):
@@ -318,8 +404,11 @@ def main(argv=None):
     ap.add_argument('features', help='h5features file of the embeddings')
     ap.add_argument('items', help='item file (#file onset offset #phone prev-phone next-phone speaker)')
     ap.add_argument('--mode', choices=MODES + ('both',), default='both')
+    ap.add_argument('--distance', choices=DISTANCES, default='cosine',
+                    help="frame distance: 'cosine' (embeddings) or 'kl' (posteriorgrams, symmetrised Kullback-Leibler)")
+    ap.add_argument('--floor', type=float, default=1e-6, help="floor of the probabilities under --distance kl")
     args = ap.parse_args(argv)
-    ev = ABXEvaluator(args.items, args.features)
+    ev = ABXEvaluator(args.items, args.features, distance=args.distance, floor=args.floor)
     for mode in (MODES if args.mode == 'both' else (args.mode,)):
         r = ev.run(mode)
         print('%s-speaker ABX error: %.3f %% (%d cells, %d triplets, %d items, %d dropped)'

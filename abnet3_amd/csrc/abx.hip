@@ -1,4 +1,4 @@
-// abx.hip -- the two kernels of the ABX evaluation (abnet3_amd/abx.py): DTW distances of token pairs without
+// abx.hip -- the kernels of the ABX evaluation (abnet3_amd/abx.py): DTW distances of token pairs without
 // paths, and the triplet scores of ABX cells.
 //
 // 1. dtw_cost_kernel (abn_dtw_cost_batched): for pair p, total_cost and path_len of the DTW alignment that
@@ -20,7 +20,16 @@
 //    ABN_DTW_COST_MAX_N2 columns; token 1 is unbounded.  Token-2 norms are computed once per pair (LDS), token-1
 //    norms once per band.  Frames are read from L1 / L2: no workspace, one launch.
 //
-// 2. abx_score_kernel (abn_abx_score): a ROW is one X of one ABX cell with its two lists of distances, d(A, X)
+//    The cell is a template parameter.  CELL_KL (abn_dtw_cost_kl_batched) is the symmetrised Kullback-Leibler
+//    divergence of two posteriorgram frames over the tables of abn_kl_tables (P = max(x, floor), L = log P):
+//    acc = acc + ((P_p[k] - P_q[k]) * (L_p[k] - L_q[k])) in ascending k, every operation rounded to float32 on its
+//    own (no fma: -ffp-contract=off), d = 0.5f * acc.  Every term is >= 0, so d >= 0 and d == 0 for identical
+//    frames.  Bands, rounds, the ring, the sweep and the boundary row are the cosine cell's; norms and their LDS do
+//    not exist, a pair with a BAD row (non-finite or negative input) is dropped before any cell is computed.
+//
+// 2. kl_tables_kernel (abn_kl_tables): P, L and the per-row BAD flag of a feature table, one wavefront per row.
+//
+// 3. abx_score_kernel (abn_abx_score): a ROW is one X of one ABX cell with its two lists of distances, d(A, X)
 //    over A and d(B, X) over B (contiguous ranges of the distance array).  One wavefront per row: each lane holds
 //    one d(B, X), the wavefront walks the d(A, X) and counts 2 per A closer than B and 1 per tie, as integers; the
 //    row's sum and its A x B triplet count go to the cell with int64 atomics (order-free: bit-identical results).
@@ -78,13 +87,63 @@ __device__ __forceinline__ void dot_tile(const float* __restrict__ x0, const flo
     acc[0] = a00; acc[1] = a01; acc[2] = a10; acc[3] = a11;
 }
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// the four symmetrised-KL sums of rows x0, x1 against rows y0, y1 (P and L tables): per k and cell a subtraction of
+// the P's, one of the L's, their product and the addition to the cell's sum, each rounded to float32 (the file is
+// compiled without fma contraction).  Two cells to a float2, so the compiler may issue v_pk_add_f32 / v_pk_mul_f32;
+// packed or not, every lane of every operation is the IEEE result.  The eight loads of a k step serve four cells.
 template <bool VEC>
+__device__ __forceinline__ void kl_tile(const float* __restrict__ px0, const float* __restrict__ px1,
+                                        const float* __restrict__ lx0, const float* __restrict__ lx1,
+                                        const float* __restrict__ py0, const float* __restrict__ py1,
+                                        const float* __restrict__ ly0, const float* __restrict__ ly1, int D, float (&acc)[4])
+{
+    f32x2 a0 = {0.0f, 0.0f}, a1 = {0.0f, 0.0f};        // (a00, a01), (a10, a11)
+#define ABN_KL_STEP(P0, P1, L0, L1, PU, PV, LU, LV)                                     \
+    do {                                                                                \
+        const f32x2 pu_ = {PU, PV}, lu_ = {LU, LV};                                     \
+        const f32x2 p0_ = {P0, P0}, l0_ = {L0, L0}, p1_ = {P1, P1}, l1_ = {L1, L1};     \
+        a0 = a0 + ((p0_ - pu_) * (l0_ - lu_));                                          \
+        a1 = a1 + ((p1_ - pu_) * (l1_ - lu_));                                          \
+    } while (0)
+    if (VEC) {
+        for (int k = 0; k < D; k += 4) {
+            const float4 p = *reinterpret_cast<const float4*>(px0 + k), q = *reinterpret_cast<const float4*>(px1 + k);
+            const float4 lp = *reinterpret_cast<const float4*>(lx0 + k), lq = *reinterpret_cast<const float4*>(lx1 + k);
+            const float4 u = *reinterpret_cast<const float4*>(py0 + k), v = *reinterpret_cast<const float4*>(py1 + k);
+            const float4 lu = *reinterpret_cast<const float4*>(ly0 + k), lv = *reinterpret_cast<const float4*>(ly1 + k);
+            ABN_KL_STEP(p.x, q.x, lp.x, lq.x, u.x, v.x, lu.x, lv.x);
+            ABN_KL_STEP(p.y, q.y, lp.y, lq.y, u.y, v.y, lu.y, lv.y);
+            ABN_KL_STEP(p.z, q.z, lp.z, lq.z, u.z, v.z, lu.z, lv.z);
+            ABN_KL_STEP(p.w, q.w, lp.w, lq.w, u.w, v.w, lu.w, lv.w);
+        }
+    } else {
+        for (int k = 0; k < D; ++k) ABN_KL_STEP(px0[k], px1[k], lx0[k], lx1[k], py0[k], py1[k], ly0[k], ly1[k]);
+    }
+#undef ABN_KL_STEP
+    acc[0] = a0.x; acc[1] = a0.y; acc[2] = a1.x; acc[3] = a1.y;
+}
+
+// what the KL cell reads beside the two P tables (feats1 / feats2 of the kernel); the cosine cell has nothing here
+template <bool KL>
+struct cell_extra {};
+template <>
+struct cell_extra<true> {
+    const float* L1;
+    const float* L2;
+    const uint8_t* bad1;
+    const uint8_t* bad2;
+};
+constexpr bool CELL_COSINE = false, CELL_KL = true;
+
+template <bool VEC, bool KL>
 __global__ __launch_bounds__(64) void dtw_cost_kernel(const float* __restrict__ feats1, int64_t rows1,
                                                       const float* __restrict__ feats2, int64_t rows2,
                                                       const int64_t* __restrict__ off1, const int32_t* __restrict__ n1,
                                                       const int64_t* __restrict__ off2, const int32_t* __restrict__ n2,
                                                       int64_t npairs, int D, double* __restrict__ total_cost,
-                                                      int32_t* __restrict__ path_len)
+                                                      int32_t* __restrict__ path_len, cell_extra<KL> ex)
 {
     __shared__ float ring[RD][CB];              // [diagonal % RD][row of the band]
     __shared__ double bnd_c[MAXN2];             // the band's last row: costs ...
@@ -107,15 +166,30 @@ __global__ __launch_bounds__(64) void dtw_cost_kernel(const float* __restrict__ 
         }
         const float* X = feats1 + o1 * D;
         const float* Y = feats2 + o2 * D;
-        for (int j = lane; j < M; j += CB) ny_s[j] = row_norm_numpy(Y + (int64_t)j * D, D);
         bool bad = false;
+        const float* LX = nullptr;
+        const float* LY = nullptr;
+        if constexpr (KL) {                                     // a BAD row in either token: the pair is dropped
+            for (int i = lane; i < N; i += CB) bad |= ex.bad1[o1 + i] != 0;
+            for (int j = lane; j < M; j += CB) bad |= ex.bad2[o2 + j] != 0;
+            if (__any(bad)) {
+                if (lane == 0) { path_len[p] = 0; total_cost[p] = 0.0; }
+                continue;
+            }
+            LX = ex.L1 + o1 * D;
+            LY = ex.L2 + o2 * D;
+        } else {
+            for (int j = lane; j < M; j += CB) ny_s[j] = row_norm_numpy(Y + (int64_t)j * D, D);
+        }
         double fin_c = 0.0;
         int fin_l = 0;
         for (int i0 = 0; i0 < N; i0 += CB) {
             const int nr = min(CB, N - i0);
             const bool feed = i0 + CB < N;                      // the last row goes to the band below
-            if (lane < nr) nx_s[lane] = row_norm_numpy(X + (int64_t)(i0 + lane) * D, D);
-            wave_lds_sync();
+            if constexpr (!KL) {
+                if (lane < nr) nx_s[lane] = row_norm_numpy(X + (int64_t)(i0 + lane) * D, D);
+                wave_lds_sync();
+            }
             // sweep state of row i0 + lane: p1 = its cost at the previous column, up_prev = the row above one
             // column back (= the diagonal neighbour of the next step); the virtual cell (-1, -1) costs 0
             double p1 = INF, up_prev = (i0 == 0 && lane == 0) ? 0.0 : INF;
@@ -131,17 +205,23 @@ __global__ __launch_bounds__(64) void dtw_cost_kernel(const float* __restrict__ 
                     const int tj = t / tr, ia = 2 * (t - tj * tr), ja = jlo + 2 * tj;
                     const int ib = min(ia + 1, nr - 1), jb = min(ja + 1, jhi - 1);
                     float dot[4];
-                    dot_tile<VEC>(X + (int64_t)(i0 + ia) * D, X + (int64_t)(i0 + ib) * D, Y + (int64_t)ja * D,
-                                  Y + (int64_t)jb * D, D, dot);
+                    const int64_t xa = (int64_t)(i0 + ia) * D, xb = (int64_t)(i0 + ib) * D;
+                    const int64_t ya = (int64_t)ja * D, yb = (int64_t)jb * D;
+                    if constexpr (KL) kl_tile<VEC>(X + xa, X + xb, LX + xa, LX + xb, Y + ya, Y + yb, LY + ya, LY + yb, D, dot);
+                    else dot_tile<VEC>(X + xa, X + xb, Y + ya, Y + yb, D, dot);
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const int il = c < 2 ? ia : ib, j = (c & 1) ? jb : ja, s = il + j;
                         if (s < s0 || s >= s0 + RD) continue;
-                        const float nx = nx_s[il], ny = ny_s[j];
-                        const float d = (norm_is_plain(nx) && norm_is_plain(ny)) ? angular_distance_ref<true>(dot[c], nx, ny)
-                                                                                 : angular_distance_ref<false>(dot[c], nx, ny);
-                        bad |= !(d >= 0.0f);                    // utils.py:59: the pair is dropped
-                        ring[s & (RD - 1)][il] = d;
+                        if constexpr (KL) {
+                            ring[s & (RD - 1)][il] = 0.5f * dot[c];
+                        } else {
+                            const float nx = nx_s[il], ny = ny_s[j];
+                            const float d = (norm_is_plain(nx) && norm_is_plain(ny)) ? angular_distance_ref<true>(dot[c], nx, ny)
+                                                                                     : angular_distance_ref<false>(dot[c], nx, ny);
+                            bad |= !(d >= 0.0f);                // utils.py:59: the pair is dropped
+                            ring[s & (RD - 1)][il] = d;
+                        }
                     }
                 }
                 wave_lds_sync();
@@ -188,6 +268,27 @@ __global__ __launch_bounds__(64) void dtw_cost_kernel(const float* __restrict__ 
             path_len[p] = dropped ? 0 : fin_l;
         }
         wave_lds_sync();                                        // ny_s / nx_s / the boundary row: the next pair's
+    }
+}
+
+// one wavefront per row: P = max(x, floor), L = float(log(double(P))), bad_row = a non-finite or negative x in the row
+__global__ __launch_bounds__(256) void kl_tables_kernel(const float* __restrict__ x, int64_t rows, int D, float floor_,
+                                                        float* __restrict__ P, float* __restrict__ L,
+                                                        uint8_t* __restrict__ bad_row)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < rows; r += waves) {
+        bool bad = false;
+        for (int k = lane; k < D; k += 64) {
+            const float v = x[r * D + k];
+            bad |= !(v >= 0.0f) || v == __builtin_inff();
+            const float pv = v > floor_ ? v : floor_;           // (NaN: the floor; the row is BAD anyway)
+            P[r * D + k] = pv;
+            L[r * D + k] = (float)log((double)pv);
+        }
+        const bool any = __any(bad);
+        if (lane == 0) bad_row[r] = any ? 1 : 0;
     }
 }
 
@@ -246,11 +347,48 @@ extern "C" int abn_dtw_cost_batched(const float* feats1, int64_t rows1, const fl
     const int64_t grid = npairs < 256 * 32 ? npairs : 256 * 32;
     const bool vec = D % 4 == 0 && aligned16(feats1) && aligned16(feats2);
     hipStream_t st = (hipStream_t)stream;
-    if (vec) hipLaunchKernelGGL(dtw_cost_kernel<true>, dim3((unsigned)grid), dim3(64), 0, st, feats1, rows1, feats2, rows2,
-                                off1, n1, off2, n2, npairs, (int)D, total_cost, path_len);
-    else hipLaunchKernelGGL(dtw_cost_kernel<false>, dim3((unsigned)grid), dim3(64), 0, st, feats1, rows1, feats2, rows2,
-                            off1, n1, off2, n2, npairs, (int)D, total_cost, path_len);
+    if (vec) hipLaunchKernelGGL((dtw_cost_kernel<true, CELL_COSINE>), dim3((unsigned)grid), dim3(64), 0, st, feats1, rows1, feats2, rows2,
+                                off1, n1, off2, n2, npairs, (int)D, total_cost, path_len, cell_extra<CELL_COSINE>());
+    else hipLaunchKernelGGL((dtw_cost_kernel<false, CELL_COSINE>), dim3((unsigned)grid), dim3(64), 0, st, feats1, rows1, feats2, rows2,
+                            off1, n1, off2, n2, npairs, (int)D, total_cost, path_len, cell_extra<CELL_COSINE>());
     ABN_CHECK_LAUNCH("dtw_cost");
+    return ABN_OK;
+}
+
+extern "C" int abn_kl_tables(const float* x, int64_t rows, int64_t D, float floor, float* P, float* L, uint8_t* bad_row,
+                             void* stream)
+{
+    ABN_REQUIRE(rows >= 0 && D >= 1 && D < (1 << 20), "kl_tables: bad rows/D");
+    ABN_REQUIRE(floor > 0.0f && floor < __builtin_inff(), "kl_tables: the floor must be a positive finite number");
+    if (rows == 0) return ABN_OK;
+    ABN_REQUIRE(x && P && L && bad_row, "kl_tables: null pointer");
+    ABN_REQUIRE(rows * D < (1LL << 62), "kl_tables: feature array too large");
+    const int64_t blocks = (rows + 3) / 4;
+    hipLaunchKernelGGL(kl_tables_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream,
+                       x, rows, (int)D, floor, P, L, bad_row);
+    ABN_CHECK_LAUNCH("kl_tables");
+    return ABN_OK;
+}
+
+extern "C" int abn_dtw_cost_kl_batched(const float* P1, const float* L1, int64_t rows1, const float* P2, const float* L2,
+                                       int64_t rows2, const int64_t* off1, const int32_t* n1, const int64_t* off2,
+                                       const int32_t* n2, int64_t npairs, int64_t D, const uint8_t* bad1,
+                                       const uint8_t* bad2, double* total_cost, int32_t* path_len, void* stream)
+{
+    ABN_REQUIRE(npairs >= 0 && D >= 1 && D < (1 << 20) && rows1 >= 0 && rows2 >= 0, "dtw_cost_kl: bad npairs/D/rows");
+    if (npairs == 0) return ABN_OK;
+    ABN_REQUIRE(P1 && L1 && P2 && L2 && bad1 && bad2 && off1 && n1 && off2 && n2 && total_cost && path_len,
+                "dtw_cost_kl: null pointer");
+    ABN_REQUIRE(rows1 * D < (1LL << 62) && rows2 * D < (1LL << 62), "dtw_cost_kl: feature array too large");
+    const int64_t grid = npairs < 256 * 32 ? npairs : 256 * 32;
+    const bool vec = D % 4 == 0 && aligned16(P1) && aligned16(L1) && aligned16(P2) && aligned16(L2);
+    hipStream_t st = (hipStream_t)stream;
+    const cell_extra<CELL_KL> ex = {L1, L2, bad1, bad2};
+    if (vec) hipLaunchKernelGGL((dtw_cost_kernel<true, CELL_KL>), dim3((unsigned)grid), dim3(64), 0, st, P1, rows1, P2, rows2,
+                                off1, n1, off2, n2, npairs, (int)D, total_cost, path_len, ex);
+    else hipLaunchKernelGGL((dtw_cost_kernel<false, CELL_KL>), dim3((unsigned)grid), dim3(64), 0, st, P1, rows1, P2, rows2,
+                            off1, n1, off2, n2, npairs, (int)D, total_cost, path_len, ex);
+    ABN_CHECK_LAUNCH("dtw_cost_kl");
     return ABN_OK;
 }
 

@@ -4,7 +4,10 @@
 Siamese training -> embedding -> ABX.  The corpus' word labels are used twice only, to report: the precision of the
 mined pairs, and the ABX item file ("phones" = word types).
 
-    python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr]
+    python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax]
+
+--softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
+error is printed under both frame distances, the angular cosine and the symmetrised Kullback-Leibler divergence.
 """
 import argparse
 import os
@@ -20,7 +23,7 @@ from abnet3_amd.dataloader import DeviceCorpus, PairsDataLoader   # noqa: E402
 from abnet3_amd.discovery import KnnPairMiner                     # noqa: E402
 from abnet3_amd.embedder import EmbedderSiamese                   # noqa: E402
 from abnet3_amd.features import FeaturesGenerator                 # noqa: E402
-from abnet3_amd.loss import coscos2                               # noqa: E402
+from abnet3_amd.loss import KLLoss, coscos2                       # noqa: E402
 from abnet3_amd.model import SiameseNetwork                       # noqa: E402
 from abnet3_amd.trainer import TrainerSiamese                     # noqa: E402
 from end_to_end import synth_corpus                               # noqa: E402
@@ -33,6 +36,7 @@ def main():
     ap.add_argument('--epochs', type=int, default=3)
     ap.add_argument('--min-similarity', type=float, default=0.8)
     ap.add_argument('--out', default='/tmp/abnet3_zr')
+    ap.add_argument('--softmax', action='store_true', help='softmax output + KLLoss; ABX under cosine and KL')
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     random.seed(0)
@@ -61,8 +65,10 @@ def main():
                          split_method='files')
     dl.set_data(fb, times)
     net = SiameseNetwork(input_dim=40, num_hidden_layers=1, hidden_dim=200, output_dim=40, p_dropout=0.0,
-                         activation_layer='sigmoid', output_path=args.out + '_network')
-    trainer = TrainerSiamese(network=net, loss=coscos2(avg=False), num_epochs=args.epochs, patience=30,
+                         activation_layer='sigmoid', output_path=args.out + '_network',
+                         last_non_linearity='softmax' if args.softmax else 'default')
+    trainer = TrainerSiamese(network=net, loss=KLLoss(avg=False) if args.softmax else coscos2(avg=False),
+                             num_epochs=args.epochs, patience=30,
                              optimizer_type='adadelta', lr=0.5, dataloader=dl, log_dir=args.out + '_runs')
     trainer.train()
     print('dev losses per epoch:', ['%.2f' % v for v in trainer.dev_losses])
@@ -74,8 +80,13 @@ def main():
     items = Items([t[0] for t in keep], [t[1] for t in keep], [t[2] for t in keep], ['w%d' % t[3] for t in keep],
                   ['-'] * len(keep), ['-'] * len(keep), ['spk'] * len(keep))
     for label, feats in (('filterbanks', fb), ('embeddings', dict(zip(names, emb)))):
-        r = ABXEvaluator(items, DeviceCorpus({k: np.asarray(feats[k], dtype=np.float32) for k in names}, times)).run('within')
-        print('ABX error on %s: %.2f %% (%d triplets)' % (label, r.error, r.n_triplets))
+        corpus = DeviceCorpus({k: np.asarray(feats[k], dtype=np.float32) for k in names}, times)
+        r = ABXEvaluator(items, corpus).run('within')
+        if args.softmax and label == 'embeddings':
+            kl = ABXEvaluator(items, corpus, distance='kl').run('within')
+            print('ABX error on %s: cosine %.2f %%, kl %.2f %% (%d triplets)' % (label, r.error, kl.error, r.n_triplets))
+        else:
+            print('ABX error on %s: %.2f %% (%d triplets)' % (label, r.error, r.n_triplets))
 
 
 if __name__ == '__main__':

@@ -527,6 +527,26 @@ int64_t abn_dtw_cost_max_n2(void);
 int abn_dtw_cost_batched(const float* feats1, int64_t rows1, const float* feats2, int64_t rows2,
                          const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
                          int64_t npairs, int64_t D, double* total_cost, int32_t* path_len, void* stream);
+/* The tables of the symmetrised Kullback-Leibler frame distance (ABX of posteriorgrams, abnet3_amd/abx.py; added
+ * within ABI 20: new symbols only).  x: [rows, D] fp32 on the device; floor > 0.  P[r, k] = max(x[r, k], floor),
+ * L[r, k] = (float)log((double)P[r, k]) (both [rows, D] fp32, no renormalisation); bad_row[r] (uint8 [rows], written
+ * for every row) = 1 when row r holds a non-finite or a negative value (the contents of its P / L rows are then
+ * unspecified), else 0.  Zeros are legal and are floored.  One launch on `stream`. */
+int abn_kl_tables(const float* x, int64_t rows, int64_t D, float floor, float* P, float* L,
+                  uint8_t* bad_row, void* stream);
+/* abn_dtw_cost_batched with the symmetrised Kullback-Leibler divergence as the frame distance: the same pair-table
+ * contract (device tables, a pair with a negative length, rows outside the tables or a token 2 of more than
+ * abn_dtw_cost_max_n2() frames is refused with path_len = -1, total_cost = 0 and nothing read; an empty token gives
+ * 0 and 0; one launch on `stream`, no workspace), the same float64 recurrence, tie-break and carried path length.  The
+ * cell of frames p (token 1) and q (token 2) over abn_kl_tables' P and L tables, in fp32 without fused multiply-add,
+ * in ascending k: acc = acc + ((P_p[k] - P_q[k]) * (L_p[k] - L_q[k])), d = 0.5f * acc -- d >= 0 always, d == 0 for
+ * identical frames.  bad1 / bad2: abn_kl_tables' row flags ([rows1] / [rows2]); a pair with a flagged row in either
+ * token is dropped: path_len = 0, total_cost = 0.  There is no second kernel for longer tokens 2. */
+int abn_dtw_cost_kl_batched(const float* P1, const float* L1, int64_t rows1, const float* P2,
+                            const float* L2, int64_t rows2, const int64_t* off1, const int32_t* n1,
+                            const int64_t* off2, const int32_t* n2, int64_t npairs, int64_t D,
+                            const uint8_t* bad1, const uint8_t* bad2, double* total_cost,
+                            int32_t* path_len, void* stream);
 /* ABX triplet scores (abnet3_amd/abx.py).  Row r is one X of ABX cell row_cell[r]: the distances d(A, X) over its A
  * are dist[a_off[r] .. a_off[r] + a_len[r]), the d(B, X) over its B dist[b_off[r] .. b_off[r] + b_len[r]) (device
  * arrays, dist: [ndist] f64).  For every cell c: score2[c] = the sum over its rows and their A x B triplets of 2 when

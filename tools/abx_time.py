@@ -8,9 +8,21 @@ with prototype trajectories (4 anchor frames, linearly interpolated) plus noise 
   abn_dtw_batched          utils.dtw_align_batch on the same pairs (paths + traceback; the same costs, checked bit for bit)
   C oracle                 oracle/dtw_oracle.dtw_batch(..., threads=16) on the same pairs (the same DP on the CPU)
 
+--distance kl times the symmetrised Kullback-Leibler route on the same set pushed through a row softmax (posteriorgrams):
+
+  both modes end to end    ABXEvaluator(distance='kl').run, wall time and phases as above
+  abn_kl_tables            the P / L / BAD tables of the whole corpus alone
+  abn_dtw_cost_kl_batched  the KL instantiation of the cost kernel alone on the within-speaker mode's pairs
+  abn_dtw_cost_batched     the cosine instantiation on the same pair table of the same posteriorgrams, in the same run
+  torch                    what a user could write before: the frame-distance matrices alone (no DTW) of the same pairs as
+                           a chunked torch expression on the GPU, pairs bucketed by (n1, n2) so that nothing is padded
+  --parent-lib FILE        the cosine kernel of another build of the library (the parent commit's), timed alternately
+                           with this build's on the same pairs
+
 Every GPU route settles the clock (untimed calls for 0.3 s) before its timed calls; medians are reported.
-python tools/abx_time.py [--items N] [--out FILE]"""
+python tools/abx_time.py [--items N] [--distance cosine|kl] [--parent-lib FILE] [--out FILE]"""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -80,23 +92,13 @@ def wall(fn):
     return time.perf_counter() - t0, out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--items', type=int, default=6000)
-    ap.add_argument('--calls', type=int, default=3)
-    ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                                  'profiles', 'abx_time.json'))
-    a = ap.parse_args()
-    items, feats, times, n_spk = synthetic(a.items)
-    ev = ABXEvaluator(items, feats, times)
-    res = {'device': torch.cuda.get_device_name(0),
-           'set': '%d items, 40 phones, D = 100, %d speakers, 9 contexts, 3-30 frames per item' % (len(items), n_spk),
-           'modes': {}}
-    plans = {}
+def time_modes(ev, calls):
+    """({mode: figures}, {mode: plan}) of ABXEvaluator.run and its phases."""
+    out, plans = {}, {}
     for mode in ('within', 'across'):
         r = ev.run(mode)                                     # warm
         walls = []
-        for _ in range(a.calls):
+        for _ in range(calls):
             s, r2 = wall(lambda: ev.run(mode))
             walls.append(s)
             assert r2.error == r.error
@@ -104,10 +106,146 @@ def main():
         t_dist, dist = wall(lambda: ev.distances(plan))
         t_score, _ = wall(lambda: abx_score(dist, plan))
         plans[mode] = plan
-        res['modes'][mode] = {'error_percent': r.error, 'cells': len(r.cells), 'pairs': r.n_pairs, 'triplets': r.n_triplets,
-                              'end_to_end_s_median': round(float(np.median(walls)), 4),
-                              'phase_s': {'host_enumeration': round(t_plan, 4), 'distances': round(t_dist, 4),
-                                          'scoring': round(t_score, 4)}}
+        out[mode] = {'error_percent': r.error, 'cells': len(r.cells), 'pairs': r.n_pairs, 'triplets': r.n_triplets,
+                     'end_to_end_s_median': round(float(np.median(walls)), 4),
+                     'phase_s': {'host_enumeration': round(t_plan, 4), 'distances': round(t_dist, 4),
+                                 'scoring': round(t_score, 4)}}
+    return out, plans
+
+
+def torch_buckets(off1, n1, off2, n2, chunk=2048):
+    """Device row indices ([c, n1], [c, n2]) of the pairs, bucketed by (n1, n2), at most `chunk` pairs each."""
+    key = n1.astype(np.int64) * 100000 + n2
+    order = np.argsort(key, kind='stable')
+    cuts = np.flatnonzero(np.diff(key[order])) + 1
+    out = []
+    for idx in np.split(order, cuts):
+        a, b = int(n1[idx[0]]), int(n2[idx[0]])
+        for c0 in range(0, len(idx), chunk):
+            sub = idx[c0:c0 + chunk]
+            out.append((torch.from_numpy(off1[sub, None] + np.arange(a)[None, :]).cuda(),
+                        torch.from_numpy(off2[sub, None] + np.arange(b)[None, :]).cuda()))
+    return out
+
+
+def torch_frame_distances(P, L, buckets):
+    """The symmetrised-KL frame-distance matrices of every pair (no DTW), as torch expressions; their sum."""
+    total = torch.zeros((), dtype=torch.float64, device=P.device)
+    for r1, r2 in buckets:
+        d = 0.5 * ((P[r1][:, :, None, :] - P[r2][:, None, :, :]) * (L[r1][:, :, None, :] - L[r2][:, None, :, :])).sum(-1)
+        total += d.sum(dtype=torch.float64)
+    return total
+
+
+def main_kl(a):
+    items, feats, times, n_spk = synthetic(a.items)
+    post = {k: torch.softmax(torch.from_numpy(v), dim=1).numpy() for k, v in feats.items()}
+    ev = ABXEvaluator(items, post, times, distance='kl')
+    res = {'device': torch.cuda.get_device_name(0),
+           'set': '%d items, 40 phones, D = 100, %d speakers, 9 contexts, 3-30 frames per item; row softmax of the '
+                  'features' % (len(items), n_spk),
+           'distance': 'kl', 'floor': 1e-6}
+    res['modes'], plans = time_modes(ev, a.calls)
+    wplan = plans['within']
+    P, Q = ev.kept[wplan.P], ev.kept[wplan.Q]
+    off1, n1, off2, n2 = ev.row[P], ev.n[P], ev.row[Q], ev.n[Q]
+    table = ev.corpus.table
+    tabs = ev.tables
+    lib = _lib.load()
+    dev = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).cuda()
+    d_tab = [dev(off1, np.int64), dev(n1, np.int32), dev(off2, np.int64), dev(n2, np.int32)]
+    npairs, rows, D = len(P), table.shape[0], table.shape[1]
+    cost = torch.empty(npairs, dtype=torch.float64, device='cuda')
+    plen = torch.empty(npairs, dtype=torch.int32, device='cuda')
+    ccost, cplen = torch.empty_like(cost), torch.empty_like(plen)
+
+    def kl_kernel():
+        _lib.check(lib.abn_dtw_cost_kl_batched(_lib.ptr(tabs.P), _lib.ptr(tabs.L), rows, _lib.ptr(tabs.P), _lib.ptr(tabs.L), rows,
+                                               *[_lib.ptr(t) for t in d_tab], npairs, D, _lib.ptr(tabs.bad), _lib.ptr(tabs.bad),
+                                               _lib.ptr(cost), _lib.ptr(plen), _lib.stream()), 'abn_dtw_cost_kl_batched')
+
+    def cosine_args():
+        return [_lib.ptr(table), rows, _lib.ptr(table), rows] + [_lib.ptr(t) for t in d_tab] + [
+            npairs, D, _lib.ptr(ccost), _lib.ptr(cplen), _lib.stream()]
+
+    def cosine_kernel():
+        _lib.check(lib.abn_dtw_cost_batched(*cosine_args()), 'abn_dtw_cost_batched')
+
+    P2, L2, bad2 = torch.empty_like(table), torch.empty_like(table), torch.empty(rows, dtype=torch.uint8, device='cuda')
+
+    def tables_kernel():
+        _lib.check(lib.abn_kl_tables(_lib.ptr(table), rows, D, 1e-6, _lib.ptr(P2), _lib.ptr(L2), _lib.ptr(bad2), _lib.stream()),
+                   'abn_kl_tables')
+
+    buckets = torch_buckets(off1, n1, off2, n2)
+    holder = {}
+
+    def torch_route():
+        holder['sum'] = torch_frame_distances(tabs.P, tabs.L, buckets)
+
+    cells = int(np.dot(n1.astype(np.int64), n2.astype(np.int64)))
+    kl_ms = median_ms(kl_kernel)
+    cos_ms = median_ms(cosine_kernel)
+    tab_ms = median_ms(tables_kernel)
+    torch_ms = median_ms(torch_route, calls=3)
+    kl_ms2 = median_ms(kl_kernel)
+    rate = lambda ms: {'pairs_per_s': round(npairs / (ms * 1e-3), 1), 'cells_per_s': round(cells / (ms * 1e-3), 1)}
+    res['kernels_on_within_pairs'] = {
+        'pairs': npairs, 'cells': cells, 'mean_cells_per_pair': round(cells / max(npairs, 1), 2), 'table_rows': rows,
+        'abn_dtw_cost_kl_batched_ms': round(kl_ms, 4), 'abn_dtw_cost_kl_batched_ms_again': round(kl_ms2, 4),
+        'abn_dtw_cost_batched_ms_same_pairs': round(cos_ms, 4), 'kl_over_cosine': round(kl_ms / cos_ms, 3),
+        'abn_kl_tables_ms': round(tab_ms, 4),
+        'torch_frame_distances_ms': round(torch_ms, 3),
+        'torch_frame_distances_is': 'frame-distance matrices alone (no DTW), %d bucketed torch expressions' % len(buckets),
+        'torch_over_kl_kernel': round(torch_ms / kl_ms, 2),
+        'kl_kernel': rate(kl_ms), 'cosine_kernel': rate(cos_ms),
+        'pairs_dropped': int((plen <= 0).sum().item())}
+    if a.parent_lib:
+        # the cosine instantiation of this build against another build's, alternating, on the same pairs
+        parent = ctypes.CDLL(os.path.abspath(a.parent_lib))
+        fn = parent.abn_dtw_cost_batched
+        fn.restype, fn.argtypes = lib.abn_dtw_cost_batched.restype, lib.abn_dtw_cost_batched.argtypes
+        pcost = torch.empty_like(ccost)
+
+        def parent_kernel():
+            args = cosine_args()
+            args[-3] = _lib.ptr(pcost)
+            assert fn(*args) == 0
+
+        this, other = [], []
+        for _ in range(4):
+            this.append(round(median_ms(cosine_kernel), 4))
+            other.append(round(median_ms(parent_kernel), 4))
+        torch.cuda.synchronize()
+        res['cosine_kernel_vs_parent_build'] = {
+            'this_build_ms': this, 'parent_build_ms': other,
+            'ratio_of_medians': round(float(np.median(this) / np.median(other)), 4),
+            'costs_bit_identical': bool(torch.equal(ccost.view(torch.int64), pcost.view(torch.int64)))}
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as fh:
+            fh.write(json.dumps(res, indent=1) + '\n')
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--items', type=int, default=6000)
+    ap.add_argument('--calls', type=int, default=3)
+    ap.add_argument('--distance', choices=('cosine', 'kl'), default='cosine')
+    ap.add_argument('--parent-lib', default=None, help='--distance kl: another build of the library to time the cosine kernel of')
+    ap.add_argument('--out', default=None, help='default: profiles/abx_time.json, profiles/abx_kl_time.json under --distance kl')
+    a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                             'abx_kl_time.json' if a.distance == 'kl' else 'abx_time.json')
+    if a.distance == 'kl':
+        return main_kl(a)
+    items, feats, times, n_spk = synthetic(a.items)
+    ev = ABXEvaluator(items, feats, times)
+    res = {'device': torch.cuda.get_device_name(0),
+           'set': '%d items, 40 phones, D = 100, %d speakers, 9 contexts, 3-30 frames per item' % (len(items), n_spk)}
+    res['modes'], plans = time_modes(ev, a.calls)
     # the kernels alone, on the within-speaker pairs
     wplan = plans['within']
     P, Q = ev.kept[wplan.P], ev.kept[wplan.Q]
