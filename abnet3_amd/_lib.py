@@ -110,6 +110,7 @@ SYMBOLS = {
     'abn_knn_ws_bytes': (_i64, [_i64, _i64, C.c_int]),
     'abn_knn_topk': (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _i64, _vp]),
     'abn_segment_vectors': (C.c_int, [_vp, _i64, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp]),
+    'abn_sample_pairs': (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_int, _vp]),
 }
 # abn_integrate_forward / _backward (include/abnet3_hip.h)
 INTEGRATE_MODE = {'sum': 0, 'concat': 1}
@@ -130,6 +131,14 @@ class TowerDesc(C.Structure):
 class StepSource(C.Structure):
     """abn_step_source (include/abnet3_hip.h): a pass's batches as the plan holds them, for steps that need no gather launch."""
     _fields_ = [('table', _vp), ('table_rows', _i64), ('idx1', _vp), ('idx2', _vp), ('labels', _vp), ('steps', _vp), ('step_ctr', _vp)]
+
+
+class SamplerTables(C.Structure):
+    """struct abn_sampler_tables (abn_sample_pairs' tables; abnet3_amd/sampler.py fills it)"""
+    POINTERS = ('spk_t', 'type_t', 'type_beg', 'f_t', 'cum_u_t', 'cum_f_t', 'tok_beg', 'toks',
+                'spk_s', 'type_s', 's2t', 'spk_beg', 'u_s', 'cum_u_s', 'cum_spk', 'cum_m')
+    _fields_ = [('n_cells', _i32), ('n_spk', _i32), ('n_type', _i32), ('n_tok', _i32), ('total', C.c_uint64 * 4)] + [
+        (name, _vp) for name in POINTERS]
 
 
 class OneShotCtx(C.Structure):

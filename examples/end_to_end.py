@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """End-to-end run of the accelerated hot path on a synthetic ZeroSpeech-shaped
 corpus (BASELINE.json configs[4]): wav -> log-mel filterbanks (HIP) -> mean /
-variance normalisation -> 7-frame stacking -> word pairs -> DTW frame alignment
+variance normalisation -> 7-frame stacking -> word clusters (.classes) -> sampled
+word pairs (SamplerClusterSiamese, HIP) -> DTW frame alignment
 (HIP, batched) -> Siamese training (HIP) -> embedding.  Everything stays in
 memory (the reference's h5features files are third-party I/O and out of scope).
 
@@ -23,13 +24,15 @@ from abnet3_amd.embedder import EmbedderSiamese                   # noqa: E402
 from abnet3_amd.features import FeaturesGenerator                 # noqa: E402
 from abnet3_amd.loss import coscos2                               # noqa: E402
 from abnet3_amd.model import SiameseNetwork                       # noqa: E402
+from abnet3_amd.sampler import SamplerClusterSiamese              # noqa: E402
 from abnet3_amd.trainer import TrainerSiamese                     # noqa: E402
+from abnet3_amd.utils import read_dataset                         # noqa: E402
 
 
 def synth_corpus(n_utts, n_words, rng, fs=16000):
     """Utterances = concatenated 'words'; a word type is a fixed formant track
     plus noise, so same-type tokens are acoustically close (what term discovery
-    clusters give the reference's sampler)."""
+    clusters give the sampler)."""
     word_len = rng.uniform(0.3, 0.8, n_words)
     formants = rng.uniform(300, 3000, (n_words, 3))
     wavs, tokens = {}, []                                   # tokens: (utt, start, end, word)
@@ -48,24 +51,22 @@ def synth_corpus(n_utts, n_words, rng, fs=16000):
     return wavs, tokens
 
 
-def sample_pairs(tokens, n_pairs, rng):
+def write_clusters(tokens, folder, n_speakers=4):
+    """The corpus' word tokens as the sampler's two input files: a .classes file (one cluster per word type:
+    "Class <id>", a "<file> <onset> <offset>" line per token, a blank line) and a "<file> <speaker>" list
+    (utterance u belongs to speaker u mod n_speakers)."""
+    os.makedirs(folder, exist_ok=True)
     by_word = {}
-    for tok in tokens:
-        by_word.setdefault(tok[3], []).append(tok)
-    words = [w for w, v in by_word.items() if len(v) >= 2]
-    pairs = []
-    while len(pairs) < n_pairs:
-        if len(pairs) % 2 == 0:
-            w = words[rng.integers(len(words))]
-            i, j = rng.choice(len(by_word[w]), 2, replace=False)
-            a, b, kind = by_word[w][i], by_word[w][j], 'same'
-        else:
-            w1, w2 = rng.choice(words, 2, replace=False)
-            a = by_word[w1][rng.integers(len(by_word[w1]))]
-            b = by_word[w2][rng.integers(len(by_word[w2]))]
-            kind = 'diff'
-        pairs.append((a[0], a[1], a[2], b[0], b[1], b[2], kind))
-    return pairs
+    for utt, on, off, w in tokens:
+        by_word.setdefault(w, []).append((utt, on, off))
+    std_file, spkid_file = os.path.join(folder, 'words.classes'), os.path.join(folder, 'wav2spk.lst')
+    with open(std_file, 'w') as fh:
+        for w in sorted(by_word):
+            fh.write('Class %d\n' % w + ''.join('%s %.2f %.2f\n' % tok for tok in by_word[w]) + '\n')
+    with open(spkid_file, 'w') as fh:
+        for utt in sorted(set(tok[0] for tok in tokens)):
+            fh.write('%s spk%d\n' % (utt, int(utt[3:]) % n_speakers))
+    return std_file, spkid_file
 
 
 def main():
@@ -94,10 +95,18 @@ def main():
     times = {k: np.arange(len(v)) * 0.01 + 0.0025 for k, v in feats.items()}
     t['normalise+stack'] = time.perf_counter() - t0
 
-    pairs = sample_pairs(tokens, args.pairs, rng)
-    split = int(0.7 * len(pairs))
+    # word clusters -> train_pairs / dev_pairs: the reference's sampler stage, pairs drawn on the GPU
+    t0 = time.perf_counter()
+    std_file, spkid_file = write_clusters(tokens, args.out + '_clusters_rank%d' % rank)
+    pairs_dir = args.out + '_pairs_rank%d' % rank             # (seeded: every rank writes the same files)
+    SamplerClusterSiamese(std_file=std_file, spkid_file=spkid_file, directory_output=pairs_dir,
+                          num_total_sampled_pairs=args.pairs, ratio_same_diff_spk=0.5, max_size_cluster=20).sample()
+    train_pairs = read_dataset(os.path.join(pairs_dir, 'train_pairs', 'dataset'))
+    dev_pairs = read_dataset(os.path.join(pairs_dir, 'dev_pairs', 'dataset'))
+    pairs = train_pairs + dev_pairs
+    t['sample pairs'] = time.perf_counter() - t0
     dl = FramesDataLoader('unused', 'unused', batch_size=args.batch)
-    dl.set_data(feats, times, pairs[:split], pairs[split:])
+    dl.set_data(feats, times, train_pairs, dev_pairs)
     t0 = time.perf_counter()
     np.random.seed(0)
     dl.load_data()                                   # batched DTW alignment of all 'same' pairs

@@ -741,6 +741,53 @@ int abn_knn_topk(const float* Q, int64_t nq, const float* C, int64_t nc, int d,
 int abn_segment_vectors(const float* table, int64_t D, const int64_t* seg_row0, const int32_t* seg_len,
                         int64_t nseg, int K, float* out, uint8_t* keep, void* stream);
 
+/* Pair sampling from word clusters (abnet3/sampler.py:404-688 without its K^2 table; added within ABI 20, backward
+ * compatible).  A CELL is a (speaker, word type) with at least one token.  The tables are O(cells + tokens) and
+ * hold the cells twice, sorted by (type, speaker) -- "T order" -- and by (speaker, type) -- "S order"; all weights
+ * are integers (abnet3_amd/sampler.py builds them and states what they quantise):
+ *   u = g(tokens of the type) f(tokens of the cell), sum over all cells < 2^32;  f = f(tokens of the cell),
+ *   sum over the cells of any one type < 2^32.
+ * cum_* are INCLUSIVE running sums over the whole order.  cum_m[q] is the running sum of configuration q's
+ * first-cell marginal (q = 0, 1 in T order, q = 2, 3 in S order), total[q] its last entry (0: empty support):
+ *   0 Stype_Sspk  u [tokens >= 2]                        2 Dtype_Sspk  u (U_speaker - u)
+ *   1 Stype_Dspk  u (F_type - f)                         3 Dtype_Dspk  u (U - U_speaker - U_type + u)
+ * All pointers are device pointers. */
+typedef struct abn_sampler_tables {
+    int32_t n_cells, n_spk, n_type, n_tok;
+    uint64_t total[4];
+    /* T order */
+    const int32_t* spk_t;      /* [n_cells] speaker index */
+    const int32_t* type_t;     /* [n_cells] type index */
+    const int32_t* type_beg;   /* [n_type + 1] first cell of each type */
+    const uint32_t* f_t;       /* [n_cells] */
+    const uint64_t* cum_u_t;   /* [n_cells] */
+    const uint64_t* cum_f_t;   /* [n_cells] */
+    const int32_t* tok_beg;    /* [n_cells + 1] first token of each cell in toks */
+    const int32_t* toks;       /* [n_tok] token ids, cell after cell */
+    /* S order */
+    const int32_t* spk_s;      /* [n_cells] */
+    const int32_t* type_s;     /* [n_cells] */
+    const int32_t* s2t;        /* [n_cells] the cell's index in T order */
+    const int32_t* spk_beg;    /* [n_spk + 1] first cell of each speaker */
+    const uint32_t* u_s;       /* [n_cells] */
+    const uint64_t* cum_u_s;   /* [n_cells] */
+    const uint64_t* cum_spk;   /* [n_spk] running sum of the speakers' totals of u */
+    const uint64_t* cum_m;     /* [4][n_cells] */
+} abn_sampler_tables;
+
+/* Draws n[q] pairs of configuration q = 0 .. 3 in ONE launch, one lane per pair; pair i of configuration q is
+ * element n[0] + .. + n[q-1] + i of tok1 / tok2 (int32 token ids; -1 where total[q] == 0) and of key (a 63-bit
+ * shuffle key: the caller orders the lines by ascending key, ties by index).  Every random number is
+ * Philox4x32-10 with key (seed low, seed high) and counter (i low, i high, q, slot): slot 0 the first cell, 1 the
+ * second cell, 2 the two tokens, 3 the shuffle key -- the output does not depend on `block`, the workgroup size (a
+ * multiple of 64 in 64 .. 1024).  A 128-bit draw r is mapped onto a range M < 2^64 as floor(r M / 2^128); the
+ * first cell comes from cum_m[q], the second by binary searches in the running sums with the excluded cell /
+ * speaker / type cut out (no rejection, every loop is a binary search).  Different-type pairs come lower type
+ * index first.  ABN_E_ARG before any launch for null pointers, sizes out of range (1 <= n_cells < 2^24,
+ * n[q] >= 0, sum n < 2^31) or a bad `block`. */
+int abn_sample_pairs(const abn_sampler_tables* tables, const int64_t* n, uint64_t seed, int32_t* tok1,
+                     int32_t* tok2, int64_t* key, int block, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

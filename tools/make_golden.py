@@ -52,6 +52,15 @@ Fixture sets:
                   id_to_file map.  split_method='files' calls random.sample on a SET (dataloader.py:484), a TypeError
                   from Python 3.11 on: for those cases only, random.sample is given sorted(set) instead (the
                   population abnet3_amd's class samples from), after random.seed(seed); the seed is recorded
+  G15 sampler     SamplerClusterSiamese (abnet3/sampler.py) on three cluster files under tests/golden/sampler/: the
+                  reference's own test/data/english.test.classes and english.split.test.classes (copied as data, with
+                  the speaker map of its test/test_sampler.py written as a spkid file) and a hand-made one (6 speakers,
+                  12 types, 60 tokens, no two speakers sharing two types: asserted) and a second hand-made one with exactly one
+                  colliding quadruple beside collision-free keys.  Recorded per file: the outputs of
+                  parse_input_file, split_each_file, analyze_clusters, generate_token_dict; the keys and probabilities
+                  of type_speaker_sampling_p in four mode pairs; the four per-configuration counts of sample_batch for
+                  several num_samples and ratios (observed as the lengths of what it returns, on the hand-made file);
+                  and the sampler section of test/data/buckeye.yaml
 
 usage: python tools/make_golden.py [--only G1,G3]
 """
@@ -1214,10 +1223,139 @@ def g14_pairs_loader(abnet3):
         fh.write('\n')
 
 
+# G15's hand-made clusters: (speakers of the type, tokens per cell).  Every two speakers share at most one type.
+SMALL_SPEAKERS = ('A', 'B', 'C', 'D', 'E', 'F')
+SMALL_TYPES = [('AB', (4, 3)), ('AC', (1, 5)), ('AD', (3, 1)), ('BC', (2, 2)), ('BD', (6, 1)), ('CD', (1, 2)),
+               ('AEF', (2, 3, 1)), ('BE', (4, 2)), ('CF', (1, 3)), ('DE', (2, 1)), ('D', (4,)), ('F', (6,))]
+SAMPLER_MODES = (('log', 'log'), ('f', 'f'), ('f2', '1'), ('1', '1'))
+SAMPLER_COUNT_CASES = [(10, 0.75, 0.5), (10.0, 0.75, 0.5), (45.0, 0.75, 0.5), (5012, 0.75, 0.5), (1000, 0.5, 0.5),
+                       (999, 0.3, 0.7), (7, 0.75, 0.5), (350000, 0.5, 0.5), (101, 0.66, 0.33), (3.0, 0.75, 0.5)]
+
+
+# G15's second hand-made set: speakers A and B share types 0 and 1 (one colliding quadruple); the keys with C are free
+COLLIDE_TYPES = [('AB', (2, 1)), ('AB', (1, 3)), ('CA', (2, 1)), ('C', (3,))]
+
+
+def write_collide_clusters(dst):
+    lines = []
+    for t, (speakers, sizes) in enumerate(COLLIDE_TYPES):
+        lines.append('%d word%02d' % (t, t))
+        for spk, size in zip(speakers, sizes):
+            lines += ['%s0 %.3f %.3f' % (spk.lower(), 1.0 + 2 * t + 0.5 * k, 1.25 + 2 * t + 0.5 * k) for k in range(size)]
+        lines.append('')
+    with open(os.path.join(dst, 'collide.classes'), 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+    with open(os.path.join(dst, 'collide.spkid'), 'w') as fh:
+        fh.write(''.join('%s0 %s\n' % (spk.lower(), spk) for spk in 'ABC'))
+
+
+def write_small_clusters(dst):
+    """The hand-made cluster file and its speaker map: two files per speaker, tokens one after the other."""
+    clock = {}
+    lines, n_tok = [], 0
+    for t, (speakers, sizes) in enumerate(SMALL_TYPES):
+        lines.append('%d word%02d' % (t, t))
+        for spk, size in zip(speakers, sizes):
+            for k in range(size):
+                fid = '%s%d' % (spk.lower(), (t + k) % 2)
+                t0 = clock.get(fid, 0.5)
+                dur = 0.25 + 0.05 * ((3 * t + k) % 7)
+                lines.append('%s %.3f %.3f' % (fid, t0, t0 + dur))
+                clock[fid] = t0 + dur + 0.125
+                n_tok += 1
+        lines.append('')
+    assert n_tok == 60 and len(SMALL_TYPES) == 12
+    with open(os.path.join(dst, 'small.classes'), 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+    with open(os.path.join(dst, 'small.spkid'), 'w') as fh:
+        for spk in SMALL_SPEAKERS:
+            for k in range(2):
+                fh.write('%s%d %s\n' % (spk.lower(), k, spk))
+
+
+def g15_sampler(abnet3):
+    """G15: the reference's sampler on its own two cluster files and on a hand-made, collision-free one."""
+    import contextlib
+    import io
+    import json
+    import shutil
+    import yaml
+    import abnet3.sampler
+    from abnet3.utils import cumulative_distribution, read_spkid_file
+    dst = os.path.join(OUT, 'sampler')
+    os.makedirs(dst, exist_ok=True)
+    for f in ('english.test.classes', 'english.split.test.classes'):
+        shutil.copyfile(os.path.join(REF, 'test', 'data', f), os.path.join(dst, f))
+    # the speaker map of the reference's test/test_sampler.py:70-81, as the file read_spkid_file reads
+    english = {'s0101a': 1, 's0102a': 1, 's2001a': 20, 's2401a': 24, 's2402b': 24, 's2403b': 24, 's2404b': 24,
+               's2405b': 24, 's2403a': 24, 's2702a': 27}
+    with open(os.path.join(dst, 'english.spkid'), 'w') as fh:
+        for fid, spk in english.items():
+            fh.write('%s %d\n' % (fid, spk))
+    write_small_clusters(dst)
+    write_collide_clusters(dst)
+    plain = lambda v: v.item() if hasattr(v, 'item') else v
+    record = {'modes': [list(m) for m in SAMPLER_MODES], 'fixtures': {}}
+    arrays = {}
+    for name, classes, spkid in (('english', 'english.test.classes', 'english.spkid'),
+                                 ('english_split', 'english.split.test.classes', 'english.spkid'),
+                                 ('small', 'small.classes', 'small.spkid'),
+                                 ('collide', 'collide.classes', 'collide.spkid')):
+        sam = abnet3.sampler.SamplerClusterSiamese()
+        spk_of = read_spkid_file(os.path.join(dst, spkid))
+        with contextlib.redirect_stdout(io.StringIO()):
+            clusters = sam.parse_input_file(os.path.join(dst, classes))
+            sam.spkid_from_file = spk_of
+            train, dev = sam.split_each_file(clusters)
+            descr = sam.analyze_clusters(clusters, spk_of)
+            token_dict = sam.generate_token_dict(descr)
+            for tm, sm in SAMPLER_MODES:
+                p = sam.type_speaker_sampling_p(std_descr=descr, type_sampling_mode=tm, spk_sampling_mode=sm)
+                if name == 'small':
+                    assert all(p[cfg] for cfg in p), (tm, sm)
+                for cfg, table in p.items():          # (the tables go to probabilities.npz: keys joined with '|')
+                    tag = '%s/%s,%s/%s' % (name, tm, sm, cfg)
+                    arrays[tag + '/keys'] = np.array(['|'.join(str(plain(k)) for k in key) for key in table], dtype=str)
+                    arrays[tag + '/p'] = np.array(list(table.values()), dtype=np.float64)
+        cells = set(zip(descr['tokens_speaker'], descr['tokens_type']))
+        speakers, types = sorted(set(s for s, t in cells)), sorted(set(t for s, t in cells))
+        quads = [(s, s2, i, j) for s in speakers for s2 in speakers if s < s2 for i in types for j in types if i < j
+                 and {(s, i), (s, j), (s2, i), (s2, j)} <= cells]
+        if name == 'collide':
+            assert len(quads) == 1, quads
+        if name == 'small':
+            assert not quads, quads
+            assert len(speakers) == 6 and len(descr['types']) == 12 and len(descr['tokens']) == 60
+        fx = {'classes': classes, 'spkid': spkid, 'ratio_train_dev': sam.ratio_train_dev, 'clusters': clusters,
+              'split_each_file': {'train': train, 'dev': dev},
+              'descr': {k: ({str(a): int(b) for a, b in v.items()} if isinstance(v, dict) else
+                            [plain(x) for x in v]) for k, v in descr.items()},
+              'token_dict': [[int(t), str(s), [int(i) for i in ids]] for (t, s), ids in token_dict.items()],
+              'n_colliding_quadruples': len(quads)}
+        if name == 'small':
+            counts = []
+            p = sam.type_speaker_sampling_p(std_descr=descr, type_sampling_mode='1', spk_sampling_mode='1')
+            cdf = {k: cumulative_distribution(v) for k, v in p.items()}
+            for num, r_spk, r_type in SAMPLER_COUNT_CASES:
+                sam.ratio_same_diff_spk, sam.ratio_same_diff_type = r_spk, r_type
+                with contextlib.redirect_stdout(io.StringIO()):
+                    drawn = sam.sample_batch(p, cdf, token_dict, num_samples=num)
+                counts.append({'num_samples': num, 'ratio_same_diff_spk': r_spk, 'ratio_same_diff_type': r_type,
+                               'counts': {cfg: len(v) for cfg, v in drawn.items()}})
+            fx['sample_batch_counts'] = counts
+        record['fixtures'][name] = fx
+    with open(os.path.join(REF, 'test', 'data', 'buckeye.yaml')) as fh:
+        record['buckeye_sampler'] = yaml.safe_load(fh)['default_params']['sampler']
+    np.savez_compressed(os.path.join(dst, 'probabilities.npz'), **arrays)
+    with open(os.path.join(dst, 'reference.json'), 'w') as fh:
+        json.dump(record, fh, separators=(',', ':'), sort_keys=True)
+        fh.write('\n')
+
+
 ALL = {'G1': g1_tower, 'G2': g2_train_c1, 'G3': g3_loss_edge,
        'G4': g4_train_mid, 'G5': g5_cosdist, 'G6': g6_stack, 'G7': g7_frames,
        'G8': g8_multitask, 'G5L': g5l_cosdist_libm, 'G9': g9_frames_loader, 'G10': g10_mvn, 'G11': g11_gridsearch,
-       'G12': g12_kl_loss, 'G13': g13_multimodal, 'G14': g14_pairs_loader}
+       'G12': g12_kl_loss, 'G13': g13_multimodal, 'G14': g14_pairs_loader, 'G15': g15_sampler}
 
 
 def main():
