@@ -111,6 +111,8 @@ SYMBOLS = {
     'abn_knn_topk': (C.c_int, [_vp, _i64, _vp, _i64, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _i64, _vp]),
     'abn_segment_vectors': (C.c_int, [_vp, _i64, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp]),
     'abn_sample_pairs': (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_int, _vp]),
+    'abn_tcl_pairs': (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.c_int, C.c_int, _i64, _i64, C.c_uint64, C.c_uint32, _vp, _vp,
+                                _vp, _vp, C.c_int, _i64, _vp]),
 }
 # abn_integrate_forward / _backward (include/abnet3_hip.h)
 INTEGRATE_MODE = {'sum': 0, 'concat': 1}

@@ -14,6 +14,7 @@
 // binary search whose trip count is bounded by the table sizes; there is no rejection and no retry.  The kernel is
 // latency-bound on dependent loads from tables that sit in L2: small register footprint, full occupancy, no LDS.
 #include "common.h"
+#include "philox.h"
 
 namespace abn {
 
@@ -24,28 +25,7 @@ struct SamplerP {
     int32_t* tok1; int32_t* tok2; int64_t* key;
 };
 
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{c0, c1, c2, c3};
-}
-
-// floor(r M / 2^128) for the 128-bit r = (x + 2^32 y) 2^64 + (z + 2^32 w): a value in [0, M), each with
-// floor(2^128 / M) or one more of the 2^128 values of r
-__device__ __forceinline__ uint64_t map128(U4 r, uint64_t M)
-{
-    const uint64_t rh = ((uint64_t)r.y << 32) | r.x, rl = ((uint64_t)r.w << 32) | r.z;
-    const uint64_t lo = rh * M, s = lo + __umul64hi(rl, M);
-    return __umul64hi(rh, M) + (s < lo ? 1 : 0);
-}
+// (philox4x32_10 and map128: philox.h, shared with tcl.hip)
 
 // first index in [lo, hi) whose running sum exceeds x (hi if none)
 __device__ __forceinline__ int upper_u64(const uint64_t* __restrict__ cum, int lo, int hi, uint64_t x)

@@ -235,7 +235,7 @@ class OriginalDataLoader(DataLoader):
     def __init__(self, pairs_path, features_path, num_max_minibatches=1000,
                  seed=None, batch_size=8, shuffle_between_epochs=False,
                  align_different_words=False,
-                 tcl=0.0):
+                 tcl=0.0, tcl_seed=None):
         assert 0 <= tcl < 1
         self.pairs_path = pairs_path
         self.features_path = features_path
@@ -247,6 +247,10 @@ class OriginalDataLoader(DataLoader):
         self.shuffle_between_epochs = shuffle_between_epochs
         self.align_different_words = align_different_words
         self.tcl = tcl
+        # None: the temporal-coherence pairs are drawn per batch from `random`, like the reference's; an integer: on the
+        # device by abn_tcl_pairs with this seed, for the whole pass at once (plan(True) then has the mixed batches)
+        self.tcl_seed = tcl_seed
+        self.tcl_epoch = 0            # passes drawn so far: the generator's epoch word
         self.train_files = None
         self.pairs = {'train': None, 'dev': None}
         self._align = AlignCache()    # (f1,s1,e1,f2,s2,e2,frames) -> (idx1, idx2) | None
@@ -494,6 +498,11 @@ class OriginalDataLoader(DataLoader):
     def batch_iterator(self, train_mode=True):
         """Iterator over (X1, X2, y) batches of `batch_size` WORD pairs
         (dataloader.py:263-312)."""
+        if train_mode and self._tcl_on_device():
+            plan = self.plan(True)           # the pass's temporal-coherence pairs are drawn at once: the plan's batches
+            for b in plan.order:
+                yield plan.materialise(b)
+            return
         self.load_data()
         mode = 'train' if train_mode else 'dev'
         pairs = self.pairs[mode]
@@ -632,8 +641,10 @@ class OriginalDataLoader(DataLoader):
 
     def plan(self, train_mode=True):
         """batch_iterator(train_mode) as a BatchPlan (same batches, same order, same draws from the global
-        RNGs), or None where only the iterator applies (temporal-coherence pairs are drawn per batch)."""
-        if self.tcl > 0:
+        RNGs), or None where only the iterator applies (temporal-coherence pairs drawn per batch from `random`).
+        With tcl > 0 and a tcl_seed the training pass has a plan: every batch is the tcl = 0 plan's batch followed by
+        its temporal-coherence pairs, drawn for the whole pass by one abn_tcl_pairs launch (_tcl_mix)."""
+        if self.tcl > 0 and not (train_mode and self._tcl_on_device()):
             return None
         self.load_data()
         mode = 'train' if train_mode else 'dev'
@@ -651,6 +662,8 @@ class OriginalDataLoader(DataLoader):
             # (np.random.seed(0); np.random.permutation(n), dataloader.py:248-249): so does the plan
             np.random.seed(0)
             np.random.permutation(int(offsets[order[-1] + 1] - offsets[order[-1]]))
+        if self.tcl > 0:
+            i1, i2, y, offsets = self._tcl_mix((i1, i2, y, offsets))
         return BatchPlan(self.features.table, i1, i2, y, offsets, order, has_arrays)
 
     @staticmethod
@@ -707,6 +720,159 @@ class OriginalDataLoader(DataLoader):
         return (gather_rows(c.table, torch.tensor(i1, dtype=torch.int64, device=dev)),
                 gather_rows(c.table, torch.tensor(i2, dtype=torch.int64, device=dev)),
                 torch.tensor(Y, device=dev))
+
+    # -- temporal-coherence pairs drawn on the device (abn_tcl_pairs) ------------------------------------------
+    def _tcl_on_device(self):
+        return self.tcl > 0 and getattr(self, 'tcl_seed', None) is not None
+
+    @classmethod
+    def tcl_iterations(cls, num_pairs):
+        """Draws that temporal_coherence_loss(num_pairs) makes (dataloader.py:332-333; Python's round): each gives
+        len(TCL_DISTANCE_SAME) + len(TCL_DISTANCES_DIFF) frame pairs."""
+        return round(num_pairs / (len(cls.TCL_DISTANCES_DIFF) + len(cls.TCL_DISTANCE_SAME)))
+
+    def tcl_pairs_to_add(self, num_pairs):
+        """Frame pairs add_tcl_to_batch asks for behind a batch of num_pairs (dataloader.py:317)."""
+        return int((self.tcl * num_pairs) / (1 - self.tcl))
+
+    def _tcl_tables(self):
+        """The files the device draw picks from, as device tables (first table row, frames) and the host copy of the
+        lengths: train_files when the pairs are loaded, else every file, sorted by name.  A file of at most
+        max(TCL_DISTANCES_DIFF) frames has no frame t with t + max in it (the reference's random.choice(range(<= 0))
+        raises when such a file is drawn): it is left out, with one warning."""
+        c = self.features
+        deltas = list(self.TCL_DISTANCE_SAME) + list(self.TCL_DISTANCES_DIFF)
+        max_diff = max(self.TCL_DISTANCES_DIFF)
+        if max(self.TCL_DISTANCE_SAME) > max_diff:
+            raise ValueError('temporal coherence: max(TCL_DISTANCE_SAME) = %d exceeds max(TCL_DISTANCES_DIFF) = %d'
+                             % (max(self.TCL_DISTANCE_SAME), max_diff))
+        files = self.train_files if self.train_files is not None else c.names
+        names = sorted({c._name(f) for f in files}, key=lambda k: k.decode('UTF-8') if isinstance(k, bytes) else str(k))
+        key = (id(c), tuple(names), tuple(deltas))
+        tab = getattr(self, '_tcl_tab', None)
+        if tab is not None and tab['key'] == key:
+            return tab
+        keep = [k for k in names if c.length[k] > max_diff]
+        if len(keep) < len(names) and not getattr(self, '_tcl_warned', False):
+            import warnings
+            self._tcl_warned = True
+            warnings.warn('temporal coherence: %d of %d files have at most %d frames and are left out of the draw'
+                          % (len(names) - len(keep), len(names), max_diff))
+        if not keep:
+            raise ValueError('temporal coherence: no file has more than %d frames' % max_diff)
+        host = np.array([[c.offset[k] for k in keep], [c.length[k] for k in keep]], dtype=np.int64)
+        dev = torch.from_numpy(host).to(c.table.device)
+        tab = self._tcl_tab = dict(key=key, names=keep, host=host, dev=dev, deltas=np.array(deltas, dtype=np.int32),
+                                   n_same=len(self.TCL_DISTANCE_SAME))
+        return tab
+
+    def _tcl_fill(self, n_iter, epoch, idx1, idx2, labels, dst=None, first_iter=0):
+        """One abn_tcl_pairs launch: iterations first_iter .. first_iter + n_iter - 1 of pass `epoch`, written into
+        idx1 / idx2 / labels at dst[i] (packed when dst is None)."""
+        tab = self._tcl_tables()
+        lib = _lib.load()
+        _lib.require_device(idx1, idx2, labels, dst)
+        assert idx1.dtype == torch.int64 and idx2.dtype == torch.int64 and labels.dtype in (torch.int64, torch.float64)
+        assert idx1.numel() == idx2.numel() == labels.numel() and (dst is None or (dst.dtype == torch.int64 and dst.numel() >= n_iter))
+        host, dev, deltas = tab['host'], tab['dev'], tab['deltas']
+        _lib.check(lib.abn_tcl_pairs(_lib.ptr(dev[0]), _lib.ptr(dev[1]), host[1].ctypes.data, host.shape[1],
+                                     deltas.ctypes.data, len(deltas), tab['n_same'], int(n_iter), int(first_iter),
+                                     int(self.tcl_seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, _lib.ptr(dst),
+                                     _lib.ptr(idx1), _lib.ptr(idx2), _lib.ptr(labels), int(labels.dtype == torch.float64),
+                                     idx1.numel(), _lib.stream()), 'abn_tcl_pairs')
+
+    def _tcl_mix(self, store):
+        """The tcl = 0 plan's arrays with every batch's temporal-coherence pairs behind its word pairs: batch b of n
+        frame pairs gets 5 * round(int(tcl n / (1 - tcl)) / 5) more (add_tcl_to_batch, dataloader.py:314-322; labels
+        float64 as np.concatenate makes them).  The arrays persist -- the word-pair part is copied once per store, the
+        drawn part is refilled in place by one launch per pass, so the addresses a trainer's captured steps hold stay
+        valid from epoch to epoch."""
+        i1, i2, y, offsets = store
+        mix = getattr(self, '_tcl_mixed', None)
+        if mix is None or mix['src'][0] is not i1 or mix['src'][1] is not offsets:
+            dev = i1.device
+            per_it = len(self.TCL_DISTANCE_SAME) + len(self.TCL_DISTANCES_DIFF)
+            n_b = np.diff(offsets).astype(np.int64)
+            its = np.array([self.tcl_iterations(self.tcl_pairs_to_add(int(n))) for n in n_b], dtype=np.int64)
+            new_off = np.concatenate(([0], np.cumsum(n_b + per_it * its))).astype(np.int64)
+            total, n_iter = int(new_off[-1]), int(its.sum())
+            # where the word pairs go (one index for all batches), and where each iteration's pairs start
+            head = np.repeat(new_off[:-1] - offsets[:-1], n_b) + np.arange(int(offsets[-1]), dtype=np.int64)
+            k = np.arange(n_iter, dtype=np.int64) - np.repeat(np.cumsum(its) - its, its)
+            dst = np.repeat(new_off[:-1] + n_b, its) + per_it * k
+            up = torch.from_numpy(np.concatenate((head, dst))).to(dev)
+            head_d, dst_d = up[:head.size], up[head.size:].contiguous()
+            m1 = torch.zeros(total, dtype=torch.int64, device=dev)
+            m2 = torch.zeros(total, dtype=torch.int64, device=dev)
+            my = torch.zeros(total, dtype=torch.float64, device=dev)
+            m1[head_d], m2[head_d], my[head_d] = i1, i2, y.to(torch.float64)
+            mix = self._tcl_mixed = dict(src=(i1, offsets), idx1=m1, idx2=m2, labels=my, offsets=new_off, dst=dst_d, n_iter=n_iter)
+        if mix['n_iter']:
+            self._tcl_fill(mix['n_iter'], self.tcl_epoch, mix['idx1'], mix['idx2'], mix['labels'], dst=mix['dst'])
+        self.tcl_epoch += 1
+        return mix['idx1'], mix['idx2'], mix['labels'], mix['offsets']
+
+
+class TemporalCoherenceDataLoader(OriginalDataLoader):
+    """Temporal-coherence pairs only (abnet3/dataloader.py:549-577; Dupoux & Synnaeve 2016): a training pass is
+    num_max_minibatches batches of round(batch_size / 5) draws -- a random file, a random frame t, the 'same' pair
+    (t, t + 1) and the 'diff' pairs (t, t + 15 / 20 / 25 / 30) --, no word pairs, no DTW; the sampled dev pairs serve
+    evaluation and early stopping as in OriginalDataLoader.
+
+    The reference draws with Python's `random` in a host loop.  Here a whole pass is drawn by ONE abn_tcl_pairs launch
+    (Philox4x32-10 keyed by `seed`, counter = (iteration, epoch): reproducible, independent of `random`) into
+    persistent index arrays, which plan(True) hands out as a BatchPlan: the trainer's captured steps read their batch
+    from them and survive from epoch to epoch, every epoch with fresh pairs.  The batches the iterator or
+    materialise() yield are views of these arrays: the next training pass overwrites them.
+    Files of at most max(TCL_DISTANCES_DIFF) frames are left out of the draw (the reference crashes when it draws one).
+    As in the reference, self.batch_size ends up as `batch_size`, so the dev batches hold batch_size WORD pairs;
+    test_words_batch_size is accepted and has no effect."""
+
+    def __init__(self, pairs_path, features_path, batch_size=500,
+                 test_words_batch_size=8,
+                 num_max_minibatches=1000, seed=0):
+        super().__init__(pairs_path, features_path,
+                         num_max_minibatches=num_max_minibatches,
+                         batch_size=test_words_batch_size)
+        self.batch_size = batch_size
+        self.seed = seed
+        self.tcl_seed = seed
+        self._tcl_arrays = None
+
+    def _tcl_on_device(self):
+        return False                       # (tcl = 0: the dev pass is OriginalDataLoader's)
+
+    def _train_plan(self):
+        self.load_data()
+        per_it = len(self.TCL_DISTANCE_SAME) + len(self.TCL_DISTANCES_DIFF)
+        its = self.tcl_iterations(self.batch_size)
+        nb = int(self.num_max_minibatches)
+        total = nb * its * per_it
+        self._tcl_tables()                 # (raises before anything is allocated when no file is eligible)
+        dev = self.features.table.device
+        a = self._tcl_arrays
+        if a is None or a[0].numel() != total or a[0].device != dev:
+            a = self._tcl_arrays = tuple(torch.zeros(total, dtype=torch.int64, device=dev) for _ in range(3))
+        # every rank draws the whole pass (one launch) and visits its share of the batches: r, r + R, ...
+        self._tcl_fill(nb * its, self.tcl_epoch, a[0], a[1], a[2])
+        self.tcl_epoch += 1
+        rank, ws = parallel.world()
+        order = parallel.shard_ids(list(range(nb)), rank, ws, equal=True)
+        offsets = np.arange(nb + 1, dtype=np.int64) * (its * per_it)
+        return BatchPlan(self.features.table, a[0], a[1], a[2], offsets, order)
+
+    def plan(self, train_mode=True):
+        if train_mode:
+            return self._train_plan()
+        return super().plan(False)
+
+    def batch_iterator(self, train_mode=True):
+        if train_mode:
+            plan = self._train_plan()
+            for b in plan.order:
+                yield plan.materialise(b)
+        else:
+            yield from super().batch_iterator(False)
 
 
 class FramesDataLoader(OriginalDataLoader):

@@ -4,10 +4,14 @@
 Siamese training -> embedding -> ABX.  The corpus' word labels are used twice only, to report: the precision of the
 mined pairs, and the ABX item file ("phones" = word types).
 
-    python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax]
+    python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl]
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
 error is printed under both frame distances, the angular cosine and the symmetrised Kullback-Leibler divergence.
+--tcl skips the discovery step altogether: TemporalCoherenceDataLoader trains on temporal-coherence pairs (a frame and
+its neighbour against frames 15-30 steps away, drawn on the GPU), and the dev pairs that early stopping needs are made
+the same way from the last fifth of the files -- a stretch of frames against itself one frame later ("same") and
+against a stretch of another file ("diff").
 """
 import argparse
 import os
@@ -19,7 +23,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from abnet3_amd.abx import ABXEvaluator, Items                    # noqa: E402
-from abnet3_amd.dataloader import DeviceCorpus, PairsDataLoader   # noqa: E402
+from abnet3_amd.dataloader import DeviceCorpus, PairsDataLoader, TemporalCoherenceDataLoader   # noqa: E402
 from abnet3_amd.discovery import KnnPairMiner                     # noqa: E402
 from abnet3_amd.embedder import EmbedderSiamese                   # noqa: E402
 from abnet3_amd.features import FeaturesGenerator                 # noqa: E402
@@ -27,6 +31,31 @@ from abnet3_amd.loss import KLLoss, coscos2                       # noqa: E402
 from abnet3_amd.model import SiameseNetwork                       # noqa: E402
 from abnet3_amd.trainer import TrainerSiamese                     # noqa: E402
 from end_to_end import synth_corpus                               # noqa: E402
+
+
+def tcl_loader(fb, times, rng, stretch=12):
+    """TemporalCoherenceDataLoader over the first four fifths of the files; label-free dev pairs from the rest."""
+    names = sorted(fb)
+    cut = max(1, len(names) * 4 // 5)
+    held = [k for k in names[cut:] if len(fb[k]) > 2 * stretch] or names[:1]
+
+    def stretch_of(k, shift=0):
+        a = int(rng.integers(0, len(fb[k]) - stretch - 1)) if shift == 0 else shift
+        return a, (k, float(times[k][a]), float(times[k][a + stretch - 1]))
+    dev = []
+    for i in range(64):
+        k = held[i % len(held)]
+        a, tok = stretch_of(k)
+        if i % 2 == 0:
+            dev.append(tok + stretch_of(k, a + 1)[1] + ('same',))
+        else:
+            dev.append(tok + stretch_of(held[(i + 1 + int(rng.integers(len(held)))) % len(held)])[1] + ('diff',))
+    # (the train "pairs" only name the files that train: this loader never reads their tokens)
+    train = [(k, 0.0, 0.1, k, 0.0, 0.1, 'diff') for k in names[:cut]]
+    dl = TemporalCoherenceDataLoader(None, None, batch_size=500, num_max_minibatches=200, seed=0)
+    dl.set_data(fb, times, train, dev)
+    print('temporal coherence: %d files train, %d dev pairs from %d held-out files' % (cut, len(dev), len(held)))
+    return dl
 
 
 def main():
@@ -37,6 +66,7 @@ def main():
     ap.add_argument('--min-similarity', type=float, default=0.8)
     ap.add_argument('--out', default='/tmp/abnet3_zr')
     ap.add_argument('--softmax', action='store_true', help='softmax output + KLLoss; ABX under cosine and KL')
+    ap.add_argument('--tcl', action='store_true', help='no mined pairs: train on temporal-coherence pairs')
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     random.seed(0)
@@ -48,22 +78,25 @@ def main():
     fb, _ = fg.normalize_features({k: fg.fbank_from_samples(v, 16000).cpu().numpy() for k, v in wavs.items()})
     times = {k: np.arange(len(v)) * 0.01 + 0.0125 for k, v in fb.items()}
 
-    miner = KnnPairMiner(fb, times, min_similarity=args.min_similarity)
-    pairs_path, map_path = miner.write(args.out + '_mined')
-    a, b, sim = miner.pairs
+    if args.tcl:
+        dl = tcl_loader(fb, times, rng)
+    else:
+        miner = KnnPairMiner(fb, times, min_similarity=args.min_similarity)
+        pairs_path, map_path = miner.write(args.out + '_mined')
+        a, b, sim = miner.pairs
 
-    def word_at(seg):
-        name = miner.names[miner.seg_file[seg]]
-        lo, hi = miner.seg_begin[seg] * 0.01, (miner.seg_begin[seg] + miner.seg_len[seg]) * 0.01
-        best = max((min(hi, t[2]) - max(lo, t[1]), t[3]) for t in tokens if t[0] == name)
-        return best[1] if best[0] >= 0.5 * (hi - lo) else -1
-    hits = [word_at(x) == word_at(y) != -1 for x, y in zip(a[:500], b[:500])]
-    print('%d segments, %d mined pairs; %.1f %% of the top %d join two tokens of one word'
-          % (miner.table.shape[0], len(a), 100 * np.mean(hits) if hits else 0.0, len(hits)))
+        def word_at(seg):
+            name = miner.names[miner.seg_file[seg]]
+            lo, hi = miner.seg_begin[seg] * 0.01, (miner.seg_begin[seg] + miner.seg_len[seg]) * 0.01
+            best = max((min(hi, t[2]) - max(lo, t[1]), t[3]) for t in tokens if t[0] == name)
+            return best[1] if best[0] >= 0.5 * (hi - lo) else -1
+        hits = [word_at(x) == word_at(y) != -1 for x, y in zip(a[:500], b[:500])]
+        print('%d segments, %d mined pairs; %.1f %% of the top %d join two tokens of one word'
+              % (miner.table.shape[0], len(a), 100 * np.mean(hits) if hits else 0.0, len(hits)))
 
-    dl = PairsDataLoader(pairs_path, None, map_path, batch_size=8, train_iterations=200, test_iterations=50,
-                         split_method='files')
-    dl.set_data(fb, times)
+        dl = PairsDataLoader(pairs_path, None, map_path, batch_size=8, train_iterations=200, test_iterations=50,
+                             split_method='files')
+        dl.set_data(fb, times)
     net = SiameseNetwork(input_dim=40, num_hidden_layers=1, hidden_dim=200, output_dim=40, p_dropout=0.0,
                          activation_layer='sigmoid', output_path=args.out + '_network',
                          last_non_linearity='softmax' if args.softmax else 'default')

@@ -788,6 +788,28 @@ typedef struct abn_sampler_tables {
 int abn_sample_pairs(const abn_sampler_tables* tables, const int64_t* n, uint64_t seed, int32_t* tok1,
                      int32_t* tok2, int64_t* key, int block, void* stream);
 
+/* ---- temporal-coherence pairs (abnet3/dataloader.py:324-352; added within ABI 20) -------------------------------
+ * Draws the temporal-coherence pairs of a pass in ONE launch, one lane per iteration, into the index arrays of a
+ * batch plan.  Iteration i = 0 .. n_iter - 1 draws a file f uniformly among n_files -- file f = rows
+ * file_row0[f] .. file_row0[f] + file_len[f] - 1 of the corpus table -- and a frame t uniformly in
+ * [0, file_len[f] - max(deltas)), and writes n_deltas consecutive elements from dst[i] on (n_deltas * i when dst is
+ * NULL):  idx1 = file_row0[f] + t,  idx2 = file_row0[f] + t + deltas[j],  labels = +1 for j < n_same, -1 after --
+ * int64, or float64 when labels_f64 is not 0.  An iteration whose elements would not lie inside [0, out_len), the
+ * length of idx1 / idx2 / labels, writes nothing.
+ * The draw is one Philox4x32-10 call with key (seed low, seed high) and counter (g low, g high, epoch, 'TCL1' =
+ * 0x54434C31), g = first_iter + i the iteration's index in the whole pass: a rank's share, launched with its
+ * first_iter, reproduces its slice of the single-process pass.  Words 0, 1 of the output, as a 64-bit r, give
+ * f = floor(r n_files / 2^64); words 2, 3 give t the same way.  Integer arithmetic only, no rejection.
+ * file_row0 / file_len / dst / idx1 / idx2 / labels are device pointers; deltas (n_deltas values) and
+ * file_len_host (the n_files values of file_len) are HOST arrays read during the call.  ABN_E_ARG before any
+ * launch for n_files < 1, n_deltas outside 1 .. 16, n_same outside 0 .. n_deltas, a negative delta, a file with
+ * file_len <= max(deltas), negative counts, null pointers, or (dst NULL) n_deltas * n_iter > out_len.
+ * n_iter == 0 launches nothing. */
+int abn_tcl_pairs(const int64_t* file_row0, const int64_t* file_len, const int64_t* file_len_host,
+                  int64_t n_files, const int32_t* deltas, int n_deltas, int n_same, int64_t n_iter,
+                  int64_t first_iter, uint64_t seed, uint32_t epoch, const int64_t* dst, int64_t* idx1,
+                  int64_t* idx2, void* labels, int labels_f64, int64_t out_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
