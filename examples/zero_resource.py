@@ -4,7 +4,7 @@
 Siamese training -> embedding -> ABX.  The corpus' word labels are used twice only, to report: the precision of the
 mined pairs, and the ABX item file ("phones" = word types).
 
-    python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl]
+    python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
 error is printed under both frame distances, the angular cosine and the symmetrised Kullback-Leibler divergence.
@@ -12,6 +12,8 @@ error is printed under both frame distances, the angular cosine and the symmetri
 its neighbour against frames 15-30 steps away, drawn on the GPU), and the dev pairs that early stopping needs are made
 the same way from the last fifth of the files -- a stretch of frames against itself one frame later ("same") and
 against a stretch of another file ("diff").
+--qbe adds query-by-example search after the embedding (abnet3_amd/qbe.py): the first token of a few word types is
+searched in every utterance by subsequence DTW, and the mean average precision of the rankings is printed.
 """
 import argparse
 import os
@@ -58,6 +60,24 @@ def tcl_loader(fb, times, rng, stretch=12):
     return dl
 
 
+def qbe_search(corpus, tokens, names, label, distance, n_queries=8):
+    """Query by example: the first token of each of a few word types is searched in every utterance; an utterance is
+    relevant when it holds a token of the query's word (the query's own utterance included: it has to find itself)."""
+    from abnet3_amd.qbe import QbeSearcher, max_query, mean_average_precision, precision_at_n
+    first = {}
+    for t in tokens:
+        if t[3] not in first and corpus.token(t[0], t[1], t[2])[1] <= max_query():
+            first[t[3]] = t
+    queries = [first[w] for w in sorted(first)][:n_queries]
+    res = QbeSearcher(corpus, distance=distance).search([(t[0], t[1], t[2]) for t in queries])
+    holds = {(t[3], t[0]) for t in tokens}
+    relevant = np.array([[(q[3], k) in holds for k in names] for q in queries])
+    own = [res.ranking(i)[0] == names.index(q[0]) for i, q in enumerate(queries)]
+    print('query by example on %s (%s): %d queries x %d utterances, MAP %.3f, P@N %.3f, %d of %d queries rank their own '
+          'utterance first' % (label, distance, len(queries), len(names), mean_average_precision(res.score, relevant),
+                               precision_at_n(res.score, relevant), sum(own), len(own)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--utts', type=int, default=40)
@@ -67,6 +87,7 @@ def main():
     ap.add_argument('--out', default='/tmp/abnet3_zr')
     ap.add_argument('--softmax', action='store_true', help='softmax output + KLLoss; ABX under cosine and KL')
     ap.add_argument('--tcl', action='store_true', help='no mined pairs: train on temporal-coherence pairs')
+    ap.add_argument('--qbe', action='store_true', help='after embedding: search a few planted words by example, print MAP')
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     random.seed(0)
@@ -120,6 +141,8 @@ def main():
             print('ABX error on %s: cosine %.2f %%, kl %.2f %% (%d triplets)' % (label, r.error, kl.error, r.n_triplets))
         else:
             print('ABX error on %s: %.2f %% (%d triplets)' % (label, r.error, r.n_triplets))
+        if args.qbe:
+            qbe_search(corpus, keep, names, label, 'kl' if args.softmax and label == 'embeddings' else 'cosine')
 
 
 if __name__ == '__main__':

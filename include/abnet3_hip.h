@@ -547,6 +547,37 @@ int abn_dtw_cost_kl_batched(const float* P1, const float* L1, int64_t rows1, con
                             const int64_t* off2, const int32_t* n2, int64_t npairs, int64_t D,
                             const uint8_t* bad1, const uint8_t* bad2, double* total_cost,
                             int32_t* path_len, void* stream);
+/* Subsequence DTW for query-by-example search (abnet3_amd/qbe.py; added within ABI 20: new symbols only).  The pair
+ * table lives on the DEVICE: pair p aligns ALL of query rows [q_off[p], q_off[p]+q_n[p]) of qry with ANY contiguous run
+ * of utterance rows [u_off[p], u_off[p]+u_n[p]) of utt ([rows, D] fp32).  Cells: abn_dtw_cost_batched's angular
+ * distance, except that no pair is dropped: a NaN cell with a finite dot product and a finite non-zero product of
+ * the norms is |cos| rounded above 1 and counts 0 (dot > 0) or 1 (dot < 0); any other NaN cell is blocked (+inf).
+ * Recurrence: float64, cost = d + min(diag, up, left), first minimum in that order, length and start row carried along
+ * the chosen predecessor; in query column 0 the diagonal predecessor of every utterance row i is a virtual cell of
+ * cost 0, length 0 and start i, and there is no left predecessor.  Result: among the utterance rows i whose cell in the
+ * last query column is finite, the first that minimises cost / length (float64): total_cost[p], path_len[p], start[p],
+ * end[p] = i (utterance-relative, inclusive).  No such row: path_len = 0, total_cost = 0, start = end = -1; the same
+ * for an empty query or utterance.  A pair with a negative length, rows outside the tables, a query of more than
+ * abn_dtw_search_max_query() frames or profile entries outside [0, prof_rows) is refused: path_len = -1,
+ * total_cost = 0, start = end = -1, nothing is read and no profile entry is written.  The utterance has no limit.
+ * Profile (prof_cost == NULL: none; else all four pointers): for utterance row i of pair p, entry prof_off[p] + i of
+ * prof_cost / prof_len / prof_start ([prof_rows]) holds the row's cell of the last query column: cost, length, start;
+ * +inf, 0, -1 where it is not finite.  One launch on `stream`, no workspace. */
+#define ABN_DTW_SEARCH_MAX_QUERY 256
+int64_t abn_dtw_search_max_query(void);
+int abn_dtw_search_batched(const float* utt, int64_t rows_u, const float* qry, int64_t rows_q,
+                           const int64_t* u_off, const int32_t* u_n, const int64_t* q_off, const int32_t* q_n,
+                           int64_t npairs, int64_t D, double* total_cost, int32_t* path_len, int32_t* start,
+                           int32_t* end, const int64_t* prof_off, int64_t prof_rows, double* prof_cost,
+                           int32_t* prof_len, int32_t* prof_start, void* stream);
+/* abn_dtw_search_batched over the symmetrised Kullback-Leibler cell of abn_dtw_cost_kl_batched (abn_kl_tables' P, L
+ * and row flags of each side).  A cell that touches a flagged row is blocked (+inf); the pair is kept. */
+int abn_dtw_search_kl_batched(const float* PU, const float* LU, int64_t rows_u, const float* PQ, const float* LQ,
+                              int64_t rows_q, const int64_t* u_off, const int32_t* u_n, const int64_t* q_off,
+                              const int32_t* q_n, int64_t npairs, int64_t D, const uint8_t* bad_u,
+                              const uint8_t* bad_q, double* total_cost, int32_t* path_len, int32_t* start,
+                              int32_t* end, const int64_t* prof_off, int64_t prof_rows, double* prof_cost,
+                              int32_t* prof_len, int32_t* prof_start, void* stream);
 /* ABX triplet scores (abnet3_amd/abx.py).  Row r is one X of ABX cell row_cell[r]: the distances d(A, X) over its A
  * are dist[a_off[r] .. a_off[r] + a_len[r]), the d(B, X) over its B dist[b_off[r] .. b_off[r] + b_len[r]) (device
  * arrays, dist: [ndist] f64).  For every cell c: score2[c] = the sum over its rows and their A x B triplets of 2 when
