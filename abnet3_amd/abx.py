@@ -205,6 +205,37 @@ def _dev(a, dtype):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
 
 
+def _kl_triples(who, t1, t2):
+    """ValueError unless t1 and t2 are (P, L, bad) as kl_tables returns them, on the device, of one frame width."""
+    _lib.require_device(*(t1 + t2))
+    for P_, L_, b_ in (t1, t2):
+        if (P_.dim() != 2 or L_.shape != P_.shape or b_.shape != P_.shape[:1] or P_.dtype != torch.float32 or
+                L_.dtype != torch.float32 or b_.dtype != torch.uint8 or
+                not (P_.is_contiguous() and L_.is_contiguous() and b_.is_contiguous())):
+            raise ValueError('%s: distance=\'kl\' takes (P, L, bad) as kl_tables returns them' % who)
+    if t1[0].shape[1] != t2[0].shape[1]:
+        raise ValueError('%s: the two sides have different frame widths' % who)
+
+
+def _pair_table(who, rows1, off1, n1, rows2, off2, n2):
+    """A pair table's columns, checked to lie inside tables of rows1 / rows2 rows: (host arrays, device tensors)."""
+    off1, off2 = (np.ascontiguousarray(a, dtype=np.int64) for a in (off1, off2))
+    n1, n2 = (np.ascontiguousarray(a, dtype=np.int32) for a in (n1, n2))
+    if not (len(off1) == len(off2) == len(n2) == len(n1)):
+        raise ValueError('%s: the pair table\'s columns differ in length' % who)
+    if len(n1) and (n1.min() < 0 or n2.min() < 0 or off1.min() < 0 or off2.min() < 0 or
+                    (off1 + n1).max() > rows1 or (off2 + n2).max() > rows2):
+        raise ValueError('%s: a pair reads outside the feature tables' % who)
+    cols = (off1, n1, off2, n2)
+    return cols, [_dev(a, a.dtype) for a in cols]
+
+
+def _beyond_cap(message, n, cap):
+    long_ = np.flatnonzero(n > cap)
+    if len(long_):
+        raise ValueError(message % (long_[0], n[long_[0]], cap, len(long_)))
+
+
 def kl_tables(table, floor=1e-6):
     """KLTables (P, L, bad) of the device feature table [rows, D] float32 (abn_kl_tables): P = max(table, floor),
     L = float32(log(float64(P))), bad[r] = 1 when row r holds a non-finite or a negative value."""
@@ -240,44 +271,29 @@ def dtw_cost_batch(feats1, off1, n1, feats2, off2, n2, distance='cosine'):
     kl = distance == 'kl'
     if kl:
         (feats1, L1, bad1), (feats2, L2, bad2) = feats1, feats2
-        _lib.require_device(feats1, L1, bad1, feats2, L2, bad2)
-        for P_, L_, b_ in ((feats1, L1, bad1), (feats2, L2, bad2)):
-            if (P_.dim() != 2 or L_.shape != P_.shape or b_.shape != P_.shape[:1] or P_.dtype != torch.float32 or
-                    L_.dtype != torch.float32 or b_.dtype != torch.uint8 or
-                    not (P_.is_contiguous() and L_.is_contiguous() and b_.is_contiguous())):
-                raise ValueError('dtw_cost_batch: distance=\'kl\' takes (P, L, bad) as kl_tables returns them')
-        if feats1.shape[1] != feats2.shape[1]:
-            raise ValueError('dtw_cost_batch: the two sides have different frame widths')
+        _kl_triples('dtw_cost_batch', (feats1, L1, bad1), (feats2, L2, bad2))
     else:
         _lib.require_device(feats1, feats2)
-    off1 = np.ascontiguousarray(off1, dtype=np.int64)
-    off2 = np.ascontiguousarray(off2, dtype=np.int64)
-    n1 = np.ascontiguousarray(n1, dtype=np.int32)
-    n2 = np.ascontiguousarray(n2, dtype=np.int32)
+    (off1, n1, off2, n2), d_tab = _pair_table('dtw_cost_batch', feats1.shape[0], off1, n1, feats2.shape[0], off2, n2)
     P = len(n1)
-    if P and (n1.min() < 0 or n2.min() < 0 or off1.min() < 0 or off2.min() < 0 or
-              (off1 + n1).max() > feats1.shape[0] or (off2 + n2).max() > feats2.shape[0]):
-        raise ValueError('dtw_cost_batch: a pair reads outside the feature tables')
     cap = lib.abn_dtw_cost_max_n2()
-    long_ = np.flatnonzero(n2 > cap)
-    if kl and len(long_):
-        raise ValueError('dtw_cost_batch: token 2 of pair %d has %d frames; distance=\'kl\' takes at most %d '
-                         '(%d pair(s) beyond it)' % (long_[0], n2[long_[0]], cap, len(long_)))
+    if kl:
+        _beyond_cap('dtw_cost_batch: token 2 of pair %d has %d frames; distance=\'kl\' takes at most %d '
+                    '(%d pair(s) beyond it)', n2, cap)
     cost = torch.empty(P, dtype=torch.float64, device=feats1.device)
     plen = torch.empty(P, dtype=torch.int32, device=feats1.device)
     if P == 0:
         return cost, plen
-    d_off1, d_n1, d_off2, d_n2 = _dev(off1, np.int64), _dev(n1, np.int32), _dev(off2, np.int64), _dev(n2, np.int32)
+    tail = [_lib.ptr(t) for t in d_tab] + [P, feats1.shape[1]]
+    out = [_lib.ptr(cost), _lib.ptr(plen), _lib.stream()]
     if kl:
         _lib.check(lib.abn_dtw_cost_kl_batched(_lib.ptr(feats1), _lib.ptr(L1), feats1.shape[0], _lib.ptr(feats2), _lib.ptr(L2),
-                                               feats2.shape[0], _lib.ptr(d_off1), _lib.ptr(d_n1), _lib.ptr(d_off2),
-                                               _lib.ptr(d_n2), P, feats1.shape[1], _lib.ptr(bad1), _lib.ptr(bad2),
-                                               _lib.ptr(cost), _lib.ptr(plen), _lib.stream()), 'abn_dtw_cost_kl_batched')
+                                               feats2.shape[0], *(tail + [_lib.ptr(bad1), _lib.ptr(bad2)] + out)),
+                   'abn_dtw_cost_kl_batched')
         return cost, plen
-    _lib.check(lib.abn_dtw_cost_batched(_lib.ptr(feats1), feats1.shape[0], _lib.ptr(feats2), feats2.shape[0],
-                                        _lib.ptr(d_off1), _lib.ptr(d_n1), _lib.ptr(d_off2), _lib.ptr(d_n2), P,
-                                        feats1.shape[1], _lib.ptr(cost), _lib.ptr(plen), _lib.stream()),
+    _lib.check(lib.abn_dtw_cost_batched(_lib.ptr(feats1), feats1.shape[0], _lib.ptr(feats2), feats2.shape[0], *(tail + out)),
                'abn_dtw_cost_batched')
+    long_ = np.flatnonzero(n2 > cap)
     if len(long_):
         from .utils import dtw_align_batch
         res = dtw_align_batch(feats1, off1[long_], n1[long_], feats2, off2[long_], n2[long_])

@@ -2,7 +2,7 @@
 
     python -m abnet3_amd.qbe FEATURES QUERIES [--distance cosine|kl] [--floor F] [--top K]
 
-The definition this module computes (tests/qbe_np.py restates it in numpy; csrc/search.hip is the kernel):
+The definition this module computes (tests/qbe_np.py restates it in numpy; the SEARCH mode of csrc/dtw_wave.h is the kernel):
 
 * A pair is a query Q of M frames and an utterance U of N frames.  A path consumes ALL of Q and ANY contiguous run of
   U (subsequence DTW).  Cell (i, j) pairs utterance frame i with query frame j.
@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .abx import DISTANCES, _dev, _read_h5features, kl_tables
+from .abx import DISTANCES, _beyond_cap, _dev, _kl_triples, _pair_table, _read_h5features, kl_tables
 
 # the per-frame output of subsequence_dtw_batch(profile=True): entry offset[p] + i is utterance frame i of pair p
 Profile = namedtuple('Profile', ['cost', 'len', 'start', 'offset'])
@@ -64,33 +64,17 @@ def subsequence_dtw_batch(q, q_off, q_n, u, u_off, u_n, distance='cosine', profi
     kl = distance == 'kl'
     if kl:
         (q, Lq, badq), (u, Lu, badu) = q, u
-        _lib.require_device(q, Lq, badq, u, Lu, badu)
-        for P_, L_, b_ in ((q, Lq, badq), (u, Lu, badu)):
-            if (P_.dim() != 2 or L_.shape != P_.shape or b_.shape != P_.shape[:1] or P_.dtype != torch.float32 or
-                    L_.dtype != torch.float32 or b_.dtype != torch.uint8 or
-                    not (P_.is_contiguous() and L_.is_contiguous() and b_.is_contiguous())):
-                raise ValueError('subsequence_dtw_batch: distance=\'kl\' takes (P, L, bad) as kl_tables returns them')
+        _kl_triples('subsequence_dtw_batch', (q, Lq, badq), (u, Lu, badu))
     else:
         _lib.require_device(q, u)
         if q.dim() != 2 or u.dim() != 2 or q.dtype != torch.float32 or u.dtype != torch.float32:
             raise ValueError('subsequence_dtw_batch: [rows, D] float32 tables are needed')
-    if q.shape[1] != u.shape[1]:
-        raise ValueError('subsequence_dtw_batch: the two sides have different frame widths')
-    q_off = np.ascontiguousarray(q_off, dtype=np.int64)
-    u_off = np.ascontiguousarray(u_off, dtype=np.int64)
-    q_n = np.ascontiguousarray(q_n, dtype=np.int32)
-    u_n = np.ascontiguousarray(u_n, dtype=np.int32)
+        if q.shape[1] != u.shape[1]:
+            raise ValueError('subsequence_dtw_batch: the two sides have different frame widths')
+    (u_off, u_n, q_off, q_n), d_tab = _pair_table('subsequence_dtw_batch', u.shape[0], u_off, u_n, q.shape[0], q_off, q_n)
     P = len(q_n)
-    if not (len(q_off) == len(u_off) == len(u_n) == P):
-        raise ValueError('subsequence_dtw_batch: the pair table\'s columns differ in length')
-    if P and (q_n.min() < 0 or u_n.min() < 0 or q_off.min() < 0 or u_off.min() < 0 or
-              (q_off + q_n).max() > q.shape[0] or (u_off + u_n).max() > u.shape[0]):
-        raise ValueError('subsequence_dtw_batch: a pair reads outside the feature tables')
-    cap = lib.abn_dtw_search_max_query()
-    long_ = np.flatnonzero(q_n > cap)
-    if len(long_):
-        raise ValueError('subsequence_dtw_batch: the query of pair %d has %d frames; at most %d are taken '
-                         '(%d pair(s) beyond it)' % (long_[0], q_n[long_[0]], cap, len(long_)))
+    _beyond_cap('subsequence_dtw_batch: the query of pair %d has %d frames; at most %d are taken (%d pair(s) beyond it)',
+                q_n, lib.abn_dtw_search_max_query())
     dev = u.device
     cost = torch.empty(P, dtype=torch.float64, device=dev)
     plen, start, end = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(3))
@@ -102,12 +86,11 @@ def subsequence_dtw_batch(q, q_off, q_n, u, u_off, u_n, distance='cosine', profi
         prof = Profile(torch.empty(rows, dtype=torch.float64, device=dev), torch.empty(rows, dtype=torch.int32, device=dev),
                        torch.empty(rows, dtype=torch.int32, device=dev), off[:-1].copy())
     if P:
-        d_uoff, d_un, d_qoff, d_qn = _dev(u_off, np.int64), _dev(u_n, np.int32), _dev(q_off, np.int64), _dev(q_n, np.int32)
+        table = [_lib.ptr(t) for t in d_tab] + [P, u.shape[1]]
         d_poff = _dev(prof.offset, np.int64) if profile else None
         tail = [_lib.ptr(cost), _lib.ptr(plen), _lib.ptr(start), _lib.ptr(end), _lib.ptr(d_poff),
                 prof.cost.numel() if profile else 0, _lib.ptr(prof.cost if profile else None),
                 _lib.ptr(prof.len if profile else None), _lib.ptr(prof.start if profile else None), _lib.stream()]
-        table = [_lib.ptr(d_uoff), _lib.ptr(d_un), _lib.ptr(d_qoff), _lib.ptr(d_qn), P, u.shape[1]]
         if kl:
             _lib.check(lib.abn_dtw_search_kl_batched(_lib.ptr(u), _lib.ptr(Lu), u.shape[0], _lib.ptr(q), _lib.ptr(Lq), q.shape[0],
                                                      *(table + [_lib.ptr(badu), _lib.ptr(badq)] + tail)),

@@ -101,6 +101,36 @@ def test_cost_kernel_unaligned_rows_take_the_scalar_path():
     assert np.array_equal(cost.cpu().numpy().view(np.int64), ref_c.view(np.int64))
 
 
+GRID = 256 * 32                     # the most wavefronts a launch of the cost kernel has
+
+
+def assert_a_drop_does_not_leak(pick, dropped, ref_l, got_l):
+    """The pairs drawn next to an occurrence of the dropped pair -- in front of and behind it in the table, and GRID
+    places apart, where its own wavefront takes them -- are not dropped (those the reference keeps; there are some)."""
+    at = np.flatnonzero(pick == dropped)
+    for step in (1, GRID):
+        for nb in (at[at >= step] - step, at[at + step < len(pick)] + step):
+            nb = nb[ref_l[pick[nb]] > 0]
+            assert len(nb), step
+            assert (got_l[nb] > 0).all(), (step, nb[got_l[nb] <= 0][:10])
+
+
+def test_cost_kernel_grid_stride_many_tiny_pairs():
+    """More pairs than the grid has wavefronts: each wavefront works through several; the drop flag and its LDS rows
+    must not leak from one pair into the next."""
+    rng = np.random.default_rng(13)
+    f1, o1, n1, f2, o2, n2 = pair_table(rng, 300, 5, True, lo=1, hi=8)
+    f1[o1[7]] = np.nan                                               # this pair is dropped
+    ref_c, ref_l = batched(f1, o1, n1, f2, o2, n2)
+    assert ref_l[7] == 0
+    pick = rng.integers(0, 300, 9000)
+    assert len(pick) > GRID
+    got_c, got_l = raw_cost(f1, o1[pick], n1[pick], f2, o2[pick], n2[pick])
+    assert np.array_equal(got_l, ref_l[pick]), np.flatnonzero(got_l != ref_l[pick])[:10]
+    assert np.array_equal(got_c.view(np.int64), ref_c[pick].view(np.int64)), np.flatnonzero(got_c != ref_c[pick])[:10]
+    assert_a_drop_does_not_leak(pick, 7, ref_l, got_l)
+
+
 def test_cost_beyond_the_cap_goes_to_dtw_batched():
     from abnet3_amd import _lib
     from abnet3_amd.abx import dtw_cost_batch

@@ -10,7 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import abx_kl_np  # noqa: E402
-from test_gpu_abx import EDGES, synthetic_set  # noqa: E402
+from test_gpu_abx import EDGES, GRID, assert_a_drop_does_not_leak, synthetic_set  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -166,6 +166,24 @@ def test_kl_cost_kernel_unaligned_tables_take_the_scalar_path():
     assert np.array_equal(got_l, ref_l) and np.array_equal(al_l, ref_l)
     assert np.array_equal(got_c.view(np.int64), ref_c.view(np.int64))
     assert np.array_equal(al_c.view(np.int64), ref_c.view(np.int64))
+
+
+def test_kl_cost_kernel_grid_stride_many_tiny_pairs():
+    """More pairs than the grid has wavefronts: each wavefront works through several; a pair dropped for a BAD row
+    must not take the next one with it."""
+    from abnet3_amd.abx import kl_tables
+    rng = np.random.default_rng(13)
+    f1, o1, n1, f2, o2, n2 = kl_pair_table(rng, 300, 5, True, lo=1, hi=8)
+    f1[o1[7], 0] = -0.25                                             # a BAD row: this pair is dropped
+    t1, t2 = kl_tables(dev(f1)), kl_tables(dev(f2))
+    ref_c, ref_l = abx_kl_np.dtw_cost_batch(host(t1), o1, n1, host(t2), o2, n2)      # the device's own P and L
+    assert ref_l[7] == 0 and (np.delete(ref_l, 7) > 0).all()
+    pick = rng.integers(0, 300, 9000)
+    assert len(pick) > GRID
+    got_c, got_l = raw_kl_cost(t1, o1[pick], n1[pick], t2, o2[pick], n2[pick])
+    assert np.array_equal(got_l, ref_l[pick]), np.flatnonzero(got_l != ref_l[pick])[:10]
+    assert np.array_equal(got_c.view(np.int64), ref_c[pick].view(np.int64)), np.flatnonzero(got_c != ref_c[pick])[:10]
+    assert_a_drop_does_not_leak(pick, 7, ref_l, got_l)
 
 
 def test_kl_cost_beyond_the_cap_raises():

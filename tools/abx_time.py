@@ -16,8 +16,10 @@ with prototype trajectories (4 anchor frames, linearly interpolated) plus noise 
   abn_dtw_cost_batched     the cosine instantiation on the same pair table of the same posteriorgrams, in the same run
   torch                    what a user could write before: the frame-distance matrices alone (no DTW) of the same pairs as
                            a chunked torch expression on the GPU, pairs bucketed by (n1, n2) so that nothing is padded
-  --parent-lib FILE        the cosine kernel of another build of the library (the parent commit's), timed alternately
-                           with this build's on the same pairs
+  --parent-lib FILE        the kernels of another build of the library (the parent commit's) -- abn_dtw_cost_batched, and
+                           under --distance kl abn_dtw_cost_kl_batched too -- timed alternately with this build's on the
+                           same pairs: several repeats per build, the outputs compared bit for bit.  A route passes when
+                           the ratio of the medians is at most 1 + twice the parent's own relative spread over its repeats
 
 Every GPU route settles the clock (untimed calls for 0.3 s) before its timed calls; medians are reported.
 python tools/abx_time.py [--items N] [--distance cosine|kl] [--parent-lib FILE] [--out FILE]"""
@@ -82,6 +84,45 @@ def median_ms(fn, calls=9):
         torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1))
     return float(np.median(ts))
+
+
+def parent_library(path, lib, names):
+    """Another build of the library, its entry points `names` typed as this build's are."""
+    parent = ctypes.CDLL(os.path.abspath(path))
+    for name in names:
+        fn, own = getattr(parent, name), getattr(lib, name)
+        fn.restype, fn.argtypes = own.restype, own.argtypes
+    return parent
+
+
+def versus_parent(this_fn, parent_fn, outputs, calls=9, repeats=4):
+    """The *_vs_parent_build block of one route: median_ms of this build's call and of the parent's, alternating,
+    `repeats` times each; outputs() -> [(this build's tensor, the parent's)], compared bit for bit after the last call.
+    The bound on the ratio of the medians is 1 + 2 x the parent's relative spread, (max - min) / median, over its repeats."""
+    this, other = [], []
+    for _ in range(repeats):
+        this.append(median_ms(this_fn, calls))
+        other.append(median_ms(parent_fn, calls))
+    torch.cuda.synchronize()
+    ratio = float(np.median(this) / np.median(other))
+    spread = float((max(other) - min(other)) / np.median(other))
+    same = all(a.dtype == b.dtype and torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in outputs())
+    return {'this_build_ms': [round(t, 4) for t in this], 'parent_build_ms': [round(t, 4) for t in other],
+            'ratio_of_medians': round(ratio, 4), 'parent_relative_spread': round(spread, 4),
+            'bound_on_the_ratio': round(1.0 + 2.0 * spread, 4), 'within_the_bound': bool(ratio <= 1.0 + 2.0 * spread),
+            'outputs_bit_identical': bool(same)}
+
+
+def finish(res, out):
+    """Prints and writes the result; a route of *_vs_parent_build whose outputs differ between the builds is an error."""
+    print(json.dumps(res))
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as fh:
+            fh.write(json.dumps(res, indent=1) + '\n')
+    for key, block in res.items():
+        if key.endswith('_vs_parent_build'):
+            assert block['outputs_bit_identical'], key
 
 
 def wall(fn):
@@ -159,17 +200,14 @@ def main_kl(a):
     plen = torch.empty(npairs, dtype=torch.int32, device='cuda')
     ccost, cplen = torch.empty_like(cost), torch.empty_like(plen)
 
-    def kl_kernel():
-        _lib.check(lib.abn_dtw_cost_kl_batched(_lib.ptr(tabs.P), _lib.ptr(tabs.L), rows, _lib.ptr(tabs.P), _lib.ptr(tabs.L), rows,
-                                               *[_lib.ptr(t) for t in d_tab], npairs, D, _lib.ptr(tabs.bad), _lib.ptr(tabs.bad),
-                                               _lib.ptr(cost), _lib.ptr(plen), _lib.stream()), 'abn_dtw_cost_kl_batched')
+    def kl_kernel(l=lib, c=cost, ln=plen):
+        _lib.check(l.abn_dtw_cost_kl_batched(_lib.ptr(tabs.P), _lib.ptr(tabs.L), rows, _lib.ptr(tabs.P), _lib.ptr(tabs.L), rows,
+                                             *[_lib.ptr(t) for t in d_tab], npairs, D, _lib.ptr(tabs.bad), _lib.ptr(tabs.bad),
+                                             _lib.ptr(c), _lib.ptr(ln), _lib.stream()), 'abn_dtw_cost_kl_batched')
 
-    def cosine_args():
-        return [_lib.ptr(table), rows, _lib.ptr(table), rows] + [_lib.ptr(t) for t in d_tab] + [
-            npairs, D, _lib.ptr(ccost), _lib.ptr(cplen), _lib.stream()]
-
-    def cosine_kernel():
-        _lib.check(lib.abn_dtw_cost_batched(*cosine_args()), 'abn_dtw_cost_batched')
+    def cosine_kernel(l=lib, c=ccost, ln=cplen):
+        _lib.check(l.abn_dtw_cost_batched(_lib.ptr(table), rows, _lib.ptr(table), rows, *[_lib.ptr(t) for t in d_tab],
+                                          npairs, D, _lib.ptr(c), _lib.ptr(ln), _lib.stream()), 'abn_dtw_cost_batched')
 
     P2, L2, bad2 = torch.empty_like(table), torch.empty_like(table), torch.empty(rows, dtype=torch.uint8, device='cuda')
 
@@ -201,31 +239,13 @@ def main_kl(a):
         'kl_kernel': rate(kl_ms), 'cosine_kernel': rate(cos_ms),
         'pairs_dropped': int((plen <= 0).sum().item())}
     if a.parent_lib:
-        # the cosine instantiation of this build against another build's, alternating, on the same pairs
-        parent = ctypes.CDLL(os.path.abspath(a.parent_lib))
-        fn = parent.abn_dtw_cost_batched
-        fn.restype, fn.argtypes = lib.abn_dtw_cost_batched.restype, lib.abn_dtw_cost_batched.argtypes
-        pcost = torch.empty_like(ccost)
-
-        def parent_kernel():
-            args = cosine_args()
-            args[-3] = _lib.ptr(pcost)
-            assert fn(*args) == 0
-
-        this, other = [], []
-        for _ in range(4):
-            this.append(round(median_ms(cosine_kernel), 4))
-            other.append(round(median_ms(parent_kernel), 4))
-        torch.cuda.synchronize()
-        res['cosine_kernel_vs_parent_build'] = {
-            'this_build_ms': this, 'parent_build_ms': other,
-            'ratio_of_medians': round(float(np.median(this) / np.median(other)), 4),
-            'costs_bit_identical': bool(torch.equal(ccost.view(torch.int64), pcost.view(torch.int64)))}
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as fh:
-            fh.write(json.dumps(res, indent=1) + '\n')
+        parent = parent_library(a.parent_lib, lib, ['abn_dtw_cost_batched', 'abn_dtw_cost_kl_batched'])
+        pcost, pplen = torch.empty_like(cost), torch.empty_like(plen)
+        res['cosine_kernel_vs_parent_build'] = versus_parent(cosine_kernel, lambda: cosine_kernel(parent, pcost, pplen),
+                                                             lambda: [(ccost, pcost), (cplen, pplen)])
+        res['kl_kernel_vs_parent_build'] = versus_parent(kl_kernel, lambda: kl_kernel(parent, pcost, pplen),
+                                                         lambda: [(cost, pcost), (plen, pplen)])
+    finish(res, a.out)
 
 
 def main():
@@ -233,7 +253,7 @@ def main():
     ap.add_argument('--items', type=int, default=6000)
     ap.add_argument('--calls', type=int, default=3)
     ap.add_argument('--distance', choices=('cosine', 'kl'), default='cosine')
-    ap.add_argument('--parent-lib', default=None, help='--distance kl: another build of the library to time the cosine kernel of')
+    ap.add_argument('--parent-lib', default=None, help="another build of the library (the parent commit's) to time the cost kernels of")
     ap.add_argument('--out', default=None, help='default: profiles/abx_time.json, profiles/abx_kl_time.json under --distance kl')
     a = ap.parse_args()
     if a.out is None:
@@ -258,10 +278,10 @@ def main():
     cost = torch.empty(npairs, dtype=torch.float64, device='cuda')
     plen = torch.empty(npairs, dtype=torch.int32, device='cuda')
 
-    def cost_kernel():
-        _lib.check(lib.abn_dtw_cost_batched(_lib.ptr(table), table.shape[0], _lib.ptr(table), table.shape[0],
-                                            *[_lib.ptr(t) for t in d_tab], npairs, table.shape[1], _lib.ptr(cost),
-                                            _lib.ptr(plen), _lib.stream()), 'abn_dtw_cost_batched')
+    def cost_kernel(l=lib, c=cost, ln=plen):
+        _lib.check(l.abn_dtw_cost_batched(_lib.ptr(table), table.shape[0], _lib.ptr(table), table.shape[0],
+                                          *[_lib.ptr(t) for t in d_tab], npairs, table.shape[1], _lib.ptr(c),
+                                          _lib.ptr(ln), _lib.stream()), 'abn_dtw_cost_batched')
 
     holder = {}
 
@@ -291,11 +311,12 @@ def main():
         'cost_kernel_speedup_over_dtw_batched': round(b_ms / k_ms, 3),
         'cost_kernel_speedup_over_oracle_16_threads': round(o_s * 1e3 / k_ms, 2),
         'costs_and_lengths_bit_identical': bool(same)}
-    print(json.dumps(res))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as fh:
-            fh.write(json.dumps(res, indent=1) + '\n')
+    if a.parent_lib:
+        parent = parent_library(a.parent_lib, lib, ['abn_dtw_cost_batched'])
+        pcost, pplen = torch.empty_like(cost), torch.empty_like(plen)
+        res['cost_kernel_vs_parent_build'] = versus_parent(cost_kernel, lambda: cost_kernel(parent, pcost, pplen),
+                                                           lambda: [(cost, pcost), (plen, pplen)])
+    finish(res, a.out)
 
 
 if __name__ == '__main__':

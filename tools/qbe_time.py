@@ -11,8 +11,12 @@ of them, every query against every utterance.
 
 --distance kl: the same over a row softmax of the features (abn_dtw_search_kl_batched against abn_dtw_cost_kl_batched).
 
+--parent-lib FILE: the same three routes (search, search with profile, cost on the same shapes) of another build of the
+library (the parent commit's), timed alternately with this build's, outputs compared bit for bit (tools/abx_time.py:
+versus_parent).
+
 Every GPU route settles the clock (untimed calls for 0.3 s) before its timed calls; medians are reported.
-python tools/qbe_time.py [--utts N] [--queries N] [--distance cosine|kl] [--out FILE]"""
+python tools/qbe_time.py [--utts N] [--queries N] [--distance cosine|kl] [--parent-lib FILE] [--out FILE]"""
 import argparse
 import json
 import os
@@ -24,7 +28,7 @@ import torch
 
 from abnet3_amd import _lib
 from abnet3_amd.qbe import QbeSearcher
-from tools.abx_time import median_ms, settle, wall  # noqa: F401
+from tools.abx_time import median_ms, parent_library, settle, versus_parent, wall  # noqa: F401
 
 
 def synthetic(n_utts, n_queries, D=100, seed=0):
@@ -53,6 +57,7 @@ def main():
     ap.add_argument('--queries', type=int, default=100)
     ap.add_argument('--distance', choices=('cosine', 'kl'), default='cosine')
     ap.add_argument('--calls', type=int, default=9)
+    ap.add_argument('--parent-lib', default=None, help="another build of the library (the parent commit's) to time beside this one")
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     kl = a.distance == 'kl'
@@ -82,25 +87,27 @@ def main():
     table, t = c.table, s.tables
     ptr = _lib.ptr
 
-    def search(profile):
-        out = [ptr(cost), ptr(plen), ptr(start), ptr(end)]
-        out += [ptr(d_poff), prows, ptr(pc), ptr(pl), ptr(ps)] if profile else [None, 0, None, None, None]
+    mine = (cost, plen, start, end, pc, pl, ps, ccost, cplen)
+
+    def search(profile, l=lib, o=mine):
+        out = [ptr(x) for x in o[:4]]
+        out += [ptr(d_poff), prows] + [ptr(x) for x in o[4:7]] if profile else [None, 0, None, None, None]
         if kl:
-            _lib.check(lib.abn_dtw_search_kl_batched(ptr(t.P), ptr(t.L), rows, ptr(t.P), ptr(t.L), rows, *[ptr(x) for x in tab],
-                                                     npairs, D, ptr(t.bad), ptr(t.bad), *out, _lib.stream()),
+            _lib.check(l.abn_dtw_search_kl_batched(ptr(t.P), ptr(t.L), rows, ptr(t.P), ptr(t.L), rows, *[ptr(x) for x in tab],
+                                                   npairs, D, ptr(t.bad), ptr(t.bad), *out, _lib.stream()),
                        'abn_dtw_search_kl_batched')
         else:
-            _lib.check(lib.abn_dtw_search_batched(ptr(table), rows, ptr(table), rows, *[ptr(x) for x in tab], npairs, D, *out,
-                                                  _lib.stream()), 'abn_dtw_search_batched')
+            _lib.check(l.abn_dtw_search_batched(ptr(table), rows, ptr(table), rows, *[ptr(x) for x in tab], npairs, D, *out,
+                                                _lib.stream()), 'abn_dtw_search_batched')
 
-    def cost_only():
+    def cost_only(l=lib, o=mine):
         if kl:
-            _lib.check(lib.abn_dtw_cost_kl_batched(ptr(t.P), ptr(t.L), rows, ptr(t.P), ptr(t.L), rows, *[ptr(x) for x in tab],
-                                                   npairs, D, ptr(t.bad), ptr(t.bad), ptr(ccost), ptr(cplen), _lib.stream()),
+            _lib.check(l.abn_dtw_cost_kl_batched(ptr(t.P), ptr(t.L), rows, ptr(t.P), ptr(t.L), rows, *[ptr(x) for x in tab],
+                                                 npairs, D, ptr(t.bad), ptr(t.bad), ptr(o[7]), ptr(o[8]), _lib.stream()),
                        'abn_dtw_cost_kl_batched')
         else:
-            _lib.check(lib.abn_dtw_cost_batched(ptr(table), rows, ptr(table), rows, *[ptr(x) for x in tab], npairs, D,
-                                                ptr(ccost), ptr(cplen), _lib.stream()), 'abn_dtw_cost_batched')
+            _lib.check(l.abn_dtw_cost_batched(ptr(table), rows, ptr(table), rows, *[ptr(x) for x in tab], npairs, D,
+                                              ptr(o[7]), ptr(o[8]), _lib.stream()), 'abn_dtw_cost_batched')
 
     s_ms = median_ms(lambda: search(False), a.calls)
     c_ms = median_ms(cost_only, a.calls)
@@ -134,6 +141,15 @@ def main():
         'protocol': 'settle 0.3 s of untimed calls, then the median of %d device-event timings per route; the routes '
                     'alternate in one process' % a.calls,
     }
+    if a.parent_lib:
+        parent = parent_library(a.parent_lib, lib, [name, cname])
+        theirs = tuple(torch.empty_like(x) for x in mine)
+        res['search_vs_parent_build'] = versus_parent(lambda: search(False), lambda: search(False, parent, theirs),
+                                                      lambda: list(zip(mine[:4], theirs[:4])), a.calls)
+        res['search_with_profile_vs_parent_build'] = versus_parent(lambda: search(True), lambda: search(True, parent, theirs),
+                                                                   lambda: list(zip(mine[:7], theirs[:7])), a.calls)
+        res['cost_same_shapes_vs_parent_build'] = versus_parent(cost_only, lambda: cost_only(parent, theirs),
+                                                                lambda: list(zip(mine[7:], theirs[7:])), a.calls)
     line = json.dumps(res)
     print(line)
     if a.out:
@@ -146,6 +162,9 @@ def main():
         with open(path, 'w') as f:
             json.dump(merged, f, indent=1)
             f.write('\n')
+    for key, block in res.items():
+        if key.endswith('_vs_parent_build'):
+            assert block['outputs_bit_identical'], key
 
 
 if __name__ == '__main__':
