@@ -96,4 +96,21 @@ __device__ __forceinline__ double abn_ticket_partial(const double* slot)
 static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// Per-device one-time set-up (the opt-in to more than 64 KiB of dynamic LDS: hipFuncSetAttribute, once per device and
+// kernel family).  A call site keeps one `static bool seen[16]` per family; devices outside 0 .. 15 share slot 0.  No
+// locking: two threads that both see "first" repeat an idempotent attribute call.
+static inline int device_slot()
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return (dev >= 0 && dev < 16) ? dev : 0;
+}
+static inline bool first_use_on_device(bool (&seen)[16])
+{
+    bool& s = seen[device_slot()];
+    const bool first = !s;
+    s = true;
+    return first;
+}
+
 }  // namespace abn

@@ -327,14 +327,9 @@ extern "C" int abn_knn_topk(const float* Q, int64_t nq, const float* C, int64_t 
     ABN_REQUIRE((int64_t)g.qblocks * g.split < (1LL << 31), "abn_knn_topk: grid too large");
     hipStream_t st = static_cast<hipStream_t>(stream);
     static bool attr_set[16] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev = (dev >= 0 && dev < 16) ? dev : 0;
-    if (!attr_set[dev]) {
+    if (first_use_on_device(attr_set))
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(knn_tile_topk_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)knn_lds_bytes(KN_MAX_K));
-        attr_set[dev] = true;
-    }
     KnnP p;
     p.Q = Q; p.C = C; p.nq = (int)nq; p.nc = (int)nc; p.d = d; p.k = k;
     const bool excl = q_meta && c_meta;

@@ -71,6 +71,15 @@ static Switches g_switches = read_switches();       // (at library load: no call
 const Switches& switches() { return g_switches; }
 void reload_switches() { g_switches = read_switches(); }
 
+#ifdef ABN_STAMPS
+// Diagnostic stamp builds only (tools/build_stamps.sh): the device buffer whose address the tool left in the environment.
+static unsigned long long* stamp_buffer(const char* name)
+{
+    const char* v = getenv(name);
+    return v ? (unsigned long long*)strtoull(v, nullptr, 0) : nullptr;
+}
+#endif
+
 // ---------------------------------------------------------------------------
 // GEMM dispatch
 // ---------------------------------------------------------------------------
@@ -80,15 +89,9 @@ static void launch_one(const GemmP& p, int splits, hipStream_t st)
     const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     constexpr size_t lds = BF16 == 3 ? gemm_lds_bytes3<BM, BN>() : gemm_lds_bytes<BM, BN, A_KC, B_KC>();
     auto k = gemm_f32_kernel<BM, BN, A_KC, B_KC, EPI, VEC, BF16>;
-    static bool attr_set[16] = {};     // > 64 KiB of dynamic LDS needs the opt-in, once per device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev = (dev >= 0 && dev < 16) ? dev : 0;
-    if (!attr_set[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set[dev] = true;
-    }
+    static bool attr_set[16] = {};     // > 64 KiB of dynamic LDS needs the opt-in, once per device (common.h)
+    if (first_use_on_device(attr_set))
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     GemmP q = p;
     q.splits = splits;
     hipLaunchKernelGGL(k, dim3(tiles * splits), dim3(256), lds, st, q);
@@ -143,7 +146,7 @@ static int prepare_gemm(GemmP& p, int splits)
     }
     p.splits = splits;
 #ifdef ABN_STAMPS
-    p.stamps = getenv("ABN_STAMP_BUF") ? (unsigned long long*)strtoull(getenv("ABN_STAMP_BUF"), nullptr, 0) : nullptr;
+    p.stamps = stamp_buffer("ABN_STAMP_BUF");
 #endif
     const int force = switches().gemm_tile;
     if (force >= 0 && force <= 3) return force;
@@ -169,11 +172,6 @@ static int launch_gemm(GemmP p, int splits, hipStream_t st)
     return ABN_OK;
 }
 
-static bool bf16x3_planes()
-{
-    return switches().bf16x3_planes;
-}
-
 // wgrad + dgrad of one backward layer in ONE grid (gemm_bwd_pair_kernel) when both take
 // their usual vectorised instantiations; otherwise two launches.
 template <int WM, int WN, int BF16>
@@ -184,14 +182,19 @@ static void launch_pair_one(const GemmP& pw, int n0, const GemmP& pd, int n1, hi
     constexpr size_t lds = lw > ld ? lw : ld;
     auto k = gemm_bwd_pair_kernel<WM, WN, BF16>;
     static bool attr_set[16] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev = (dev >= 0 && dev < 16) ? dev : 0;
-    if (!attr_set[dev]) {
+    if (first_use_on_device(attr_set))
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set[dev] = true;
-    }
     hipLaunchKernelGGL(k, dim3(n0 + n1), dim3(256), lds, st, pw, n0, pd);
+}
+
+// ... in the pair's arithmetic (the instantiations launch_cfg picks for a vectorised GEMM)
+template <int WM>
+static void launch_pair_tile(const GemmP& pw, int n0, const GemmP& pd, int n1, hipStream_t st)
+{
+    if (pw.bf16 == 1) launch_pair_one<WM, 64, 1>(pw, n0, pd, n1, st);
+    else if (pw.bf16 == 2 && switches().bf16x3_planes) launch_pair_one<WM, 64, 3>(pw, n0, pd, n1, st);
+    else if (pw.bf16 == 2) launch_pair_one<WM, 64, 2>(pw, n0, pd, n1, st);
+    else launch_pair_one<WM, 64, 0>(pw, n0, pd, n1, st);
 }
 
 static int launch_bwd_pair(GemmP pw, int splits, GemmP pd, hipStream_t st)
@@ -208,17 +211,8 @@ static int launch_bwd_pair(GemmP pw, int splits, GemmP pd, hipStream_t st)
         const int n0 = ((pw.M + wm - 1) / wm) * ((pw.N + 63) / 64) * splits;
         const int n1 = ((pd.M + 127) / 128) * ((pd.N + 63) / 64);
         if (n0 % 8 == 0) {
-            if (tw == 1) {
-                if (pw.bf16 == 1) launch_pair_one<128, 64, 1>(pw, n0, pd, n1, st);
-                else if (pw.bf16 == 2 && bf16x3_planes()) launch_pair_one<128, 64, 3>(pw, n0, pd, n1, st);
-                else if (pw.bf16 == 2) launch_pair_one<128, 64, 2>(pw, n0, pd, n1, st);
-                else launch_pair_one<128, 64, 0>(pw, n0, pd, n1, st);
-            } else {
-                if (pw.bf16 == 1) launch_pair_one<64, 64, 1>(pw, n0, pd, n1, st);
-                else if (pw.bf16 == 2 && bf16x3_planes()) launch_pair_one<64, 64, 3>(pw, n0, pd, n1, st);
-                else if (pw.bf16 == 2) launch_pair_one<64, 64, 2>(pw, n0, pd, n1, st);
-                else launch_pair_one<64, 64, 0>(pw, n0, pd, n1, st);
-            }
+            if (tw == 1) launch_pair_tile<128>(pw, n0, pd, n1, st);
+            else launch_pair_tile<64>(pw, n0, pd, n1, st);
             ABN_CHECK_LAUNCH("gemm_bwd_pair");
             return ABN_OK;
         }
@@ -226,6 +220,70 @@ static int launch_bwd_pair(GemmP pw, int splits, GemmP pd, hipStream_t st)
     int rc = launch_gemm<false, false, EPI_WGRAD>(pw, splits, st);
     if (rc != ABN_OK) return rc;
     return launch_gemm<true, false, EPI_DGRAD>(pd, 1, st);
+}
+
+// ---------------------------------------------------------------------------
+// The three GEMMs of one Linear layer, each described once.  Row-major fp32 operands, W[N][K]; `prec` is GemmP.bf16
+// (gemm_prec() of a descriptor's precision; the abn_linear_* entries that take none pass 0).
+// ---------------------------------------------------------------------------
+// 16-byte global loads need the operand aligned and its leading dimension a multiple of 4 floats; anything else takes
+// the element-wise build (launch_cfg)
+static inline bool vec_ok(const float* p, int64_t ld) { return aligned16(p) && ld % 4 == 0; }
+
+// y[rows][N] = act(mask * (x[rows][K] W^T + b))
+static GemmP fwd_gemm(const float* x, const float* W, const float* b, float* y, int64_t rows, int64_t K, int64_t N, int act,
+                      const float* mask, int prec)
+{
+    GemmP p = {};
+    p.A = x; p.lda = K;
+    p.B = W; p.ldb = K;
+    p.C = y; p.ldc = N;
+    p.M = (int)rows; p.N = (int)N; p.K = (int)K; p.k_chunk = (int)K;
+    p.bias = b; p.act = act; p.mask = mask; p.ones_col = -1;
+    p.a_vec = vec_ok(x, K);
+    p.b_vec = vec_ok(W, K);
+    p.bf16 = prec;
+    return p;
+}
+
+// The data gradient's epilogue d a_prev *= act'(a_prev) * mask: the previous layer's output [rows][K], its activation and
+// its dropout multiplier.  {} = none (the tower's bottom layer, or BatchNorm in between); the single-layer entries pass
+// the leading dimension and the activation even without an array -- callers differ on purpose, nothing is filled in here.
+struct DgradAux { const float* a_prev; int64_t ld; int act; const float* mask; };
+
+// dx[rows][K] = dz[rows][N] W (* aux)
+static GemmP dgrad_gemm(const float* dz, const float* W, float* dx, int64_t rows, int64_t K, int64_t N, const DgradAux& aux, int prec)
+{
+    GemmP p = {};
+    p.A = dz; p.lda = N;
+    p.B = W; p.ldb = K;
+    p.C = dx; p.ldc = K;
+    p.M = (int)rows; p.N = (int)K; p.K = (int)N; p.k_chunk = (int)N;
+    p.aux = aux.a_prev; p.ldaux = aux.ld; p.act = aux.act; p.mask = aux.mask; p.ones_col = -1;
+    p.a_vec = vec_ok(dz, N);
+    p.b_vec = vec_ok(W, K);
+    p.bf16 = prec;
+    return p;
+}
+
+// Split-K weight gradient: slab s of `slabs` (slab_stride floats apart) = [dW[N][K] | db[N]] over rows [s * k_chunk, + k_chunk);
+// db rides along as the product with an all-ones column K of a_in
+static GemmP wgrad_gemm(const float* dz, const float* a_in, int64_t rows, int64_t K, int64_t N, float* slabs, int64_t slab_stride,
+                        int splits, int prec)
+{
+    GemmP p = {};
+    p.A = dz; p.lda = N;
+    p.B = a_in; p.ldb = K;
+    p.C = slabs; p.ldc = K;
+    p.C2 = slabs + N * K;
+    p.slab_stride = slab_stride;
+    p.M = (int)N; p.N = (int)K + 1; p.K = (int)rows;
+    p.k_chunk = (int)align_up((rows + splits - 1) / splits, BK);
+    p.ones_col = (int)K;
+    p.a_vec = vec_ok(dz, N);
+    p.b_vec = vec_ok(a_in, K);
+    p.bf16 = prec;
+    return p;
 }
 
 // ---------------------------------------------------------------------------
@@ -928,13 +986,8 @@ static void launch_wgrad(int np, const WgradP& w, int n_wg, hipStream_t st)
 #ifndef WG128_GENERAL
     if (wgrad_all128(np, w)) {
         static bool attr_set[16] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        dev = (dev >= 0 && dev < 16) ? dev : 0;
-        if (!attr_set[dev]) {
+        if (first_use_on_device(attr_set))
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_planes128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WGRAD128_LDS);
-            attr_set[dev] = true;
-        }
         hipLaunchKernelGGL(wgrad_planes128_kernel, dim3((unsigned)n_wg), dim3(PL_NT), WGRAD128_LDS, st, w);
         return;
     }
@@ -1104,9 +1157,7 @@ static bool bn_train_planes_path(const abn_tower_desc* t, int64_t rows, int64_t 
 static int device_cus()
 {
     static int cus[16] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev = (dev >= 0 && dev < 16) ? dev : 0;
+    const int dev = device_slot();
     if (!cus[dev]) {
         int n = 0;
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 1;
@@ -1282,6 +1333,36 @@ static ReduceTable make_reduce_table(const abn_tower_desc* t, const BwdLayout& B
     return rt;
 }
 
+// dW / db of ONE Linear from its split-K slabs (the abn_linear_* entries)
+static void reduce_one_layer(const float* slabs, int64_t slab_stride, int splits, int64_t in_dim, int64_t out_dim, float* dW, float* db,
+                             hipStream_t st)
+{
+    ReduceTable rt = {};
+    rt.n_layers = 1; rt.splits[0] = splits; rt.slab_stride = slab_stride;
+    rt.off[0] = 0; rt.nW[0] = out_dim * in_dim; rt.nb[0] = out_dim; rt.dW[0] = dW; rt.db[0] = db;
+    rt.total = out_dim * in_dim + out_dim;
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3(grid_for((rt.total + 3) / 4)), dim3(256), 0, st, slabs, rt);
+}
+
+// BatchNorm's backward on the per-layer kernels: d a_l (da) -> d z_l (dz; may alias da) through act' and the batch
+// statistics, and layer l's d gamma / d beta.  Three launches: partial sums, their finish, the element-wise apply.
+static void bn_layer_backward(const abn_tower_desc* t, int l, int act, const float* da, float* dz, int64_t rows, int64_t n_calls,
+                              const Layout& L, const BwdLayout& B, const float* ws, float* scratch, hipStream_t st)
+{
+    const int C = (int)t->dims[l + 1];
+    const int64_t rpc = rows / n_calls;
+    const float* a = ws + L.a[l];
+    const int nch = bn_chunks(rpc);
+    double* part = reinterpret_cast<double*>(scratch + B.bn_part);
+    hipLaunchKernelGGL(bn_partial_kernel<true>, dim3((C + 63) / 64, nch, (int)n_calls), dim3(256), 0, st, da, a,
+                       ws + L.xhat[l], rpc, C, bn_chunk_rows(rpc), act, part);
+    hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((unsigned)((n_calls * C + 63) / 64)), dim3(64), 0, st, part,
+                       nch, C, (int)n_calls, scratch + B.bn_s1, scratch + B.bn_s2);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(rows * C)), dim3(256), 0, st, a, da,
+                       ws + L.xhat[l], rows, rpc, C, act, t->bn_w[l], ws + L.invstd[l], scratch + B.bn_s1, scratch + B.bn_s2,
+                       (int)n_calls, t->drop_mask[l], dz, t->dbn_w[l], t->dbn_b[l]);
+}
+
 // The pair loss riding in the chain kernel's first phase (abn_tower_backward_loss)
 struct LossArgs {
     const void* y;
@@ -1330,7 +1411,7 @@ static WgradP make_wgrad(const abn_tower_desc* t, int64_t rows, const Layout& L,
     // (ABN_WGRAD_XCD=0: workgroups in launch order, A/B measurements)
     w.xcd_groups = switches().wgrad_xcd;
 #ifdef ABN_STAMPS
-    w.stamps = getenv("ABN_WSTAMP_BUF") ? (unsigned long long*)strtoull(getenv("ABN_WSTAMP_BUF"), nullptr, 0) : nullptr;
+    w.stamps = stamp_buffer("ABN_WSTAMP_BUF");
 #endif
     if (w.xcd_groups) {
         int most = 0;
@@ -1353,11 +1434,19 @@ static int wgrad_range(const abn_tower_desc* t, int* l_first, int* l_end)
     else *l_end = t->wgrad_split;
     return ABN_OK;
 }
-static void reduce_range(ReduceTable& rt, const abn_tower_desc* t, const BwdLayout& B, int l_first, int l_end)
+// The tail of every backward launcher: dW / db of layers [l_first, l_end) from the slabs, unless abn_tower_reduce_step
+// finishes the job (defer_reduce)
+static int reduce_slabs(const abn_tower_desc* t, const BwdLayout& B, const float* scratch, int l_first, int l_end, hipStream_t st)
 {
+    if (t->defer_reduce) return ABN_OK;
+    ReduceTable rt = make_reduce_table(t, B);
     rt.begin = B.off[l_first < t->n_layers ? l_first : t->n_layers - 1];
     if (l_first >= t->n_layers) rt.begin = rt.total;
     if (l_end < t->n_layers) rt.total = B.off[l_end];
+    if (rt.total > rt.begin)
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3(grid_for((rt.total - rt.begin + 3) / 4)), dim3(256), 0, st, scratch + B.slabs, rt);
+    ABN_CHECK_LAUNCH("slab_reduce");
+    return ABN_OK;
 }
 
 // Backward of a BatchNorm tower whose forward went through bn_fwd_layer_kernel (same predicate): per layer,
@@ -1378,13 +1467,9 @@ static int bn_planes_backward(const abn_tower_desc* t, const float* d_out, const
     const PackLayout PL = make_pack_layout(t);
     const char* const image = t->wpack ? reinterpret_cast<const char*>(t->wpack) : reinterpret_cast<const char*>(ws + L.wpack);
     static bool attr_set[16] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev = (dev >= 0 && dev < 16) ? dev : 0;
-    if (!attr_set[dev]) {
+    if (first_use_on_device(attr_set)) {
         PL_LDS_ATTR(bn_bwd_layer_kernel, pl_lds_bytes);
         PL_LDS_ATTR(wgrad_planes_kernel, wgrad_lds_of);
-        attr_set[dev] = true;
     }
     const int wgs_per_call = (int)bn_wgs_per_call(rows, n_calls);
     const dim3 cgrid((unsigned)(n_calls * wgs_per_call));
@@ -1410,10 +1495,7 @@ static int bn_planes_backward(const abn_tower_desc* t, const float* d_out, const
     if (bn_persist_path(t, rows, n_calls)) {
         // every layer in ONE resident launch, grid barriers in between (tower_bn_persist.h)
         static bool bt_attr_set[16] = {};
-        if (!bt_attr_set[dev]) {
-            PL_LDS_ATTR(bn_bwd_tower_kernel, bnp_lds_bytes);
-            bt_attr_set[dev] = true;
-        }
+        if (first_use_on_device(bt_attr_set)) PL_LDS_ATTR(bn_bwd_tower_kernel, bnp_lds_bytes);
         BnBwdTowerP q = {};
         q.n_layers = nl; q.rows = (int)rows; q.rows_call = (int)rpc; q.n_calls = (int)n_calls;
         for (int l = 0; l <= nl; ++l) q.dims[l] = (int)t->dims[l];
@@ -1516,11 +1598,7 @@ static int bn_planes_backward(const abn_tower_desc* t, const float* d_out, const
     w.tp_steps = tp_steps;
     launch_wgrad(np, w, n_wg, st);
     ABN_CHECK_LAUNCH("tower_backward (BatchNorm, planes)");
-    if (t->defer_reduce) return ABN_OK;               // abn_tower_reduce_step finishes the job (the slabs of THIS launch: psplits)
-    const ReduceTable rt = make_reduce_table(t, B);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(grid_for((rt.total + 3) / 4)), dim3(256), 0, st, scratch + B.slabs, rt);
-    ABN_CHECK_LAUNCH("slab_reduce");
-    return ABN_OK;
+    return reduce_slabs(t, B, scratch, 0, nl, st);    // (the slabs of THIS launch: psplits)
 }
 
 // part: PLANES_BWD_ALL for the product entries; the measurement entry abn_tower_backward_launch
@@ -1533,7 +1611,7 @@ static int planes_backward(const abn_tower_desc* t, const float* d_out, const Lo
     const int np = planes_of(t);
     PlanesBwdP b = {};
 #ifdef ABN_STAMPS
-    b.stamps = getenv("ABN_DSTAMP_BUF") ? (unsigned long long*)strtoull(getenv("ABN_DSTAMP_BUF"), nullptr, 0) : nullptr;
+    b.stamps = stamp_buffer("ABN_DSTAMP_BUF");
 #endif
     b.n_layers = nl;
     b.rows = (int)rows;
@@ -1578,26 +1656,16 @@ static int planes_backward(const abn_tower_desc* t, const float* d_out, const Lo
     int n_wg = 0;
     const WgradP w = make_wgrad(t, rows, L, B, ws, scratch, &n_wg, l_first, l_end);
     static bool bw_attr_set[16] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev = (dev >= 0 && dev < 16) ? dev : 0;
-    if (!bw_attr_set[dev]) {
+    if (first_use_on_device(bw_attr_set)) {
         PL_LDS_ATTR(tower_dgrad_planes_kernel, pl_lds_bytes);
         PL_LDS_ATTR(wgrad_planes_kernel, wgrad_lds_of);
-        bw_attr_set[dev] = true;
     }
     const dim3 cgrid((unsigned)((rows + PL_ROWS - 1) / PL_ROWS));
     const bool do_dgrad = part != PLANES_BWD_WGRAD, do_wgrad = part != PLANES_BWD_DGRAD;
     if (do_dgrad) PL_LAUNCH(np, tower_dgrad_planes_kernel, cgrid, dim3(PL_NT), pl_lds_bytes(np), st, b);
     if (do_wgrad && n_wg > 0) launch_wgrad(np, w, n_wg, st);
     ABN_CHECK_LAUNCH("tower_backward (planes)");
-    if (t->defer_reduce) return ABN_OK;      // abn_tower_reduce_step finishes the job
-    ReduceTable rt = make_reduce_table(t, B);
-    reduce_range(rt, t, B, l_first, l_end);
-    if (rt.total > rt.begin)
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(grid_for((rt.total - rt.begin + 3) / 4)), dim3(256), 0, st, scratch + B.slabs, rt);
-    ABN_CHECK_LAUNCH("slab_reduce");
-    return ABN_OK;
+    return reduce_slabs(t, B, scratch, l_first, l_end, st);
 }
 
 // Backward of a forward that went through the layer-per-launch kernels (same predicate): per layer, top down,
@@ -1626,13 +1694,9 @@ static int wide_backward(const abn_tower_desc* t, const float* d_out, const Loss
     const PackLayout PL = make_pack_layout(t);
     const char* const image = t->wpack ? reinterpret_cast<const char*>(t->wpack) : reinterpret_cast<const char*>(ws + L.wpack);
     static bool attr_set[16] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev = (dev >= 0 && dev < 16) ? dev : 0;
-    if (!attr_set[dev]) {
+    if (first_use_on_device(attr_set)) {
         PL_LDS_ATTR(wide_dgrad_layer_kernel, wd_lds_bytes);
         PL_LDS_ATTR(wgrad_planes_kernel, wgrad_lds_of);
-        attr_set[dev] = true;
     }
     const int64_t rpc = rows / n_calls;
     const int64_t wpc = bn_wgs_per_call(rows, n_calls), nrb = n_calls * wpc;
@@ -1696,13 +1760,376 @@ static int wide_backward(const abn_tower_desc* t, const float* d_out, const Loss
     w.tp_steps = 2 * nrb;
     if (n_wg > 0) launch_wgrad(np, w, n_wg, st);
     ABN_CHECK_LAUNCH("tower_backward (layer per launch)");
-    if (t->defer_reduce) return ABN_OK;               // abn_tower_reduce_step finishes the job
-    ReduceTable rt = make_reduce_table(t, B);
-    reduce_range(rt, t, B, l_first, l_end);
-    if (rt.total > rt.begin)
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(grid_for((rt.total - rt.begin + 3) / 4)), dim3(256), 0, st, scratch + B.slabs, rt);
-    ABN_CHECK_LAUNCH("slab_reduce");
+    return reduce_slabs(t, B, scratch, l_first, l_end, st);
+}
+
+// ---------------------------------------------------------------------------
+// forward launchers: one per ABN_PATH_* (abn_tower_forward checks, refuses and dispatches)
+// ---------------------------------------------------------------------------
+// What the operand-plane forwards share, as make_wgrad is to the weight gradients: the kernels' descriptor, the pack
+// jobs of the weight image (W_l and W_l^T as operand fragments) and -- unless the caller keeps a valid persistent
+// image -- the pack launch.  The one refusal (a misaligned image) comes before that launch.
+static int make_planes_fwd(const abn_tower_desc* t, const float* x1, const float* x2, int64_t rows, int64_t n_calls, int train,
+                           const Layout& L, float* ws, hipStream_t st, PlanesFwdP* out)
+{
+    const int np = planes_of(t);
+    PackTable pk = {};
+    PlanesFwdP f = {};
+    f.n_layers = t->n_layers;
+    f.rows = (int)rows;
+    f.rows_call = (int)(rows / n_calls);
+    f.x1 = x1; f.x2 = x2;
+    f.x_copy = nullptr;                      // the planes backward reads the transposed images only
+    const PackLayout PL = make_pack_layout(t);
+    char* const image = t->wpack ? reinterpret_cast<char*>(t->wpack) : reinterpret_cast<char*>(ws + L.wpack);
+    const bool repack = !(t->wpack && t->wpack_valid);
+    ABN_REQUIRE(aligned16(image), "tower_forward: wpack must be 16-byte aligned");
+    pk.base = image;
+    f.wbase = image; f.wbytes = PL.bytes;
+    for (int l = 0; l <= t->n_layers; ++l) f.dims[l] = (int)t->dims[l];
+    for (int l = 0; l < t->n_layers; ++l) {
+        f.act[l] = (l == t->n_layers - 1) ? t->last_act : t->act;
+        f.b[l] = t->b[l];
+        f.mask[l] = train ? t->drop_mask[l] : nullptr;
+        f.out[l] = l == t->n_layers - 1 ? ws + L.a[l] : nullptr;     // hidden activations live in tp[l + 1] only
+        f.wp[l] = image + PL.wp[l];
+        PackJob& J = pk.job[pk.n_jobs++];
+        J.W = t->W[l]; J.N = (int)t->dims[l + 1]; J.K = (int)t->dims[l]; J.transposed = 0;
+        J.nblk = pl_blocks(J.N); J.nsteps = pl_steps(J.K);
+        J.tile0 = pk.n_tiles; J.dst = PL.wp[l];
+        J.blk0 = pk.n_blocks;
+        pk.n_tiles += J.nblk * J.nsteps;
+        pk.n_blocks += J.nblk;
+        {                                    // W_l^T for the backward's data-gradient chain (l = 0: d loss / d input)
+            PackJob& T = pk.job[pk.n_jobs++];
+            T.W = t->W[l]; T.N = J.N; T.K = J.K; T.transposed = 1;
+            T.nblk = pl_blocks(T.K); T.nsteps = pl_steps(T.N);
+            T.tile0 = pk.n_tiles; T.dst = PL.wpt[l];
+            T.blk0 = pk.n_blocks;
+            pk.n_tiles += T.nblk * T.nsteps;
+            pk.n_blocks += T.nblk;
+        }
+        f.tp[l] = (t->forward_only || t->batch_norm) ? nullptr : reinterpret_cast<char*>(ws + L.tp[l]);     // (inference: nothing kept for a backward)
+        f.amax[l] = f.tp[l] && L.amax[l] >= 0 ? ws + L.amax[l] : nullptr;
+        if (t->batch_norm) { f.bn_rm[l] = t->bn_rm[l]; f.bn_rv[l] = t->bn_rv[l]; f.bn_w[l] = t->bn_w[l]; f.bn_b[l] = t->bn_b[l]; }
+    }
+    f.tp_steps = pl_row_steps(rows);
+    f.drop_seed = train ? reinterpret_cast<const unsigned long long*>(t->drop_seed) : nullptr;
+    f.drop_p = t->drop_p;
+    f.bn_eps = BN_EPS;
+#ifdef ABN_STAMPS
+    f.stamps = stamp_buffer("ABN_STAMP_BUF");
+#endif
+    if (repack) {
+        const dim3 pgrid((unsigned)((pk.n_tiles + 3) / 4));
+        if (np == 3) hipLaunchKernelGGL(pack_planes_kernel<3>, pgrid, dim3(256), 0, st, pk);
+        else if (np == 2) hipLaunchKernelGGL(pack_planes_scaled_kernel, dim3((unsigned)pk.n_blocks), dim3(PL_NT), 0, st, pk);
+        else hipLaunchKernelGGL(pack_planes_kernel<1>, pgrid, dim3(256), 0, st, pk);
+    }
+    *out = f;
     return ABN_OK;
+}
+
+// ABN_PATH_WIDE: one wide_fwd_layer_kernel per layer (tower_wide.h)
+static int wide_forward(const abn_tower_desc* t, const float* x1, const float* x2, int64_t rows, int64_t n_calls, int train,
+                        const Layout& L, float* ws, hipStream_t st)
+{
+    PlanesFwdP f;
+    { const int rc = make_planes_fwd(t, x1, x2, rows, n_calls, train, L, ws, st, &f); if (rc != ABN_OK) return rc; }
+    const int np = planes_of(t);
+    static bool wd_attr_set[16] = {};
+    if (first_use_on_device(wd_attr_set)) PL_LDS_ATTR(wide_fwd_layer_kernel, wd_lds_bytes);
+    const int nl = t->n_layers;
+    const int64_t wpc = bn_wgs_per_call(rows, n_calls), nrb = n_calls * wpc;
+    const int G = wide_groups_for(t, nrb * PL_ROWS);
+    const bool keep = !t->forward_only;              // transposed images for a backward
+    for (int l = 0; l < nl; ++l) {
+        WideFwdP q = {};
+        q.l = l; q.last = l == nl - 1;
+        q.K = (int)t->dims[l]; q.N = (int)t->dims[l + 1];
+        q.act = f.act[l];
+        q.rows_call = f.rows_call; q.n_calls = (int)n_calls; q.wpc = (int)wpc;
+        const int nblk = pl_blocks(q.N);
+        q.G = G < nblk ? G : nblk;
+        q.x1 = x1; q.x2 = x2;
+        q.a_prev = l >= 1 ? ws + L.a[l - 1] : nullptr;
+        q.wp = f.wp[l];
+        q.b = t->b[l];
+        q.a_out = q.last ? nullptr : ws + L.a[l];
+        q.out = q.last ? ws + L.a[l] : nullptr;
+        q.tp_in = keep && l == 0 ? reinterpret_cast<char*>(ws + L.tp[0]) : nullptr;
+        q.tp_out = keep && !q.last ? reinterpret_cast<char*>(ws + L.tp[l + 1]) : nullptr;
+        if (np == 2 && keep) { q.amax_in = ws + L.amax[0]; q.amax_out = q.last ? nullptr : ws + L.amax[l + 1]; }
+        q.tp_steps = 2 * nrb;
+        q.drop_seed = f.drop_seed; q.drop_p = f.drop_p;
+        if (t->source && l == 0) {
+            q.g_table = t->source->table; q.g_rows = t->source->table_rows;
+            q.g_idx1 = t->source->idx1; q.g_idx2 = t->source->idx2;
+            q.g_steps = t->source->steps; q.g_ctr = t->source->step_ctr;
+        }
+#ifdef ABN_STAMPS
+        q.stamps = f.stamps;                          // (the same buffer: read once per call)
+#endif
+        const dim3 wgrid((unsigned)(nrb * q.G));
+        PL_LAUNCH(np, wide_fwd_layer_kernel, wgrid, dim3(PL_NT), wd_lds_bytes(np), st, q);
+    }
+    ABN_CHECK_LAUNCH("tower_forward (layer per launch)");
+    return ABN_OK;
+}
+
+// ABN_PATH_BN_TOWER: every layer in ONE resident launch, grid barriers in between (tower_bn_persist.h)
+static int bn_tower_forward(const abn_tower_desc* t, const PlanesFwdP& f, int64_t n_calls, dim3 bgrid, const Layout& L, float* ws,
+                            hipStream_t st)
+{
+    const int nl = t->n_layers, np = planes_of(t);
+    static bool bt_attr_set[16] = {};
+    if (first_use_on_device(bt_attr_set)) PL_LDS_ATTR(bn_fwd_tower_kernel, bnp_lds_bytes);
+    PlanesFwdP fl = f;
+    BnPersistP q = {};
+    for (int l = 0; l < nl; ++l) {
+        fl.tp[l] = reinterpret_cast<char*>(ws + L.tp[l]);        // [a_{l-1} | 1] transposed: the weight gradient's operand
+        fl.amax[l] = L.amax[l] >= 0 ? ws + L.amax[l] : nullptr;
+        fl.out[l] = nullptr;
+        q.z[l] = ws + L.xhat[l];
+        q.mean[l] = ws + L.mean[l]; q.invstd[l] = ws + L.invstd[l]; q.var[l] = ws + L.var[l];
+        q.rm[l] = t->bn_rm[l]; q.rv[l] = t->bn_rv[l];
+        q.nbt[l] = reinterpret_cast<long long*>(t->bn_nbt[l]);
+    }
+    q.sync_ws = t->sync_ws;
+    q.sync_bytes = bnp_sync_bytes(BNP_MAX_WGS);
+    q.n_valid = t->n_valid;
+    q.n_calls = (int)n_calls;
+    q.a_top = ws + L.a[nl - 1];
+    PL_LAUNCH(np, bn_fwd_tower_kernel, bgrid, dim3(PL_NT), bnp_lds_bytes(np), st, fl, q);
+    ABN_CHECK_LAUNCH("tower_forward (BatchNorm, resident tower)");
+    return ABN_OK;
+}
+
+// ABN_PATH_BN_LAYERS: per layer [bn_fwd_layer_kernel, bn_stats_finish_wg_kernel (+ the cross-replica exchange)], then the
+// output layer's normalisation and the call counters.  The two cross-replica refusals stay inside the loop: layer 0's
+// launch (and the pack launch) are out by the time they can fire.
+static int bn_layers_forward(const abn_tower_desc* t, const PlanesFwdP& f, int64_t rows, int64_t n_calls, dim3 bgrid,
+                             const Layout& L, float* ws, hipStream_t st)
+{
+    const int nl = t->n_layers, np = planes_of(t);
+    const int64_t rpc = rows / n_calls, wpc = bn_wgs_per_call(rows, n_calls);
+    for (int l = 0; l < nl; ++l) {
+        PlanesFwdP fl = f;
+        for (int i = 0; i < nl; ++i) { fl.tp[i] = nullptr; fl.out[i] = nullptr; }
+        fl.tp[l] = reinterpret_cast<char*>(ws + L.tp[l]);        // [a_{l-1} | 1] transposed: the weight gradient's operand
+        fl.amax[l] = L.amax[l] >= 0 ? ws + L.amax[l] : nullptr;
+        fl.act[l] = ACT_NONE;                          // z_l leaves the launch as it is; act[l - 1] is applied on the way in
+        fl.out[l] = ws + L.xhat[l];                    // (z lands where xhat will live)
+        BnTrainP q = {};
+        q.l = l;
+        if (l > 0) { q.mean = ws + L.mean[l - 1]; q.invstd = ws + L.invstd[l - 1]; q.z_prev = ws + L.xhat[l - 1]; q.a_prev = nullptr; }
+        q.n_valid = t->n_valid;
+        PL_LAUNCH(np, bn_fwd_layer_kernel, bgrid, dim3(PL_NT), pl_lds_bytes(np), st, fl, q);
+        const int N = (int)t->dims[l + 1];
+        const bool sync = bn_sync_on(t);
+        ABN_REQUIRE(!sync || t->bn_sync_fn, "tower_forward: bn_sync_world = %d without bn_sync_fn", t->bn_sync_world);
+        if (sync && t->n_valid) { set_error("tower_forward: n_valid (a padded batch) cannot be combined with cross-replica BatchNorm statistics"); return ABN_E_UNSUPPORTED; }
+        double* const sums = reinterpret_cast<double*>(ws + L.bn_part);       // (the per-layer kernels' partials: idle here)
+        hipLaunchKernelGGL(bn_stats_finish_wg_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64 * BN_WG_GROUPS), 0, st, ws + L.bn_wg,
+                           (int)wpc, rpc, N, (int)n_calls, ws + L.mean[l], ws + L.invstd[l], ws + L.var[l],
+                           t->bn_rm[l], t->bn_rv[l], sync ? sums : static_cast<double*>(nullptr), t->n_valid);
+        if (sync) {
+            if (t->bn_sync_fn(t->bn_sync_ctx, sums, n_calls * 2 * N + n_calls, st) != 0) { set_error("tower_forward: bn_sync_fn failed"); return ABN_E_LAUNCH; }
+            hipLaunchKernelGGL(bn_stats_from_sums_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, sums,
+                               N, (int)n_calls, ws + L.mean[l], ws + L.invstd[l], ws + L.var[l],
+                               t->bn_rm[l], t->bn_rv[l], ws + L.bn_nstat + 8 * l);
+        }
+    }
+    const int N = (int)t->dims[nl];
+    const float* z = ws + L.xhat[nl - 1];      // (stays un-normalised, like every layer's: the backward normalises again)
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(rows * N)), dim3(256), 0, st, z, rows, rpc, N, ws + L.mean[nl - 1],
+                       ws + L.invstd[nl - 1], t->bn_rm[nl - 1], t->bn_rv[nl - 1], 1, t->bn_w[nl - 1], t->bn_b[nl - 1],
+                       t->last_act, static_cast<float*>(nullptr), ws + L.a[nl - 1], t->n_valid);
+    launch_nbt(t, n_calls, st);
+    ABN_CHECK_LAUNCH("tower_forward (BatchNorm, planes)");
+    return ABN_OK;
+}
+
+// The two BatchNorm training paths' common prologue: workgroups cut per forward_once call.
+static int bn_train_forward(const abn_tower_desc* t, const float* x1, const float* x2, int64_t rows, int64_t n_calls, int path,
+                            const Layout& L, float* ws, hipStream_t st)
+{
+    PlanesFwdP f;
+    { const int rc = make_planes_fwd(t, x1, x2, rows, n_calls, 1, L, ws, st, &f); if (rc != ABN_OK) return rc; }
+    static bool bn_attr_set[16] = {};
+    if (first_use_on_device(bn_attr_set)) PL_LDS_ATTR(bn_fwd_layer_kernel, pl_lds_bytes);
+    f.bn_part = ws + L.bn_wg;
+    const int64_t wpc = bn_wgs_per_call(rows, n_calls);
+    const dim3 bgrid((unsigned)(n_calls * wpc));
+    f.tp_steps = 2 * n_calls * wpc;                    // (the images' row axis is padded per call)
+    if (path == ABN_PATH_BN_TOWER) return bn_tower_forward(t, f, n_calls, bgrid, L, ws, st);
+    return bn_layers_forward(t, f, rows, n_calls, bgrid, L, ws, st);
+}
+
+// ABN_PATH_PLANES / _INFER / _INFER_BN: the whole tower in one tower_fwd_planes_kernel launch.  Inference (no mask, no
+// seed, nothing kept for a backward) has its own, lighter instantiations.
+static int planes_forward(const abn_tower_desc* t, const float* x1, const float* x2, int64_t rows, int64_t n_calls, int train,
+                          int path, const Layout& L, float* ws, hipStream_t st)
+{
+    PlanesFwdP f;
+    { const int rc = make_planes_fwd(t, x1, x2, rows, n_calls, train, L, ws, st, &f); if (rc != ABN_OK) return rc; }
+    const int np = planes_of(t);
+    const int mode = path == ABN_PATH_PLANES_INFER_BN ? PL_INFER_BN : path == ABN_PATH_PLANES_INFER ? PL_INFER : PL_TRAIN;
+    const size_t lds = mode == PL_INFER_BN ? pl_lds_bytes_bn(np) : pl_lds_bytes_stag(np);      // (the layers may stagger: two operand images)
+    const void* kernels[3][3] = {
+        {reinterpret_cast<const void*>(tower_fwd_planes_kernel<1, PL_TRAIN>), reinterpret_cast<const void*>(tower_fwd_planes_kernel<1, PL_INFER>),
+         reinterpret_cast<const void*>(tower_fwd_planes_kernel<1, PL_INFER_BN>)},
+        {reinterpret_cast<const void*>(tower_fwd_planes_kernel<2, PL_TRAIN>), reinterpret_cast<const void*>(tower_fwd_planes_kernel<2, PL_INFER>),
+         reinterpret_cast<const void*>(tower_fwd_planes_kernel<2, PL_INFER_BN>)},
+        {reinterpret_cast<const void*>(tower_fwd_planes_kernel<3, PL_TRAIN>), reinterpret_cast<const void*>(tower_fwd_planes_kernel<3, PL_INFER>),
+         reinterpret_cast<const void*>(tower_fwd_planes_kernel<3, PL_INFER_BN>)}};
+    static bool pl_attr_set[16] = {};
+    if (first_use_on_device(pl_attr_set))
+        for (int a = 0; a < 3; ++a)
+            for (int m = 0; m < 3; ++m)
+                (void)hipFuncSetAttribute(kernels[a][m], hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)(m == PL_INFER_BN ? pl_lds_bytes_bn(a + 1) : pl_lds_bytes_stag(a + 1)));
+    const dim3 fgrid((unsigned)((rows + PL_ROWS - 1) / PL_ROWS));
+    void* kargs[] = {&f};
+    (void)hipLaunchKernel(kernels[np - 1][mode], fgrid, dim3(PL_NT), kargs, lds, st);
+    ABN_CHECK_LAUNCH("tower_fwd_planes");
+    return ABN_OK;
+}
+
+// ABN_PATH_FUSED_F32: the whole tower in one tower_fwd_fused_kernel launch (tower_fused.h)
+static int fused_forward(const abn_tower_desc* t, const float* x1, const float* x2, int64_t rows, int64_t n_calls, int train,
+                         const Layout& L, float* ws, hipStream_t st)
+{
+    FusedFwdP f = {};
+    f.n_layers = t->n_layers;
+    f.rows = (int)rows;
+    f.rows_call = (int)(rows / n_calls);
+    f.bf16 = gemm_prec(t->precision);
+    f.x1 = x1; f.x2 = x2;
+    f.x_copy = x2 ? ws + L.x : nullptr;
+    for (int l = 0; l <= t->n_layers; ++l) f.dims[l] = (int)t->dims[l];
+    for (int l = 0; l < t->n_layers; ++l) {
+        f.act[l] = (l == t->n_layers - 1) ? t->last_act : t->act;
+        f.W[l] = t->W[l]; f.b[l] = t->b[l];
+        f.mask[l] = train ? t->drop_mask[l] : nullptr;
+        f.out[l] = ws + L.a[l];
+    }
+#ifdef ABN_STAMPS
+    f.stamps = stamp_buffer("ABN_STAMP_BUF");
+#endif
+    static bool attr_set[16] = {};
+    if (first_use_on_device(attr_set)) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tower_fwd_fused_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS_BYTES);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tower_fwd_fused_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS_BYTES);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tower_fwd_fused_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS_BYTES);
+    }
+    const dim3 fgrid((unsigned)((rows + FUSED_ROWS - 1) / FUSED_ROWS));
+    if (f.bf16 == 1) hipLaunchKernelGGL(tower_fwd_fused_kernel<1>, fgrid, dim3(FUSED_NT), FUSED_LDS_BYTES, st, f);
+    else if (f.bf16 == 2) hipLaunchKernelGGL(tower_fwd_fused_kernel<2>, fgrid, dim3(FUSED_NT), FUSED_LDS_BYTES, st, f);
+    else hipLaunchKernelGGL(tower_fwd_fused_kernel<0>, fgrid, dim3(FUSED_NT), FUSED_LDS_BYTES, st, f);
+    ABN_CHECK_LAUNCH("tower_fwd_fused");
+    return ABN_OK;
+}
+
+// ABN_PATH_PER_LAYER: one GEMM per layer (gemm_f32.h), BatchNorm as its own small launches
+static int gemm_forward(const abn_tower_desc* t, const float* x1, const float* x2, int64_t rows, int64_t n_calls, int train,
+                        const Layout& L, float* ws, hipStream_t st)
+{
+    const int64_t rpc = rows / n_calls;
+    const float* in = x1;
+    if (x2) {    // the two towers' inputs become one [2B, D] operand
+        const size_t half = (size_t)rpc * t->dims[0] * sizeof(float);
+        if (hipMemcpyAsync(ws + L.x, x1, half, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(ws + L.x + rpc * t->dims[0], x2, half, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+            set_error("tower_forward: input copy failed");
+            return ABN_E_LAUNCH;
+        }
+        in = ws + L.x;
+    }
+    for (int l = 0; l < t->n_layers; ++l) {
+        const int K = (int)t->dims[l], N = (int)t->dims[l + 1];
+        const int act = (l == t->n_layers - 1) ? t->last_act : t->act;
+        const float* mask = train ? t->drop_mask[l] : nullptr;
+        float* a = ws + L.a[l];
+        float* z = t->batch_norm ? ws + L.xhat[l] : a;      // BatchNorm: z lands where xhat will live, the activation follows it
+        const int rc = launch_gemm<true, true, EPI_FWD>(
+            fwd_gemm(in, t->W[l], t->b[l], z, rows, K, N, t->batch_norm ? (int)ACT_NONE : act, mask, gemm_prec(t->precision)), 1, st);
+        if (rc != ABN_OK) return rc;
+        if (t->batch_norm) {
+            if (train) {
+                const int nch = bn_chunks(rpc);
+                double* part = reinterpret_cast<double*>(ws + L.bn_part);
+                hipLaunchKernelGGL(bn_partial_kernel<false>, dim3((N + 63) / 64, nch, (int)n_calls), dim3(256), 0, st, z,
+                                   nullptr, nullptr, rpc, N, bn_chunk_rows(rpc), 0, part);
+                hipLaunchKernelGGL(bn_stats_finish_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, part, nch, rpc,
+                                   N, (int)n_calls, ws + L.mean[l], ws + L.invstd[l], ws + L.var[l], t->bn_rm[l],
+                                   t->bn_rv[l]);
+            }
+            hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(rows * N)), dim3(256), 0, st, z, rows, rpc, N,
+                               ws + L.mean[l], ws + L.invstd[l], t->bn_rm[l], t->bn_rv[l], train, t->bn_w[l],
+                               t->bn_b[l], act, z, a);
+            ABN_CHECK_LAUNCH("batch_norm forward");
+        }
+        in = a;
+    }
+    if (train && t->batch_norm) { launch_nbt(t, n_calls, st); ABN_CHECK_LAUNCH("batch_norm counters"); }
+    return ABN_OK;
+}
+
+// ABN_PATH_PER_LAYER, backward: per layer, top down, the weight-gradient and data-gradient GEMMs (one grid where
+// launch_bwd_pair can), BatchNorm's backward as its own launches, then the slab reduction.
+static int gemm_backward(const abn_tower_desc* t, const float* xin, const float* d_out, int64_t rows, int64_t n_calls, const Layout& L,
+                         const BwdLayout& B, const float* ws, float* scratch, float* dx, hipStream_t st)
+{
+    const int nl = t->n_layers;
+    const int prec = gemm_prec(t->precision);
+    int cur = 0;
+    const float* dz_in = nullptr;                // the output layer's dz when the caller supplied it
+
+    // dz of the output layer from d_out
+    {
+        const int N = (int)t->dims[nl];
+        const float* a = ws + L.a[nl - 1];
+        float* dz = scratch + B.dz[cur];
+        if (t->d_out_is_dz) {
+            ABN_REQUIRE(!t->batch_norm, "tower_backward: d_out_is_dz cannot be combined with batch_norm");
+            dz_in = d_out;                       // abn_pair_loss_dz already applied act' and the dropout mask
+        } else if (!t->batch_norm) {
+            hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(rows * N)), dim3(256), 0, st, a, d_out,
+                               t->drop_mask[nl - 1], dz, rows * N, t->last_act);
+        } else {
+            bn_layer_backward(t, nl - 1, t->last_act, d_out, dz, rows, n_calls, L, B, ws, scratch, st);
+        }
+        ABN_CHECK_LAUNCH("output-layer dz");
+    }
+
+    float* slabs = scratch + B.slabs;
+    for (int l = nl - 1; l >= 0; --l) {
+        const int Kin = (int)t->dims[l], Nout = (int)t->dims[l + 1];
+        const float* dz = (l == nl - 1 && dz_in) ? dz_in : scratch + B.dz[cur];
+        const float* a_in = (l == 0) ? xin : ws + L.a[l - 1];
+        // wgrad: dW[Nout, Kin] (+ db via the ones column) = dz^T a_in, split over rows
+        // (slices past the end of the reduction write zero slabs: k range empty)
+        const GemmP pw = wgrad_gemm(dz, a_in, rows, Kin, Nout, slabs + B.off[l], B.slab_stride, B.splits[l], prec);
+        if (!(l > 0 || dx)) {
+            const int rc = launch_gemm<false, false, EPI_WGRAD>(pw, B.splits[l], st);
+            if (rc != ABN_OK) return rc;
+            continue;
+        }
+        // dgrad: d a_{l-1} = dz W_l, times act'(a_{l-1}) when no BN sits in between.  Both
+        // GEMMs read dz only: they go out as one grid (launch_bwd_pair).
+        float* dst = (l == 0) ? dx : scratch + B.dz[cur ^ 1];
+        const bool fuse_act = l > 0 && !t->batch_norm;
+        const DgradAux aux = fuse_act ? DgradAux{ws + L.a[l - 1], Kin, t->act, t->drop_mask[l - 1]} : DgradAux{};
+        const int rc = launch_bwd_pair(pw, B.splits[l], dgrad_gemm(dz, t->W[l], dst, rows, Kin, Nout, aux, prec), st);
+        if (rc != ABN_OK) return rc;
+        if (l > 0 && t->batch_norm) {            // dst holds d a_{l-1}; turn it into d z_{l-1} through act' and BN
+            bn_layer_backward(t, l - 1, t->act, dst, dst, rows, n_calls, L, B, ws, scratch, st);
+            ABN_CHECK_LAUNCH("batch_norm backward");
+        }
+        cur ^= 1;
+    }
+    return reduce_slabs(t, B, scratch, 0, nl, st);
 }
 
 }  // namespace abn
@@ -1827,12 +2254,11 @@ int abn_tower_forward(const abn_tower_desc* t, const float* x1, const float* x2,
     if (rows == 0) return ABN_OK;
     hipStream_t st = (hipStream_t)stream;
     const Layout L = make_layout(t, rows, n_calls);
-    const int64_t rpc = rows / n_calls;
 
+    // the path abn_tower_path reports; what it cannot serve is refused here, before any launch
     const int path = forward_path(t, x1, x2, rows, n_calls, train, ws);
-    const bool fusable = path == ABN_PATH_FUSED_F32;
-    const int pmode = train ? PLANES_TRAIN : PLANES_EVAL_FORWARD;
-    const bool bn_train = train && bn_train_planes_path(t, rows, n_calls, x1, x2, ws);
+    const bool bn_train = path == ABN_PATH_BN_TOWER || path == ABN_PATH_BN_LAYERS;
+    const bool gemm_kernels = path == ABN_PATH_PER_LAYER || path == ABN_PATH_FUSED_F32;      // (no operand planes)
     if (train && t->batch_norm && bn_sync_on(t) && !bn_train) {
         set_error("tower_forward: cross-replica BatchNorm statistics (bn_sync_world) need the operand-plane launches");
         return ABN_E_UNSUPPORTED;
@@ -1841,309 +2267,27 @@ int abn_tower_forward(const abn_tower_desc* t, const float* x1, const float* x2,
         set_error("tower_forward: a padded batch (n_valid) through a BatchNorm tower in training needs the BatchNorm layer launches");
         return ABN_E_UNSUPPORTED;
     }
-    const int kind = planes_kind(t, rows, n_calls, x1, x2, ws, pmode);
-    if (t->source && !(train && !bn_train && kind == PLANES_WIDE && n_calls == 2 && x2 && !t->forward_only)) {
+    if (t->source && !(train && path == ABN_PATH_WIDE && n_calls == 2 && x2 && !t->forward_only)) {
         set_error("tower_forward: a step source (abn_tower_desc.source) needs the layer-per-launch kernels in training, two calls");
         return ABN_E_UNSUPPORTED;
     }
     if (t->source) ABN_REQUIRE(t->source->table && t->source->idx1 && t->source->idx2 && t->source->steps && t->source->step_ctr &&
                                    aligned16(t->source->table) && t->dims[0] % 4 == 0,
                                "tower_forward: abn_step_source: null or misaligned array");
-    if (t->drop_seed && train && !bn_train && kind == PLANES_NONE) {
+    if (t->drop_seed && train && gemm_kernels) {
         for (int l = 0; l < t->n_layers; ++l)
             if (!t->drop_mask[l]) { set_error("tower_forward: in-kernel dropout (drop_seed) needs the operand-plane kernels: pass drop_mask tensors"); return ABN_E_UNSUPPORTED; }
     }
-    if (bn_train || kind != PLANES_NONE) {
-        const int np = planes_of(t);
-        PackTable pk = {};
-        PlanesFwdP f = {};
-        f.n_layers = t->n_layers;
-        f.rows = (int)rows;
-        f.rows_call = (int)rpc;
-        f.x1 = x1; f.x2 = x2;
-        f.x_copy = nullptr;                      // the planes backward reads the transposed images only
-        const PackLayout PL = make_pack_layout(t);
-        char* const image = t->wpack ? reinterpret_cast<char*>(t->wpack) : reinterpret_cast<char*>(ws + L.wpack);
-        const bool repack = !(t->wpack && t->wpack_valid);
-        ABN_REQUIRE(aligned16(image), "tower_forward: wpack must be 16-byte aligned");
-        pk.base = image;
-        f.wbase = image; f.wbytes = PL.bytes;
-        for (int l = 0; l <= t->n_layers; ++l) f.dims[l] = (int)t->dims[l];
-        for (int l = 0; l < t->n_layers; ++l) {
-            f.act[l] = (l == t->n_layers - 1) ? t->last_act : t->act;
-            f.b[l] = t->b[l];
-            f.mask[l] = train ? t->drop_mask[l] : nullptr;
-            f.out[l] = l == t->n_layers - 1 ? ws + L.a[l] : nullptr;     // hidden activations live in tp[l + 1] only
-            f.wp[l] = image + PL.wp[l];
-            PackJob& J = pk.job[pk.n_jobs++];
-            J.W = t->W[l]; J.N = (int)t->dims[l + 1]; J.K = (int)t->dims[l]; J.transposed = 0;
-            J.nblk = pl_blocks(J.N); J.nsteps = pl_steps(J.K);
-            J.tile0 = pk.n_tiles; J.dst = PL.wp[l];
-            J.blk0 = pk.n_blocks;
-            pk.n_tiles += J.nblk * J.nsteps;
-            pk.n_blocks += J.nblk;
-            {                                    // W_l^T for the backward's data-gradient chain (l = 0: d loss / d input)
-                PackJob& T = pk.job[pk.n_jobs++];
-                T.W = t->W[l]; T.N = J.N; T.K = J.K; T.transposed = 1;
-                T.nblk = pl_blocks(T.K); T.nsteps = pl_steps(T.N);
-                T.tile0 = pk.n_tiles; T.dst = PL.wpt[l];
-                T.blk0 = pk.n_blocks;
-                pk.n_tiles += T.nblk * T.nsteps;
-                pk.n_blocks += T.nblk;
-            }
-            f.tp[l] = (t->forward_only || t->batch_norm) ? nullptr : reinterpret_cast<char*>(ws + L.tp[l]);     // (inference: nothing kept for a backward)
-            f.amax[l] = f.tp[l] && L.amax[l] >= 0 ? ws + L.amax[l] : nullptr;
-            if (t->batch_norm) { f.bn_rm[l] = t->bn_rm[l]; f.bn_rv[l] = t->bn_rv[l]; f.bn_w[l] = t->bn_w[l]; f.bn_b[l] = t->bn_b[l]; }
-        }
-        f.tp_steps = pl_row_steps(rows);
-        f.drop_seed = train ? reinterpret_cast<const unsigned long long*>(t->drop_seed) : nullptr;
-        f.drop_p = t->drop_p;
-        f.bn_eps = BN_EPS;
-#ifdef ABN_STAMPS
-        f.stamps = getenv("ABN_STAMP_BUF") ? (unsigned long long*)strtoull(getenv("ABN_STAMP_BUF"), nullptr, 0) : nullptr;
-#endif
-        static bool pl_attr_set[16] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        dev = (dev >= 0 && dev < 16) ? dev : 0;
-        const dim3 pgrid((unsigned)((pk.n_tiles + 3) / 4));
-        const dim3 fgrid((unsigned)((rows + PL_ROWS - 1) / PL_ROWS));
-        if (repack) {
-            if (np == 3) hipLaunchKernelGGL(pack_planes_kernel<3>, pgrid, dim3(256), 0, st, pk);
-            else if (np == 2) hipLaunchKernelGGL(pack_planes_scaled_kernel, dim3((unsigned)pk.n_blocks), dim3(PL_NT), 0, st, pk);
-            else hipLaunchKernelGGL(pack_planes_kernel<1>, pgrid, dim3(256), 0, st, pk);
-        }
-        if (!bn_train && kind == PLANES_WIDE) {
-            static bool wd_attr_set[16] = {};
-            if (!wd_attr_set[dev]) {
-                PL_LDS_ATTR(wide_fwd_layer_kernel, wd_lds_bytes);
-                wd_attr_set[dev] = true;
-            }
-            const int nl = t->n_layers;
-            const int64_t wpc = bn_wgs_per_call(rows, n_calls), nrb = n_calls * wpc;
-            const int G = wide_groups_for(t, nrb * PL_ROWS);
-            const bool keep = !t->forward_only;              // transposed images for a backward
-            for (int l = 0; l < nl; ++l) {
-                WideFwdP q = {};
-                q.l = l; q.last = l == nl - 1;
-                q.K = (int)t->dims[l]; q.N = (int)t->dims[l + 1];
-                q.act = f.act[l];
-                q.rows_call = (int)rpc; q.n_calls = (int)n_calls; q.wpc = (int)wpc;
-                const int nblk = pl_blocks(q.N);
-                q.G = G < nblk ? G : nblk;
-                q.x1 = x1; q.x2 = x2;
-                q.a_prev = l >= 1 ? ws + L.a[l - 1] : nullptr;
-                q.wp = f.wp[l];
-                q.b = t->b[l];
-                q.a_out = q.last ? nullptr : ws + L.a[l];
-                q.out = q.last ? ws + L.a[l] : nullptr;
-                q.tp_in = keep && l == 0 ? reinterpret_cast<char*>(ws + L.tp[0]) : nullptr;
-                q.tp_out = keep && !q.last ? reinterpret_cast<char*>(ws + L.tp[l + 1]) : nullptr;
-                if (np == 2 && keep) { q.amax_in = ws + L.amax[0]; q.amax_out = q.last ? nullptr : ws + L.amax[l + 1]; }
-                q.tp_steps = 2 * nrb;
-                q.drop_seed = f.drop_seed; q.drop_p = f.drop_p;
-                if (t->source && l == 0) {
-                    q.g_table = t->source->table; q.g_rows = t->source->table_rows;
-                    q.g_idx1 = t->source->idx1; q.g_idx2 = t->source->idx2;
-                    q.g_steps = t->source->steps; q.g_ctr = t->source->step_ctr;
-                }
-#ifdef ABN_STAMPS
-                q.stamps = getenv("ABN_STAMP_BUF") ? (unsigned long long*)strtoull(getenv("ABN_STAMP_BUF"), nullptr, 0) : nullptr;
-#endif
-                const dim3 wgrid((unsigned)(nrb * q.G));
-                PL_LAUNCH(np, wide_fwd_layer_kernel, wgrid, dim3(PL_NT), wd_lds_bytes(np), st, q);
-            }
-            ABN_CHECK_LAUNCH("tower_forward (layer per launch)");
-            return ABN_OK;
-        }
-        if (bn_train) {
-            static bool bn_attr_set[16] = {};
-            if (!bn_attr_set[dev]) {
-                PL_LDS_ATTR(bn_fwd_layer_kernel, pl_lds_bytes);
-                bn_attr_set[dev] = true;
-            }
-            f.bn_part = ws + L.bn_wg;
-            const int nl = t->n_layers;
-            const int64_t wpc = bn_wgs_per_call(rows, n_calls);
-            const dim3 bgrid((unsigned)(n_calls * wpc));
-            f.tp_steps = 2 * n_calls * wpc;                    // (the images' row axis is padded per call)
-            if (bn_persist_path(t, rows, n_calls)) {
-                // every layer in ONE resident launch, grid barriers in between (tower_bn_persist.h)
-                static bool bt_attr_set[16] = {};
-                if (!bt_attr_set[dev]) {
-                    PL_LDS_ATTR(bn_fwd_tower_kernel, bnp_lds_bytes);
-                    bt_attr_set[dev] = true;
-                }
-                PlanesFwdP fl = f;
-                BnPersistP q = {};
-                for (int l = 0; l < nl; ++l) {
-                    fl.tp[l] = reinterpret_cast<char*>(ws + L.tp[l]);        // [a_{l-1} | 1] transposed: the weight gradient's operand
-                    fl.amax[l] = L.amax[l] >= 0 ? ws + L.amax[l] : nullptr;
-                    fl.out[l] = nullptr;
-                    q.z[l] = ws + L.xhat[l];
-                    q.mean[l] = ws + L.mean[l]; q.invstd[l] = ws + L.invstd[l]; q.var[l] = ws + L.var[l];
-                    q.rm[l] = t->bn_rm[l]; q.rv[l] = t->bn_rv[l];
-                    q.nbt[l] = reinterpret_cast<long long*>(t->bn_nbt[l]);
-                }
-                q.sync_ws = t->sync_ws;
-                q.sync_bytes = bnp_sync_bytes(BNP_MAX_WGS);
-                q.n_valid = t->n_valid;
-                q.n_calls = (int)n_calls;
-                q.a_top = ws + L.a[nl - 1];
-                PL_LAUNCH(np, bn_fwd_tower_kernel, bgrid, dim3(PL_NT), bnp_lds_bytes(np), st, fl, q);
-                ABN_CHECK_LAUNCH("tower_forward (BatchNorm, resident tower)");
-                return ABN_OK;
-            }
-            for (int l = 0; l < nl; ++l) {
-                PlanesFwdP fl = f;
-                for (int i = 0; i < nl; ++i) { fl.tp[i] = nullptr; fl.out[i] = nullptr; }
-                fl.tp[l] = reinterpret_cast<char*>(ws + L.tp[l]);        // [a_{l-1} | 1] transposed: the weight gradient's operand
-                fl.amax[l] = L.amax[l] >= 0 ? ws + L.amax[l] : nullptr;
-                fl.act[l] = ACT_NONE;                          // z_l leaves the launch as it is; act[l - 1] is applied on the way in
-                fl.out[l] = ws + L.xhat[l];                    // (z lands where xhat will live)
-                BnTrainP q = {};
-                q.l = l;
-                if (l > 0) { q.mean = ws + L.mean[l - 1]; q.invstd = ws + L.invstd[l - 1]; q.z_prev = ws + L.xhat[l - 1]; q.a_prev = nullptr; }
-                q.n_valid = t->n_valid;
-                PL_LAUNCH(np, bn_fwd_layer_kernel, bgrid, dim3(PL_NT), pl_lds_bytes(np), st, fl, q);
-                const int N = (int)t->dims[l + 1];
-                const bool sync = bn_sync_on(t);
-                ABN_REQUIRE(!sync || t->bn_sync_fn, "tower_forward: bn_sync_world = %d without bn_sync_fn", t->bn_sync_world);
-                if (sync && t->n_valid) { set_error("tower_forward: n_valid (a padded batch) cannot be combined with cross-replica BatchNorm statistics"); return ABN_E_UNSUPPORTED; }
-                double* const sums = reinterpret_cast<double*>(ws + L.bn_part);       // (the per-layer kernels' partials: idle here)
-                hipLaunchKernelGGL(bn_stats_finish_wg_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64 * BN_WG_GROUPS), 0, st, ws + L.bn_wg,
-                                   (int)wpc, rpc, N, (int)n_calls, ws + L.mean[l], ws + L.invstd[l], ws + L.var[l],
-                                   t->bn_rm[l], t->bn_rv[l], sync ? sums : static_cast<double*>(nullptr), t->n_valid);
-                if (sync) {
-                    if (t->bn_sync_fn(t->bn_sync_ctx, sums, n_calls * 2 * N + n_calls, st) != 0) { set_error("tower_forward: bn_sync_fn failed"); return ABN_E_LAUNCH; }
-                    hipLaunchKernelGGL(bn_stats_from_sums_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, sums,
-                                       N, (int)n_calls, ws + L.mean[l], ws + L.invstd[l], ws + L.var[l],
-                                       t->bn_rm[l], t->bn_rv[l], ws + L.bn_nstat + 8 * l);
-                }
-            }
-            const int N = (int)t->dims[nl];
-            const float* z = ws + L.xhat[nl - 1];      // (stays un-normalised, like every layer's: the backward normalises again)
-            hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(rows * N)), dim3(256), 0, st, z, rows, rpc, N, ws + L.mean[nl - 1],
-                               ws + L.invstd[nl - 1], t->bn_rm[nl - 1], t->bn_rv[nl - 1], 1, t->bn_w[nl - 1], t->bn_b[nl - 1],
-                               t->last_act, static_cast<float*>(nullptr), ws + L.a[nl - 1], t->n_valid);
-            launch_nbt(t, n_calls, st);
-            ABN_CHECK_LAUNCH("tower_forward (BatchNorm, planes)");
-            return ABN_OK;
-        }
-        // inference (no mask, no seed, nothing kept for a backward) has its own, lighter instantiations
-        const bool infer = t->batch_norm || (t->forward_only && !f.drop_seed && !train);
-        const int mode = t->batch_norm ? PL_INFER_BN : infer ? PL_INFER : PL_TRAIN;
-        const size_t lds = t->batch_norm ? pl_lds_bytes_bn(np) : pl_lds_bytes_stag(np);      // (the layers may stagger: two operand images)
-        const void* kernels[3][3] = {
-            {reinterpret_cast<const void*>(tower_fwd_planes_kernel<1, PL_TRAIN>), reinterpret_cast<const void*>(tower_fwd_planes_kernel<1, PL_INFER>),
-             reinterpret_cast<const void*>(tower_fwd_planes_kernel<1, PL_INFER_BN>)},
-            {reinterpret_cast<const void*>(tower_fwd_planes_kernel<2, PL_TRAIN>), reinterpret_cast<const void*>(tower_fwd_planes_kernel<2, PL_INFER>),
-             reinterpret_cast<const void*>(tower_fwd_planes_kernel<2, PL_INFER_BN>)},
-            {reinterpret_cast<const void*>(tower_fwd_planes_kernel<3, PL_TRAIN>), reinterpret_cast<const void*>(tower_fwd_planes_kernel<3, PL_INFER>),
-             reinterpret_cast<const void*>(tower_fwd_planes_kernel<3, PL_INFER_BN>)}};
-        if (!pl_attr_set[dev]) {
-            for (int a = 0; a < 3; ++a)
-                for (int m = 0; m < 3; ++m)
-                    if (kernels[a][m])
-                        (void)hipFuncSetAttribute(kernels[a][m], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)(m == PL_INFER_BN ? pl_lds_bytes_bn(a + 1) : pl_lds_bytes_stag(a + 1)));
-            pl_attr_set[dev] = true;
-        }
-        void* kargs[] = {&f};
-        (void)hipLaunchKernel(kernels[np - 1][mode], fgrid, dim3(PL_NT), kargs, lds, st);
-        ABN_CHECK_LAUNCH("tower_fwd_planes");
-        return ABN_OK;
+    switch (path) {
+        case ABN_PATH_WIDE: return wide_forward(t, x1, x2, rows, n_calls, train, L, ws, st);
+        case ABN_PATH_BN_TOWER:
+        case ABN_PATH_BN_LAYERS: return bn_train_forward(t, x1, x2, rows, n_calls, path, L, ws, st);
+        case ABN_PATH_PLANES:
+        case ABN_PATH_PLANES_INFER:
+        case ABN_PATH_PLANES_INFER_BN: return planes_forward(t, x1, x2, rows, n_calls, train, path, L, ws, st);
+        case ABN_PATH_FUSED_F32: return fused_forward(t, x1, x2, rows, n_calls, train, L, ws, st);
+        default: return gemm_forward(t, x1, x2, rows, n_calls, train, L, ws, st);
     }
-    if (fusable) {
-        FusedFwdP f = {};
-        f.n_layers = t->n_layers;
-        f.rows = (int)rows;
-        f.rows_call = (int)rpc;
-        f.bf16 = gemm_prec(t->precision);
-        f.x1 = x1; f.x2 = x2;
-        f.x_copy = x2 ? ws + L.x : nullptr;
-        for (int l = 0; l <= t->n_layers; ++l) f.dims[l] = (int)t->dims[l];
-        for (int l = 0; l < t->n_layers; ++l) {
-            f.act[l] = (l == t->n_layers - 1) ? t->last_act : t->act;
-            f.W[l] = t->W[l]; f.b[l] = t->b[l];
-            f.mask[l] = train ? t->drop_mask[l] : nullptr;
-            f.out[l] = ws + L.a[l];
-        }
-#ifdef ABN_STAMPS
-        f.stamps = getenv("ABN_STAMP_BUF") ? (unsigned long long*)strtoull(getenv("ABN_STAMP_BUF"), nullptr, 0) : nullptr;
-#endif
-        static bool attr_set[16] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        dev = (dev >= 0 && dev < 16) ? dev : 0;
-        if (!attr_set[dev]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tower_fwd_fused_kernel<0>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS_BYTES);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tower_fwd_fused_kernel<1>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS_BYTES);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(tower_fwd_fused_kernel<2>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS_BYTES);
-            attr_set[dev] = true;
-        }
-        const dim3 fgrid((unsigned)((rows + FUSED_ROWS - 1) / FUSED_ROWS));
-        if (f.bf16 == 1) hipLaunchKernelGGL(tower_fwd_fused_kernel<1>, fgrid, dim3(FUSED_NT), FUSED_LDS_BYTES, st, f);
-        else if (f.bf16 == 2) hipLaunchKernelGGL(tower_fwd_fused_kernel<2>, fgrid, dim3(FUSED_NT), FUSED_LDS_BYTES, st, f);
-        else hipLaunchKernelGGL(tower_fwd_fused_kernel<0>, fgrid, dim3(FUSED_NT), FUSED_LDS_BYTES, st, f);
-        ABN_CHECK_LAUNCH("tower_fwd_fused");
-        return ABN_OK;
-    }
-
-    const float* in = x1;
-    if (x2) {    // the two towers' inputs become one [2B, D] operand
-        const size_t half = (size_t)rpc * t->dims[0] * sizeof(float);
-        if (hipMemcpyAsync(ws + L.x, x1, half, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(ws + L.x + rpc * t->dims[0], x2, half, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-            set_error("tower_forward: input copy failed");
-            return ABN_E_LAUNCH;
-        }
-        in = ws + L.x;
-    }
-    for (int l = 0; l < t->n_layers; ++l) {
-        const int K = (int)t->dims[l], N = (int)t->dims[l + 1];
-        const int act = (l == t->n_layers - 1) ? t->last_act : t->act;
-        float* a = ws + L.a[l];
-        GemmP p = {};
-        p.A = in; p.lda = K;
-        p.B = t->W[l]; p.ldb = K;
-        p.M = (int)rows; p.N = N; p.K = K; p.k_chunk = K;
-        p.bias = t->b[l];
-        p.mask = train ? t->drop_mask[l] : nullptr;
-        p.a_vec = aligned16(in) && (K % 4 == 0);
-        p.b_vec = aligned16(t->W[l]) && (K % 4 == 0);
-        p.ones_col = -1;
-        p.bf16 = gemm_prec(t->precision);
-        if (!t->batch_norm) {
-            p.C = a; p.ldc = N; p.act = act;
-            rc = launch_gemm<true, true, EPI_FWD>(p, 1, st);
-            if (rc != ABN_OK) return rc;
-        } else {
-            float* z = ws + L.xhat[l];          // z lands where xhat will live
-            p.C = z; p.ldc = N; p.act = ACT_NONE;
-            rc = launch_gemm<true, true, EPI_FWD>(p, 1, st);
-            if (rc != ABN_OK) return rc;
-            if (train) {
-                const int nch = bn_chunks(rpc);
-                double* part = reinterpret_cast<double*>(ws + L.bn_part);
-                hipLaunchKernelGGL(bn_partial_kernel<false>, dim3((N + 63) / 64, nch, (int)n_calls), dim3(256), 0, st, z,
-                                   nullptr, nullptr, rpc, N, bn_chunk_rows(rpc), 0, part);
-                hipLaunchKernelGGL(bn_stats_finish_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, part, nch, rpc,
-                                   N, (int)n_calls, ws + L.mean[l], ws + L.invstd[l], ws + L.var[l], t->bn_rm[l],
-                                   t->bn_rv[l]);
-            }
-            hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(rows * N)), dim3(256), 0, st, z, rows, rpc, N,
-                               ws + L.mean[l], ws + L.invstd[l], t->bn_rm[l], t->bn_rv[l], train, t->bn_w[l],
-                               t->bn_b[l], act, z, a);
-            ABN_CHECK_LAUNCH("batch_norm forward");
-        }
-        in = a;
-    }
-    if (train && t->batch_norm) { launch_nbt(t, n_calls, st); ABN_CHECK_LAUNCH("batch_norm counters"); }
-    return ABN_OK;
 }
 
 int abn_tower_backward(const abn_tower_desc* t, const float* x1, const float* x2, const float* d_out,
@@ -2165,24 +2309,18 @@ int abn_tower_backward(const abn_tower_desc* t, const float* x1, const float* x2
         set_error("tower_backward: scratch too small (%lld < %lld floats)", (long long)scratch_floats, (long long)B.total);
         return ABN_E_WORKSPACE;
     }
-    const int64_t rpc = rows / n_calls;
-    const float* xin = x2 ? ws + L.x : x1;
-    const int nl = t->n_layers;
-
-    // The forward that filled `ws` went through the planes kernels (same predicate): its workspace
-    // holds W^T and the weight-gradient operands as operand fragments.  Two launches: the data
-    // gradient chain (one workgroup per 32 rows, all layers), then every layer's weight gradient.
     ABN_REQUIRE(!t->source, "tower_backward: a step source (abn_tower_desc.source) goes with abn_tower_backward_loss (the labels are the plan's)");
-    {
-        const int kind = planes_kind(t, rows, n_calls, x1, x2, ws);
-        if (kind == PLANES_WIDE) { return wide_backward(t, d_out, nullptr, rows, n_calls, L, B, ws, scratch, dx, st); }
-        if (kind == PLANES_CHAIN) { return planes_backward(t, d_out, nullptr, rows, L, B, ws, scratch, dx, st); }
-    }
+
+    // The path abn_tower_path reports for the backward: the forward that filled `ws` took the same kernels' path
+    // (same predicates) and left what they read -- W^T and the weight-gradient operands as operand fragments.
+    const int path = backward_path(t, x1, x2, rows, n_calls, ws);
+    if (path == ABN_PATH_WIDE) return wide_backward(t, d_out, nullptr, rows, n_calls, L, B, ws, scratch, dx, st);
+    if (path == ABN_PATH_PLANES) return planes_backward(t, d_out, nullptr, rows, L, B, ws, scratch, dx, st);
     if (t->wgrad_part != 0) {
         set_error("tower_backward: wgrad_part needs the operand-plane launches of a tower without BatchNorm");
         return ABN_E_UNSUPPORTED;
     }
-    if (bn_train_planes_path(t, rows, n_calls, x1, x2, ws)) { return bn_planes_backward(t, d_out, nullptr, rows, n_calls, L, B, ws, scratch, dx, st); }
+    if (path == ABN_PATH_BN_TOWER || path == ABN_PATH_BN_LAYERS) return bn_planes_backward(t, d_out, nullptr, rows, n_calls, L, B, ws, scratch, dx, st);
     if (t->batch_norm && bn_sync_on(t)) {
         set_error("tower_backward: cross-replica BatchNorm statistics (bn_sync_world) need the operand-plane launches");
         return ABN_E_UNSUPPORTED;
@@ -2191,98 +2329,7 @@ int abn_tower_backward(const abn_tower_desc* t, const float* x1, const float* x2
         set_error("tower_backward: a padded batch (n_valid) through a BatchNorm tower needs the BatchNorm layer launches");
         return ABN_E_UNSUPPORTED;
     }
-
-    int cur = 0;
-    const float* dz_in = nullptr;                // the output layer's dz when the caller supplied it
-
-    // dz of the output layer from d_out
-    {
-        const int N = (int)t->dims[nl];
-        const float* a = ws + L.a[nl - 1];
-        float* dz = scratch + B.dz[cur];
-        if (t->d_out_is_dz) {
-            ABN_REQUIRE(!t->batch_norm, "tower_backward: d_out_is_dz cannot be combined with batch_norm");
-            dz_in = d_out;                       // abn_pair_loss_dz already applied act' and the dropout mask
-        } else if (!t->batch_norm) {
-            hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(rows * N)), dim3(256), 0, st, a, d_out,
-                               t->drop_mask[nl - 1], dz, rows * N, t->last_act);
-        } else {
-            const int nch = bn_chunks(rpc);
-            double* part = reinterpret_cast<double*>(scratch + B.bn_part);
-            hipLaunchKernelGGL(bn_partial_kernel<true>, dim3((N + 63) / 64, nch, (int)n_calls), dim3(256), 0, st, d_out, a,
-                               ws + L.xhat[nl - 1], rpc, N, bn_chunk_rows(rpc), t->last_act, part);
-            hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((unsigned)((n_calls * N + 63) / 64)), dim3(64), 0, st, part,
-                               nch, N, (int)n_calls, scratch + B.bn_s1, scratch + B.bn_s2);
-            hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(rows * N)), dim3(256), 0, st, a, d_out,
-                               ws + L.xhat[nl - 1], rows, rpc, N, t->last_act, t->bn_w[nl - 1],
-                               ws + L.invstd[nl - 1], scratch + B.bn_s1, scratch + B.bn_s2, (int)n_calls,
-                               t->drop_mask[nl - 1], dz, t->dbn_w[nl - 1], t->dbn_b[nl - 1]);
-        }
-        ABN_CHECK_LAUNCH("output-layer dz");
-    }
-
-    float* slabs = scratch + B.slabs;
-    for (int l = nl - 1; l >= 0; --l) {
-        const int Kin = (int)t->dims[l], Nout = (int)t->dims[l + 1];
-        const float* dz = (l == nl - 1 && dz_in) ? dz_in : scratch + B.dz[cur];
-        const float* a_in = (l == 0) ? xin : ws + L.a[l - 1];
-        // wgrad: dW[Nout, Kin] (+ db via the ones column) = dz^T a_in, split over rows
-        GemmP pw = {};
-        pw.A = dz; pw.lda = Nout;
-        pw.B = a_in; pw.ldb = Kin;
-        pw.C = slabs + B.off[l]; pw.ldc = Kin;
-        pw.C2 = slabs + B.off[l] + (int64_t)Nout * Kin;
-        pw.slab_stride = B.slab_stride;
-        pw.M = Nout; pw.N = Kin + 1; pw.K = (int)rows;
-        pw.k_chunk = (int)align_up((rows + B.splits[l] - 1) / B.splits[l], BK);
-        pw.ones_col = Kin;
-        pw.bf16 = gemm_prec(t->precision);
-        pw.a_vec = aligned16(dz) && (Nout % 4 == 0);
-        pw.b_vec = aligned16(a_in) && (Kin % 4 == 0);
-        // slices past the end of the reduction write zero slabs (k range empty)
-        if (!(l > 0 || dx)) {
-            rc = launch_gemm<false, false, EPI_WGRAD>(pw, B.splits[l], st);
-            if (rc != ABN_OK) return rc;
-        }
-        // dgrad: d a_{l-1} = dz W_l, times act'(a_{l-1}) when no BN sits in between.  Both
-        // GEMMs read dz only: they go out as one grid (launch_bwd_pair).
-        if (l > 0 || dx) {
-            float* dst = (l == 0) ? dx : scratch + B.dz[cur ^ 1];
-            GemmP p = {};
-            p.A = dz; p.lda = Nout;
-            p.B = t->W[l]; p.ldb = Kin;
-            p.C = dst; p.ldc = Kin;
-            p.M = (int)rows; p.N = Kin; p.K = Nout; p.k_chunk = Nout;
-            p.a_vec = aligned16(dz) && (Nout % 4 == 0);
-            p.b_vec = aligned16(t->W[l]) && (Kin % 4 == 0);
-            p.ones_col = -1;
-            p.bf16 = gemm_prec(t->precision);
-            if (l > 0 && !t->batch_norm) { p.aux = ws + L.a[l - 1]; p.ldaux = Kin; p.act = t->act; p.mask = t->drop_mask[l - 1]; }
-            rc = launch_bwd_pair(pw, B.splits[l], p, st);
-            if (rc != ABN_OK) return rc;
-            if (l > 0 && t->batch_norm) {
-                // dst holds d a_{l-1}; turn it into d z_{l-1} through act' and BN
-                const float* a = ws + L.a[l - 1];
-                const int nch = bn_chunks(rpc);
-                double* part = reinterpret_cast<double*>(scratch + B.bn_part);
-                hipLaunchKernelGGL(bn_partial_kernel<true>, dim3((Kin + 63) / 64, nch, (int)n_calls), dim3(256), 0, st,
-                                   dst, a, ws + L.xhat[l - 1], rpc, Kin, bn_chunk_rows(rpc), t->act, part);
-                hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((unsigned)((n_calls * Kin + 63) / 64)), dim3(64), 0, st,
-                                   part, nch, Kin, (int)n_calls, scratch + B.bn_s1, scratch + B.bn_s2);
-                hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(rows * Kin)), dim3(256), 0, st, a, dst,
-                                   ws + L.xhat[l - 1], rows, rpc, Kin, t->act, t->bn_w[l - 1], ws + L.invstd[l - 1],
-                                   scratch + B.bn_s1, scratch + B.bn_s2, (int)n_calls, t->drop_mask[l - 1], dst,
-                                   t->dbn_w[l - 1], t->dbn_b[l - 1]);
-                ABN_CHECK_LAUNCH("batch_norm backward");
-            }
-            cur ^= 1;
-        }
-    }
-    if (t->defer_reduce) return ABN_OK;          // abn_tower_reduce_step finishes the job
-    const ReduceTable rt = make_reduce_table(t, B);
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(grid_for((rt.total + 3) / 4)), dim3(256), 0, st, slabs, rt);
-    ABN_CHECK_LAUNCH("slab_reduce");
-    return ABN_OK;
+    return gemm_backward(t, x2 ? ws + L.x : x1, d_out, rows, n_calls, L, B, ws, scratch, dx, st);
 }
 
 // ONE of the two launches of the operand-plane backward -- part 1 the data-gradient chain, 2 the weight gradients --
@@ -2408,10 +2455,8 @@ int abn_tower_reduce_step(const abn_tower_desc* t, int64_t rows, const float* sc
         w.fail_word = nullptr;
         w.step_ctr = t->source ? t->source->step_ctr : nullptr;
         static bool wgs_attr[16] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        dev = (dev >= 0 && dev < 16) ? dev : 0;
-        if (!wgs_attr[dev]) {
+        const int dev = device_slot();
+        if (!wgs_attr[dev]) {                    // (the one opt-in whose failure is reported: the flag stays clear and the next call asks again)
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_step_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WGS_LDS_BYTES) != hipSuccess) {
                 set_error("tower_reduce_step: cannot reserve %zu bytes of LDS", WGS_LDS_BYTES);
                 return ABN_E_LAUNCH;
@@ -2452,14 +2497,7 @@ int abn_linear_forward(const float* x, const float* W, const float* b, int64_t r
     ABN_REQUIRE(rows >= 0 && rows < (1LL << 30) && in_dim >= 1 && out_dim >= 1 && in_dim < (1 << 24) && out_dim < (1 << 24),
                 "linear_forward: bad shape");
     ABN_REQUIRE(act >= ABN_ACT_NONE && act <= ABN_ACT_TANH, "linear_forward: unsupported activation %d", act);
-    GemmP p = {};
-    p.A = x; p.lda = in_dim;
-    p.B = W; p.ldb = in_dim;
-    p.C = y; p.ldc = out_dim;
-    p.M = (int)rows; p.N = (int)out_dim; p.K = (int)in_dim; p.k_chunk = (int)in_dim;
-    p.bias = b; p.act = act; p.ones_col = -1;
-    p.a_vec = aligned16(x) && (in_dim % 4 == 0);
-    p.b_vec = aligned16(W) && (in_dim % 4 == 0);
+    const GemmP p = fwd_gemm(x, W, b, y, rows, in_dim, out_dim, act, nullptr, 0);
     return launch_gemm<true, true, EPI_FWD>(p, 1, (hipStream_t)stream);
 }
 
@@ -2470,14 +2508,7 @@ int abn_linear_dgrad(const float* dz, const float* W, int64_t rows, int64_t in_d
     ABN_REQUIRE(rows >= 0 && rows < (1LL << 30) && in_dim >= 1 && out_dim >= 1 && in_dim < (1 << 24) && out_dim < (1 << 24),
                 "linear_dgrad: bad shape");
     ABN_REQUIRE(act_prev >= ABN_ACT_NONE && act_prev <= ABN_ACT_TANH, "linear_dgrad: unsupported activation %d", act_prev);
-    GemmP p = {};
-    p.A = dz; p.lda = out_dim;
-    p.B = W; p.ldb = in_dim;
-    p.C = dx; p.ldc = in_dim;
-    p.M = (int)rows; p.N = (int)in_dim; p.K = (int)out_dim; p.k_chunk = (int)out_dim;
-    p.aux = a_prev; p.ldaux = in_dim; p.act = act_prev; p.ones_col = -1;
-    p.a_vec = aligned16(dz) && (out_dim % 4 == 0);
-    p.b_vec = aligned16(W) && (in_dim % 4 == 0);
+    const GemmP p = dgrad_gemm(dz, W, dx, rows, in_dim, out_dim, DgradAux{a_prev, in_dim, act_prev, nullptr}, 0);
     return launch_gemm<true, false, EPI_DGRAD>(p, 1, (hipStream_t)stream);
 }
 
@@ -2497,24 +2528,9 @@ int abn_linear_wgrad(const float* dz, const float* a_in, int64_t rows, int64_t i
     const int64_t stride = align_up(out_dim * in_dim + out_dim, 64);
     if (scratch_floats < stride * splits) { set_error("linear_wgrad: scratch too small"); return ABN_E_WORKSPACE; }
     hipStream_t st = (hipStream_t)stream;
-    GemmP p = {};
-    p.A = dz; p.lda = out_dim;
-    p.B = a_in; p.ldb = in_dim;
-    p.C = scratch; p.ldc = in_dim;
-    p.C2 = scratch + out_dim * in_dim;
-    p.slab_stride = stride;
-    p.M = (int)out_dim; p.N = (int)in_dim + 1; p.K = (int)rows;
-    p.k_chunk = (int)align_up((rows + splits - 1) / splits, BK);
-    p.ones_col = (int)in_dim;
-    p.a_vec = aligned16(dz) && (out_dim % 4 == 0);
-    p.b_vec = aligned16(a_in) && (in_dim % 4 == 0);
-    int rc = launch_gemm<false, false, EPI_WGRAD>(p, splits, st);
+    const int rc = launch_gemm<false, false, EPI_WGRAD>(wgrad_gemm(dz, a_in, rows, in_dim, out_dim, scratch, stride, splits, 0), splits, st);
     if (rc != ABN_OK) return rc;
-    ReduceTable rt = {};
-    rt.n_layers = 1; rt.splits[0] = splits; rt.slab_stride = stride;
-    rt.off[0] = 0; rt.nW[0] = out_dim * in_dim; rt.nb[0] = out_dim; rt.dW[0] = dW; rt.db[0] = db;
-    rt.total = out_dim * in_dim + out_dim;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(grid_for((rt.total + 3) / 4)), dim3(256), 0, st, scratch, rt);
+    reduce_one_layer(scratch, stride, splits, in_dim, out_dim, dW, db, st);
     ABN_CHECK_LAUNCH("linear_wgrad");
     return ABN_OK;
 }
@@ -2542,34 +2558,13 @@ int abn_linear_backward_prec(const float* dz, const float* W, const float* a_in,
     const int64_t stride = align_up(out_dim * in_dim + out_dim, 64);
     if (scratch_floats < stride * splits) { set_error("linear_backward: scratch too small"); return ABN_E_WORKSPACE; }
     hipStream_t st = (hipStream_t)stream;
-    GemmP pw = {};
-    pw.A = dz; pw.lda = out_dim;
-    pw.B = a_in; pw.ldb = in_dim;
-    pw.C = scratch; pw.ldc = in_dim;
-    pw.C2 = scratch + out_dim * in_dim;
-    pw.slab_stride = stride;
-    pw.M = (int)out_dim; pw.N = (int)in_dim + 1; pw.K = (int)rows;
-    pw.k_chunk = (int)align_up((rows + splits - 1) / splits, BK);
-    pw.ones_col = (int)in_dim;
-    pw.a_vec = aligned16(dz) && (out_dim % 4 == 0);
-    pw.b_vec = aligned16(a_in) && (in_dim % 4 == 0);
-    GemmP pd = {};
-    pd.A = dz; pd.lda = out_dim;
-    pd.B = W; pd.ldb = in_dim;
-    pd.C = dx; pd.ldc = in_dim;
-    pd.M = (int)rows; pd.N = (int)in_dim; pd.K = (int)out_dim; pd.k_chunk = (int)out_dim;
-    pd.aux = act_prev == ABN_ACT_NONE ? nullptr : a_in; pd.ldaux = in_dim; pd.act = act_prev; pd.ones_col = -1;
-    pd.a_vec = aligned16(dz) && (out_dim % 4 == 0);
-    pd.b_vec = aligned16(W) && (in_dim % 4 == 0);
-    pw.bf16 = pd.bf16 = gemm_prec(precision);
-    int rc = launch_bwd_pair(pw, splits, pd, st);
+    const int prec = gemm_prec(precision);
+    const DgradAux aux = {act_prev == ABN_ACT_NONE ? nullptr : a_in, in_dim, act_prev, nullptr};
+    const int rc = launch_bwd_pair(wgrad_gemm(dz, a_in, rows, in_dim, out_dim, scratch, stride, splits, prec), splits,
+                                   dgrad_gemm(dz, W, dx, rows, in_dim, out_dim, aux, prec), st);
     if (rc != ABN_OK) return rc;
     if (!dW) return ABN_OK;                      // slabs left unreduced in scratch: the pair grid alone (kernel timing)
-    ReduceTable rt = {};
-    rt.n_layers = 1; rt.splits[0] = splits; rt.slab_stride = stride;
-    rt.off[0] = 0; rt.nW[0] = out_dim * in_dim; rt.nb[0] = out_dim; rt.dW[0] = dW; rt.db[0] = db;
-    rt.total = out_dim * in_dim + out_dim;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(grid_for((rt.total + 3) / 4)), dim3(256), 0, st, scratch, rt);
+    reduce_one_layer(scratch, stride, splits, in_dim, out_dim, dW, db, st);
     ABN_CHECK_LAUNCH("linear_backward");
     return ABN_OK;
 }
