@@ -118,6 +118,13 @@ SYMBOLS = {
     'abn_sample_pairs': (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_int, _vp]),
     'abn_tcl_pairs': (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.c_int, C.c_int, _i64, _i64, C.c_uint64, C.c_uint32, _vp, _vp,
                                 _vp, _vp, C.c_int, _i64, _vp]),
+    'abn_gmm_max_d': (_i64, []),
+    'abn_gmm_max_k': (_i64, []),
+    'abn_gmm_posteriors': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    'abn_gmm_ws_bytes': (_i64, [_i64, _i64, _i64, C.c_int]),
+    'abn_gmm_accumulate': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, C.c_int, _vp, _i64, _vp]),
+    'abn_gmm_mstep': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, C.c_int, _vp, C.c_double, C.c_double, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 # abn_integrate_forward / _backward (include/abnet3_hip.h)
 INTEGRATE_MODE = {'sum': 0, 'concat': 1}

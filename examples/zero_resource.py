@@ -5,6 +5,7 @@ Siamese training -> embedding -> ABX.  The corpus' word labels are used twice on
 mined pairs, and the ABX item file ("phones" = word types).
 
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
+                                     [--gmm] [--gmm-components 64] [--no-network]
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
 error is printed under both frame distances, the angular cosine and the symmetrised Kullback-Leibler divergence.
@@ -14,6 +15,9 @@ the same way from the last fifth of the files -- a stretch of frames against its
 against a stretch of another file ("diff").
 --qbe adds query-by-example search after the embedding (abnet3_amd/qbe.py): the first token of a few word types is
 searched in every utterance by subsequence DTW, and the mean average precision of the rankings is printed.
+--gmm adds the untrained baseline (abnet3_amd/gmm.py): a Gaussian mixture fitted on the filterbanks, its posteriorgrams
+under the KL frame distance -- ABX, and with --qbe the search.  No network is trained on this route; --no-network stops
+after it, otherwise its figures are printed again beside the embeddings'.
 """
 import argparse
 import os
@@ -29,6 +33,7 @@ from abnet3_amd.dataloader import DeviceCorpus, PairsDataLoader, TemporalCoheren
 from abnet3_amd.discovery import KnnPairMiner                     # noqa: E402
 from abnet3_amd.embedder import EmbedderSiamese                   # noqa: E402
 from abnet3_amd.features import FeaturesGenerator                 # noqa: E402
+from abnet3_amd.gmm import GmmPosteriorgram                       # noqa: E402
 from abnet3_amd.loss import KLLoss, coscos2                       # noqa: E402
 from abnet3_amd.model import SiameseNetwork                       # noqa: E402
 from abnet3_amd.trainer import TrainerSiamese                     # noqa: E402
@@ -78,6 +83,28 @@ def qbe_search(corpus, tokens, names, label, distance, n_queries=8):
                                precision_at_n(res.score, relevant), sum(own), len(own)))
 
 
+def word_items(tokens):
+    keep = [t for t in tokens if t[2] - t[1] >= 0.1]
+    return keep, Items([t[0] for t in keep], [t[1] for t in keep], [t[2] for t in keep], ['w%d' % t[3] for t in keep],
+                       ['-'] * len(keep), ['-'] * len(keep), ['spk'] * len(keep))
+
+
+def gmm_route(fb, times, tokens, n_components, qbe):
+    """features -> GmmPosteriorgram.fit -> transform -> ABX (kl), and the search: the line main() prints."""
+    names = list(fb)
+    keep, items = word_items(tokens)
+    corpus = DeviceCorpus({k: np.asarray(fb[k], dtype=np.float32) for k in names}, times)
+    g = GmmPosteriorgram(n_components).fit(corpus)
+    post = g.transform(corpus)
+    r = ABXEvaluator(items, post, distance='kl').run('within')
+    line = ('ABX error on GMM posteriorgrams (K = %d, %d EM iterations, log-likelihood %.3f, %d starved): kl %.2f %% '
+            '(%d triplets)' % (n_components, len(g.log_likelihoods), g.log_likelihoods[-1], g.n_starved_, r.error, r.n_triplets))
+    print(line)
+    if qbe:
+        qbe_search(post, keep, names, 'GMM posteriorgrams', 'kl')
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--utts', type=int, default=40)
@@ -88,6 +115,9 @@ def main():
     ap.add_argument('--softmax', action='store_true', help='softmax output + KLLoss; ABX under cosine and KL')
     ap.add_argument('--tcl', action='store_true', help='no mined pairs: train on temporal-coherence pairs')
     ap.add_argument('--qbe', action='store_true', help='after embedding: search a few planted words by example, print MAP')
+    ap.add_argument('--gmm', action='store_true', help='the untrained baseline: GMM posteriorgrams of the filterbanks, ABX (kl)')
+    ap.add_argument('--gmm-components', type=int, default=64)
+    ap.add_argument('--no-network', action='store_true', help='with --gmm: stop after the mixture, train nothing')
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     random.seed(0)
@@ -98,6 +128,12 @@ def main():
     fg = FeaturesGenerator(norm_per_channel=True)
     fb, _ = fg.normalize_features({k: fg.fbank_from_samples(v, 16000).cpu().numpy() for k, v in wavs.items()})
     times = {k: np.arange(len(v)) * 0.01 + 0.0125 for k, v in fb.items()}
+
+    gmm_line = gmm_route(fb, times, tokens, args.gmm_components, args.qbe) if args.gmm else None
+    if args.no_network:
+        if not args.gmm:
+            ap.error('--no-network leaves nothing to do without --gmm')
+        return
 
     if args.tcl:
         dl = tcl_loader(fb, times, rng)
@@ -130,9 +166,7 @@ def main():
     names = list(fb)
     emb = EmbedderSiamese(network=net, network_path=args.out + '_network.pth', feature_path=None,
                           output_path=None).embed_features([fb[k] for k in names])
-    keep = [t for t in tokens if t[2] - t[1] >= 0.1]
-    items = Items([t[0] for t in keep], [t[1] for t in keep], [t[2] for t in keep], ['w%d' % t[3] for t in keep],
-                  ['-'] * len(keep), ['-'] * len(keep), ['spk'] * len(keep))
+    keep, items = word_items(tokens)
     for label, feats in (('filterbanks', fb), ('embeddings', dict(zip(names, emb)))):
         corpus = DeviceCorpus({k: np.asarray(feats[k], dtype=np.float32) for k in names}, times)
         r = ABXEvaluator(items, corpus).run('within')
@@ -143,6 +177,8 @@ def main():
             print('ABX error on %s: %.2f %% (%d triplets)' % (label, r.error, r.n_triplets))
         if args.qbe:
             qbe_search(corpus, keep, names, label, 'kl' if args.softmax and label == 'embeddings' else 'cosine')
+    if gmm_line:
+        print(gmm_line)
 
 
 if __name__ == '__main__':

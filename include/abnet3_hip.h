@@ -841,6 +841,44 @@ int abn_tcl_pairs(const int64_t* file_row0, const int64_t* file_len, const int64
                   int64_t first_iter, uint64_t seed, uint32_t epoch, const int64_t* dst, int64_t* idx1,
                   int64_t* idx2, void* labels, int labels_f64, int64_t out_len, void* stream);
 
+/* ---- Gaussian-mixture posteriorgrams (no counterpart in the reference; added within ABI 20) ----------------------
+ * A diagonal-covariance mixture of K components over D-dimensional frames, as abnet3_amd/gmm.py defines it.  The
+ * model reaches the kernels as three fp32 score tables (m = mean - shift, v = variance, w = weight):
+ *   A [K][D] = m / v,   B [K][D] = -0.5 / v,   c [K] = log w - 0.5 sum_d (log(2 pi v) + m^2 / v),
+ * and the frames x [T][D] are centred on load, xc = x - shift in fp32.  The score
+ *   s[t][k] = c[k] + sum_d xc A + sum_d xc^2 B
+ * is one fp32 GEMM of depth 2 D + 1 on the matrix cores (v_mfma_f32_32x32x2_f32, the augmented row
+ * [xc | xc^2 | 1] formed on the way into LDS, columns in that order).  lse[t] = log sum_k exp s[t][k]; a frame with
+ * a non-finite xc^2 is BAD: lse[t] = NaN, its posteriors are 0, it adds nothing to the statistics.
+ * D <= abn_gmm_max_d(), K <= abn_gmm_max_k(): beyond them ABN_E_UNSUPPORTED; T < 2^31 - 128; null pointers and
+ * sizes < 1 are ABN_E_ARG -- all before any launch.  No floating-point atomics: every call is bit-reproducible. */
+int64_t abn_gmm_max_d(void);               /* host */
+int64_t abn_gmm_max_k(void);               /* host */
+
+/* lse [T]; post [T][K] = exp(s - lse), or NULL for the likelihoods alone.  One launch; the T x K matrix is written
+ * here and nowhere else. */
+int abn_gmm_posteriors(const float* x, int64_t T, int64_t D, const float* shift, const float* A, const float* B,
+                       const float* c, int64_t K, float* lse, float* post, void* stream);
+
+/* Sufficient statistics N[k] = sum_t g, S1[k][d] = sum_t g xc, S2[k][d] = sum_t g xc^2 with g = exp(s - lse[t])
+ * recomputed tile by tile from lse (abn_gmm_posteriors' output for the same tables), never stored.  A workgroup owns
+ * 128 components and one of n_ranges ranges of 128-frame blocks (0: chosen from the grid, at most 256) and leaves
+ * one fp32 slab [128][2 D + 1] in ws (abn_gmm_ws_bytes, host, -1 for refused sizes).  One launch. */
+int64_t abn_gmm_ws_bytes(int64_t T, int64_t K, int64_t D, int n_ranges);
+int abn_gmm_accumulate(const float* x, int64_t T, int64_t D, const float* shift, const float* A, const float* B,
+                       const float* c, int64_t K, const float* lse, int n_ranges, void* ws, int64_t ws_bytes,
+                       void* stream);
+
+/* Sums the slabs of abn_gmm_accumulate (same T, K, D, n_ranges) in range order in float64 into
+ * sums [K][2 D + 1] = [S1 | S2 | N], then the M-step in float64 with Tg = T - (BAD frames):
+ *   w = N / Tg, renormalised to sum 1;  m = S1 / N;  v = max(S2 / N - m^2, var_floor gv[d]);
+ * a component with N < min_count keeps its mu / var.  w [K], mu [K][D] (centred means), var [K][D]: float64, mu and
+ * var in / out; A, B, c: the next tables, rounded once from float64; gv [D] float64.
+ * stats [4] float64: sum of lse over the good frames, BAD frames, starved components, Tg.  Two small launches. */
+int abn_gmm_mstep(const void* ws, int64_t ws_bytes, const float* lse, int64_t T, int64_t K, int64_t D, int n_ranges,
+                  const double* gv, double var_floor, double min_count, double* sums, double* w, double* mu,
+                  double* var, float* A, float* B, float* c, double* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
