@@ -86,6 +86,11 @@ SYMBOLS = {
                                           _vp, _vp, _vp]),
     'abn_dtw_search_kl_batched': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
                                              _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'abn_dtw_local_max_n2': (_i64, []),
+    'abn_dtw_local_batched': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp]),
+    'abn_dtw_local_kl_batched': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _i64,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'abn_cosine_distance': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     'abn_cosine_distance_f64': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     'abn_arccos_f32': (C.c_int, [_vp, _i64, C.c_int, _vp, _vp]),

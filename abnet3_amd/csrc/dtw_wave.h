@@ -1,9 +1,9 @@
-// dtw_wave.h -- the wavefront-per-pair DTW: ONE kernel body, dtw_wave_kernel<VEC, KL, SEARCH>, and its host launcher.
+// dtw_wave.h -- the wavefront-per-pair DTW: ONE kernel body, dtw_wave_kernel<VEC, KL, MODE>, and its host launcher.
 // abx.hip instantiates the COST mode (abn_dtw_cost_batched, abn_dtw_cost_kl_batched), search.hip the SEARCH mode
-// (abn_dtw_search_batched, abn_dtw_search_kl_batched).  Every translation unit that includes this file is compiled
-// with -ffp-contract=off.
+// (abn_dtw_search_batched, abn_dtw_search_kl_batched), local.hip the LOCAL mode (abn_dtw_local_batched,
+// abn_dtw_local_kl_batched).  Every translation unit that includes this file is compiled with -ffp-contract=off.
 //
-// Shared by both modes.  One wavefront per pair (a grid-stride loop over the device-resident pair table).  Side 1 (ABX:
+// Shared by all modes.  One wavefront per pair (a grid-stride loop over the device-resident pair table).  Side 1 (ABX:
 // token 1; search: the utterance) is cut into BANDS of 64 rows, one row per lane, and is unbounded; a band into ROUNDS
 // of 64 anti-diagonals.  A round first computes the cells of its 64 diagonals CELL-PARALLEL -- every lane takes 2 x 2
 // tiles of the rectangle of rows x columns that holds them (four chains sharing their loads), so a 15 x 15 pair keeps
@@ -11,7 +11,7 @@
 // the lanes sweep the 64 diagonals: lane i holds row i's cell, the row above arrives over a DPP wave shift, the diagonal
 // neighbour is the previous step's upper value; cost = d + min(diag, up, left) in float64 with the first minimum in the
 // order diag, up, left, and the path length is carried along the predecessor that rule picks.  The band's last row is
-// handed to the next band through LDS, which caps side 2 (ABX: token 2; search: the query) at dtw_out<SEARCH>::CAP
+// handed to the next band through LDS, which caps side 2 (ABX: token 2; search: the query) at dtw_out<MODE>::CAP
 // columns.  Side-2 norms are computed once per pair (LDS), side-1 norms once per band.  Frames are read from L1 / L2:
 // no workspace, one launch.
 //
@@ -31,6 +31,16 @@
 //           lane that leaves the last column keeps its row's cell, and after each band a wave reduction of
 //           (cost / length, row) is merged into the running best with a strict <, so the first row wins ties; the
 //           optional profile: the lanes write what they kept, per row.
+//   LOCAL   Smith-Waterman over the similarity theta - d (abnet3_amd/terms.py's module docstring): any stretch of side
+//           1 against any stretch of side 2.  The cells are SEARCH's (no pair is dropped, the same blocked cells); the
+//           produce phase also blocks the cells of the exclusion band |(off1 + i) - (off2 + j)| < exclude, so the ring
+//           holds d or +inf and the SWEEP subtracts: s = (double)theta - (double)d, one float64 subtraction.  The sweep
+//           carries (H, length, start row, start column) and the boundary row holds four; a cell outside the matrix is
+//           DEAD (H = 0, length 0, start (-1, -1)) instead of +inf; the predecessor is the first MAXIMUM in the order
+//           diag, up, left; a cell whose H is not > 0 is dead.  Every lane keeps the best cell of its row as it goes (a
+//           new one only on strictly greater H: the first column wins), and after each band a wave reduction of
+//           (H, row), the smaller row winning a tie, is merged into the running best with a strict >: the result is
+//           the largest H, ties to the smallest row, then the smallest column, whatever the order of execution.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -137,18 +147,21 @@ struct cell_extra<true> {
     bool complete() const { return L1 && L2 && bad1 && bad2; }
     bool aligned() const { return aligned16(L1) && aligned16(L2); }
 };
-constexpr bool CELL_COSINE = false, CELL_KL = true, MODE_COST = false, MODE_SEARCH = true;
+constexpr bool CELL_COSINE = false, CELL_KL = true;
+enum dtw_mode { MODE_COST, MODE_SEARCH, MODE_LOCAL };
 
-// what a mode writes per pair, and the columns it takes (its LDS boundary row)
-template <bool SEARCH>
-struct dtw_out {
+// what a mode writes per pair, and the columns it takes (its LDS boundary row); LOCAL: its two parameters ride along
+template <dtw_mode MODE>
+struct dtw_out;
+template <>
+struct dtw_out<MODE_COST> {
     static constexpr int CAP = ABN_DTW_COST_MAX_N2;
     double* total_cost;
     int32_t* path_len;
     bool complete() const { return total_cost && path_len; }
 };
 template <>
-struct dtw_out<true> {
+struct dtw_out<MODE_SEARCH> {
     static constexpr int CAP = ABN_DTW_SEARCH_MAX_QUERY;
     double* total_cost;
     int32_t* path_len;
@@ -161,26 +174,62 @@ struct dtw_out<true> {
     int32_t* prof_start;
     bool complete() const { return total_cost && path_len && start && end; }
 };
+template <>
+struct dtw_out<MODE_LOCAL> {
+    static constexpr int CAP = ABN_DTW_LOCAL_MAX_N2;
+    double* score;                  // H of the best cell
+    int32_t* path_len;
+    int32_t* start1;                // the path's first cell (side 1 row, side 2 column) ...
+    int32_t* start2;
+    int32_t* end1;                  // ... and the best cell itself; stretch-relative, inclusive
+    int32_t* end2;
+    float theta;                    // similarity = theta - distance
+    int64_t exclude;                // > 0: the cells with |(off1 + i) - (off2 + j)| < exclude are blocked
+    bool complete() const { return score && path_len && start1 && start2 && end1 && end2; }
+};
+
+// what only the LOCAL sweep carries (the other modes' instances are empty, so their code does not change with it):
+// per band, beside (p1, l1, s1) = (H, length, start row): the start column of the lane's cell, of the row above one
+// column back and of the boundary row's next entry, and the best cell of the lane's row so far
+template <bool LOCAL>
+struct local_sweep {};
+template <>
+struct local_sweep<true> {
+    int t1 = -1, tup_prev = -1, ttnext = -1;
+    double rb_h = 0.0;
+    int rb_l = 0, rb_si = -1, rb_sj = -1, rb_j = -1;
+};
+// ... and per pair: the running best over the bands done so far (the same in every lane; H = 0: no live cell yet)
+template <bool LOCAL>
+struct local_best {};
+template <>
+struct local_best<true> {
+    double h = 0.0;
+    int l = 0, si = -1, sj = -1, ei = -1, ej = -1;
+};
 
 namespace {
 
 __device__ __forceinline__ bool finite_f32(float v) { return fabsf(v) < __builtin_inff(); }
 
-template <bool VEC, bool KL, bool SEARCH>
+template <bool VEC, bool KL, dtw_mode MODE>
 __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ feats1, int64_t rows1,
                                                       const float* __restrict__ feats2, int64_t rows2,
                                                       const int64_t* __restrict__ off1, const int32_t* __restrict__ n1,
                                                       const int64_t* __restrict__ off2, const int32_t* __restrict__ n2,
-                                                      int64_t npairs, int D, dtw_out<SEARCH> out, cell_extra<KL> ex)
+                                                      int64_t npairs, int D, dtw_out<MODE> out, cell_extra<KL> ex)
 {
+    constexpr bool SEARCH = MODE == MODE_SEARCH, LOCAL = MODE == MODE_LOCAL;
+    constexpr bool FREE = MODE != MODE_COST;    // SEARCH and LOCAL: no pair is dropped, cells are blocked instead
     constexpr int CB = 64;                      // rows of a band = lanes
     constexpr int RD = 64;                      // anti-diagonals of a round (the LDS ring's rows; 32 measured the same)
-    constexpr int CAP = dtw_out<SEARCH>::CAP;
+    constexpr int CAP = dtw_out<MODE>::CAP;
     __shared__ float ring[RD][CB];              // [diagonal % RD][row of the band]
     __shared__ double bnd_c[CAP];               // the band's last row: costs ...
     __shared__ int32_t bnd_l[CAP];              // ... path lengths ...
-    __shared__ int32_t bnd_s[CAP];              // ... and (SEARCH) start rows, per column
-    __shared__ float ny_s[CAP];                 // cosine: side 2's norms; KL SEARCH: 1 for a BAD row, else 0; KL COST: none
+    __shared__ int32_t bnd_s[CAP];              // ... and (SEARCH, LOCAL) start rows, per column ...
+    __shared__ int32_t bnd_t[LOCAL ? CAP : 1];  // ... and (LOCAL) start columns
+    __shared__ float ny_s[CAP];                 // cosine: side 2's norms; KL SEARCH / LOCAL: 1 for a BAD row, else 0; KL COST: none
     __shared__ float nx_s[CB];                  // the same of the band's rows
     const int lane = threadIdx.x;
     const double INF = __builtin_inf();
@@ -201,7 +250,12 @@ __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ 
         if (refused || N == 0 || M == 0) {                      // refused: nothing is read, no profile entry is written
             if (lane == 0) {
                 out.path_len[p] = refused ? -1 : 0;
-                out.total_cost[p] = 0.0;
+                if constexpr (LOCAL) {
+                    out.score[p] = 0.0;
+                    out.start1[p] = -1; out.start2[p] = -1; out.end1[p] = -1; out.end2[p] = -1;
+                } else {
+                    out.total_cost[p] = 0.0;
+                }
                 if constexpr (SEARCH) { out.start[p] = -1; out.end[p] = -1; }
             }
             if constexpr (SEARCH) {
@@ -218,7 +272,7 @@ __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ 
         if constexpr (KL) {
             LX = ex.L1 + o1 * D;
             LY = ex.L2 + o2 * D;
-            if constexpr (SEARCH) {
+            if constexpr (FREE) {
                 for (int j = lane; j < M; j += CB) ny_s[j] = ex.bad2[o2 + j] != 0 ? 1.0f : 0.0f;
             } else {                                            // a BAD row in either token: dropped before any cell
                 for (int i = lane; i < N; i += CB) bad |= ex.bad1[o1 + i] != 0;
@@ -235,10 +289,11 @@ __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ 
         int fin_l = 0;
         double best_sc = INF, best_c = 0.0;                     // SEARCH: the running best over the bands done so far
         int best_l = 0, best_s = -1, best_e = -1;               // (the same in every lane)
+        local_best<LOCAL> lb;                                   // LOCAL: the same
         for (int i0 = 0; i0 < N; i0 += CB) {
             const int nr = min(CB, N - i0);
             const bool feed = i0 + CB < N;                      // the last row goes to the band below
-            if constexpr (!KL || SEARCH) {
+            if constexpr (!KL || FREE) {
                 if (lane < nr) {
                     if constexpr (KL) nx_s[lane] = ex.bad1[o1 + i0 + lane] != 0 ? 1.0f : 0.0f;
                     else nx_s[lane] = row_norm_numpy(X + (int64_t)(i0 + lane) * D, D);
@@ -247,8 +302,10 @@ __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ 
             }
             // sweep state of row i0 + lane: (p1, l1, s1) = its cell at the previous column, (up_prev, ...) = the row
             // above one column back (= the diagonal neighbour of the next step); COST: the virtual cell (-1, -1) costs 0
-            double p1 = INF, up_prev = (!SEARCH && i0 == 0 && lane == 0) ? 0.0 : INF;
+            // LOCAL: (p1, l1, s1, ls.t1) = (H, length, start row, start column); outside the matrix: the dead cell
+            double p1 = LOCAL ? 0.0 : INF, up_prev = (!SEARCH && i0 == 0 && lane == 0) || LOCAL ? 0.0 : INF;
             int l1 = 0, lup_prev = 0, s1 = -1, sup_prev = -1;
+            local_sweep<LOCAL> ls;
             double fc = INF;                                    // SEARCH: the row's cell in the last column
             int fl = 0, fs = -1;
             const int ndiag = nr + M - 1;
@@ -273,13 +330,13 @@ __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ 
                         float d;
                         if constexpr (KL) {
                             d = 0.5f * dot[c];
-                            if constexpr (SEARCH)                   // a BAD row: blocked
+                            if constexpr (FREE)                     // a BAD row: blocked
                                 if (nx_s[il] != 0.0f || ny_s[j] != 0.0f || !(d >= 0.0f)) d = __builtin_inff();
                         } else {
                             const float nx = nx_s[il], ny = ny_s[j];
                             d = (norm_is_plain(nx) && norm_is_plain(ny)) ? angular_distance_ref<true>(dot[c], nx, ny)
                                                                          : angular_distance_ref<false>(dot[c], nx, ny);
-                            if constexpr (!SEARCH) {
+                            if constexpr (!FREE) {
                                 bad |= !(d >= 0.0f);                // utils.py:59: the pair is dropped
                             } else if (!(d >= 0.0f)) {
                                 // NaN.  With a finite dot product and a finite non-zero product of the norms it is
@@ -289,6 +346,10 @@ __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ 
                                 d = rounding ? (dot[c] > 0.0f ? 0.0f : 1.0f) : __builtin_inff();
                             }
                         }
+                        if constexpr (LOCAL) {                      // the exclusion band, in table rows
+                            const int64_t gap = (o1 + i0 + il) - (o2 + j);
+                            if ((gap < 0 ? -gap : gap) < out.exclude) d = __builtin_inff();
+                        }
                         ring[s & (RD - 1)][il] = d;
                     }
                 }
@@ -297,25 +358,27 @@ __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ 
                 // (the step's LDS operands are read one step ahead: they do not depend on the chain)
                 const int ns = min(RD, ndiag - s0);
                 float dnext = ring[s0 & (RD - 1)][lane];
-                double tnext = INF;
+                double tnext = LOCAL ? 0.0 : INF;
                 int tlnext = 0, tsnext = -1;
+                if constexpr (LOCAL) ls.ttnext = -1;
                 if (lane == 0 && i0 > 0 && s0 < M) {
                     tnext = bnd_c[s0];
                     tlnext = bnd_l[s0];
-                    if constexpr (SEARCH) tsnext = bnd_s[s0];
+                    if constexpr (FREE) tsnext = bnd_s[s0];
+                    if constexpr (LOCAL) ls.ttnext = bnd_t[s0];
                 }
                 for (int e = 0; e < ns; ++e) {
                     const int s = s0 + e, j = s - lane;
                     const float dist = dnext;
                     double up = shr1_f64(p1);
                     int lup = shr1_i32(l1), sup = -1;
-                    if constexpr (SEARCH) sup = shr1_i32(s1);
+                    if constexpr (FREE) sup = shr1_i32(s1);
                     if (lane == 0) { up = tnext; lup = tlnext; sup = tsnext; }
                     dnext = ring[(s + 1) & (RD - 1)][lane];
                     if (lane == 0 && i0 > 0 && s + 1 < M) {
                         tnext = bnd_c[s + 1];
                         tlnext = bnd_l[s + 1];
-                        if constexpr (SEARCH) tsnext = bnd_s[s + 1];
+                        if constexpr (FREE) tsnext = bnd_s[s + 1];
                     }
                     double dg = up_prev;
                     int ldg = lup_prev, sdg = sup_prev;
@@ -323,7 +386,34 @@ __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ 
                     up_prev = up;
                     lup_prev = lup;
                     sup_prev = sup;
-                    if (lane < nr && (unsigned)j < (unsigned)M) {
+                    if constexpr (LOCAL) {
+                        int tup = shr1_i32(ls.t1);                  // (the step's values were fetched above: dist, up, ...)
+                        if (lane == 0) tup = ls.ttnext;
+                        if (lane == 0 && i0 > 0 && s + 1 < M) ls.ttnext = bnd_t[s + 1];
+                        const int tdg = ls.tup_prev;
+                        ls.tup_prev = tup;
+                        if (lane < nr && (unsigned)j < (unsigned)M) {
+                            const bool take_up = up > dg;           // first maximum in the order diag, up, left
+                            const double b1 = take_up ? up : dg;
+                            const bool take_left = left > b1;
+                            const double best = take_left ? left : b1;
+                            const int lbest = take_left ? l1 : (take_up ? lup : ldg);
+                            const int sbest = take_left ? s1 : (take_up ? sup : sdg);
+                            const int tbest = take_left ? ls.t1 : (take_up ? tup : tdg);
+                            // a dead predecessor is (0, 0): best + sim is sim and lbest + 1 is 1, the start is the cell's own
+                            const bool ext = best > 0.0;
+                            const double h = best + ((double)out.theta - (double)dist);
+                            const bool live = h > 0.0;
+                            p1 = live ? h : 0.0;
+                            l1 = live ? lbest + 1 : 0;
+                            s1 = live ? (ext ? sbest : i0 + lane) : -1;
+                            ls.t1 = live ? (ext ? tbest : j) : -1;
+                            if (feed && lane == CB - 1) { bnd_c[j] = p1; bnd_l[j] = l1; bnd_s[j] = s1; bnd_t[j] = ls.t1; }
+                            if (p1 > ls.rb_h) {                     // strict: the first column
+                                ls.rb_h = p1; ls.rb_l = l1; ls.rb_si = s1; ls.rb_sj = ls.t1; ls.rb_j = j;
+                            }
+                        }
+                    } else if (lane < nr && (unsigned)j < (unsigned)M) {
                         if constexpr (SEARCH)                       // the free start: the virtual cell (i - 1, -1)
                             if (j == 0) { dg = 0.0; ldg = 0; sdg = i0 + lane; }
                         const bool take_up = up < dg;               // first minimum in the order diag, up, left
@@ -345,7 +435,27 @@ __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ 
                 }
                 wave_lds_sync();                                // the next round's cells overwrite the ring
             }
-            if constexpr (!SEARCH) {
+            if constexpr (LOCAL) {
+                // ---- the band's best cell: the largest H, the smaller row on a tie (lanes >= nr hold 0: never taken)
+                double h = ls.rb_h;
+                int row = lane;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const double oh = __shfl_xor(h, o);
+                    const int orow = __shfl_xor(row, o);
+                    if (oh > h || (oh == h && orow < row)) { h = oh; row = orow; }
+                }
+                const int wl = __shfl(ls.rb_l, row), wsi = __shfl(ls.rb_si, row), wsj = __shfl(ls.rb_sj, row);
+                const int wj = __shfl(ls.rb_j, row);
+                if (h > lb.h) {                                 // strict: an earlier band's row wins a tie
+                    lb.h = h;
+                    lb.l = wl;
+                    lb.si = wsi;
+                    lb.sj = wsj;
+                    lb.ei = i0 + row;
+                    lb.ej = wj;
+                }
+            } else if constexpr (!SEARCH) {
                 if (i0 + nr == N) {                             // lane nr - 1 holds cell (N - 1, M - 1)
                     fin_c = __shfl(p1, nr - 1);
                     fin_l = __shfl(l1, nr - 1);
@@ -377,7 +487,16 @@ __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ 
                 }
             }
         }
-        if constexpr (!SEARCH) {
+        if constexpr (LOCAL) {
+            if (lane == 0) {
+                out.score[p] = lb.h;
+                out.path_len[p] = lb.l;
+                out.start1[p] = lb.si;
+                out.start2[p] = lb.sj;
+                out.end1[p] = lb.ei;
+                out.end2[p] = lb.ej;
+            }
+        } else if constexpr (!SEARCH) {
             const bool dropped = __any(bad);
             if (lane == 0) {
                 out.total_cost[p] = dropped ? 0.0 : fin_c;
@@ -395,24 +514,24 @@ __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ 
 
 // the host side of every entry point: argument checks (errors are prefixed with `what`), the grid (a wavefront per pair,
 // at most 256 * 32 of them), vector loads when every table the cell reads allows them, the launch
-template <bool KL, bool SEARCH>
+template <bool KL, dtw_mode MODE>
 int launch_dtw_wave(const char* what, const float* feats1, int64_t rows1, const float* feats2, int64_t rows2,
                     const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int64_t npairs,
-                    int64_t D, const dtw_out<SEARCH>& out, const cell_extra<KL>& ex, void* stream)
+                    int64_t D, const dtw_out<MODE>& out, const cell_extra<KL>& ex, void* stream)
 {
     ABN_REQUIRE(npairs >= 0 && D >= 1 && D < (1 << 20) && rows1 >= 0 && rows2 >= 0, "%s: bad npairs/D/rows", what);
     if (npairs == 0) return ABN_OK;
     ABN_REQUIRE(feats1 && feats2 && ex.complete() && off1 && n1 && off2 && n2 && out.complete(), "%s: null pointer", what);
-    if constexpr (SEARCH)
+    if constexpr (MODE == MODE_SEARCH)
         ABN_REQUIRE(!out.prof_cost || (out.prof_off && out.prof_len && out.prof_start && out.prof_rows >= 0),
                     "%s: an incomplete profile", what);
     ABN_REQUIRE(rows1 * D < (1LL << 62) && rows2 * D < (1LL << 62), "%s: feature array too large", what);
     const int64_t grid = npairs < 256 * 32 ? npairs : 256 * 32;
     const bool vec = D % 4 == 0 && aligned16(feats1) && aligned16(feats2) && ex.aligned();
     hipStream_t st = (hipStream_t)stream;
-    if (vec) hipLaunchKernelGGL((dtw_wave_kernel<true, KL, SEARCH>), dim3((unsigned)grid), dim3(64), 0, st, feats1, rows1, feats2, rows2,
+    if (vec) hipLaunchKernelGGL((dtw_wave_kernel<true, KL, MODE>), dim3((unsigned)grid), dim3(64), 0, st, feats1, rows1, feats2, rows2,
                                 off1, n1, off2, n2, npairs, (int)D, out, ex);
-    else hipLaunchKernelGGL((dtw_wave_kernel<false, KL, SEARCH>), dim3((unsigned)grid), dim3(64), 0, st, feats1, rows1, feats2, rows2,
+    else hipLaunchKernelGGL((dtw_wave_kernel<false, KL, MODE>), dim3((unsigned)grid), dim3(64), 0, st, feats1, rows1, feats2, rows2,
                             off1, n1, off2, n2, npairs, (int)D, out, ex);
     ABN_CHECK_LAUNCH(what);
     return ABN_OK;

@@ -5,7 +5,7 @@ Siamese training -> embedding -> ABX.  The corpus' word labels are used twice on
 mined pairs, and the ABX item file ("phones" = word types).
 
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
-                                     [--gmm] [--gmm-components 64] [--no-network]
+                                     [--gmm] [--gmm-components 64] [--no-network] [--terms] [--terms-theta T]
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
 error is printed under both frame distances, the angular cosine and the symmetrised Kullback-Leibler divergence.
@@ -18,6 +18,10 @@ searched in every utterance by subsequence DTW, and the mean average precision o
 --gmm adds the untrained baseline (abnet3_amd/gmm.py): a Gaussian mixture fitted on the filterbanks, its posteriorgrams
 under the KL frame distance -- ABX, and with --qbe the search.  No network is trained on this route; --no-network stops
 after it, otherwise its figures are printed again beside the embeddings'.
+--terms replaces the pair miner by term discovery (abnet3_amd/terms.py): local-alignment DTW of every utterance against
+every other -- over the filterbanks, or with --gmm over the mixture's posteriorgrams under the KL distance -- clustered
+into a .classes file, from which SamplerClusterSiamese draws the train and dev pairs: the reference's canonical route,
+with discovered clusters in place of labelled ones.  The purity of the clusters against the planted words is printed.
 """
 import argparse
 import os
@@ -29,13 +33,15 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from abnet3_amd.abx import ABXEvaluator, Items                    # noqa: E402
-from abnet3_amd.dataloader import DeviceCorpus, PairsDataLoader, TemporalCoherenceDataLoader   # noqa: E402
+from abnet3_amd.dataloader import DeviceCorpus, OriginalDataLoader, PairsDataLoader, TemporalCoherenceDataLoader   # noqa: E402
 from abnet3_amd.discovery import KnnPairMiner                     # noqa: E402
 from abnet3_amd.embedder import EmbedderSiamese                   # noqa: E402
 from abnet3_amd.features import FeaturesGenerator                 # noqa: E402
 from abnet3_amd.gmm import GmmPosteriorgram                       # noqa: E402
 from abnet3_amd.loss import KLLoss, coscos2                       # noqa: E402
 from abnet3_amd.model import SiameseNetwork                       # noqa: E402
+from abnet3_amd.sampler import SamplerClusterSiamese              # noqa: E402
+from abnet3_amd.terms import TermDiscoverer                       # noqa: E402
 from abnet3_amd.trainer import TrainerSiamese                     # noqa: E402
 from end_to_end import synth_corpus                               # noqa: E402
 
@@ -89,7 +95,53 @@ def word_items(tokens):
                        ['-'] * len(keep), ['-'] * len(keep), ['spk'] * len(keep))
 
 
-def gmm_route(fb, times, tokens, n_components, qbe):
+def guess_theta(table, distance, rng, quantile=0.04, n=20000):
+    """A crude, untuned stand-in for a tuned theta: the 4 % quantile of the frame distance between random frame pairs of
+    the corpus, so that only the closest frame pairs add to a path."""
+    x = table.cpu().numpy().astype(np.float64)
+    a, b = x[rng.integers(0, len(x), n)], x[rng.integers(0, len(x), n)]
+    if distance == 'kl':
+        a, b = np.maximum(a, 1e-6), np.maximum(b, 1e-6)
+        d = 0.5 * ((a - b) * (np.log(a) - np.log(b))).sum(axis=1)
+    else:
+        cos = (a * b).sum(axis=1) / np.maximum(np.linalg.norm(a, axis=1) * np.linalg.norm(b, axis=1), 1e-30)
+        d = np.arccos(np.clip(cos, -1.0, 1.0)) / np.pi
+    return float(np.quantile(d, quantile))
+
+
+def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frames=15):
+    """features or posteriorgrams -> TermDiscoverer -> terms.classes -> SamplerClusterSiamese -> the loader of its pairs."""
+    if theta is None:
+        theta = guess_theta(corpus.table, distance, rng)
+    td = TermDiscoverer(corpus, distance=distance, theta=theta, min_frames=min_frames)
+    matches, clusters = td.discover()
+    classes = td.write(out + '_terms')[0]
+
+    def word_at(f, lo, hi):
+        t = times[td.names[f]]
+        best = max((min(t[hi], tok[2]) - max(t[lo], tok[1]), tok[3]) for tok in tokens if tok[0] == td.names[f])
+        return best[1] if best[0] >= 0.5 * (t[hi] - t[lo]) else -1
+    pure = []
+    for c in clusters:
+        words = [word_at(*tok) for tok in c]
+        pure.append(max(words.count(w) for w in set(words) if w != -1) / len(words) if set(words) != {-1} else 0.0)
+    print('term discovery (%s, theta %.3g): %d matches, %d clusters, %d tokens; mean share of a cluster\'s tokens on its '
+          'commonest planted word %.2f' % (distance, theta, len(matches), len(clusters), sum(len(c) for c in clusters),
+                                          float(np.mean(pure)) if pure else 0.0))
+    if len(clusters) < 2:
+        sys.exit('term discovery found %d cluster(s): nothing to sample pairs from (try another --terms-theta)' % len(clusters))
+    spkid = out + '_terms/wav2spk.lst'
+    with open(spkid, 'w') as fh:
+        fh.write(''.join('%s spk\n' % k for k in td.names))
+    pairs_dir = out + '_terms_pairs'
+    SamplerClusterSiamese(std_file=classes, spkid_file=spkid, directory_output=pairs_dir, num_total_sampled_pairs=400,
+                          ratio_same_diff_spk=1.0, max_size_cluster=20).sample()
+    dl = OriginalDataLoader(pairs_path=pairs_dir, features_path=None, batch_size=8, num_max_minibatches=200)
+    dl.set_data(fb, times)
+    return dl
+
+
+def gmm_route(fb, times, tokens, n_components, qbe, want_post=False):
     """features -> GmmPosteriorgram.fit -> transform -> ABX (kl), and the search: the line main() prints."""
     names = list(fb)
     keep, items = word_items(tokens)
@@ -102,7 +154,7 @@ def gmm_route(fb, times, tokens, n_components, qbe):
     print(line)
     if qbe:
         qbe_search(post, keep, names, 'GMM posteriorgrams', 'kl')
-    return line
+    return (line, post) if want_post else line
 
 
 def main():
@@ -118,6 +170,8 @@ def main():
     ap.add_argument('--gmm', action='store_true', help='the untrained baseline: GMM posteriorgrams of the filterbanks, ABX (kl)')
     ap.add_argument('--gmm-components', type=int, default=64)
     ap.add_argument('--no-network', action='store_true', help='with --gmm: stop after the mixture, train nothing')
+    ap.add_argument('--terms', action='store_true', help='pairs from term discovery: clusters -> SamplerClusterSiamese')
+    ap.add_argument('--terms-theta', type=float, default=None, help='default: a low quantile of random frame distances (untuned)')
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     random.seed(0)
@@ -129,7 +183,9 @@ def main():
     fb, _ = fg.normalize_features({k: fg.fbank_from_samples(v, 16000).cpu().numpy() for k, v in wavs.items()})
     times = {k: np.arange(len(v)) * 0.01 + 0.0125 for k, v in fb.items()}
 
-    gmm_line = gmm_route(fb, times, tokens, args.gmm_components, args.qbe) if args.gmm else None
+    gmm_line = post = None
+    if args.gmm:
+        gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True)
     if args.no_network:
         if not args.gmm:
             ap.error('--no-network leaves nothing to do without --gmm')
@@ -137,6 +193,12 @@ def main():
 
     if args.tcl:
         dl = tcl_loader(fb, times, rng)
+    elif args.terms:
+        if post is not None:
+            dl = terms_loader(post, fb, times, tokens, args.out, 'kl', args.terms_theta, rng)
+        else:
+            corpus = DeviceCorpus({k: np.asarray(v, dtype=np.float32) for k, v in fb.items()}, times)
+            dl = terms_loader(corpus, fb, times, tokens, args.out, 'cosine', args.terms_theta, rng)
     else:
         miner = KnnPairMiner(fb, times, min_similarity=args.min_similarity)
         pairs_path, map_path = miner.write(args.out + '_mined')

@@ -578,6 +578,34 @@ int abn_dtw_search_kl_batched(const float* PU, const float* LU, int64_t rows_u, 
                               const uint8_t* bad_q, double* total_cost, int32_t* path_len, int32_t* start,
                               int32_t* end, const int64_t* prof_off, int64_t prof_rows, double* prof_cost,
                               int32_t* prof_len, int32_t* prof_start, void* stream);
+/* Local-alignment DTW for spoken-term discovery (abnet3_amd/terms.py, whose module docstring is the definition; added
+ * within ABI 20: new symbols only).  The pair table lives on the DEVICE: pair p aligns ANY stretch of rows
+ * [off1[p], off1[p]+n1[p]) of feats1 with ANY stretch of rows [off2[p], off2[p]+n2[p]) of feats2 ([rows, D] fp32).
+ * Cells: abn_dtw_search_batched's d(i, j), blocked cells included.  exclude > 0 also blocks every cell with
+ * |(off1[p] + i) - (off2[p] + j)| < exclude -- table rows, so it needs both sides to be ONE table: feats1 == feats2
+ * and rows1 == rows2, else ABN_E_ARG.  Similarity s = (double)theta - (double)d (theta finite and > 0, else
+ * ABN_E_ARG), -inf for a blocked cell.  Recurrence in float64 (Smith-Waterman): best = the first MAXIMUM of H(i-1, j-1),
+ * H(i-1, j), H(i, j-1) in that order (a cell outside the matrix is dead: H = 0, length 0); best > 0: H = best + s, the
+ * length and the start cell are carried; else H = s, length 1, start (i, j); a cell whose H is not > 0 is dead.
+ * Result: the cell of largest H > 0, ties to the smallest i, then the smallest j: score[p] = H, path_len[p],
+ * start1[p], start2[p] (the path's first cell), end1[p] = i, end2[p] = j, stretch-relative and inclusive.  No live cell
+ * or an empty side: path_len = 0, score = 0, the four bounds -1.  A pair with a negative length, rows outside the
+ * tables or side 2 of more than abn_dtw_local_max_n2() frames is refused: path_len = -1, score = 0, bounds -1, nothing
+ * is read.  Side 1 has no limit.  One launch on `stream`, no workspace. */
+#define ABN_DTW_LOCAL_MAX_N2 512
+int64_t abn_dtw_local_max_n2(void);
+int abn_dtw_local_batched(const float* feats1, int64_t rows1, const float* feats2, int64_t rows2,
+                          const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                          int64_t npairs, int64_t D, float theta, int64_t exclude, double* score,
+                          int32_t* path_len, int32_t* start1, int32_t* start2, int32_t* end1, int32_t* end2,
+                          void* stream);
+/* abn_dtw_local_batched over the symmetrised Kullback-Leibler cell (abn_kl_tables' P, L and row flags of each side).
+ * A cell that touches a flagged row is blocked.  exclude > 0 needs P1 == P2, L1 == L2, bad1 == bad2, rows1 == rows2. */
+int abn_dtw_local_kl_batched(const float* P1, const float* L1, int64_t rows1, const float* P2, const float* L2,
+                             int64_t rows2, const int64_t* off1, const int32_t* n1, const int64_t* off2,
+                             const int32_t* n2, int64_t npairs, int64_t D, const uint8_t* bad1,
+                             const uint8_t* bad2, float theta, int64_t exclude, double* score, int32_t* path_len,
+                             int32_t* start1, int32_t* start2, int32_t* end1, int32_t* end2, void* stream);
 /* ABX triplet scores (abnet3_amd/abx.py).  Row r is one X of ABX cell row_cell[r]: the distances d(A, X) over its A
  * are dist[a_off[r] .. a_off[r] + a_len[r]), the d(B, X) over its B dist[b_off[r] .. b_off[r] + b_len[r]) (device
  * arrays, dist: [ndist] f64).  For every cell c: score2[c] = the sum over its rows and their A x B triplets of 2 when
