@@ -7,3 +7,11 @@ of abnet3/gridsearch.py:145-202 resolves against this package unchanged:
     abnet3_amd.model, .loss, .trainer, .embedder, .dataloader, .features, .utils
 """
 __version__ = '0.1.0'
+
+
+def __getattr__(name):
+    # `from abnet3_amd import KMeansQuantizer`, without importing torch when the package alone is imported
+    if name == 'KMeansQuantizer':
+        from .kmeans import KMeansQuantizer
+        return KMeansQuantizer
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))

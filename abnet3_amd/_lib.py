@@ -77,6 +77,7 @@ SYMBOLS = {
                                            _i64, _vp, _vp]),
     'abn_dtw_cost_max_n2': (_i64, []),
     'abn_dtw_cost_batched': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    'abn_dtw_cost_parallel_batched': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     'abn_kl_tables': (C.c_int, [_vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     'abn_dtw_cost_kl_batched': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
                                            _vp]),
@@ -130,6 +131,12 @@ SYMBOLS = {
     'abn_gmm_accumulate': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, C.c_int, _vp, _i64, _vp]),
     'abn_gmm_mstep': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, C.c_int, _vp, C.c_double, C.c_double, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _vp, _vp]),
+    'abn_kmeans_max_d': (_i64, []),
+    'abn_kmeans_max_k': (_i64, []),
+    'abn_kmeans_assign': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'abn_kmeans_ws_bytes': (_i64, [_i64, _i64, _i64, C.c_int]),
+    'abn_kmeans_accumulate': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, C.c_int, _vp, _i64, _vp]),
+    'abn_kmeans_update': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 # abn_integrate_forward / _backward (include/abnet3_hip.h)
 INTEGRATE_MODE = {'sum': 0, 'concat': 1}

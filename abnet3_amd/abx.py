@@ -11,7 +11,10 @@ The definition this module computes:
 * Distance: d(P, Q) = total_cost / path_len in float64 of the DTW alignment of P (token 1, rows) with Q (token 2)
   over the angular frame distance -- exactly what ``utils.dtw_align_batch`` computes, by the cost-only kernel
   ``abn_dtw_cost_batched``.  Not symmetrised.  A pair the alignment drops (a NaN frame distance: identical or
-  parallel frames whose cosine rounds above 1, or non-finite values) raises ValueError naming the items.  An
+  parallel frames whose cosine rounds above 1, or non-finite values) raises ValueError naming the items.  With
+  ``parallel='zero'`` (default 'drop': the reference's rule) a cosine that rounds beyond +-1 is read as distance 0
+  (1 for opposite frames) instead, the rule of the search kernel: the setting for corpora made of repeated frames,
+  such as ``KMeansQuantizer.quantize`` returns; every pair without such a cell keeps its bits.  An
   all-zero frame is not dropped: it is at distance 1 from every other frame and 0 from another zero frame
   (the reference's rule, csrc/dist_ref.h).
 * Distance, ``distance='kl'`` (posteriorgrams: the rows a softmax network trained with KLLoss emits, the ZeroSpeech
@@ -255,7 +258,10 @@ def kl_tables(table, floor=1e-6):
     return KLTables(P, L, bad)
 
 
-def dtw_cost_batch(feats1, off1, n1, feats2, off2, n2, distance='cosine'):
+PARALLEL = ('drop', 'zero')
+
+
+def dtw_cost_batch(feats1, off1, n1, feats2, off2, n2, distance='cosine', parallel='drop'):
     """(total_cost float64, path_len int32) device tensors of pair p = rows [off1[p], off1[p]+n1[p]) of feats1 against
     [off2[p], off2[p]+n2[p]) of feats2.
 
@@ -264,9 +270,13 @@ def dtw_cost_batch(feats1, off1, n1, feats2, off2, n2, distance='cosine'):
     (utils.dtw_align_batch) for the others.
     distance='kl': feats* are KLTables (or any (P, L, bad) triple) as kl_tables returns them;
     abn_dtw_cost_kl_batched.  A token 2 beyond the cap raises ValueError (there is no second kernel); a pair with a
-    BAD row comes back with path_len = 0."""
+    BAD row comes back with path_len = 0.
+    parallel='zero' (cosine only): abn_dtw_cost_parallel_batched -- a cosine rounded beyond +-1 is distance 0 / 1, the
+    pair is not dropped; it has no second kernel either, so a token 2 beyond the cap raises ValueError."""
     if distance not in DISTANCES:
         raise ValueError('distance must be one of %s, not %r' % (DISTANCES, distance))
+    if parallel not in PARALLEL or (parallel == 'zero' and distance != 'cosine'):
+        raise ValueError('parallel must be one of %s (\'zero\': distance=\'cosine\' only), not %r' % (PARALLEL, parallel))
     lib = _lib.load()
     kl = distance == 'kl'
     if kl:
@@ -280,6 +290,9 @@ def dtw_cost_batch(feats1, off1, n1, feats2, off2, n2, distance='cosine'):
     if kl:
         _beyond_cap('dtw_cost_batch: token 2 of pair %d has %d frames; distance=\'kl\' takes at most %d '
                     '(%d pair(s) beyond it)', n2, cap)
+    if parallel == 'zero':
+        _beyond_cap('dtw_cost_batch: token 2 of pair %d has %d frames; parallel=\'zero\' takes at most %d '
+                    '(%d pair(s) beyond it)', n2, cap)
     cost = torch.empty(P, dtype=torch.float64, device=feats1.device)
     plen = torch.empty(P, dtype=torch.int32, device=feats1.device)
     if P == 0:
@@ -290,6 +303,10 @@ def dtw_cost_batch(feats1, off1, n1, feats2, off2, n2, distance='cosine'):
         _lib.check(lib.abn_dtw_cost_kl_batched(_lib.ptr(feats1), _lib.ptr(L1), feats1.shape[0], _lib.ptr(feats2), _lib.ptr(L2),
                                                feats2.shape[0], *(tail + [_lib.ptr(bad1), _lib.ptr(bad2)] + out)),
                    'abn_dtw_cost_kl_batched')
+        return cost, plen
+    if parallel == 'zero':
+        _lib.check(lib.abn_dtw_cost_parallel_batched(_lib.ptr(feats1), feats1.shape[0], _lib.ptr(feats2), feats2.shape[0],
+                                                     *(tail + out)), 'abn_dtw_cost_parallel_batched')
         return cost, plen
     _lib.check(lib.abn_dtw_cost_batched(_lib.ptr(feats1), feats1.shape[0], _lib.ptr(feats2), feats2.shape[0], *(tail + out)),
                'abn_dtw_cost_batched')
@@ -357,11 +374,16 @@ class ABXEvaluator(object):
     a {name: [T, D]} features dict together with `times` ({name: [T] frame times in seconds}), or the path of an
     h5features file (needs the h5features package).
     distance: 'cosine' (embeddings) or 'kl' (posteriorgrams: the symmetrised Kullback-Leibler divergence over the
-    tables of kl_tables(corpus.table, floor), built here once and kept for every run)."""
+    tables of kl_tables(corpus.table, floor), built here once and kept for every run).
+    parallel: 'drop' (default, the reference's rule: identical or parallel frames whose cosine rounds above 1 drop the
+    pair, which raises) or 'zero' (such frames are at distance 0: for quantised corpora; cosine only)."""
 
-    def __init__(self, items, corpus, times=None, distance='cosine', floor=1e-6):
+    def __init__(self, items, corpus, times=None, distance='cosine', floor=1e-6, parallel='drop'):
         if distance not in DISTANCES:
             raise ValueError('distance must be one of %s, not %r' % (DISTANCES, distance))
+        if parallel not in PARALLEL or (parallel == 'zero' and distance != 'cosine'):
+            raise ValueError('parallel must be one of %s (\'zero\': distance=\'cosine\' only), not %r' % (PARALLEL, parallel))
+        self.parallel = parallel
         from .dataloader import DeviceCorpus
         self.distance = distance
         self.items = read_item_file(items) if isinstance(items, str) else items
@@ -391,7 +413,8 @@ class ABXEvaluator(object):
         """d(P, Q) of every needed pair of `plan` (float64, device)."""
         P, Q = self.kept[plan.P], self.kept[plan.Q]
         t = self.tables if self.distance == 'kl' else self.corpus.table
-        cost, plen = dtw_cost_batch(t, self.row[P], self.n[P], t, self.row[Q], self.n[Q], distance=self.distance)
+        cost, plen = dtw_cost_batch(t, self.row[P], self.n[P], t, self.row[Q], self.n[Q], distance=self.distance,
+                                    parallel=self.parallel)
         ln = plen.cpu().numpy()
         bad = np.flatnonzero(ln <= 0)
         if len(bad):

@@ -90,7 +90,15 @@ extern "C" int abn_dtw_cost_batched(const float* feats1, int64_t rows1, const fl
                                     int64_t npairs, int64_t D, double* total_cost, int32_t* path_len, void* stream)
 {
     return launch_dtw_wave("dtw_cost", feats1, rows1, feats2, rows2, off1, n1, off2, n2, npairs, D,
-                           dtw_out<MODE_COST>{total_cost, path_len}, cell_extra<CELL_COSINE>(), stream);
+                           dtw_out<MODE_COST>{total_cost, path_len, 0}, cell_extra<CELL_COSINE>(), stream);
+}
+
+extern "C" int abn_dtw_cost_parallel_batched(const float* feats1, int64_t rows1, const float* feats2, int64_t rows2,
+                                             const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                                             int64_t npairs, int64_t D, double* total_cost, int32_t* path_len, void* stream)
+{
+    return launch_dtw_wave("dtw_cost_parallel", feats1, rows1, feats2, rows2, off1, n1, off2, n2, npairs, D,
+                           dtw_out<MODE_COST>{total_cost, path_len, 1}, cell_extra<CELL_COSINE>(), stream);
 }
 
 extern "C" int abn_kl_tables(const float* x, int64_t rows, int64_t D, float floor, float* P, float* L, uint8_t* bad_row,
@@ -114,7 +122,7 @@ extern "C" int abn_dtw_cost_kl_batched(const float* P1, const float* L1, int64_t
                                        const uint8_t* bad2, double* total_cost, int32_t* path_len, void* stream)
 {
     return launch_dtw_wave("dtw_cost_kl", P1, rows1, P2, rows2, off1, n1, off2, n2, npairs, D,
-                           dtw_out<MODE_COST>{total_cost, path_len}, cell_extra<CELL_KL>{L1, L2, bad1, bad2}, stream);
+                           dtw_out<MODE_COST>{total_cost, path_len, 0}, cell_extra<CELL_KL>{L1, L2, bad1, bad2}, stream);
 }
 
 extern "C" int abn_abx_score(const double* dist, int64_t ndist, const int64_t* a_off, const int32_t* a_len,

@@ -158,6 +158,7 @@ struct dtw_out<MODE_COST> {
     static constexpr int CAP = ABN_DTW_COST_MAX_N2;
     double* total_cost;
     int32_t* path_len;
+    int parallel_zero;              // cosine cell: != 0 reads a cosine rounded beyond +-1 as distance 0 / 1 (as SEARCH does), 0 drops the pair
     bool complete() const { return total_cost && path_len; }
 };
 template <>
@@ -337,7 +338,12 @@ __global__ __launch_bounds__(64) void dtw_wave_kernel(const float* __restrict__ 
                             d = (norm_is_plain(nx) && norm_is_plain(ny)) ? angular_distance_ref<true>(dot[c], nx, ny)
                                                                          : angular_distance_ref<false>(dot[c], nx, ny);
                             if constexpr (!FREE) {
-                                bad |= !(d >= 0.0f);                // utils.py:59: the pair is dropped
+                                if (!(d >= 0.0f)) {                 // utils.py:59: the pair is dropped, unless the caller
+                                    const float pr = nx * ny;       // asked for the SEARCH rule below and it applies
+                                    if (out.parallel_zero && finite_f32(dot[c]) && finite_f32(pr) && pr != 0.0f)
+                                        d = dot[c] > 0.0f ? 0.0f : 1.0f;
+                                    else bad = true;
+                                }
                             } else if (!(d >= 0.0f)) {
                                 // NaN.  With a finite dot product and a finite non-zero product of the norms it is
                                 // |cos| rounded above 1: parallel frames (0) or opposite ones (1).  Else: blocked.

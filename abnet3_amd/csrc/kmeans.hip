@@ -1,0 +1,537 @@
+// kmeans.hip -- k-means vector quantisation: hard assignment and a deterministic update (abn_kmeans_assign,
+// abn_kmeans_accumulate, abn_kmeans_update).  abnet3_amd/kmeans.py states the definition; DESIGN.md section 3.4d the
+// shape.
+//
+// The score of frame t under centroid k is one row of a GEMM of depth D + 1,
+//   s[t][k] = sum_ka X~[t][ka] W~[k][ka],   X~ = [xc | 1],  W~ = [m | b],  xc = x - shift (fp32),  b = -|m|^2 / 2,
+// so argmax_k s = argmin_k |xc - m[k]|^2.  It is formed on the matrix cores in exact fp32 (v_mfma_f32_32x32x2_f32, ka
+// ascending; the 128 x 32 operand tiles, the fragment reads and the register-staged double buffering of gemm_f32.h, as
+// gmm.hip's likelihood pass uses them).  Neither augmented operand exists in memory, and no T x K array either:
+//   * km_assign_kernel: a workgroup owns 128 frames and sweeps the centroid tiles with a running (best score, best
+//     index) per frame (two threads per frame, 64 centroids of the tile each, ascending k, strict >: equal scores go
+//     to the lowest k), writes ids[t] (-1 for a BAD frame) and adds its count of changed ids to an integer counter;
+//   * km_accum_kernel: the responsibilities are one-hot, so the statistics are D additions per frame, not a GEMM.  A
+//     workgroup owns a tile of centroids and a range of frames; each of its four waves owns a quarter of the tile, scans
+//     the range's ids 64 at a time and, for the frames that are its own, IN FRAME ORDER, adds the row (lanes over
+//     columns) into its accumulators in LDS and the row's squared distance to its centroid into a float64 per lane.
+//     Every row of x is loaded by exactly one wave; the ids are read once per centroid tile;
+//   * km_reduce_kernel sums the partials in range order in float64; km_update_kernel applies the update in float64 and
+//     emits the next tables.
+// No floating-point atomics anywhere: every sum has one fixed order, two calls give the same bits.
+#include "common.h"
+#include "gemm_f32.h"
+
+#include <limits.h>
+#include <math.h>
+
+namespace abn {
+
+constexpr int KM_B = 128;                  // frame block = centroid tile of the assign pass (2 x 2 waves of 2 x 2 MFMA blocks)
+constexpr int KM_MAX_D = 512;
+constexpr int KM_MAX_K = 4096;
+constexpr int KM_MAX_RANGES = 1024;
+constexpr int KM_PT = KM_B * BK / 256;     // elements per thread of a 128 x 32 operand tile (scalar loads: D = 39 rows are not 16-byte aligned)
+constexpr int KM_LST = KM_B + 1;           // a thread walks its frame's row of the staged scores, 129 dwords apart = conflict-free
+constexpr int KM_ACC_FLOATS = 8192;        // accumulate pass: LDS accumulators of one workgroup (32 KiB)
+using KmTile = TileShape<KM_B, true>;
+constexpr size_t KM_TILE_BYTES = sizeof(float) * 4 * KmTile::floats;      // two stages of each operand
+static_assert(KM_TILE_BYTES >= sizeof(float) * KM_B * KM_LST, "the score tile is staged in the operand buffers");
+
+struct KmP {
+    const float* x; const float* shift;
+    const float* m; const float* b;
+    int T, K, D;
+    int* ids; const int* prev; float* best; int* changed;
+    int tiles_k;
+};
+
+// 128 x 32 tiles, K-contiguous in LDS ([row][36]).  Thread t owns column k0 + (t & 31) of rows (t >> 5) + 8 i; column
+// ka < D is xc / m, column D the ones column / b, the rest the zero fill up to the k-tile.  Branch-free issue from
+// clamped addresses, validity applied at commit (gemm_f32.h's tile_issue / tile_commit).
+__device__ __forceinline__ void km_x_issue(float* r, const KmP& p, int m0, int k0)
+{
+    const int t = threadIdx.x, ka = k0 + (t & 31);
+#pragma unroll
+    for (int i = 0; i < KM_PT; ++i) {
+        const int row = m0 + (t >> 5) + 8 * i;
+        r[i] = p.x[(ka < p.D && row < p.T) ? (int64_t)row * p.D + ka : 0];
+    }
+}
+// A non-finite value contributes 0 (its frame is BAD: the kernel marks it and nobody uses its scores).
+__device__ __forceinline__ void km_x_commit(const float* r, float* __restrict__ lds, const KmP& p, int m0, int k0)
+{
+    const int t = threadIdx.x, ka = k0 + (t & 31);
+    const float sh = p.shift[ka < p.D ? ka : 0];
+#pragma unroll
+    for (int i = 0; i < KM_PT; ++i) {
+        const int rl = (t >> 5) + 8 * i;
+        const float xc = r[i] - sh;
+        float v = ka < p.D ? (__builtin_isfinite(xc * xc) ? xc : 0.0f) : ka == p.D ? 1.0f : 0.0f;
+        lds[rl * KmTile::stride + (t & 31)] = m0 + rl < p.T ? v : 0.0f;
+    }
+}
+__device__ __forceinline__ void km_w_issue(float* r, const KmP& p, int n0, int k0)
+{
+    const int t = threadIdx.x, ka = k0 + (t & 31);
+    const float* const base = ka < p.D ? p.m : p.b;
+#pragma unroll
+    for (int i = 0; i < KM_PT; ++i) {
+        const int comp = n0 + (t >> 5) + 8 * i;
+        const int64_t off = ka < p.D ? (int64_t)comp * p.D + ka : (int64_t)comp;
+        r[i] = base[(ka <= p.D && comp < p.K) ? off : 0];
+    }
+}
+__device__ __forceinline__ void km_w_commit(const float* r, float* __restrict__ lds, const KmP& p, int n0, int k0)
+{
+    const int t = threadIdx.x, ka = k0 + (t & 31);
+#pragma unroll
+    for (int i = 0; i < KM_PT; ++i) {
+        const int rl = (t >> 5) + 8 * i;
+        lds[rl * KmTile::stride + (t & 31)] = (ka <= p.D && n0 + rl < p.K) ? r[i] : 0.0f;
+    }
+}
+
+// The 128 x 128 score tile of frames m0 .. and centroids n0 ..: rows = frames, columns = centroids, wave w owns the
+// 64 x 64 block ((w >> 1) 64, (w & 1) 64).  The caller guarantees that nobody still reads the operand buffers; on
+// return every wave has passed the last barrier, so the buffers are free again.  Depth runs in BK chunks, so D up to
+// 512 needs no larger accumulator.
+__device__ __forceinline__ void km_score_tile(const KmP& p, int m0, int n0, float* As, float* Bs, f32x16 (&acc)[2][2])
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
+    const int nkt = (p.D + 1 + BK - 1) / BK;
+    float ra[KM_PT], rb[KM_PT];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    km_x_issue(ra, p, m0, 0);
+    km_w_issue(rb, p, n0, 0);
+    km_x_commit(ra, As, p, m0, 0);
+    km_w_commit(rb, Bs, p, n0, 0);
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+        const int cur = kt & 1;
+        const bool more = kt + 1 < nkt;
+        const float* as = As + cur * KmTile::floats;
+        const float* bs = Bs + cur * KmTile::floats;
+        if (more) {
+            km_x_issue(ra, p, m0, (kt + 1) * BK);
+            km_w_issue(rb, p, n0, (kt + 1) * BK);
+        }
+#pragma unroll
+        for (int g = 0; g < BK / 8; ++g) {
+            f32x4 fa[2], fb[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) fa[i] = frag_read<KM_B, true>(as, wm0 + 32 * i, g, lane);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) fb[j] = frag_read<KM_B, true>(bs, wn0 + 32 * j, g, lane);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][e], fb[j][e], acc[i][j], 0, 0, 0);
+        }
+        if (more) {
+            km_x_commit(ra, As + (cur ^ 1) * KmTile::floats, p, m0, (kt + 1) * BK);
+            km_w_commit(rb, Bs + (cur ^ 1) * KmTile::floats, p, n0, (kt + 1) * BK);
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void km_assign_kernel(KmP p)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const As = smem;
+    float* const Bs = smem + 2 * KmTile::floats;
+    float* const stage = smem;
+    __shared__ float red_s[KM_B];
+    __shared__ int red_i[KM_B], red_c[KM_B];
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
+    const int m0 = (int)blockIdx.x * KM_B;
+    const int row = t & (KM_B - 1), half = t >> 7;       // this thread's frame and its 64 centroids of every tile
+    const int fr = m0 + row;
+
+    // (half 0 always owns centroid 0: its index starts there, so that a frame whose scores never compare greater
+    // than -inf still gets an id inside 0 .. K - 1)
+    float bs = -INFINITY;
+    int bi = half ? INT_MAX : 0;
+    for (int ct = 0; ct < p.tiles_k; ++ct) {
+        const int n0 = ct * KM_B;
+        f32x16 acc[2][2];
+        km_score_tile(p, m0, n0, As, Bs, acc);
+        {   // accumulator register r of lane l: row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31 of its block
+            const int col_l = lane & 31, rsub = 4 * (lane >> 5);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        stage[(wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + rsub) * KM_LST + wn0 + 32 * j + col_l] = acc[i][j][r];
+        }
+        __syncthreads();
+        {
+            const float* const rp = stage + row * KM_LST + 64 * half;
+            const int c0 = n0 + 64 * half;
+            const int nv = min(64, p.K - c0);                      // <= 0: nothing of this tile is mine
+            for (int c = 0; c < nv; ++c) {
+                const float v = rp[c];
+                if (v > bs) { bs = v; bi = c0 + c; }
+            }
+        }
+        __syncthreads();
+    }
+    if (half) { red_s[row] = bs; red_i[row] = bi; }
+    __syncthreads();
+    int diff = 0;
+    if (!half) {
+        const float s1 = red_s[row];
+        const int i1 = red_i[row];
+        if (s1 > bs || (s1 == bs && i1 < bi)) { bs = s1; bi = i1; }
+        if (fr < p.T) {
+            bool bad = false;
+            for (int d = 0; d < p.D; ++d) {
+                const float xc = p.x[(int64_t)fr * p.D + d] - p.shift[d];
+                bad |= !__builtin_isfinite(xc * xc);
+            }
+            const int id = bad ? -1 : bi;
+            if (p.prev) diff = p.prev[fr] != id;                   // (prev may be ids itself: read before the write)
+            p.ids[fr] = id;
+            if (p.best) p.best[fr] = bad ? NAN : bs;
+        }
+        red_c[row] = diff;
+    }
+    if (!p.prev || !p.changed) return;
+    __syncthreads();
+    if (t == 0) {
+        int n = 0;
+        for (int i = 0; i < KM_B; ++i) n += red_c[i];
+        if (n) atomicAdd(p.changed, n);                            // integer: any order gives the same count
+    }
+}
+
+// ---- accumulate ----------------------------------------------------------------------------------------------------
+struct KmGrid { int ct, tiles, fblocks, n_ranges, blocks_per_range; };
+
+struct KmAccP {
+    const float* x; const float* shift; const float* m; const int* ids;
+    int T, K, D;
+    float* S;                   // [n_ranges][K][D]
+    int* N;                     // [n_ranges][K]
+    double* E;                  // [n_ranges][tiles][4]
+    KmGrid g;
+};
+
+// NP: column passes of a lane (columns lane, lane + 64, ...: NP 64 >= D); U: rows whose loads are in flight together.
+template <int NP, int U>
+__global__ __launch_bounds__(256) void km_accum_kernel(KmAccP p)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ int cnt_s[KM_B];
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ct = (int)blockIdx.x % p.g.tiles, rg = (int)blockIdx.x / p.g.tiles;
+    const int cw = p.g.ct >> 2;                               // centroids of a wave
+    const int lc0 = wave * cw, c0 = ct * p.g.ct + lc0;        // first of them: in the tile, in the table
+    const int D = p.D;
+    float* const acc = smem + lc0 * D;                        // [cw][D]: this wave's alone, so no barrier in the loop
+    int* const cnt = cnt_s + lc0;
+
+    for (int u = lane; u < cw * D; u += 64) acc[u] = 0.0f;
+    if (lane < cw) cnt[lane] = 0;
+    __syncthreads();
+
+    float sh[NP];
+#pragma unroll
+    for (int q = 0; q < NP; ++q) sh[q] = p.shift[lane + 64 * q < D ? lane + 64 * q : 0];
+
+    const int64_t f0 = (int64_t)rg * p.g.blocks_per_range * KM_B;
+    const int64_t fe = f0 + (int64_t)p.g.blocks_per_range * KM_B;
+    const int64_t f1 = fe < p.T ? fe : p.T;
+    double e = 0.0;
+    int idn = f0 + lane < f1 ? p.ids[f0 + lane] : -1;
+    for (int64_t base = f0; base < f1; base += 64) {
+        const int id = idn;
+        idn = base + 64 + lane < f1 ? p.ids[base + 64 + lane] : -1;      // the next 64 ids travel behind this block's rows
+        const bool mine = (unsigned)(id - c0) < (unsigned)cw && id < p.K;
+        unsigned long long mask = __ballot(mine);
+        while (mask) {                                        // set bits = this wave's frames of the block, ascending
+            int lc[U];
+            int64_t fr[U];
+            bool on[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                on[u] = mask != 0;
+                const int j = on[u] ? __builtin_ctzll(mask) : 0;
+                if (on[u]) mask &= mask - 1;
+                const int k = __shfl(id, j);                  // (j is wave-uniform)
+                lc[u] = on[u] ? k - c0 : 0;
+                fr[u] = on[u] ? base + j : f0;
+            }
+            float xv[U][NP], mv[U][NP];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int q = 0; q < NP; ++q) {
+                    const int d = lane + 64 * q < D ? lane + 64 * q : 0;
+                    xv[u][q] = p.x[fr[u] * D + d];
+                    mv[u][q] = p.m[(int64_t)(c0 + lc[u]) * D + d];
+                }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (!on[u]) continue;
+                float qs = 0.0f;
+#pragma unroll
+                for (int q = 0; q < NP; ++q) {
+                    const int d = lane + 64 * q;
+                    if (d < D) {
+                        const float xc = xv[u][q] - sh[q];
+                        acc[lc[u] * D + d] += xc;
+                        const float df = xc - mv[u][q];
+                        qs += df * df;
+                    }
+                }
+                e += (double)qs;
+                if (lane == 0) cnt[lc[u]] += 1;
+            }
+        }
+    }
+
+    // this wave's part of the range's partials: every (range, centroid < K) is written by exactly one wave
+    __syncthreads();
+    for (int u = lane; u < cw * D; u += 64) {
+        const int k = c0 + u / D;
+        if (k < p.K) p.S[((int64_t)rg * p.K + k) * D + u % D] = acc[u];
+    }
+    if (lane < cw && c0 + lane < p.K) p.N[(int64_t)rg * p.K + c0 + lane] = cnt[lane];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);   // a fixed tree
+    if (lane == 0) p.E[((int64_t)rg * p.g.tiles + ct) * 4 + wave] = e;
+}
+
+// 256 doubles of LDS summed in a fixed tree; the result is returned to every thread.
+__device__ __forceinline__ double km_block_sum(double v, double* sh)
+{
+    const int t = threadIdx.x;
+    __syncthreads();
+    sh[t] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) sh[t] += sh[t + o];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+// Block k < K: sums[k] = [S[k][0 .. D) | N[k]], the partials in range order in float64 (the counts in integers).
+// Block K: the inertia partials in index order, the BAD frames (id < 0) and the empty centroids -> stats.
+__global__ __launch_bounds__(256) void km_reduce_kernel(const float* __restrict__ S, const int* __restrict__ N,
+                                                         const double* __restrict__ E, const int* __restrict__ ids, int T,
+                                                         int K, int D, int n_ranges, int n_e, double* __restrict__ sums,
+                                                         double* __restrict__ stats)
+{
+    __shared__ double sh[256];
+    const int t = threadIdx.x, k = (int)blockIdx.x;
+    if (k < K) {
+        for (int d = t; d < D; d += 256) {
+            double a = 0.0;
+            for (int r = 0; r < n_ranges; ++r) a += (double)S[((int64_t)r * K + k) * D + d];
+            sums[(int64_t)k * (D + 1) + d] = a;
+        }
+        if (t == 0) {
+            long long n = 0;
+            for (int r = 0; r < n_ranges; ++r) n += N[(int64_t)r * K + k];
+            sums[(int64_t)k * (D + 1) + D] = (double)n;
+        }
+        return;
+    }
+    double in = 0.0, bad = 0.0, empty = 0.0;
+    if (t == 0)
+        for (int i = 0; i < n_e; ++i) in += E[i];
+    for (int i = t; i < T; i += 256) bad += ids[i] < 0 ? 1.0 : 0.0;
+    for (int j = t; j < K; j += 256) {
+        long long n = 0;
+        for (int r = 0; r < n_ranges; ++r) n += N[(int64_t)r * K + j];
+        empty += n == 0 ? 1.0 : 0.0;
+    }
+    bad = km_block_sum(bad, sh);
+    empty = km_block_sum(empty, sh);
+    if (t == 0) { stats[0] = in; stats[1] = bad; stats[2] = empty; stats[3] = (double)T - bad; }
+}
+
+// One workgroup per centroid: mu = S / N in float64 (an empty centroid keeps its mu), the spherical variant
+// renormalises mu to unit length; then m = fp32(mu) and b = fp32(-|m|^2 / 2) over the ROUNDED m (0 when spherical).
+__global__ __launch_bounds__(256) void km_update_kernel(const double* __restrict__ sums, int D, int cosine,
+                                                         double* __restrict__ mu, float* __restrict__ m, float* __restrict__ b)
+{
+    __shared__ double sh[256];
+    const int t = threadIdx.x, k = (int)blockIdx.x;
+    const double n = sums[(int64_t)k * (D + 1) + D];
+    double* const mk = mu + (int64_t)k * D;
+    if (n > 0.0) {
+        double sq = 0.0;
+        for (int d = t; d < D; d += 256) {
+            const double v = sums[(int64_t)k * (D + 1) + d] / n;
+            sq += v * v;
+            if (!cosine) mk[d] = v;
+        }
+        if (cosine) {
+            const double nrm = sqrt(km_block_sum(sq, sh));
+            if (nrm > 0.0)                                    // (a mean of zero length has no direction: mu stays)
+                for (int d = t; d < D; d += 256) mk[d] = sums[(int64_t)k * (D + 1) + d] / n / nrm;
+        }
+    }
+    double hs = 0.0;
+    for (int d = t; d < D; d += 256) {
+        const float r = (float)mk[d];
+        m[(int64_t)k * D + d] = r;
+        hs += (double)r * (double)r;
+    }
+    hs = km_block_sum(hs, sh);
+    if (t == 0) b[k] = cosine ? 0.0f : (float)(-0.5 * hs);
+}
+
+static KmGrid km_grid(int64_t T, int64_t K, int64_t D, int n_ranges)
+{
+    KmGrid g;
+    g.ct = KM_B;                                              // centroids per workgroup: what fits the LDS accumulators
+    while (g.ct > 16 && g.ct * D > KM_ACC_FLOATS) g.ct >>= 1;
+    g.tiles = (int)((K + g.ct - 1) / g.ct);
+    g.fblocks = (int)((T + KM_B - 1) / KM_B);
+    int r = n_ranges;
+    if (r <= 0) r = (2048 + g.tiles - 1) / g.tiles;           // auto: eight workgroups per CU's worth of (tile, range) pairs
+    if (r > KM_MAX_RANGES) r = KM_MAX_RANGES;
+    if (r > g.fblocks) r = g.fblocks;
+    g.blocks_per_range = (g.fblocks + r - 1) / r;
+    g.n_ranges = (g.fblocks + g.blocks_per_range - 1) / g.blocks_per_range;
+    return g;
+}
+
+static int km_check_sizes(int64_t T, int64_t K, int64_t D, int n_ranges, const char* what)
+{
+    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - KM_B, "%s: T = %lld out of range", what, (long long)T);
+    ABN_REQUIRE(K >= 1 && D >= 1, "%s: K = %lld, D = %lld out of range", what, (long long)K, (long long)D);
+    ABN_REQUIRE(n_ranges >= 0 && n_ranges <= KM_MAX_RANGES, "%s: n_ranges = %d, supported 0 (by the grid) .. %d", what,
+                n_ranges, KM_MAX_RANGES);
+    if (D > KM_MAX_D || K > KM_MAX_K) {
+        set_error("%s: D = %lld, K = %lld, supported D <= %d (abn_kmeans_max_d), K <= %d (abn_kmeans_max_k)", what,
+                  (long long)D, (long long)K, KM_MAX_D, KM_MAX_K);
+        return ABN_E_UNSUPPORTED;
+    }
+    return ABN_OK;
+}
+
+// Workspace: [n_ranges][K][D] fp32 sums, [n_ranges][K] int32 counts, [n_ranges][tiles][4] float64 inertia partials.
+struct KmWs { int64_t s_off, n_off, e_off, bytes; };
+static KmWs km_ws(const KmGrid& g, int64_t K, int64_t D)
+{
+    KmWs w;
+    w.s_off = 0;
+    w.n_off = align_up((int64_t)g.n_ranges * K * D * (int64_t)sizeof(float), 16);
+    w.e_off = align_up(w.n_off + (int64_t)g.n_ranges * K * (int64_t)sizeof(int), 16);
+    w.bytes = w.e_off + (int64_t)g.n_ranges * g.tiles * 4 * (int64_t)sizeof(double);
+    return w;
+}
+
+}  // namespace abn
+
+using namespace abn;
+
+extern "C" int64_t abn_kmeans_max_d(void) { return KM_MAX_D; }
+extern "C" int64_t abn_kmeans_max_k(void) { return KM_MAX_K; }
+
+extern "C" int64_t abn_kmeans_ws_bytes(int64_t T, int64_t K, int64_t D, int n_ranges)
+{
+    if (km_check_sizes(T, K, D, n_ranges, "abn_kmeans_ws_bytes") != ABN_OK) return -1;
+    return km_ws(km_grid(T, K, D, n_ranges), K, D).bytes;
+}
+
+extern "C" int abn_kmeans_assign(const float* x, int64_t T, int64_t D, const float* shift, const float* m, const float* b,
+                                 int64_t K, const int32_t* prev_ids, int32_t* ids, float* best, int32_t* changed, void* stream)
+{
+    const int rc = km_check_sizes(T, K, D, 0, "abn_kmeans_assign");
+    if (rc != ABN_OK) return rc;
+    ABN_REQUIRE(x && shift && m && b && ids, "abn_kmeans_assign: null pointer");
+    ABN_REQUIRE(!prev_ids || changed, "abn_kmeans_assign: prev_ids without a counter");
+    static bool attr_set[16] = {};
+    if (first_use_on_device(attr_set))
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(km_assign_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)KM_TILE_BYTES);
+    KmP p;
+    p.x = x; p.shift = shift; p.m = m; p.b = b;
+    p.T = (int)T; p.K = (int)K; p.D = (int)D;
+    p.ids = ids; p.prev = prev_ids; p.best = best; p.changed = changed;
+    p.tiles_k = (int)((K + KM_B - 1) / KM_B);
+    hipLaunchKernelGGL(km_assign_kernel, dim3((unsigned)((T + KM_B - 1) / KM_B)), dim3(256), KM_TILE_BYTES,
+                       static_cast<hipStream_t>(stream), p);
+    ABN_CHECK_LAUNCH("abn_kmeans_assign");
+    return ABN_OK;
+}
+
+extern "C" int abn_kmeans_accumulate(const float* x, int64_t T, int64_t D, const float* shift, const float* m, int64_t K,
+                                     const int32_t* ids, int n_ranges, void* ws, int64_t ws_bytes, void* stream)
+{
+    const int rc = km_check_sizes(T, K, D, n_ranges, "abn_kmeans_accumulate");
+    if (rc != ABN_OK) return rc;
+    ABN_REQUIRE(x && shift && m && ids, "abn_kmeans_accumulate: null pointer");
+    const KmGrid g = km_grid(T, K, D, n_ranges);
+    const KmWs w = km_ws(g, K, D);
+    if (!ws || ws_bytes < w.bytes) {
+        set_error("abn_kmeans_accumulate: workspace of %lld bytes, %lld needed (abn_kmeans_ws_bytes)", (long long)ws_bytes,
+                  (long long)w.bytes);
+        return ABN_E_WORKSPACE;
+    }
+    ABN_REQUIRE(aligned16(ws), "abn_kmeans_accumulate: the workspace must be 16-byte aligned");
+    KmAccP p;
+    p.x = x; p.shift = shift; p.m = m; p.ids = ids;
+    p.T = (int)T; p.K = (int)K; p.D = (int)D;
+    char* const base = static_cast<char*>(ws);
+    p.S = reinterpret_cast<float*>(base + w.s_off);
+    p.N = reinterpret_cast<int*>(base + w.n_off);
+    p.E = reinterpret_cast<double*>(base + w.e_off);
+    p.g = g;
+    const dim3 grid((unsigned)(g.tiles * g.n_ranges));
+    const size_t lds = sizeof(float) * (size_t)g.ct * (size_t)D;          // <= 32 KiB
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (D <= 64) hipLaunchKernelGGL((km_accum_kernel<1, 4>), grid, dim3(256), lds, st, p);
+    else if (D <= 128) hipLaunchKernelGGL((km_accum_kernel<2, 4>), grid, dim3(256), lds, st, p);
+    else if (D <= 256) hipLaunchKernelGGL((km_accum_kernel<4, 2>), grid, dim3(256), lds, st, p);
+    else hipLaunchKernelGGL((km_accum_kernel<8, 2>), grid, dim3(256), lds, st, p);
+    ABN_CHECK_LAUNCH("abn_kmeans_accumulate");
+    return ABN_OK;
+}
+
+extern "C" int abn_kmeans_update(const void* ws, int64_t ws_bytes, const int32_t* ids, int64_t T, int64_t K, int64_t D,
+                                 int n_ranges, int cosine, double* sums, double* mu, float* m, float* b, double* stats,
+                                 void* stream)
+{
+    const int rc = km_check_sizes(T, K, D, n_ranges, "abn_kmeans_update");
+    if (rc != ABN_OK) return rc;
+    ABN_REQUIRE(ids && sums && stats, "abn_kmeans_update: null pointer");
+    ABN_REQUIRE((mu && m && b) || (!mu && !m && !b), "abn_kmeans_update: mu, m and b go together (all null: statistics only)");
+    const KmGrid g = km_grid(T, K, D, n_ranges);
+    const KmWs w = km_ws(g, K, D);
+    if (!ws || ws_bytes < w.bytes) {
+        set_error("abn_kmeans_update: workspace of %lld bytes, %lld needed (abn_kmeans_ws_bytes)", (long long)ws_bytes,
+                  (long long)w.bytes);
+        return ABN_E_WORKSPACE;
+    }
+    const char* const base = static_cast<const char*>(ws);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(km_reduce_kernel, dim3((unsigned)K + 1), dim3(256), 0, st, reinterpret_cast<const float*>(base + w.s_off),
+                       reinterpret_cast<const int*>(base + w.n_off), reinterpret_cast<const double*>(base + w.e_off), ids, (int)T,
+                       (int)K, (int)D, g.n_ranges, g.n_ranges * g.tiles * 4, sums, stats);
+    ABN_CHECK_LAUNCH("abn_kmeans_update (reduce)");
+    if (!mu) return ABN_OK;
+    hipLaunchKernelGGL(km_update_kernel, dim3((unsigned)K), dim3(256), 0, st, sums, (int)D, cosine ? 1 : 0, mu, m, b);
+    ABN_CHECK_LAUNCH("abn_kmeans_update");
+    return ABN_OK;
+}

@@ -205,7 +205,9 @@ class GmmPosteriorgram(object):
             raise ValueError('GmmPosteriorgram: K = %d, the kernels take 1 .. %d (abn_gmm_max_k)' % (self.n_components, max_k()))
 
     # -- fit ------------------------------------------------------------------------------------------------------
-    def fit(self, corpus, n_ranges=0):
+    def fit(self, corpus, n_ranges=0, init_means=None):
+        """init_means: a [K, D] array of means to start from (KMeansQuantizer.centroids_, say) instead of the
+        documented draw; the variances and weights start as documented."""
         self._check_k()
         table, _ = self._corpus(corpus)
         K = self.n_components
@@ -214,6 +216,11 @@ class GmmPosteriorgram(object):
         if not (gv > 0).all():
             raise ValueError('GmmPosteriorgram.fit: dimension %d of the table is constant' % int(np.argmin(gv > 0)))
         w, m, v = initial_parameters(table, shift, gv, good, K, self.seed)
+        if init_means is not None:
+            m = np.array(init_means, dtype=np.float64)
+            if m.shape != (K, table.shape[1]) or not np.isfinite(m).all():
+                raise ValueError('GmmPosteriorgram.fit: init_means must be a finite [%d, %d] array' % (K, table.shape[1]))
+            m -= shift.cpu().numpy().astype(np.float64)
         st = EMState(w, m, v, gv, table.device)
         self.log_likelihoods = []
         for it in range(self.n_iter):

@@ -6,6 +6,7 @@ mined pairs, and the ABX item file ("phones" = word types).
 
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
                                      [--gmm] [--gmm-components 64] [--no-network] [--terms] [--terms-theta T]
+                                     [--kmeans] [--kmeans-clusters 50]
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
 error is printed under both frame distances, the angular cosine and the symmetrised Kullback-Leibler divergence.
@@ -22,6 +23,9 @@ after it, otherwise its figures are printed again beside the embeddings'.
 every other -- over the filterbanks, or with --gmm over the mixture's posteriorgrams under the KL distance -- clustered
 into a .classes file, from which SamplerClusterSiamese draws the train and dev pairs: the reference's canonical route,
 with discovered clusters in place of labelled ones.  The purity of the clusters against the planted words is printed.
+--kmeans adds discrete units (abnet3_amd/kmeans.py): k-means over the embeddings -- with --no-network over the
+filterbanks -- and prints the units' bitrate and the ABX error of the quantised frames (each frame replaced by its
+centroid, the ZeroSpeech way of scoring units) next to the continuous ones.
 """
 import argparse
 import os
@@ -38,6 +42,7 @@ from abnet3_amd.discovery import KnnPairMiner                     # noqa: E402
 from abnet3_amd.embedder import EmbedderSiamese                   # noqa: E402
 from abnet3_amd.features import FeaturesGenerator                 # noqa: E402
 from abnet3_amd.gmm import GmmPosteriorgram                       # noqa: E402
+from abnet3_amd.kmeans import KMeansQuantizer, bitrate, unit_sequences   # noqa: E402
 from abnet3_amd.loss import KLLoss, coscos2                       # noqa: E402
 from abnet3_amd.model import SiameseNetwork                       # noqa: E402
 from abnet3_amd.sampler import SamplerClusterSiamese              # noqa: E402
@@ -157,6 +162,21 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False):
     return (line, post) if want_post else line
 
 
+def kmeans_route(corpus, items, label, n_clusters):
+    """frames -> KMeansQuantizer.fit -> unit ids (bitrate) and quantised frames (ABX) beside the continuous ones."""
+    q = KMeansQuantizer(n_clusters).fit(corpus)
+    seconds = 0.01 * corpus.total
+    rate = bitrate(unit_sequences(q.predict(corpus), collapse=False), seconds)
+    merged = bitrate(unit_sequences(q.predict(corpus)), seconds)
+    cont = ABXEvaluator(items, corpus).run('within')
+    # (quantised frames are identical by construction: parallel='zero' reads a cosine that rounds above 1 as distance 0
+    # where the reference's rule drops the pair)
+    quant = 'quantised %.2f %%' % ABXEvaluator(items, q.quantize(corpus), parallel='zero').run('within').error
+    print('k-means units of the %s (K = %d, %d iterations, inertia %.4f, %d empty): %.0f bit/s (%.0f with runs merged); '
+          'ABX error continuous %.2f %%, %s (%d triplets)'
+          % (label, n_clusters, len(q.inertias), q.inertias[-1], q.n_empty_, rate, merged, cont.error, quant, cont.n_triplets))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--utts', type=int, default=40)
@@ -172,6 +192,8 @@ def main():
     ap.add_argument('--no-network', action='store_true', help='with --gmm: stop after the mixture, train nothing')
     ap.add_argument('--terms', action='store_true', help='pairs from term discovery: clusters -> SamplerClusterSiamese')
     ap.add_argument('--terms-theta', type=float, default=None, help='default: a low quantile of random frame distances (untuned)')
+    ap.add_argument('--kmeans', action='store_true', help='discrete units: k-means of the embeddings (--no-network: of the filterbanks), bitrate and ABX')
+    ap.add_argument('--kmeans-clusters', type=int, default=50)
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     random.seed(0)
@@ -187,8 +209,11 @@ def main():
     if args.gmm:
         gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True)
     if args.no_network:
-        if not args.gmm:
-            ap.error('--no-network leaves nothing to do without --gmm')
+        if not (args.gmm or args.kmeans):
+            ap.error('--no-network leaves nothing to do without --gmm or --kmeans')
+        if args.kmeans:
+            corpus = DeviceCorpus({k: np.asarray(v, dtype=np.float32) for k, v in fb.items()}, times)
+            kmeans_route(corpus, word_items(tokens)[1], 'filterbanks', args.kmeans_clusters)
         return
 
     if args.tcl:
@@ -239,6 +264,8 @@ def main():
             print('ABX error on %s: %.2f %% (%d triplets)' % (label, r.error, r.n_triplets))
         if args.qbe:
             qbe_search(corpus, keep, names, label, 'kl' if args.softmax and label == 'embeddings' else 'cosine')
+        if args.kmeans and label == 'embeddings':
+            kmeans_route(corpus, items, label, args.kmeans_clusters)
     if gmm_line:
         print(gmm_line)
 

@@ -527,6 +527,14 @@ int64_t abn_dtw_cost_max_n2(void);
 int abn_dtw_cost_batched(const float* feats1, int64_t rows1, const float* feats2, int64_t rows2,
                          const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
                          int64_t npairs, int64_t D, double* total_cost, int32_t* path_len, void* stream);
+/* abn_dtw_cost_batched, except that a cosine which rounds beyond +-1 -- parallel or opposite frames, identical ones
+ * among them: a finite dot product over a finite non-zero product of the norms -- is read as distance 0 (1 when
+ * opposite), the rule of abn_dtw_search_batched, instead of dropping the pair.  Every pair without such a cell gets
+ * the same bits as from abn_dtw_cost_batched.  For corpora made of repeated frames (KMeansQuantizer.quantize); added
+ * within ABI 20: a new symbol only. */
+int abn_dtw_cost_parallel_batched(const float* feats1, int64_t rows1, const float* feats2, int64_t rows2,
+                                  const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                                  int64_t npairs, int64_t D, double* total_cost, int32_t* path_len, void* stream);
 /* The tables of the symmetrised Kullback-Leibler frame distance (ABX of posteriorgrams, abnet3_amd/abx.py; added
  * within ABI 20: new symbols only).  x: [rows, D] fp32 on the device; floor > 0.  P[r, k] = max(x[r, k], floor),
  * L[r, k] = (float)log((double)P[r, k]) (both [rows, D] fp32, no renormalisation); bad_row[r] (uint8 [rows], written
@@ -906,6 +914,44 @@ int abn_gmm_accumulate(const float* x, int64_t T, int64_t D, const float* shift,
 int abn_gmm_mstep(const void* ws, int64_t ws_bytes, const float* lse, int64_t T, int64_t K, int64_t D, int n_ranges,
                   const double* gv, double var_floor, double min_count, double* sums, double* w, double* mu,
                   double* var, float* A, float* B, float* c, double* stats, void* stream);
+
+/* ---- k-means discrete units (no counterpart in the reference; added within ABI 20) ---------------------------------
+ * K centroids over D-dimensional frames, as abnet3_amd/kmeans.py defines it.  The model reaches the kernels as two
+ * fp32 tables, m [K][D] = centroid - shift and b [K] = -|m|^2 / 2 (0 for spherical k-means, whose caller passes unit
+ * rows and a zero shift); the frames x [T][D] are centred on load, xc = x - shift in fp32.  The score
+ *   s[t][k] = sum_d xc m + b[k]
+ * is one fp32 GEMM of depth D + 1 on the matrix cores (v_mfma_f32_32x32x2_f32, the augmented row [xc | 1] formed on
+ * the way into LDS), and ids[t] = argmax_k s, equal scores to the lowest k; a frame with a non-finite xc^2 is BAD:
+ * ids[t] = -1, it adds nothing to the statistics.
+ * D <= abn_kmeans_max_d(), K <= abn_kmeans_max_k(): beyond them ABN_E_UNSUPPORTED; T < 2^31 - 128; n_ranges 0 .. 1024;
+ * null pointers and sizes < 1 are ABN_E_ARG -- all before any launch.  No floating-point atomics: every call is
+ * bit-reproducible. */
+int64_t abn_kmeans_max_d(void);            /* host */
+int64_t abn_kmeans_max_k(void);            /* host */
+
+/* ids [T] int32; best [T] = the winning score (NaN for a BAD frame), or NULL.  With prev_ids [T] (which may be ids
+ * itself) the number of frames whose id differs from it is ADDED to *changed (int32, device; the caller zeroes it).
+ * One launch; no T x K array. */
+int abn_kmeans_assign(const float* x, int64_t T, int64_t D, const float* shift, const float* m, const float* b,
+                      int64_t K, const int32_t* prev_ids, int32_t* ids, float* best, int32_t* changed, void* stream);
+
+/* Partial statistics of the hard assignment ids (an id outside 0 .. K - 1 is skipped): per range of 128-frame blocks
+ * (n_ranges, 0: chosen from the grid) and centroid the count (int32) and the fp32 sum of xc over its frames in frame
+ * order, and partial sums (float64) of the frames' distortions |xc - m[ids[t]]|^2, formed directly.  A memory-bound
+ * pass: every row of x is loaded once.  ws: abn_kmeans_ws_bytes (host, -1 for refused sizes), 16-byte aligned.
+ * One launch. */
+int64_t abn_kmeans_ws_bytes(int64_t T, int64_t K, int64_t D, int n_ranges);
+int abn_kmeans_accumulate(const float* x, int64_t T, int64_t D, const float* shift, const float* m, int64_t K,
+                          const int32_t* ids, int n_ranges, void* ws, int64_t ws_bytes, void* stream);
+
+/* Sums the partials of abn_kmeans_accumulate (same T, K, D, n_ranges, ids) in range order in float64 into
+ * sums [K][D + 1] = [S | N] and stats [4] float64: sum of the distortions, BAD frames, empty centroids, good frames.
+ * Then the update in float64: mu [K][D] (centred centroids, in / out) = S / N, a centroid with N = 0 keeps its mu;
+ * cosine != 0 renormalises each new mu to unit length; m, b: the next tables, rounded once (b from the rounded m).
+ * mu, m and b all NULL: the statistics alone.  Two small launches. */
+int abn_kmeans_update(const void* ws, int64_t ws_bytes, const int32_t* ids, int64_t T, int64_t K, int64_t D,
+                      int n_ranges, int cosine, double* sums, double* mu, float* m, float* b, double* stats,
+                      void* stream);
 
 #ifdef __cplusplus
 }
