@@ -14,4 +14,7 @@ def __getattr__(name):
     if name == 'KMeansQuantizer':
         from .kmeans import KMeansQuantizer
         return KMeansQuantizer
+    if name in ('TermEvaluator', 'edit_distance_batch', 'read_alignment', 'read_classes', 'transcribe'):
+        from . import tde
+        return getattr(tde, name)
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -92,6 +92,8 @@ SYMBOLS = {
                                          _vp, _vp]),
     'abn_dtw_local_kl_batched': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _f32, _i64,
                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'abn_edit_max_short': (_i64, []),
+    'abn_edit_distance_batched': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     'abn_cosine_distance': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     'abn_cosine_distance_f64': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     'abn_arccos_f32': (C.c_int, [_vp, _i64, C.c_int, _vp, _vp]),
@@ -228,6 +230,11 @@ PATH_PER_LAYER, PATH_FUSED_F32, PATH_PLANES, PATH_PLANES_INFER, PATH_PLANES_INFE
 PRECISION_NAMES = {0: 'fp32', 1: 'bf16', 2: 'bf16x3', 3: 'f16x2'}
 # abn_mfcc_path's answers
 MFCC_GENERAL, MFCC_WAVE512 = 0, 1
+# abn_edit_distance_batched: ABN_EDIT_MAX_SHORT, and the grid cap ABN_EDIT_GRID_BLOCKS x ABN_EDIT_BLOCK_PAIRS = the pairs
+# one pass of its grid-stride loop holds
+EDIT_MAX_SHORT = 256
+EDIT_GRID_BLOCKS, EDIT_BLOCK_PAIRS = 4096, 64
+EDIT_GRID_PAIRS = EDIT_GRID_BLOCKS * EDIT_BLOCK_PAIRS
 
 # Which kernels the tower calls of this process took: filled in by model.py from abn_tower_path (a pure
 # query with the call's own arguments) while `trace_paths` is on -- tests, bench.py and the trainer's log

@@ -614,6 +614,25 @@ int abn_dtw_local_kl_batched(const float* P1, const float* L1, int64_t rows1, co
                              const int32_t* n2, int64_t npairs, int64_t D, const uint8_t* bad1,
                              const uint8_t* bad2, float theta, int64_t exclude, double* score, int32_t* path_len,
                              int32_t* start1, int32_t* start2, int32_t* end1, int32_t* end2, void* stream);
+/* Batched Levenshtein distance over int32 symbol sequences (abnet3_amd/tde.py: the normalised edit distance of
+ * discovered term pairs; added within ABI 20: new symbols only).  All tables live on the DEVICE; sym1 == sym2 is
+ * allowed.  A symbol is any int32, compared by equality only.  dist[p] = the Levenshtein distance, insertion, deletion
+ * and substitution costing 1 each, of sym1[off1[p] .. off1[p]+n1[p]) and sym2[off2[p] .. off2[p]+n2[p]).  An empty side
+ * is legal: the distance is the other side's length.  The distance is symmetric and the kernel itself puts the SHORTER
+ * side where its cap applies: a pair is refused when min(n1[p], n2[p]) > max_short, when a length is negative or when
+ * its rows lie outside their table -- dist[p] = -1 and nothing is read.  The longer side has no limit.
+ * max_short is the caller's promise, 1 .. ABN_EDIT_MAX_SHORT (else ABN_E_ARG): the host picks the kernel from it
+ * without reading device memory (<= 32, <= 64, <= 256).  One launch on `stream`, no workspace, any npairs (a
+ * grid-stride loop over at most ABN_EDIT_GRID_BLOCKS workgroups of ABN_EDIT_BLOCK_PAIRS pairs); npairs == 0 returns at
+ * once.  Null pointers (a table of 0 rows may be NULL) and a max_short out of range are ABN_E_ARG before any launch,
+ * with a message in abn_last_error(). */
+#define ABN_EDIT_MAX_SHORT 256
+#define ABN_EDIT_GRID_BLOCKS 4096
+#define ABN_EDIT_BLOCK_PAIRS 64
+int64_t abn_edit_max_short(void);
+int abn_edit_distance_batched(const int32_t* sym1, int64_t rows1, const int32_t* sym2, int64_t rows2,
+                              const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                              int64_t npairs, int64_t max_short, int32_t* dist, void* stream);
 /* ABX triplet scores (abnet3_amd/abx.py).  Row r is one X of ABX cell row_cell[r]: the distances d(A, X) over its A
  * are dist[a_off[r] .. a_off[r] + a_len[r]), the d(B, X) over its B dist[b_off[r] .. b_off[r] + b_len[r]) (device
  * arrays, dist: [ndist] f64).  For every cell c: score2[c] = the sum over its rows and their A x B triplets of 2 when
