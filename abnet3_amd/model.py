@@ -412,7 +412,7 @@ def _segment_backward(seg, sv, d_out, grad_pass, need_dx, d_out_is_dz=False, def
     """Raw backward of one segment: abn_tower_backward into the pass's flat gradient
     buffer.  Returns (per-parameter gradient views, dx or None).  With defer_reduce the
     weight gradients stay unreduced in the scratch and the third return value is what
-    abn_tower_reduce_step needs to finish: (descriptor, rows, scratch, scratch floats, buffer)."""
+    abn_tower_reduce_step needs to finish: (descriptor, rows, scratch, scratch floats, buffer, segment, forward workspace)."""
     lib = _lib.load()
     if seg.batch_norm and not sv.train:
         raise NotImplementedError(
@@ -443,7 +443,8 @@ def _segment_backward(seg, sv, d_out, grad_pass, need_dx, d_out_is_dz=False, def
         _lib.ptr(dx), _lib.stream()), 'abn_tower_backward')
     _lib.note_path(desc, sv.x1, sv.x2, rows, sv.n_calls, True, sv.ws, backward=True)
     if defer_reduce:
-        return grads, dx, (desc, rows, scratch, scratch_floats, grad_buf, seg)
+        # (the last entry keeps the lent forward workspace -- desc.fwd_ws is a bare address -- alive until the optimizer's launch)
+        return grads, dx, (desc, rows, scratch, scratch_floats, grad_buf, seg, sv.ws)
     return grads, dx
 
 
@@ -666,6 +667,16 @@ class _HipNetwork(NetworkBuilder):
             if p.grad is not None:
                 buf[off:off + p.numel()].copy_(p.grad.reshape(-1))
                 p.grad = buf[off:off + p.numel()].view(p.shape)
+        self._last_grad_flat = buf
+        return buf
+
+    def zero_flat_grad(self):
+        """Installs an all-zero flat gradient buffer as every live p.grad (its views) and returns it: what a backward
+        over a batch of no rows leaves behind in the reference (every gradient is a sum over the rows)."""
+        self.flat_parameters()
+        buf = torch.zeros_like(self._flat)
+        for p, off in zip(self.live_parameters(), self._offsets):
+            p.grad = buf[off:off + p.numel()].view(p.shape)
         self._last_grad_flat = buf
         return buf
 
@@ -995,7 +1006,7 @@ class SiameseNetwork(_HipNetwork):
             return None
         _lib.check(rc, 'abn_tower_backward_loss')
         _lib.note_path(desc, sv.x1, sv.x2, rows, sv.n_calls, True, sv.ws, backward=True)
-        self._pending_reduce = (desc, rows, scratch, scratch_floats, grad_buf, seg) if defer_reduce else None
+        self._pending_reduce = (desc, rows, scratch, scratch_floats, grad_buf, seg, sv.ws) if defer_reduce else None      # (sv.ws: see _segment_backward)
         self._pending_lower = (desc, rows, scratch, scratch_floats, sv) if wgrad_split is not None else None
         for p, g in zip(seg.params, grads):
             p.grad = g
@@ -1023,7 +1034,8 @@ class SiameseNetwork(_HipNetwork):
         return int(offs[layer * per_layer])
 
     def take_pending_reduce(self):
-        """The unfinished reduction a direct_backward(defer_reduce=True) left (or None); clears it."""
+        """The unfinished reduction a direct_backward(defer_reduce=True) left (or None); clears it.  The tuple owns the
+        scratch and the forward workspace the launch reads: the caller drops it once abn_tower_reduce_step is enqueued."""
         pending = getattr(self, '_pending_reduce', None)
         self._pending_reduce = None
         return pending

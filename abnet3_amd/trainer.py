@@ -148,7 +148,7 @@ class FlatOptimizer(object):
             hp0 = self.momentum
         if pending is not None:
             # the backward left its split-K slabs unreduced: reduction + update in one launch
-            desc, rows, scratch, scratch_floats, grad_buf, seg = pending
+            desc, rows, scratch, scratch_floats, grad_buf, seg = pending[:6]      # (pending[6]: the lent forward workspace, alive until here)
             if grad_buf.data_ptr() != grad.data_ptr():
                 raise RuntimeError('abnet3_amd: gradients were replaced between a deferred backward and step()')
             _lib.check(lib.abn_tower_reduce_step(
@@ -477,6 +477,18 @@ class TrainerSiamese(TrainerBuilder):
                     self.optimizer.grad_scale = parallel.all_reduce_gradients(
                         self.network.flat_grad(), self._loss_is_mean(), self.oneshot)
             self.optimizer.step()
+        elif do_training and self._direct_ok() and not getattr(self.network, 'batch_norm', False):
+            # A batch of no frame pairs (word pairs whose tokens are empty: the reference's iterator yields it,
+            # abnet3/dataloader.py:248-255).  There is nothing to launch a tower or a pair loss on (the library takes B >= 1);
+            # the reference's five statements still run: embeddings of zero rows, a loss that is the sum over no pairs (0; as a
+            # mean 0 / 0), every gradient a sum over no rows, and an optimizer step on them (momentum and the running averages
+            # move on).  (With BatchNorm the reference's forward raises on such a batch; so does the path below.)
+            loss_value = torch.full((), float('nan') if self.loss.avg else 0.0, dtype=torch.float32, device=self.network.flat_parameters().device)
+            self.network.take_pending_reduce()
+            grad = self.network.zero_flat_grad()
+            if self.dp:
+                self.optimizer.grad_scale = parallel.all_reduce_gradients(grad, self._loss_is_mean(), self.oneshot)
+            self.optimizer.step()
         elif do_training:
             loss_value = self.give_batch_to_network(batch)
             self.optimizer.zero_grad()
@@ -714,7 +726,9 @@ class TrainerSiamese(TrainerBuilder):
     def _planned_step(self, plan, bid, source=None):
         """One training step on batch `bid` of the plan; returns 0 (nothing stepped) when the library refuses
         the padded form for this network / batch size: the caller then takes the iterator's step on the batch; 1: stepped;
-        2: stepped from the plan itself (`source`: the step's own last launch has advanced the pass's step counter)."""
+        2: stepped from the plan itself AND the step's last launch was abn_tower_reduce_step, the one launch that advances the
+        pass's step counter (`source`).  A sourced step whose reduction was not deferred (ABN_FUSED_STEP=0, parameters outside
+        the segment: SiameseNetwork.can_defer_reduce) ends in abn_optimizer_step, which knows no counter: 1, the caller moves it."""
         lib = _lib.load()
         first, n = plan.span(bid)
         if n == 0:        # no arrays: ValueError like the reference's np.vstack([]); zero frames: the iterator's (empty) step
@@ -738,7 +752,6 @@ class TrainerSiamese(TrainerBuilder):
                                             first, n, b['npad'], _lib.ptr(plan.labels), plan.labels.element_size(),
                                             _lib.ptr(b['x12']), _lib.ptr(b['y']), _lib.ptr(b['nv']), _lib.stream()),
                        'abn_gather_pairs')
-        done = 2 if sourced else 1
         opt = self.optimizer
         in_graph_opt = not self.dp and opt.kind != 'adam'      # (Adam's bias correction is host arithmetic per step)
         if b['graph'] is not None:
@@ -754,13 +767,16 @@ class TrainerSiamese(TrainerBuilder):
             else:
                 net._pending_reduce = pending
                 self._bucket_finish()
-            return done
+            return 2 if sourced and in_graph_opt and pending is not None else 1
         # first batch of this bucket: the step itself runs eagerly (and warms everything up), then the same
         # launch sequence is captured for the batches to come (capturing executes nothing)
         if getattr(self.network, 'batch_norm', False) and not self.network.takes_padded_batch_norm(b['x12'], b['npad']):
             return 0                          # (odd widths: the per-layer kernels, no real-row count inside their statistics)
         if self._bucket_body(b) is None:
             return 0
+        # (who ends the step: the deferred reduction's launch advances the counter, every other ending leaves it to the caller --
+        # the capture below records the same launches, so an eager step and its replays answer alike)
+        done = 2 if sourced and getattr(self.network, '_pending_reduce', None) is not None else 1
         self._bucket_finish()
         if len([1 for v in self._buckets.values() if v['graph'] is not None]) >= self.MAX_BUCKET_GRAPHS:
             return done
