@@ -17,4 +17,7 @@ def __getattr__(name):
     if name in ('TermEvaluator', 'edit_distance_batch', 'read_alignment', 'read_classes', 'transcribe'):
         from . import tde
         return getattr(tde, name)
+    if name in ('TermPrefilter', 'lsh_planes', 'lsh_signatures', 'diag_hits_batch'):
+        from . import prefilter
+        return getattr(prefilter, name)
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -94,6 +94,9 @@ SYMBOLS = {
                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'abn_edit_max_short': (_i64, []),
     'abn_edit_distance_batched': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    'abn_lsh_signatures': (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    'abn_lsh_diag_hits_batched': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
+                                             _vp, _vp, _vp, _vp]),
     'abn_cosine_distance': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     'abn_cosine_distance_f64': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     'abn_arccos_f32': (C.c_int, [_vp, _i64, C.c_int, _vp, _vp]),

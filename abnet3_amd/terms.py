@@ -4,6 +4,7 @@ features -> (GmmPosteriorgram) -> TermDiscoverer -> .classes -> SamplerClusterSi
 
     python -m abnet3_amd.terms FEATURES OUT_DIR [--distance cosine|kl] [--floor F] [--theta T] [--min-frames N]
                                [--max-distance D] [--exclude N] [--window N] [--merge-overlap R]
+                               [--prefilter [--bits B] [--max-hamming H] [--span S] [--dilate C] [--min-hits N] [--lsh-seed K]]
 
 The definition this module computes (tests/terms_np.py restates it in numpy bit for bit; the LOCAL mode of
 csrc/dtw_wave.h is the kernel):
@@ -42,6 +43,8 @@ csrc/dtw_wave.h is the kernel):
   one window when v fits, none when it is empty (nor when u is).  Order: the utterance pairs', windows by first frame.
   The pairs of an utterance with ITSELF run with `exclude` (default min_frames), all others with 0 -- in launches of
   their own, because the last rows of one file and the first of the next are neighbours in the table.
+* With a prefilter (abnet3_amd/prefilter.py: LSH signatures, the dot plot's longest diagonal run per kernel pair) only
+  the kernel pairs it keeps are aligned, in the same order; without one (the default) all are, and nothing else runs.
 * A match is kept when path_len > 0, both of its stretches have at least min_frames frames and, if max_distance is
   given, theta - score / path_len <= max_distance.  A repeat of the same (u, first1, last1, v, first2, last2) -- two
   windows that see one match -- is left out.  Matches stay in kernel-pair order.
@@ -260,12 +263,13 @@ class TermDiscoverer(object):
     shortest stretch kept.  max_distance: the largest mean frame distance kept (None: no limit).  exclude: the
     half-width of the band around the diagonal blocked when an utterance meets itself (None: min_frames).  window:
     side-2 window in frames (None: max_n2(), the maximum).  chunk_pairs: how many kernel pairs one launch takes.
+    prefilter: a prefilter.TermPrefilter that picks the kernel pairs worth aligning (None: all are aligned).
 
     After discover(): names (sorted), matches (Match tuples, files as numbers), clusters (lists of (file number, first
     frame, last frame))."""
 
     def __init__(self, corpus, times=None, distance='cosine', floor=1e-6, theta=0.25, min_frames=50, max_distance=None,
-                 exclude=None, window=None, merge_overlap=0.5, chunk_pairs=1 << 18):
+                 exclude=None, window=None, merge_overlap=0.5, chunk_pairs=1 << 18, prefilter=None):
         if distance not in DISTANCES:
             raise ValueError('distance must be one of %s, not %r' % (DISTANCES, distance))
         if chunk_pairs < 1:
@@ -292,6 +296,7 @@ class TermDiscoverer(object):
         self.corpus, self.distance, self.floor = corpus, distance, floor
         self.min_frames, self.max_distance, self.merge_overlap = int(min_frames), max_distance, merge_overlap
         self.chunk_pairs = int(chunk_pairs)
+        self.prefilter = prefilter
         self.names = sorted(corpus.names, key=_text)
         self.tables = kl_tables(corpus.table, floor) if distance == 'kl' else None
 
@@ -315,9 +320,12 @@ class TermDiscoverer(object):
             raise RuntimeError('the local-alignment kernel refused %d pairs of a table this module built' % int((out[1] < 0).sum()))
         return tuple(out)
 
-    def discover(self, pairs=None):
+    def discover(self, pairs=None, prefilter=None):
         """(matches, clusters).  pairs: [(name u, name v)] utterance pairs (u is side 1, whole; v is windowed); default:
-        every unordered pair, an utterance with itself included."""
+        every unordered pair, an utterance with itself included.  prefilter (default: the constructor's): a
+        prefilter.TermPrefilter -- only the kernel pairs its keep() passes are aligned, in their order; None: all of them,
+        without any further launch.  Afterwards n_kernel_pairs, n_aligned_pairs and, with a prefilter, prefilter_best
+        (the int32 array of the best runs over ALL kernel pairs; None without one)."""
         n = len(self.names)
         if pairs is None:
             upairs = [(u, v) for u in range(n) for v in range(u, n)]
@@ -326,6 +334,15 @@ class TermDiscoverer(object):
             upairs = [(number[self.corpus._name(a)], number[self.corpus._name(b)]) for a, b in pairs]
         lengths = [self.corpus.length[k] for k in self.names]
         kp = kernel_pairs(lengths, upairs, self.window)
+        prefilter = self.prefilter if prefilter is None else prefilter
+        self.n_kernel_pairs, self.prefilter_best = len(kp), None
+        if prefilter is not None:
+            mask = np.asarray(prefilter.keep(self, kp), dtype=bool)
+            if mask.shape != (len(kp),):
+                raise ValueError('TermDiscoverer: the prefilter\'s mask does not cover the kernel pairs')
+            self.prefilter_best = getattr(prefilter, 'best', None)
+            kp = [q for q, m in zip(kp, mask) if m]
+        self.n_aligned_pairs = len(kp)
         self.matches = keep_matches(kp, self.align(kp), self.theta, self.min_frames, self.max_distance)
         self.clusters = cluster_matches(self.matches, self.merge_overlap)
         return self.matches, self.clusters
@@ -354,13 +371,27 @@ def main(argv=None):
     ap.add_argument('--exclude', type=int, default=None, help='band blocked around the diagonal of a self-pair (default: --min-frames)')
     ap.add_argument('--window', type=int, default=None)
     ap.add_argument('--merge-overlap', type=float, default=0.5)
+    ap.add_argument('--prefilter', action='store_true',
+                    help='align only the kernel pairs whose dot plot of LSH signatures holds a diagonal run (abnet3_amd.prefilter; untuned)')
+    ap.add_argument('--bits', type=int, default=64, help='signature bits, a multiple of 32 in 32 .. 256')
+    ap.add_argument('--max-hamming', type=int, default=None, help='most differing bits of a hit (default: bits // 4)')
+    ap.add_argument('--span', type=int, default=32, help='frames of the window along a diagonal, 1 .. 64')
+    ap.add_argument('--dilate', type=int, default=1, help='columns a hit is spread to either side, 0 .. 8')
+    ap.add_argument('--min-hits', type=int, default=None, help='hits a kept pair\'s best window holds (default: 3 * span // 4)')
+    ap.add_argument('--lsh-seed', type=int, default=0)
     args = ap.parse_args(argv)
+    pre = None
+    if args.prefilter:
+        from .prefilter import TermPrefilter
+        pre = TermPrefilter(bits=args.bits, seed=args.lsh_seed, max_hamming=args.max_hamming, span=args.span, dilate=args.dilate,
+                            min_hits=args.min_hits)
     td = TermDiscoverer(args.features, distance=args.distance, floor=args.floor, theta=args.theta, min_frames=args.min_frames,
                         max_distance=args.max_distance, exclude=args.exclude, window=args.window,
-                        merge_overlap=args.merge_overlap)
+                        merge_overlap=args.merge_overlap, prefilter=pre)
     paths = td.write(args.out_dir)
-    print('%d utterances, %d matches, %d clusters (%d tokens) -> %s' % (
-        len(td.names), len(td.matches), len(td.clusters), sum(len(c) for c in td.clusters), ', '.join(paths)))
+    print('%d utterances, %d matches, %d clusters (%d tokens), %d of %d kernel pairs aligned -> %s' % (
+        len(td.names), len(td.matches), len(td.clusters), sum(len(c) for c in td.clusters), td.n_aligned_pairs,
+        td.n_kernel_pairs, ', '.join(paths)))
     return 0
 
 

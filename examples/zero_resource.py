@@ -6,7 +6,7 @@ mined pairs, and the ABX item file ("phones" = word types).
 
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
                                      [--gmm] [--gmm-components 64] [--no-network] [--terms] [--terms-theta T]
-                                     [--alignment FILE]
+                                     [--prefilter] [--alignment FILE]
                                      [--kmeans] [--kmeans-clusters 50]
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
@@ -24,6 +24,8 @@ after it, otherwise its figures are printed again beside the embeddings'.
 every other -- over the filterbanks, or with --gmm over the mixture's posteriorgrams under the KL distance -- clustered
 into a .classes file, from which SamplerClusterSiamese draws the train and dev pairs: the reference's canonical route,
 with discovered clusters in place of labelled ones.  The purity of the clusters against the planted words is printed.
+With --prefilter only the kernel pairs whose dot plot of LSH signatures holds a diagonal run are aligned
+(abnet3_amd/prefilter.py, its untuned defaults); the share of kernel pairs aligned is printed.
 With --alignment FILE (`file onset offset symbol` lines, a phone alignment of the corpus' files) the clusters are also
 scored against it: NED and coverage (abnet3_amd/tde.py), the line `python -m abnet3_amd.tde` prints.
 --kmeans adds discrete units (abnet3_amd/kmeans.py): k-means over the embeddings -- with --no-network over the
@@ -48,6 +50,7 @@ from abnet3_amd.gmm import GmmPosteriorgram                       # noqa: E402
 from abnet3_amd.kmeans import KMeansQuantizer, bitrate, unit_sequences   # noqa: E402
 from abnet3_amd.loss import KLLoss, coscos2                       # noqa: E402
 from abnet3_amd.model import SiameseNetwork                       # noqa: E402
+from abnet3_amd.prefilter import TermPrefilter                   # noqa: E402
 from abnet3_amd.sampler import SamplerClusterSiamese              # noqa: E402
 from abnet3_amd.tde import TermEvaluator, summary                 # noqa: E402
 from abnet3_amd.terms import TermDiscoverer                       # noqa: E402
@@ -118,11 +121,12 @@ def guess_theta(table, distance, rng, quantile=0.04, n=20000):
     return float(np.quantile(d, quantile))
 
 
-def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frames=15, alignment=None):
+def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frames=15, alignment=None, prefilter=False):
     """features or posteriorgrams -> TermDiscoverer -> terms.classes -> SamplerClusterSiamese -> the loader of its pairs."""
     if theta is None:
         theta = guess_theta(corpus.table, distance, rng)
-    td = TermDiscoverer(corpus, distance=distance, theta=theta, min_frames=min_frames)
+    td = TermDiscoverer(corpus, distance=distance, theta=theta, min_frames=min_frames,
+                        prefilter=TermPrefilter(span=min_frames, min_hits=3 * min_frames // 4) if prefilter else None)
     matches, clusters = td.discover()
     classes = td.write(out + '_terms')[0]
 
@@ -135,8 +139,9 @@ def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frame
         words = [word_at(*tok) for tok in c]
         pure.append(max(words.count(w) for w in set(words) if w != -1) / len(words) if set(words) != {-1} else 0.0)
     print('term discovery (%s, theta %.3g): %d matches, %d clusters, %d tokens; mean share of a cluster\'s tokens on its '
-          'commonest planted word %.2f' % (distance, theta, len(matches), len(clusters), sum(len(c) for c in clusters),
-                                          float(np.mean(pure)) if pure else 0.0))
+          'commonest planted word %.2f; %d of %d kernel pairs aligned'
+          % (distance, theta, len(matches), len(clusters), sum(len(c) for c in clusters), float(np.mean(pure)) if pure else 0.0,
+             td.n_aligned_pairs, td.n_kernel_pairs))
     if alignment is not None:
         print(summary(TermEvaluator(alignment).evaluate(clusters, td.names, td.corpus.times)))
     if len(clusters) < 2:
@@ -198,6 +203,7 @@ def main():
     ap.add_argument('--no-network', action='store_true', help='with --gmm: stop after the mixture, train nothing')
     ap.add_argument('--terms', action='store_true', help='pairs from term discovery: clusters -> SamplerClusterSiamese')
     ap.add_argument('--terms-theta', type=float, default=None, help='default: a low quantile of random frame distances (untuned)')
+    ap.add_argument('--prefilter', action='store_true', help='with --terms: align only the kernel pairs the LSH dot-plot prefilter keeps (untuned)')
     ap.add_argument('--alignment', default=None, metavar='FILE', help='with --terms: a phone alignment; NED and coverage of the clusters')
     ap.add_argument('--kmeans', action='store_true', help='discrete units: k-means of the embeddings (--no-network: of the filterbanks), bitrate and ABX')
     ap.add_argument('--kmeans-clusters', type=int, default=50)
@@ -227,10 +233,10 @@ def main():
         dl = tcl_loader(fb, times, rng)
     elif args.terms:
         if post is not None:
-            dl = terms_loader(post, fb, times, tokens, args.out, 'kl', args.terms_theta, rng, alignment=args.alignment)
+            dl = terms_loader(post, fb, times, tokens, args.out, 'kl', args.terms_theta, rng, alignment=args.alignment, prefilter=args.prefilter)
         else:
             corpus = DeviceCorpus({k: np.asarray(v, dtype=np.float32) for k, v in fb.items()}, times)
-            dl = terms_loader(corpus, fb, times, tokens, args.out, 'cosine', args.terms_theta, rng, alignment=args.alignment)
+            dl = terms_loader(corpus, fb, times, tokens, args.out, 'cosine', args.terms_theta, rng, alignment=args.alignment, prefilter=args.prefilter)
     else:
         miner = KnnPairMiner(fb, times, min_similarity=args.min_similarity)
         pairs_path, map_path = miner.write(args.out + '_mined')

@@ -633,6 +633,42 @@ int64_t abn_edit_max_short(void);
 int abn_edit_distance_batched(const int32_t* sym1, int64_t rows1, const int32_t* sym2, int64_t rows2,
                               const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
                               int64_t npairs, int64_t max_short, int32_t* dist, void* stream);
+/* The prefilter of term discovery (abnet3_amd/prefilter.py, whose module docstring is the definition; added within
+ * ABI 20: new symbols only).  Neither entry uses atomics or a workspace; one launch each on `stream`.
+ *
+ * abn_lsh_signatures: random-hyperplane signatures of the rows of table [rows][D] fp32 under planes [bits][D] fp32.
+ * sig [rows][bits / 32] uint32: bit b is bit b % 32 of word b / 32 (least significant first) and is 1 iff the fp32 dot
+ * product <table[r], planes[b]> is > 0 (fused multiply-adds in ascending column order).  live [rows] uint8: 1 iff every
+ * element of the row is finite and at least one is non-zero -- exact, whatever the dot products are; a dead row's words
+ * are 0.  bits: a multiple of 32 in 32 .. ABN_LSH_MAX_BITS; D in 1 .. ABN_LSH_MAX_D; else ABN_E_ARG, like null pointers,
+ * before any launch.  rows == 0 returns at once.  The table is read from memory once.
+ *
+ * abn_lsh_diag_hits_batched: the pair table lives on the DEVICE, as abn_dtw_local_batched's: pair p is rows
+ * [off1[p], off1[p]+n1[p]) of (sig1, live1) [rows1] against rows [off2[p], off2[p]+n2[p]) of (sig2, live2) [rows2], the
+ * signatures `words` uint32 wide (1 .. ABN_LSH_MAX_BITS / 32).  For 0 <= i < n1, 0 <= j < n2:
+ *   hit(i, j) = live1[off1+i] and live2[off2+j] and popcount(sig1[off1+i] ^ sig2[off2+j]) <= max_hamming and
+ *               (exclude == 0 or |(off1+i) - (off2+j)| >= exclude)
+ *   hd(i, j)  = OR of hit(i, j+t) over |t| <= dilate with 0 <= j+t < n2
+ *   run(i, j) = the sum over s = 0 .. span-1 of hd(i-s, j-s), the terms inside the matrix only
+ * best[p] = the largest run, diag[p] = i - j and end1[p] = i of the cell that reaches it, ties to the smallest i - j,
+ * then the smallest i.  No hit or an empty side: best 0, diag 0, end1 -1.  A pair with a negative length, rows outside
+ * its tables or side 2 of more than abn_dtw_local_max_n2() frames is refused: best -1, diag 0, end1 -1, nothing is read.
+ * Side 1 has no limit.  max_hamming in 0 .. 32 words, span in 1 .. ABN_LSH_MAX_SPAN, dilate in 0 .. ABN_LSH_MAX_DILATE,
+ * exclude >= 0, and exclude > 0 needs sig1 == sig2, live1 == live2 and rows1 == rows2: else ABN_E_ARG, like null
+ * pointers (a table of 0 rows may be NULL), before any launch.  npairs == 0 returns at once.  Any npairs: a grid-stride
+ * loop over at most ABN_LSH_GRID_BLOCKS workgroups, one pair each at a time. */
+#define ABN_LSH_MAX_BITS 256
+#define ABN_LSH_MAX_D 4096
+#define ABN_LSH_MAX_SPAN 64
+#define ABN_LSH_MAX_DILATE 8
+#define ABN_LSH_GRID_BLOCKS 2048
+int abn_lsh_signatures(const float* table, int64_t rows, int64_t D, const float* planes, int64_t bits,
+                       uint32_t* sig, uint8_t* live, void* stream);
+int abn_lsh_diag_hits_batched(const uint32_t* sig1, const uint8_t* live1, int64_t rows1, const uint32_t* sig2,
+                              const uint8_t* live2, int64_t rows2, const int64_t* off1, const int32_t* n1,
+                              const int64_t* off2, const int32_t* n2, int64_t npairs, int64_t words,
+                              int64_t max_hamming, int64_t span, int64_t dilate, int64_t exclude, int32_t* best,
+                              int32_t* diag, int32_t* end1, void* stream);
 /* ABX triplet scores (abnet3_amd/abx.py).  Row r is one X of ABX cell row_cell[r]: the distances d(A, X) over its A
  * are dist[a_off[r] .. a_off[r] + a_len[r]), the d(B, X) over its B dist[b_off[r] .. b_off[r] + b_len[r]) (device
  * arrays, dist: [ndist] f64).  For every cell c: score2[c] = the sum over its rows and their A x B triplets of 2 when
