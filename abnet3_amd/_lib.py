@@ -142,6 +142,10 @@ SYMBOLS = {
     'abn_kmeans_ws_bytes': (_i64, [_i64, _i64, _i64, C.c_int]),
     'abn_kmeans_accumulate': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, C.c_int, _vp, _i64, _vp]),
     'abn_kmeans_update': (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'abn_kmeans_viterbi_max_len': (_i64, []),
+    'abn_kmeans_viterbi_max_k': (_i64, []),
+    'abn_kmeans_viterbi_ws_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'abn_kmeans_viterbi': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 # abn_integrate_forward / _backward (include/abnet3_hip.h)
 INTEGRATE_MODE = {'sum': 0, 'concat': 1}

@@ -1,6 +1,6 @@
 // kmeans.hip -- k-means vector quantisation: hard assignment and a deterministic update (abn_kmeans_assign,
-// abn_kmeans_accumulate, abn_kmeans_update).  abnet3_amd/kmeans.py states the definition; DESIGN.md section 3.4d the
-// shape.
+// abn_kmeans_accumulate, abn_kmeans_update), and the penalised segmentation of the ids (abn_kmeans_viterbi, at the end
+// of the file).  abnet3_amd/kmeans.py states the definitions; DESIGN.md sections 3.4d and 3.4e the shapes.
 //
 // The score of frame t under centroid k is one row of a GEMM of depth D + 1,
 //   s[t][k] = sum_ka X~[t][ka] W~[k][ka],   X~ = [xc | 1],  W~ = [m | b],  xc = x - shift (fp32),  b = -|m|^2 / 2,
@@ -441,9 +441,319 @@ static KmWs km_ws(const KmGrid& g, int64_t K, int64_t D)
     return w;
 }
 
+// ---- penalised segmentation (abn_kmeans_viterbi) ---------------------------------------------------------------------
+// Persistent workgroups, utterance u = blockIdx.x, + gridDim.x, ...  Per block of 128 frames the workgroup sweeps the
+// centroid tiles with km_score_tile (the assign pass's bits) into its own slab [128][ks] -- in LDS behind the operand
+// tiles where K <= 128 (the one shape whose 128 frames x K floats fit beside them), otherwise in the workspace --, then takes
+// one sequential step per frame: centroid k = 256 q + thread, W in registers, the max and its lowest index by a wave
+// reduction and one LDS exchange, one ballot word of stay bits per 64 centroids, and the previous good frame's j* as an
+// int32 (-1: the first good frame, -2: a BAD frame).  Wave 0 then walks the stay bits backwards 64 frames at a time.
+// The slab, the stay bits and prevj are written and read by this workgroup alone, on one CU, with a workgroup barrier
+// between: plain stores and plain loads are ordered there (the stale-line hazard is another CU's stores); the
+// per-workgroup regions are 256-byte aligned so that no cache line is shared between two workgroups.
+constexpr int KM_VIT_GRID = 256;           // one workgroup per CU (the score tile keeps the register file to itself)
+constexpr int KM_VIT_MAX_LEN = 1 << 20;
+constexpr int KM_VIT_LDS_KS = KM_B + 8;    // K <= 128: the slab lives in LDS behind the operand tiles; rows 136 floats apart, so
+                                           // that the two half-waves of a deposit (4 rows apart) fall on different banks
+constexpr size_t KM_VIT_LDS_BYTES = KM_TILE_BYTES + sizeof(float) * KM_B * KM_VIT_LDS_KS;     // 140 KiB of the CU's 160
+
+struct KmVitP {
+    const float* x; const float* shift; const float* m; const float* b;
+    const int64_t* off; const int* len;
+    int T, K, D, n_utt, tiles_k;
+    float pen;                              // penalty / 2, in score units
+    int* ids; double* objective; int* n_switch;
+    char* ws; int64_t per_wg;               // bytes of a workgroup's region
+    int ks, kw, cap;                        // slab row stride (floats), stay words per frame, frames the region holds
+};
+
+struct KmVitWs { int64_t slab_bytes, per_frame, per_wg; int grid, ks, kw; };
+static KmVitWs km_vit_ws(int64_t n_utt, int64_t max_len, int64_t K)
+{
+    KmVitWs w;
+    w.grid = (int)(n_utt < KM_VIT_GRID ? n_utt : KM_VIT_GRID);
+    w.ks = (int)((K + KM_B - 1) / KM_B) * KM_B;
+    int nq = 1;
+    while (nq * 256 < K) nq <<= 1;
+    w.kw = 4 * nq;
+    w.slab_bytes = (int64_t)sizeof(float) * KM_B * w.ks;
+    w.per_frame = 8LL * w.kw + 4;
+    w.per_wg = align_up(w.slab_bytes + max_len * w.per_frame + 8, 256);
+    return w;
+}
+
+// (score, index) as one integer whose unsigned order is: the greater score first, then the LOWER index -- so that the
+// max and its lowest index are one max-reduction.  -0 is read as +0, as the float comparison reads it.
+__device__ __forceinline__ unsigned long long km_vit_key(float v, int k)
+{
+    unsigned u = __float_as_uint(v == 0.0f ? 0.0f : v);
+    u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
+    return ((unsigned long long)u << 32) | (unsigned)~k;
+}
+__device__ __forceinline__ float km_vit_key_score(unsigned long long key)
+{
+    unsigned u = (unsigned)(key >> 32);
+    u ^= (u >> 31) ? 0x80000000u : 0xffffffffu;
+    return __uint_as_float(u);
+}
+// One DPP exchange inside the rows of 16 lanes (every lane has a source under these controls) and the max of the two.
+template <int CTRL>
+__device__ __forceinline__ unsigned long long km_vit_dpp_max(unsigned long long v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xf, 0xf, false);
+    const unsigned long long o = ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+    return o > v ? o : v;
+}
+// The max over the wave, in every lane: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror leave the
+// row's max in its 16 lanes; the four rows' values are read with v_readlane.  All 64 lanes must be active.
+__device__ __forceinline__ unsigned long long km_vit_wave_max(unsigned long long v)
+{
+    v = km_vit_dpp_max<0xB1>(v);
+    v = km_vit_dpp_max<0x4E>(v);
+    v = km_vit_dpp_max<0x141>(v);
+    v = km_vit_dpp_max<0x140>(v);
+    unsigned long long r = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 16 * i);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 16 * i);
+        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+        r = o > r ? o : r;
+    }
+    return r;
+}
+
+template <int NQ, bool LDSS>
+__global__ __launch_bounds__(256) void km_viterbi_kernel(KmVitP p)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const As = smem;
+    float* const Bs = smem + 2 * KmTile::floats;
+    __shared__ int bad_s[KM_B];
+    __shared__ unsigned long long red_k[2][4];
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
+    char* const base = p.ws + (int64_t)blockIdx.x * p.per_wg;
+    float* const slab = LDSS ? smem + 4 * KmTile::floats : reinterpret_cast<float*>(base);
+    const int ks = LDSS ? KM_VIT_LDS_KS : p.ks;
+    unsigned long long* const stay = reinterpret_cast<unsigned long long*>(base + (int64_t)sizeof(float) * KM_B * p.ks);
+    int* const prevj = reinterpret_cast<int*>(stay + (int64_t)p.cap * p.kw);
+    const float pen = p.pen;
+
+    KmP kp;
+    kp.x = p.x; kp.shift = p.shift; kp.m = p.m; kp.b = p.b;
+    kp.T = p.T; kp.K = p.K; kp.D = p.D;
+    kp.ids = nullptr; kp.prev = nullptr; kp.best = nullptr; kp.changed = nullptr;
+    kp.tiles_k = p.tiles_k;
+
+    for (int u = (int)blockIdx.x; u < p.n_utt; u += (int)gridDim.x) {
+        const int64_t o = p.off[u];
+        const int L = p.len[u];
+        if (o < 0 || L < 0 || o + L > p.T || L > p.cap) {            // (uniform) nothing of this utterance is touched
+            if (t == 0) {
+                if (p.objective) p.objective[u] = NAN;
+                if (p.n_switch) p.n_switch[u] = -1;
+            }
+            continue;
+        }
+        float W[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) W[q] = 0.0f;
+        bool started = false;
+        int jprev = -1, par = 0;
+        double obj = 0.0;
+
+        for (int f0 = 0; f0 < L; f0 += KM_B) {
+            const int m0 = (int)o + f0;
+            const int nf = min(KM_B, L - f0);
+            if (t < KM_B) {
+                bool bad = false;
+                if (t < nf)
+                    for (int d = 0; d < p.D; ++d) {
+                        const float xc = p.x[(int64_t)(m0 + t) * p.D + d] - p.shift[d];
+                        bad |= !__builtin_isfinite(xc * xc);
+                    }
+                bad_s[t] = bad;
+            }
+            for (int ct = 0; ct < p.tiles_k; ++ct) {
+                const int n0 = ct * KM_B;
+                f32x16 acc[2][2];
+                km_score_tile(kp, m0, n0, As, Bs, acc);
+                const int col_l = lane & 31, rsub = 4 * (lane >> 5);
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            slab[(int64_t)(wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + rsub) * ks + n0 + wn0 + 32 * j + col_l] =
+                                acc[i][j][r];
+            }
+            __syncthreads();                                          // the slab and bad_s are this workgroup's own
+
+            float sn[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) sn[q] = 256 * q + t < p.K ? slab[256 * q + t] : 0.0f;
+            for (int f = 0; f < nf; ++f) {
+                const int g = f0 + f;
+                float s[NQ];
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) s[q] = sn[q];
+                if (f + 1 < nf) {
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) sn[q] = 256 * q + t < p.K ? slab[(int64_t)(f + 1) * ks + 256 * q + t] : 0.0f;
+                }
+                if (bad_s[f]) {                                       // (uniform) the state passes through
+                    if (t == 0) prevj[g] = -2;
+                    continue;
+                }
+                unsigned long long key = 0;                           // (below the key of -inf)
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const int k = 256 * q + t;
+                    const bool st = started && W[q] > -pen;
+                    const unsigned long long word = __ballot(st);
+                    if (lane == 0) stay[(int64_t)g * p.kw + 4 * q + wave] = word;
+                    float uq = started ? s[q] + (st ? W[q] : -pen) : s[q];
+                    if (k >= p.K) uq = -INFINITY;
+                    W[q] = uq;
+                    const unsigned long long kq = km_vit_key(uq, k);
+                    key = kq > key ? kq : key;
+                }
+                key = km_vit_wave_max(key);
+                if (lane == 0) red_k[par][wave] = key;
+                __syncthreads();
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned long long o = red_k[par][w];
+                    key = o > key ? o : key;
+                }
+                par ^= 1;                                             // (the other set is not rewritten before the next barrier)
+                const float bv = km_vit_key_score(key);
+                int bi = (int)~(unsigned)key;
+                if ((unsigned)bi >= (unsigned)p.K) bi = 0;            // no score compared greater than -inf: still an id
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) W[q] -= bv;
+                obj += (double)bv;
+                if (t == 0) prevj[g] = jprev;
+                jprev = bi;
+                started = true;
+            }
+            __syncthreads();                                          // before the next block's scores replace these
+        }
+
+        if (wave == 0) {                                              // traceback: jprev is the last good frame's j*
+            int cur = jprev, te = L - 1, nsw = 0;
+            while (te >= 0) {
+                const int g = te - lane;
+                int pj = -2;
+                bool cleared = false;
+                if (g >= 0) {
+                    pj = prevj[g];
+                    if (cur >= 0 && pj != -2) cleared = !((stay[(int64_t)g * p.kw + (cur >> 6)] >> (cur & 63)) & 1ull);
+                }
+                const unsigned long long mask = __ballot(cleared);
+                const int l1 = mask ? __builtin_ctzll(mask) : 63;     // frames te .. te - l1 keep cur
+                if (g >= 0 && lane <= l1) p.ids[o + g] = (pj == -2 || cur < 0) ? -1 : cur;
+                if (mask) {
+                    const int nj = __shfl(pj, l1);                    // -1: that was the first good frame
+                    nsw += nj >= 0 && nj != cur;                      // (equal only with a penalty of 0, where nothing stays)
+                    cur = nj;
+                }
+                te -= l1 + 1;
+            }
+            if (lane == 0) {
+                if (p.objective) p.objective[u] = obj;
+                if (p.n_switch) p.n_switch[u] = nsw;
+            }
+        }
+        __syncthreads();                                              // the traceback's reads before the next utterance's writes
+    }
+}
+
 }  // namespace abn
 
 using namespace abn;
+
+extern "C" int64_t abn_kmeans_viterbi_max_len(void) { return KM_VIT_MAX_LEN; }
+extern "C" int64_t abn_kmeans_viterbi_max_k(void) { return KM_MAX_K; }
+
+static int km_vit_check_sizes(int64_t n_utt, int64_t K, int64_t D, const char* what)
+{
+    ABN_REQUIRE(n_utt >= 1 && n_utt < (1LL << 31), "%s: n_utt = %lld out of range", what, (long long)n_utt);
+    ABN_REQUIRE(K >= 1 && D >= 1, "%s: K = %lld, D = %lld out of range", what, (long long)K, (long long)D);
+    if (D > KM_MAX_D || K > KM_MAX_K) {
+        set_error("%s: D = %lld, K = %lld, supported D <= %d (abn_kmeans_max_d), K <= %d (abn_kmeans_viterbi_max_k)", what,
+                  (long long)D, (long long)K, KM_MAX_D, KM_MAX_K);
+        return ABN_E_UNSUPPORTED;
+    }
+    return ABN_OK;
+}
+
+extern "C" int64_t abn_kmeans_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D)
+{
+    if (km_vit_check_sizes(n_utt, K, D, "abn_kmeans_viterbi_ws_bytes") != ABN_OK) return -1;
+    if (max_len < 0 || max_len > KM_VIT_MAX_LEN) {
+        set_error("abn_kmeans_viterbi_ws_bytes: max_len = %lld, supported 0 .. %d (abn_kmeans_viterbi_max_len)",
+                  (long long)max_len, KM_VIT_MAX_LEN);
+        return -1;
+    }
+    const KmVitWs w = km_vit_ws(n_utt, max_len, K);
+    return w.per_wg * w.grid;
+}
+
+extern "C" int abn_kmeans_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                                  const float* shift, const float* m, const float* b, int64_t K, float penalty_score,
+                                  int32_t* ids, double* objective, int32_t* n_switch, void* ws, int64_t ws_bytes, void* stream)
+{
+    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - KM_B, "abn_kmeans_viterbi: T = %lld out of range", (long long)T);
+    const int rc = km_vit_check_sizes(n_utt, K, D, "abn_kmeans_viterbi");
+    if (rc != ABN_OK) return rc;
+    ABN_REQUIRE(x && off && len && shift && m && b && ids, "abn_kmeans_viterbi: null pointer");
+    ABN_REQUIRE(penalty_score >= 0.0f && __builtin_isfinite(penalty_score),
+                "abn_kmeans_viterbi: penalty_score = %g, a finite value >= 0 is needed", (double)penalty_score);
+    const KmVitWs w = km_vit_ws(n_utt, 0, K);
+    const int64_t per_wg = ws_bytes > 0 ? (ws_bytes / w.grid) & ~255LL : 0;
+    int64_t cap = (per_wg - w.slab_bytes - 8) / w.per_frame;
+    if (!ws || cap < 1) {
+        set_error("abn_kmeans_viterbi: workspace of %lld bytes holds no frame (abn_kmeans_viterbi_ws_bytes)", (long long)ws_bytes);
+        return ABN_E_WORKSPACE;
+    }
+    ABN_REQUIRE(aligned16(ws), "abn_kmeans_viterbi: the workspace must be 16-byte aligned");
+    if (cap > KM_VIT_MAX_LEN) cap = KM_VIT_MAX_LEN;
+    static bool attr_set[16] = {};
+    if (first_use_on_device(attr_set)) {
+        const auto opt_in = [](const void* k, size_t bytes) { (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+        opt_in(reinterpret_cast<const void*>(km_viterbi_kernel<1, true>), KM_VIT_LDS_BYTES);
+        opt_in(reinterpret_cast<const void*>(km_viterbi_kernel<1, false>), KM_TILE_BYTES);
+        opt_in(reinterpret_cast<const void*>(km_viterbi_kernel<2, false>), KM_TILE_BYTES);
+        opt_in(reinterpret_cast<const void*>(km_viterbi_kernel<4, false>), KM_TILE_BYTES);
+        opt_in(reinterpret_cast<const void*>(km_viterbi_kernel<8, false>), KM_TILE_BYTES);
+        opt_in(reinterpret_cast<const void*>(km_viterbi_kernel<16, false>), KM_TILE_BYTES);
+    }
+    KmVitP p;
+    p.x = x; p.shift = shift; p.m = m; p.b = b; p.off = off; p.len = len;
+    p.T = (int)T; p.K = (int)K; p.D = (int)D; p.n_utt = (int)n_utt;
+    p.tiles_k = (int)((K + KM_B - 1) / KM_B);
+    p.pen = penalty_score;
+    p.ids = ids; p.objective = objective; p.n_switch = n_switch;
+    p.ws = static_cast<char*>(ws); p.per_wg = per_wg;
+    p.ks = w.ks; p.kw = w.kw; p.cap = (int)cap;
+    const dim3 grid((unsigned)w.grid);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (K <= KM_B) hipLaunchKernelGGL((km_viterbi_kernel<1, true>), grid, dim3(256), KM_VIT_LDS_BYTES, st, p);
+    else switch (w.kw / 4) {
+    case 1: hipLaunchKernelGGL((km_viterbi_kernel<1, false>), grid, dim3(256), KM_TILE_BYTES, st, p); break;
+    case 2: hipLaunchKernelGGL((km_viterbi_kernel<2, false>), grid, dim3(256), KM_TILE_BYTES, st, p); break;
+    case 4: hipLaunchKernelGGL((km_viterbi_kernel<4, false>), grid, dim3(256), KM_TILE_BYTES, st, p); break;
+    case 8: hipLaunchKernelGGL((km_viterbi_kernel<8, false>), grid, dim3(256), KM_TILE_BYTES, st, p); break;
+    default: hipLaunchKernelGGL((km_viterbi_kernel<16, false>), grid, dim3(256), KM_TILE_BYTES, st, p); break;
+    }
+    ABN_CHECK_LAUNCH("abn_kmeans_viterbi");
+    return ABN_OK;
+}
 
 extern "C" int64_t abn_kmeans_max_d(void) { return KM_MAX_D; }
 extern "C" int64_t abn_kmeans_max_k(void) { return KM_MAX_K; }

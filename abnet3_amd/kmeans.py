@@ -1,7 +1,7 @@
 """K-means discrete units on the MI355X: vector quantisation of frames or embeddings with no labels.
 
     python -m abnet3_amd.kmeans fit FEATURES MODEL.npz [-k K] [--n-iter N] [--tol T] [--metric M] [--seed S]
-    python -m abnet3_amd.kmeans transform MODEL.npz FEATURES OUT [--quantize]
+    python -m abnet3_amd.kmeans transform MODEL.npz FEATURES OUT [--quantize] [--penalty P]
 
 Unit ids are how the ZeroSpeech 2019 / 2020 / 2021 systems are scored: the ids give the bitrate (``unit_sequences``,
 ``bitrate``), and ABX is run over the quantised frames (``quantize`` gives the corpus that ``ABXEvaluator`` and
@@ -35,6 +35,33 @@ The definition this module computes:
   assignment, then it updates.  It stops after n_iter iterations, or when no id changed since the previous iteration,
   or when (inertias[i - 1] - inertias[i]) / inertias[i - 1] < tol.  The number of changed ids is an integer counter the
   assign launch adds to.
+
+Penalised segmentation (``segment``, ``predict(penalty=)``, ``quantize(penalty=)``, ``viterbi``): frame-wise ids flicker,
+and every flicker is a symbol of the bitrate.  The ids are smoothed by a constant cost per new segment (Kamper & van
+Niekerk 2021, "DPDP"), an HMM Viterbi with a uniform switching cost over the same scores (tests/units_np.py restates it):
+
+* Inputs: the tables xc, m, b and the scores s[t, k] above: the same fp32 GEMM of depth D + 1, ka ascending, on the
+  matrix cores.
+* Chain: an utterance is a run of len[u] consecutive rows starting at off[u]; within it the chain runs over the good
+  frames in order.  A BAD frame keeps id -1; the chain neither breaks there nor pays for it: the state passes through.
+* ``penalty`` >= 0 is in the units of the distortion d2 = |xc - m|^2.  Since d2 = |xc|^2 - 2 s the kernel works with
+  p = fp32(penalty / 2) in score units, for both metrics.  It has no tuned default: it trades bitrate against ABX and
+  has to be swept on the data at hand.
+* Objective: choose a[t] to maximise  J(a) = sum_t s[t, a_t] - p #{consecutive good frames with different ids}.
+* Recurrence, all in fp32 and normalised so that nothing grows with T.  First good frame: U[k] = s[t, k].  Later good
+  frames: stay[t, k] = (W[k] > -p) (strict), U[k] = s[t, k] + (stay[t, k] ? W[k] : -p).  Every good frame:
+  M_t = max_k U[k], j*[t] = the lowest k attaining it, W[k] = U[k] - M_t.  objective[u] = the sum of the M_t in frame
+  order, accumulated in float64.
+* Traceback: the id of the last good frame is its j*; going backwards, the previous good frame's id is the same id if
+  stay[t, a_t], otherwise j* of the previous good frame.  n_switch[u] = the number of switches on the path.
+* The strict > is deliberate: with penalty = 0 nothing ever stays, every id is j*[t], and the result is
+  abn_kmeans_assign's ids bit for bit.
+* An utterance with no good frame gives all ids -1, objective 0 and 0 switches; len[u] = 0 is allowed.  Rows outside
+  every utterance keep what ``ids`` held.
+* Limits: K <= abn_kmeans_viterbi_max_k() (4096), D <= abn_kmeans_max_d(), an utterance of at most
+  abn_kmeans_viterbi_max_len() frames (2^20).  One launch (abn_kmeans_viterbi) for the whole corpus; no T x K array:
+  the workspace is, per workgroup (at most 256), 128 x K scores, one stay bit per (frame of the longest utterance,
+  centroid) and an int32 per frame.  With K <= 128 the score slab lives in LDS instead of the workspace.
 
 On the device an iteration is abn_kmeans_assign, abn_kmeans_accumulate and abn_kmeans_update: four launches and one
 read-back of five numbers for the stopping rule.
@@ -109,6 +136,70 @@ def assign(table, shift, m, b, prev=None, ids=None, changed=None, want_best=Fals
                                          _lib.ptr(ids), _lib.ptr(best), _lib.ptr(changed if prev is not None else None),
                                          _lib.stream()), 'abn_kmeans_assign')
     return ids, best
+
+
+def viterbi_max_len():
+    return int(_lib.load().abn_kmeans_viterbi_max_len())
+
+
+def viterbi_max_k():
+    return int(_lib.load().abn_kmeans_viterbi_max_k())
+
+
+def check_penalty(who, penalty):
+    try:
+        p = float(penalty)
+    except (TypeError, ValueError):
+        raise ValueError('%s: penalty = %r, a finite number >= 0 is needed' % (who, penalty))
+    if not (p >= 0.0 and p / 2.0 <= float(np.finfo(np.float32).max)):
+        raise ValueError('%s: penalty = %r, a finite number >= 0 is needed' % (who, penalty))
+    return p
+
+
+def viterbi(table, off, lens, shift, m, b, penalty, ids=None, want_objective=False):
+    """(ids [T] int32, objective [n_utt] float64 or None, n_switch [n_utt] int32 or None) of the penalised segmentation
+    the module docstring defines (abn_kmeans_viterbi, one launch).  off, lens: the utterances' first rows and lengths
+    (host sequences or device tensors).  Rows outside every utterance keep what `ids` held (-1 in a fresh `ids`)."""
+    lib = _lib.load()
+    penalty = check_penalty('kmeans.viterbi', penalty)
+    table = _check_table('kmeans.viterbi', table)
+    T, D = table.shape
+    K = b.shape[0]
+    _lib.require_device(shift, m, b)
+    if m.shape != (K, D) or shift.shape != (D,) or any(t.dtype != torch.float32 for t in (shift, m, b)):
+        raise ValueError('kmeans.viterbi: shift [D], m [K, D], b [K] float32 are needed')
+    if K < 1 or K > viterbi_max_k():
+        raise ValueError('kmeans.viterbi: K = %d, the kernel takes 1 .. %d (abn_kmeans_viterbi_max_k)' % (K, viterbi_max_k()))
+    host = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    off_h, len_h = host(off).astype(np.int64).ravel(), host(lens).astype(np.int64).ravel()
+    n_utt = len(off_h)
+    if len(len_h) != n_utt:
+        raise ValueError('kmeans.viterbi: %d offsets and %d lengths' % (n_utt, len(len_h)))
+    if n_utt and ((off_h < 0).any() or (len_h < 0).any() or (off_h + len_h > T).any()):
+        raise ValueError('kmeans.viterbi: an utterance lies outside the table\'s %d rows' % T)
+    max_len = int(len_h.max()) if n_utt else 0
+    if max_len > viterbi_max_len():
+        raise ValueError('kmeans.viterbi: an utterance of %d frames, the kernel takes up to %d (abn_kmeans_viterbi_max_len)'
+                         % (max_len, viterbi_max_len()))
+    if ids is None:
+        ids = torch.full((T,), -1, dtype=torch.int32, device=table.device)
+    if ids.shape != (T,) or ids.dtype != torch.int32 or not ids.is_contiguous():
+        raise ValueError('kmeans.viterbi: ids must be a contiguous [T] int32 tensor')
+    _lib.require_device(ids)
+    obj = torch.zeros(n_utt, dtype=torch.float64, device=table.device) if want_objective else None
+    nsw = torch.zeros(n_utt, dtype=torch.int32, device=table.device) if want_objective else None
+    if T and n_utt and max_len:
+        need = lib.abn_kmeans_viterbi_ws_bytes(n_utt, max_len, K, D)
+        if need < 0:
+            raise ValueError('kmeans.viterbi: %s' % lib.abn_last_error().decode('utf-8', 'replace'))
+        ws = torch.empty(int(need), dtype=torch.uint8, device=table.device)
+        off_d = torch.from_numpy(off_h).to(table.device)
+        len_d = torch.from_numpy(len_h.astype(np.int32)).to(table.device)
+        _lib.check(lib.abn_kmeans_viterbi(_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift),
+                                          _lib.ptr(m), _lib.ptr(b), K, float(np.float32(penalty / 2.0)), _lib.ptr(ids),
+                                          _lib.ptr(obj), _lib.ptr(nsw), _lib.ptr(ws), ws.numel(), _lib.stream()),
+                   'abn_kmeans_viterbi')
+    return ids, obj, nsw
 
 
 class LloydState(object):
@@ -205,6 +296,7 @@ class KMeansQuantizer(object):
         self.inertias = []
         self.n_changed = []             # per iteration: ids that differ from the previous iteration's (None for the first)
         self.n_bad_ = self.n_empty_ = 0
+        self.last_objective_ = self.last_n_switch_ = None      # segment(): per utterance, in corpus order
         self._tables = None
 
     def whoami(self):
@@ -287,11 +379,32 @@ class KMeansQuantizer(object):
             accumulate(table, shift, st, n_ranges, update=False)
         return st
 
-    def predict(self, corpus):
-        """The unit ids, int32, -1 for a BAD frame: a device tensor [rows] for a table, {name: host array} in corpus
-        order for a DeviceCorpus, a dict or a file."""
-        table, _, rows = self._corpus(corpus)
-        ids = self._assign(table)
+    def _segment_ids(self, table, rows, penalty):
+        """Device ids of the penalised segmentation; fills last_objective_ / last_n_switch_."""
+        penalty = check_penalty('KMeansQuantizer.segment', penalty)
+        if self.centroids_ is None:
+            raise ValueError('KMeansQuantizer: fit or load first')
+        lens = np.array([table.shape[0]] if rows is None else list(rows.values()), dtype=np.int64)
+        if isinstance(table, torch.Tensor) and table.dim() == 2 and table.dtype == torch.float32:      # (host checks first)
+            if table.shape[1] != self.shift_.shape[0]:
+                raise ValueError('KMeansQuantizer: the table has D = %d, the model D = %d' % (table.shape[1], self.shift_.shape[0]))
+            if self.n_clusters > viterbi_max_k():
+                raise ValueError('KMeansQuantizer.segment: K = %d, the kernel takes 1 .. %d (abn_kmeans_viterbi_max_k)'
+                                 % (self.n_clusters, viterbi_max_k()))
+            if len(lens) and int(lens.max()) > viterbi_max_len():
+                raise ValueError('KMeansQuantizer.segment: an utterance of %d frames, the kernel takes up to %d '
+                                 '(abn_kmeans_viterbi_max_len); pass a corpus of utterances' % (int(lens.max()), viterbi_max_len()))
+        table = _check_table('KMeansQuantizer.segment', table)
+        off = np.cumsum(lens) - lens
+        if self.metric == 'cosine':
+            table = table / table.norm(dim=1, keepdim=True)
+        shift, m, b, _ = self.device_tables(table.device)
+        ids, obj, nsw = viterbi(table, off, lens, shift, m, b, penalty, want_objective=True)
+        self.last_objective_, self.last_n_switch_ = obj.cpu().numpy(), nsw.cpu().numpy()
+        return ids
+
+    @staticmethod
+    def _by_name(ids, rows):
         if rows is None:
             return ids
         host, out, o = ids.cpu().numpy(), {}, 0
@@ -300,12 +413,28 @@ class KMeansQuantizer(object):
             o += n
         return out
 
-    def quantize(self, corpus):
+    def segment(self, corpus, penalty):
+        """The unit ids of the penalised segmentation (module docstring), in predict's forms.  Each file of a corpus is
+        an utterance; a [T, D] table is ONE utterance (ValueError beyond abn_kmeans_viterbi_max_len frames).
+        ``last_objective_`` (float64) and ``last_n_switch_`` (int32) hold the utterances' objectives and switch counts."""
+        table, _, rows = self._corpus(corpus)
+        return self._by_name(self._segment_ids(table, rows, penalty), rows)
+
+    def predict(self, corpus, penalty=None):
+        """The unit ids, int32, -1 for a BAD frame: a device tensor [rows] for a table, {name: host array} in corpus
+        order for a DeviceCorpus, a dict or a file.  penalty=None: the frame-wise ids; a number: ``segment``."""
+        if penalty is not None:
+            return self.segment(corpus, penalty)
+        table, _, rows = self._corpus(corpus)
+        return self._by_name(self._assign(table), rows)
+
+    def quantize(self, corpus, penalty=None):
         """Each frame replaced by its centroid, [rows, D] float32 on the device (a BAD frame: zeros); for a DeviceCorpus
-        a new DeviceCorpus with the same names, lengths and times."""
+        a new DeviceCorpus with the same names, lengths and times.  penalty: the ids of ``segment`` instead of the
+        frame-wise ones."""
         from .dataloader import DeviceCorpus
-        table, dc, _ = self._corpus(corpus)
-        ids = self._assign(table)
+        table, dc, rows = self._corpus(corpus)
+        ids = self._assign(table) if penalty is None else self._segment_ids(table, rows, penalty)
         cent = self.device_tables(ids.device)[3]
         out = cent[ids.clamp(min=0).to(torch.int64)]
         out[ids < 0] = 0.0
@@ -356,6 +485,22 @@ def unit_sequences(ids_by_name, collapse=True):
     return out
 
 
+def segments(ids_by_name):
+    """{name: (start, end, unit) int64 arrays}: the runs of equal ids of each file, frames start .. end - 1; the BAD
+    frames (id -1) are left out, and a BAD frame ends a run."""
+    out = {}
+    for k, ids in ids_by_name.items():
+        a = np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids).astype(np.int64).ravel()
+        if not a.size:
+            out[k] = tuple(np.zeros(0, dtype=np.int64) for _ in range(3))
+            continue
+        start = np.flatnonzero(np.concatenate(([True], a[1:] != a[:-1])))
+        end = np.concatenate((start[1:], [a.size]))
+        keep = a[start] >= 0
+        out[k] = (start[keep], end[keep], a[start][keep])
+    return out
+
+
 def bitrate(sequences, total_seconds):
     """(n / total_seconds) H, n the number of symbols of all sequences and H = -sum p log2 p over the symbol
     distribution of the whole set: the ZeroSpeech 2019 bitrate, in bits per second."""
@@ -386,6 +531,8 @@ def parser():
     t.add_argument('features', help='h5features file, or an .npz of name -> [T, D]')
     t.add_argument('out', help='.npz of name -> [T] ids or [T, D] frames, or an h5features file (when the input has times)')
     t.add_argument('--quantize', action='store_true', help='write each frame\'s centroid instead of its id')
+    t.add_argument('--penalty', type=float, default=None, metavar='P',
+                   help='penalised segmentation: cost of a new segment, in units of the distortion (no tuned default)')
     return ap
 
 
@@ -401,12 +548,12 @@ def main(argv=None):
         return 0
     q = KMeansQuantizer.load(args.model)
     if args.quantize:
-        table, out, o = q.quantize(feats).cpu().numpy(), {}, 0
+        table, out, o = q.quantize(feats, penalty=args.penalty).cpu().numpy(), {}, 0
         for k, v in feats.items():
             out[k] = table[o:o + v.shape[0]]
             o += v.shape[0]
     else:
-        out = q.predict(feats)
+        out = q.predict(feats, penalty=args.penalty)
     if args.out.endswith('.npz'):
         np.savez(args.out, **{str(k): v for k, v in out.items()})
     else:

@@ -3,6 +3,7 @@ scores), the edit distances of all within-cluster pairs in one launch of the bat
 (csrc/edit.hip, abn_edit_distance_batched).
 
     python -m abnet3_amd.tde CLASSES ALIGNMENT [--ignore SIL ...]
+    python -m abnet3_amd.tde ALIGNMENT --boundaries FILE.npz [--tolerance 0.02] [--ignore SIL ...]
 
 The definition this module computes (tests/tde_np.py restates it with explicit loops; the two agree with ==):
 
@@ -24,7 +25,14 @@ The definition this module computes (tests/tde_np.py restates it with explicit l
 * Coverage: the phones not in `ignore` that belong to at least one token, over all phones not in `ignore` (nan without
   any).  SIMPLIFICATION: TDE restricts the denominator to the "discoverable" phones (those inside some repeated n-gram
   of the gold transcription); this one counts every phone, so it reads lower than TDE's on the same clusters.
-  TDE's matching, grouping, type, token and boundary scores are not computed.
+  TDE's matching, grouping, type and token scores are not computed.
+* Boundary scores (``boundary_scores``, host only, float64): the standard phone-segmentation scores of a set of found
+  boundaries -- ``unit_boundaries`` puts one midway between the two frames of each switch of unit, so a segmentation
+  penalty (abnet3_amd/kmeans.py) can be judged against an alignment.  Gold boundaries are the phone onsets of a file
+  except its first (an onset between two phones of `ignore` is none).  Both lists sorted, two pointers: |f - g| <=
+  tolerance is a hit and both advance, otherwise the smaller advances.  precision = hits / found, recall = hits / gold,
+  F their harmonic mean, OS = recall / precision - 1, R-value = 1 - (sqrt((1 - recall)^2 + OS^2) +
+  |(-OS + recall - 1) / sqrt 2|) / 2; a ratio with an empty denominator is 0.
 """
 import argparse
 import sys
@@ -288,6 +296,73 @@ def ned(dist, max_len):
     return float(np.mean(np.asarray(dist).astype(np.float64) / np.asarray(max_len).astype(np.float64)))
 
 
+BoundaryScores = namedtuple('BoundaryScores', ['precision', 'recall', 'f', 'os', 'r_value', 'n_found', 'n_gold', 'n_hit'])
+BoundaryScores.__doc__ = """boundary_scores()'s result: precision, recall, F, the over-segmentation OS = recall / precision - 1
+and the R-value 1 - (sqrt((1 - recall)^2 + OS^2) + |(-OS + recall - 1) / sqrt 2|) / 2, with the three counts."""
+
+
+def unit_boundaries(ids_by_name, times):
+    """{file: float64 boundary times}: one boundary midway between the two frames of each switch of unit, the BAD
+    frames (id < 0) left out first.  times: {file: [T] frame times in seconds}."""
+    out = {}
+    for k, ids in ids_by_name.items():
+        a = np.asarray(ids).astype(np.int64).ravel()
+        t = np.asarray(times[k], dtype=np.float64).ravel()
+        if len(t) != len(a):
+            raise ValueError('unit_boundaries: %r has %d ids and %d times' % (k, len(a), len(t)))
+        t, a = t[a >= 0], a[a >= 0]
+        sw = np.flatnonzero(a[1:] != a[:-1])
+        out[_text(k)] = 0.5 * (t[sw] + t[sw + 1])
+    return out
+
+
+def gold_boundaries(alignment, ignore=()):
+    """{file: float64 times}: the phone onsets of each file except its first; an onset between two phones that are both in
+    `ignore` (silence, noise) is no boundary."""
+    if isinstance(alignment, str):
+        alignment = read_alignment(alignment)
+    ign = _ignored(alignment, ignore)[alignment.ids] if len(alignment.ids) else np.zeros(0, dtype=bool)
+    out = {}
+    for f, name in enumerate(alignment.names):
+        a, b = int(alignment.first[f]), int(alignment.first[f + 1])
+        keep = ~(ign[a + 1:b] & ign[a:b - 1]) if b - a > 1 else np.zeros(0, dtype=bool)
+        out[name] = alignment.onset[a + 1:b][keep]
+    return out
+
+
+def boundary_scores(found, alignment, tolerance=0.02, ignore=()):
+    """The standard phone-segmentation scores of `found` = {file: boundary times} against an Alignment (or the path of
+    one), host only, float64.  Per file of the alignment both lists are sorted and walked with two pointers:
+    |f - g| <= tolerance counts a hit and advances both, otherwise the smaller advances.  A file that `found` lacks has
+    no found boundary; a file the alignment lacks is a ValueError.  Empty sides give 0 for the ratios they define."""
+    gold = gold_boundaries(alignment, ignore)
+    found = {_text(k): v for k, v in found.items()}
+    for k in found:
+        if k not in gold:
+            raise ValueError('boundary_scores: file %r is not in the alignment' % k)
+    tolerance = float(tolerance)
+    hits = n_found = n_gold = 0
+    for name, g in gold.items():
+        f = np.sort(np.asarray(found.get(name, ()), dtype=np.float64).ravel())
+        g = np.sort(g)
+        n_found, n_gold = n_found + len(f), n_gold + len(g)
+        i = j = 0
+        while i < len(f) and j < len(g):
+            if abs(f[i] - g[j]) <= tolerance:
+                hits, i, j = hits + 1, i + 1, j + 1
+            elif f[i] < g[j]:
+                i += 1
+            else:
+                j += 1
+    prec = hits / n_found if n_found else 0.0
+    rec = hits / n_gold if n_gold else 0.0
+    fsc = 2.0 * prec * rec / (prec + rec) if prec + rec > 0 else 0.0
+    osg = rec / prec - 1.0 if prec > 0 else 0.0
+    r1 = float(np.sqrt((1.0 - rec) ** 2 + osg ** 2))
+    r2 = abs((-osg + rec - 1.0) / float(np.sqrt(2.0)))
+    return BoundaryScores(prec, rec, fsc, osg, 1.0 - (r1 + r2) / 2.0, n_found, n_gold, hits)
+
+
 def summary(s):
     """The one line the command line and examples/zero_resource.py print."""
     return 'NED %.4f coverage %.4f (%d clusters, %d tokens, %d pairs, %d skipped)' % (s.ned, s.coverage, s.n_clusters, s.n_tokens,
@@ -296,11 +371,22 @@ def summary(s):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog='python -m abnet3_amd.tde', description='NED and coverage of a .classes file against a phone alignment')
-    ap.add_argument('classes', help='.classes file (terms.write_classes)')
+    ap.add_argument('classes', nargs='?', default=None, help='.classes file (terms.write_classes)')
     ap.add_argument('alignment', help='phone alignment: "file onset offset symbol" lines')
     ap.add_argument('--ignore', nargs='*', default=[], metavar='SYMBOL', help='symbols that are no phones (silence, noise)')
+    ap.add_argument('--boundaries', default=None, metavar='FILE.npz', help='an .npz of file -> boundary times: the boundary scores')
+    ap.add_argument('--tolerance', type=float, default=0.02, help='seconds within which a found boundary hits a gold one')
     args = ap.parse_args(argv)
-    print(summary(TermEvaluator(args.alignment, ignore=args.ignore).evaluate(args.classes)))
+    if args.classes is None and args.boundaries is None:
+        ap.error('a .classes file or --boundaries is needed')
+    if args.classes is not None:
+        print(summary(TermEvaluator(args.alignment, ignore=args.ignore).evaluate(args.classes)))
+    if args.boundaries is not None:
+        with np.load(args.boundaries) as z:
+            found = {k: z[k] for k in z.files}
+        b = boundary_scores(found, read_alignment(args.alignment), args.tolerance, args.ignore)
+        print('boundaries: precision %.4f recall %.4f F %.4f OS %.4f R-value %.4f (%d found, %d gold, %d hits, tolerance %g s)'
+              % (b.precision, b.recall, b.f, b.os, b.r_value, b.n_found, b.n_gold, b.n_hit, args.tolerance))
     return 0
 
 

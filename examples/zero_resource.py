@@ -7,7 +7,7 @@ mined pairs, and the ABX item file ("phones" = word types).
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
                                      [--gmm] [--gmm-components 64] [--no-network] [--terms] [--terms-theta T]
                                      [--prefilter] [--alignment FILE]
-                                     [--kmeans] [--kmeans-clusters 50]
+                                     [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P]
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
 error is printed under both frame distances, the angular cosine and the symmetrised Kullback-Leibler divergence.
@@ -30,7 +30,9 @@ With --alignment FILE (`file onset offset symbol` lines, a phone alignment of th
 scored against it: NED and coverage (abnet3_amd/tde.py), the line `python -m abnet3_amd.tde` prints.
 --kmeans adds discrete units (abnet3_amd/kmeans.py): k-means over the embeddings -- with --no-network over the
 filterbanks -- and prints the units' bitrate and the ABX error of the quantised frames (each frame replaced by its
-centroid, the ZeroSpeech way of scoring units) next to the continuous ones.
+centroid, the ZeroSpeech way of scoring units) next to the continuous ones.  --kmeans-penalty P prints a second line
+for the penalised segmentation (KMeansQuantizer.segment: a cost of P, in units of the distortion, per new segment; no
+tuned default): bitrate and ABX with the penalty beside those without.
 """
 import argparse
 import os
@@ -173,8 +175,9 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False):
     return (line, post) if want_post else line
 
 
-def kmeans_route(corpus, items, label, n_clusters):
-    """frames -> KMeansQuantizer.fit -> unit ids (bitrate) and quantised frames (ABX) beside the continuous ones."""
+def kmeans_route(corpus, items, label, n_clusters, penalty=None):
+    """frames -> KMeansQuantizer.fit -> unit ids (bitrate) and quantised frames (ABX) beside the continuous ones; with a
+    penalty the same for the penalised segmentation."""
     q = KMeansQuantizer(n_clusters).fit(corpus)
     seconds = 0.01 * corpus.total
     rate = bitrate(unit_sequences(q.predict(corpus), collapse=False), seconds)
@@ -186,6 +189,13 @@ def kmeans_route(corpus, items, label, n_clusters):
     print('k-means units of the %s (K = %d, %d iterations, inertia %.4f, %d empty): %.0f bit/s (%.0f with runs merged); '
           'ABX error continuous %.2f %%, %s (%d triplets)'
           % (label, n_clusters, len(q.inertias), q.inertias[-1], q.n_empty_, rate, merged, cont.error, quant, cont.n_triplets))
+    if penalty is not None:
+        ids = q.segment(corpus, penalty)
+        pen_abx = ABXEvaluator(items, q.quantize(corpus, penalty=penalty), parallel='zero').run('within').error
+        print('  with penalty %g: %.0f bit/s with runs merged (%.0f without the penalty), %d switches (%d without); '
+              'ABX error quantised %.2f %% (%s without)'
+              % (penalty, bitrate(unit_sequences(ids), seconds), merged, int(q.last_n_switch_.sum()),
+                 sum(len(v) - 1 for v in unit_sequences(q.predict(corpus)).values() if len(v)), pen_abx, quant[len('quantised '):]))
 
 
 def main():
@@ -207,6 +217,8 @@ def main():
     ap.add_argument('--alignment', default=None, metavar='FILE', help='with --terms: a phone alignment; NED and coverage of the clusters')
     ap.add_argument('--kmeans', action='store_true', help='discrete units: k-means of the embeddings (--no-network: of the filterbanks), bitrate and ABX')
     ap.add_argument('--kmeans-clusters', type=int, default=50)
+    ap.add_argument('--kmeans-penalty', type=float, default=None, metavar='P',
+                    help='with --kmeans: also the penalised segmentation, P per new segment in units of the distortion (untuned)')
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     random.seed(0)
@@ -226,7 +238,7 @@ def main():
             ap.error('--no-network leaves nothing to do without --gmm or --kmeans')
         if args.kmeans:
             corpus = DeviceCorpus({k: np.asarray(v, dtype=np.float32) for k, v in fb.items()}, times)
-            kmeans_route(corpus, word_items(tokens)[1], 'filterbanks', args.kmeans_clusters)
+            kmeans_route(corpus, word_items(tokens)[1], 'filterbanks', args.kmeans_clusters, args.kmeans_penalty)
         return
 
     if args.tcl:
@@ -278,7 +290,7 @@ def main():
         if args.qbe:
             qbe_search(corpus, keep, names, label, 'kl' if args.softmax and label == 'embeddings' else 'cosine')
         if args.kmeans and label == 'embeddings':
-            kmeans_route(corpus, items, label, args.kmeans_clusters)
+            kmeans_route(corpus, items, label, args.kmeans_clusters, args.kmeans_penalty)
     if gmm_line:
         print(gmm_line)
 

@@ -1008,6 +1008,27 @@ int abn_kmeans_update(const void* ws, int64_t ws_bytes, const int32_t* ids, int6
                       int n_ranges, int cosine, double* sums, double* mu, float* m, float* b, double* stats,
                       void* stream);
 
+/* ---- penalised unit segmentation (added within ABI 20) ---------------------------------------------------------------
+ * The same scores s[t][k], smoothed by a constant cost per change of unit (abnet3_amd/kmeans.py states the recurrence):
+ * utterance u is the len[u] rows from off[u] (off int64, len int32, device arrays); over its good frames the ids
+ * maximise  sum_t s[t][a_t] - penalty_score * #{changes}, penalty_score = penalty / 2 for a penalty in units of the
+ * distortion |xc - m|^2.  BAD frames keep id -1 and cost nothing; rows outside every utterance keep what ids held.
+ * objective [n_utt] float64 and n_switch [n_utt] int32 may be NULL.  penalty_score = 0 gives abn_kmeans_assign's ids.
+ * One launch of persistent workgroups; fp32 recurrence, bit-reproducible; no T x K array: the workspace holds, per
+ * workgroup (at most 256), a 128-frame slab of scores, one stay bit per (frame, centroid) and an int32 per frame of
+ * the longest utterance.  An utterance that does not lie in 0 .. T, or is longer than the workspace was sized for,
+ * is left untouched: objective NaN, n_switch -1.
+ * abn_kmeans_viterbi_ws_bytes: -1 (abn_last_error) for refused sizes; max_len 0 .. abn_kmeans_viterbi_max_len(),
+ * K <= abn_kmeans_viterbi_max_k(), D <= abn_kmeans_max_d().  Null pointers, sizes < 1, a negative or non-finite
+ * penalty_score: ABN_E_ARG; limits: ABN_E_UNSUPPORTED; a workspace too small for one frame: ABN_E_WORKSPACE -- all
+ * before any launch. */
+int64_t abn_kmeans_viterbi_max_len(void);  /* host */
+int64_t abn_kmeans_viterbi_max_k(void);    /* host */
+int64_t abn_kmeans_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D);
+int abn_kmeans_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                       const float* shift, const float* m, const float* b, int64_t K, float penalty_score,
+                       int32_t* ids, double* objective, int32_t* n_switch, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
