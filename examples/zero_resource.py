@@ -8,6 +8,7 @@ mined pairs, and the ABX item file ("phones" = word types).
                                      [--gmm] [--gmm-components 64] [--no-network] [--terms] [--terms-theta T]
                                      [--prefilter] [--alignment FILE]
                                      [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P]
+                                     [--eskmeans] [--eskmeans-clusters 24]
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
 error is printed under both frame distances, the angular cosine and the symmetrised Kullback-Leibler divergence.
@@ -33,6 +34,9 @@ filterbanks -- and prints the units' bitrate and the ABX error of the quantised 
 centroid, the ZeroSpeech way of scoring units) next to the continuous ones.  --kmeans-penalty P prints a second line
 for the penalised segmentation (KMeansQuantizer.segment: a cost of P, in units of the distortion, per new segment; no
 tuned default): bitrate and ABX with the penalty beside those without.
+--eskmeans (with --kmeans --kmeans-penalty P) adds full-coverage word segmentation (abnet3_amd/eskmeans.py): landmarks
+at the boundaries of the penalised units, ES-KMeans over them, the number of segments and clusters, and how many edges
+of the planted words lie within 30 ms of a chosen cut.  n_clusters, max_span and the landmark density are untuned.
 """
 import argparse
 import os
@@ -175,9 +179,27 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False):
     return (line, post) if want_post else line
 
 
-def kmeans_route(corpus, items, label, n_clusters, penalty=None):
+def eskmeans_route(corpus, unit_ids, n_clusters, tokens=None, tolerance=0.03):
+    """penalised unit ids -> landmarks -> ESKMeans.fit: segments, clusters, and how many edges of the planted words
+    (`tokens`: (file, onset, offset, word) in seconds) lie within `tolerance` seconds of a chosen cut."""
+    from abnet3_amd import eskmeans
+    from abnet3_amd.kmeans import segments
+    lms = eskmeans.landmarks_from_units(segments(unit_ids), {k: corpus.length[k] for k in corpus.names})
+    esk = eskmeans.ESKMeans(n_clusters, frames=10, max_span=6, max_frames=100).fit(corpus, lms)
+    line = ('ES-KMeans over %d landmarks (K = %d, %d iterations): %d segments in %d clusters, objective %.2f'
+            % (sum(len(v) for v in lms.values()), n_clusters, len(esk.objective_), esk.n_segments_[-1], len(esk.clusters), esk.objective_[-1]))
+    if tokens:
+        cuts = esk.boundaries()
+        edges = [(t[0].decode('UTF-8') if isinstance(t[0], bytes) else str(t[0]), e) for t in tokens for e in (t[1], t[2])]
+        hit = sum(bool(len(cuts.get(f, ())) and np.abs(cuts[f] - e).min() <= tolerance) for f, e in edges)
+        line += '; %d of %d planted word edges within %.0f ms of a cut' % (hit, len(edges), 1000 * tolerance)
+    print(line)
+    return esk
+
+
+def kmeans_route(corpus, items, label, n_clusters, penalty=None, esk_clusters=None, tokens=None):
     """frames -> KMeansQuantizer.fit -> unit ids (bitrate) and quantised frames (ABX) beside the continuous ones; with a
-    penalty the same for the penalised segmentation."""
+    penalty the same for the penalised segmentation, and with esk_clusters ES-KMeans over its landmarks."""
     q = KMeansQuantizer(n_clusters).fit(corpus)
     seconds = 0.01 * corpus.total
     rate = bitrate(unit_sequences(q.predict(corpus), collapse=False), seconds)
@@ -196,6 +218,8 @@ def kmeans_route(corpus, items, label, n_clusters, penalty=None):
               'ABX error quantised %.2f %% (%s without)'
               % (penalty, bitrate(unit_sequences(ids), seconds), merged, int(q.last_n_switch_.sum()),
                  sum(len(v) - 1 for v in unit_sequences(q.predict(corpus)).values() if len(v)), pen_abx, quant[len('quantised '):]))
+        if esk_clusters:
+            eskmeans_route(corpus, ids, esk_clusters, tokens)
 
 
 def main():
@@ -219,7 +243,12 @@ def main():
     ap.add_argument('--kmeans-clusters', type=int, default=50)
     ap.add_argument('--kmeans-penalty', type=float, default=None, metavar='P',
                     help='with --kmeans: also the penalised segmentation, P per new segment in units of the distortion (untuned)')
+    ap.add_argument('--eskmeans', action='store_true', help='with --kmeans --kmeans-penalty P: ES-KMeans word segmentation over the units\' boundaries (untuned)')
+    ap.add_argument('--eskmeans-clusters', type=int, default=24)
     args = ap.parse_args()
+    if args.eskmeans and not (args.kmeans and args.kmeans_penalty is not None):
+        ap.error('--eskmeans takes its landmarks from --kmeans --kmeans-penalty P')
+    esk_k = args.eskmeans_clusters if args.eskmeans else None
     rng = np.random.default_rng(0)
     random.seed(0)
     np.random.seed(0)
@@ -238,7 +267,7 @@ def main():
             ap.error('--no-network leaves nothing to do without --gmm or --kmeans')
         if args.kmeans:
             corpus = DeviceCorpus({k: np.asarray(v, dtype=np.float32) for k, v in fb.items()}, times)
-            kmeans_route(corpus, word_items(tokens)[1], 'filterbanks', args.kmeans_clusters, args.kmeans_penalty)
+            kmeans_route(corpus, word_items(tokens)[1], 'filterbanks', args.kmeans_clusters, args.kmeans_penalty, esk_k, tokens)
         return
 
     if args.tcl:
@@ -290,7 +319,7 @@ def main():
         if args.qbe:
             qbe_search(corpus, keep, names, label, 'kl' if args.softmax and label == 'embeddings' else 'cosine')
         if args.kmeans and label == 'embeddings':
-            kmeans_route(corpus, items, label, args.kmeans_clusters, args.kmeans_penalty)
+            kmeans_route(corpus, items, label, args.kmeans_clusters, args.kmeans_penalty, esk_k, tokens)
     if gmm_line:
         print(gmm_line)
 

@@ -1029,6 +1029,39 @@ int abn_kmeans_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off,
                        const float* shift, const float* m, const float* b, int64_t K, float penalty_score,
                        int32_t* ids, double* objective, int32_t* n_switch, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- embedded segmental k-means (added within ABI 20) ----------------------------------------------------------------
+ * Full-coverage word segmentation (abnet3_amd/eskmeans.py states the definitions).  Landmarks: lm [n_lm] int64 row
+ * indices into table [T][D]; utterance u owns lm[lm_off[u] .. lm_off[u + 1]) (lm_off [n_utt + 1] int64), at least two
+ * entries, strictly increasing, the first its first row and the last one past its last row.  The candidate (g, s),
+ * 1 <= s <= S, runs from landmark g to g + s inside one utterance, covers rows lm[g] .. lm[g + s] - 1 (n of them), lives
+ * at index g S + s - 1 and is allowed if s == 1 or n <= max_frames.  All arrays are device arrays.
+ *
+ * abn_esk_score: cand_best [n_lm S] fp32 and cand_id [n_lm S] int32 = the best score <v, m_k> + b_k and the lowest k
+ * attaining it, v the candidate's unit vector exactly as abn_segment_vectors forms it (`frames` sampled rows, sum of
+ * squares in float64, scale in fp32), scored exactly as abn_kmeans_assign scores a row of depth frames D under a zero
+ * shift (m [K][frames D], b [K]): the same bits, but no candidate table is formed -- the rows are gathered on the way
+ * into LDS.  A candidate that crosses an utterance, is not allowed, lies outside 0 .. T, is longer than
+ * INT_MAX / (2 frames) rows, is all zero or has a non-finite sampled value: id -1, best NaN.
+ * frames D <= abn_kmeans_max_d(), K <= abn_kmeans_max_k(), S <= abn_esk_max_span(): beyond them ABN_E_UNSUPPORTED;
+ * null pointers, sizes < 1, n_lm < 2, n_lm S >= 2^31 - 128: ABN_E_ARG -- all before the launch.  One launch, no
+ * workspace, no floating-point atomics: bit-reproducible.
+ *
+ * abn_esk_segment: per utterance with L = (its landmarks) - 1, in fp32,
+ *   c(g, s) = (float)n * (1.0f - 2.0f * best)  (each operation rounded once; +inf where id < 0),
+ *   gamma[0] = 0,  gamma[j] = min_s gamma[j - s] + c(j - s, s),  equal sums to the smallest s,
+ * and the traceback from L: cut [n_lm] uint8 = 1 at every chosen boundary (first and last included), word [n_lm] int32 =
+ * the segment's cluster id and span [n_lm] int32 = its span at every chosen start, both -1 elsewhere; objective [n_utt]
+ * float64 = gamma[L] and n_seg [n_utt] int32 (either may be NULL).  An utterance whose end cannot be reached: objective
+ * NaN, n_seg -1, nothing marked.  One launch, one wavefront per utterance.  S <= abn_esk_max_span(): beyond it
+ * ABN_E_UNSUPPORTED; null pointers and sizes < 1: ABN_E_ARG. */
+int64_t abn_esk_max_span(void);            /* host */
+int abn_esk_score(const float* table, int64_t T, int64_t D, const int64_t* lm, const int64_t* lm_off, int64_t n_utt,
+                  int64_t n_lm, int frames, int S, int64_t max_frames, const float* m, const float* b, int64_t K,
+                  float* cand_best, int32_t* cand_id, void* stream);
+int abn_esk_segment(const float* cand_best, const int32_t* cand_id, const int64_t* lm, const int64_t* lm_off,
+                    int64_t n_utt, int64_t n_lm, int S, uint8_t* cut, int32_t* word, int32_t* span, double* objective,
+                    int32_t* n_seg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
