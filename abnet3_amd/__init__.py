@@ -20,4 +20,7 @@ def __getattr__(name):
     if name in ('TermPrefilter', 'lsh_planes', 'lsh_signatures', 'diag_hits_batch'):
         from . import prefilter
         return getattr(prefilter, name)
+    if name in ('SameDifferentEvaluator', 'scores_from_histogram', 'pair_histogram'):
+        from . import samediff
+        return getattr(samediff, name)
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

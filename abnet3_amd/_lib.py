@@ -149,7 +149,13 @@ SYMBOLS = {
     'abn_esk_max_span': (_i64, []),
     'abn_esk_score': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, C.c_int, C.c_int, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     'abn_esk_segment': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'abn_sd_grid_runs': (_i64, [_i64]),
+    'abn_sd_collect': (C.c_int, [_vp, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    'abn_sd_count': (C.c_int, [_vp, _i64, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _i64, _vp, _vp, _vp]),
 }
+# abn_sd_count's conditions and the limits of abn_sd_collect / abn_sd_count (include/abnet3_hip.h)
+SD_CONDITION = {'all': 0, 'swdp': 1, 'swsp': 2}
+SD_MAX_N, SD_MAX_THR, SD_MAX_D = 1 << 22, 1 << 30, 4096
 # abn_integrate_forward / _backward (include/abnet3_hip.h)
 INTEGRATE_MODE = {'sum': 0, 'concat': 1}
 W_NONE, W_FIXED, W_SCALAR, W_ATTENTION = range(4)

@@ -53,6 +53,7 @@ struct Switches {
     bool dtw_dealt;           // ABN_DTW_SCHED=0: the gang DTW kernel on round 4's schedule (a pair per slot), not the dealt one
     int oneshot_wgs;          // ABN_ONESHOT_WGS: most workgroups of abn_allreduce_oneshot (default 32, <= 256)
     int knn_split;            // ABN_KNN_SPLIT: workgroups that share a query block's candidates in abn_knn_topk (0 / unset / "auto": by the grid; same bits for any value)
+    int sd_tiles;             // ABN_SD_TILES: column tiles per workgroup of abn_sd_collect / abn_sd_count (1 .. 4096; 0 / unset: by the grid; same counts for any value)
 };
 const Switches& switches();
 void reload_switches();

@@ -65,6 +65,8 @@ static Switches read_switches()
     if (s.oneshot_wgs < 1 || s.oneshot_wgs > 256) s.oneshot_wgs = 32;
     s.knn_split = getenv("ABN_KNN_SPLIT") ? atoi(getenv("ABN_KNN_SPLIT")) : 0;
     if (s.knn_split < 0) s.knn_split = 0;
+    s.sd_tiles = getenv("ABN_SD_TILES") ? atoi(getenv("ABN_SD_TILES")) : 0;
+    if (s.sd_tiles < 0 || s.sd_tiles > 4096) s.sd_tiles = 0;
     return s;
 }
 static Switches g_switches = read_switches();       // (at library load: no call ever reads the environment)

@@ -8,7 +8,7 @@ mined pairs, and the ABX item file ("phones" = word types).
                                      [--gmm] [--gmm-components 64] [--no-network] [--terms] [--terms-theta T]
                                      [--prefilter] [--alignment FILE]
                                      [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P]
-                                     [--eskmeans] [--eskmeans-clusters 24]
+                                     [--eskmeans] [--eskmeans-clusters 24] [--samediff]
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
 error is printed under both frame distances, the angular cosine and the symmetrised Kullback-Leibler divergence.
@@ -37,6 +37,9 @@ tuned default): bitrate and ABX with the penalty beside those without.
 --eskmeans (with --kmeans --kmeans-penalty P) adds full-coverage word segmentation (abnet3_amd/eskmeans.py): landmarks
 at the boundaries of the penalised units, ES-KMeans over them, the number of segments and clusters, and how many edges
 of the planted words lie within 30 ms of a chosen cut.  n_clusters, max_span and the landmark density are untuned.
+--samediff adds same-different word discrimination (abnet3_amd/samediff.py) over the planted words' tokens: the average
+precision of "same word" among all token pairs, under DTW over the filterbanks, under DTW over the embeddings, and under
+the cosine of the embeddings' segment vectors (the objects KnnPairMiner searches and ESKMeans clusters).
 """
 import argparse
 import os
@@ -57,6 +60,7 @@ from abnet3_amd.kmeans import KMeansQuantizer, bitrate, unit_sequences   # noqa:
 from abnet3_amd.loss import KLLoss, coscos2                       # noqa: E402
 from abnet3_amd.model import SiameseNetwork                       # noqa: E402
 from abnet3_amd.prefilter import TermPrefilter                   # noqa: E402
+from abnet3_amd.samediff import SameDifferentEvaluator            # noqa: E402
 from abnet3_amd.sampler import SamplerClusterSiamese              # noqa: E402
 from abnet3_amd.tde import TermEvaluator, summary                 # noqa: E402
 from abnet3_amd.terms import TermDiscoverer                       # noqa: E402
@@ -111,6 +115,17 @@ def word_items(tokens):
     keep = [t for t in tokens if t[2] - t[1] >= 0.1]
     return keep, Items([t[0] for t in keep], [t[1] for t in keep], [t[2] for t in keep], ['w%d' % t[3] for t in keep],
                        ['-'] * len(keep), ['-'] * len(keep), ['spk'] * len(keep))
+
+
+def samediff_lines(corpus, tokens, label, vectors):
+    """Same-different AP of the planted words' tokens (a word type per planted word) over `corpus`."""
+    words = sorted({t[3] for t in tokens})
+    ev = SameDifferentEvaluator([[(t[0], t[1], t[2]) for t in tokens if t[3] == w] for w in words], corpus)
+    for distance in ('dtw', 'vectors') if vectors else ('dtw',):
+        r = ev.evaluate(distance)
+        print('same-different on %s (%s): AP %.3f, PRB %.3f (%d tokens of %d words, %d positives in %d pairs, %d dropped)'
+              % (label, 'segment vectors' if distance == 'vectors' else 'DTW', r.ap, r.prb, r.n_tokens, r.n_types,
+                 r.n_positives, r.n_pairs, r.n_bad + r.n_dropped_tokens))
 
 
 def guess_theta(table, distance, rng, quantile=0.04, n=20000):
@@ -245,6 +260,7 @@ def main():
                     help='with --kmeans: also the penalised segmentation, P per new segment in units of the distortion (untuned)')
     ap.add_argument('--eskmeans', action='store_true', help='with --kmeans --kmeans-penalty P: ES-KMeans word segmentation over the units\' boundaries (untuned)')
     ap.add_argument('--eskmeans-clusters', type=int, default=24)
+    ap.add_argument('--samediff', action='store_true', help='same-different AP of the planted words: DTW over filterbanks and embeddings, the embeddings\' segment vectors')
     args = ap.parse_args()
     if args.eskmeans and not (args.kmeans and args.kmeans_penalty is not None):
         ap.error('--eskmeans takes its landmarks from --kmeans --kmeans-penalty P')
@@ -310,6 +326,8 @@ def main():
     keep, items = word_items(tokens)
     for label, feats in (('filterbanks', fb), ('embeddings', dict(zip(names, emb)))):
         corpus = DeviceCorpus({k: np.asarray(feats[k], dtype=np.float32) for k in names}, times)
+        if args.samediff:
+            samediff_lines(corpus, keep, label, vectors=label == 'embeddings')
         r = ABXEvaluator(items, corpus).run('within')
         if args.softmax and label == 'embeddings':
             kl = ABXEvaluator(items, corpus, distance='kl').run('within')

@@ -1062,6 +1062,39 @@ int abn_esk_segment(const float* cand_best, const int32_t* cand_id, const int64_
                     int64_t n_utt, int64_t n_lm, int S, uint8_t* cut, int32_t* word, int32_t* span, double* objective,
                     int32_t* n_seg, void* stream);
 
+/* ---- same-different word discrimination (added within ABI 20) --------------------------------------------------------
+ * Every pair i < j of the n rows of X [n][d] (row-major fp32, 16-byte aligned; unit rows for a cosine), scored behind
+ * the tile that forms its similarity (abnet3_amd/samediff.py states the task and its scores).  sim(i, j) = <X_i, X_j>
+ * is accumulated exactly as abn_knn_topk accumulates it (v_mfma_f32_32x32x2_f32, k ascending, 128 x 128 tiles at
+ * multiples of 128): the same bits there, in abn_sd_collect and in abn_sd_count.  Only tiles on or above the diagonal
+ * are formed and the n x n matrix is never written.
+ * The rows are sorted by word type: row i carries the half-open range [cbeg[i], cend[i]) of its type (int32, device;
+ * cbeg[i] <= i < cend[i] <= n, equal for all rows of the range -- the caller guarantees it; the kernels read cend
+ * only, because j > i >= cbeg[i]).  The pair (i, j) is of one type when j < cend[i].
+ * d a multiple of 4 in [4, 4096], n <= ABN_SD_MAX_N, n_thr <= ABN_SD_MAX_THR: anything else is ABN_E_UNSUPPORTED;
+ * null pointers, n < 1, n_thr < 0, an unknown condition or a speaker condition without spk are ABN_E_ARG -- all before
+ * any launch.  ABN_SD_TILES (1 .. 4096; unset or 0: chosen from the grid) sets the column tiles per workgroup; the
+ * results do not depend on it.
+ *
+ * abn_sd_collect: writes sim(i, j) of every same-type pair to pos_sim[pos_off[i] + (j - i - 1)] (pos_off [n] int64,
+ * device; the caller sizes pos_sim as the sum over types of n_c (n_c - 1) / 2 and lays the rows out without gaps).
+ * One launch; column tiles past the end of a row block's last type are skipped.
+ *
+ * abn_sd_count: hist [n_thr + 1] and n_bad [1] (uint64, device) are cleared by the call.  thr [n_thr]: fp32,
+ * descending (NULL when n_thr == 0).  A same-type pair is left out when condition is ABN_SD_SWDP and
+ * spk[i] == spk[j], or ABN_SD_SWSP and spk[i] != spk[j] (spk [n] int32, device; may be NULL under ABN_SD_ALL).
+ * Of the others, a pair whose similarity is NaN or +-inf adds 1 to n_bad and nothing else; every other pair adds 1 to
+ * hist[#{r : thr[r] > sim}].  Integer atomics only: the counts are the same for any grid. */
+#define ABN_SD_MAX_N (1 << 22)
+#define ABN_SD_MAX_THR (1 << 30)
+enum { ABN_SD_ALL = 0, ABN_SD_SWDP = 1, ABN_SD_SWSP = 2 };
+int64_t abn_sd_grid_runs(int64_t n);       /* host: the grid's x extent (runs of column tiles per row block) for n rows
+                                              under the current ABN_SD_TILES; -1 for an n the kernels refuse */
+int abn_sd_collect(const float* X, int64_t n, int d, const int32_t* cbeg, const int32_t* cend,
+                   const int64_t* pos_off, float* pos_sim, void* stream);
+int abn_sd_count(const float* X, int64_t n, int d, const int32_t* cbeg, const int32_t* cend, const int32_t* spk,
+                 int condition, const float* thr, int64_t n_thr, uint64_t* hist, uint64_t* n_bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
