@@ -14,6 +14,9 @@ def __getattr__(name):
     if name == 'KMeansQuantizer':
         from .kmeans import KMeansQuantizer
         return KMeansQuantizer
+    if name in ('StickyHmmPosteriorgram',):
+        from . import hmm
+        return getattr(hmm, name)
     if name in ('TermEvaluator', 'edit_distance_batch', 'read_alignment', 'read_classes', 'transcribe'):
         from . import tde
         return getattr(tde, name)

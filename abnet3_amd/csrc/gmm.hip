@@ -18,142 +18,11 @@
 // No floating-point atomics anywhere: every sum has one fixed order, two calls give the same bits.
 #include "common.h"
 #include "gemm_f32.h"
+#include "gmm_tile.h"
 
 #include <math.h>
 
 namespace abn {
-
-constexpr int GM_B = 128;                  // frame block = component tile (2 x 2 waves of 2 x 2 MFMA blocks)
-constexpr int GM_MAX_D = 127;              // 2 D + 1 <= 256 columns of statistics in one workgroup's accumulators
-constexpr int GM_MAX_K = 4096;
-constexpr int GM_MAX_RANGES = 256;
-constexpr int GM_PT = GM_B * BK / 256;     // elements per thread of a 128 x 32 operand tile (scalar loads: D = 39 rows are not 16-byte aligned)
-constexpr int GM_LST = GM_B + 1;           // likelihood pass: a thread walks its frame's row, 129 dwords apart = conflict-free
-constexpr int GM_GST = GM_B + MPAD;        // accumulate pass: the staged tile IS a k-major operand (TileShape<128, false>::stride)
-using GmTile = TileShape<GM_B, true>;
-constexpr size_t GM_TILE_BYTES = sizeof(float) * 4 * GmTile::floats;      // two stages of each operand
-static_assert(GM_TILE_BYTES >= sizeof(float) * GM_B * GM_GST, "the score tile is staged in the operand buffers");
-static_assert(GM_GST == TileShape<GM_B, false>::stride, "frag_read<128, false> reads the staged responsibilities");
-template <int BN> constexpr size_t gmm_accum_lds() { return GM_TILE_BYTES + sizeof(float) * 2 * TileShape<BN, false>::floats; }
-
-struct GmmP {
-    const float* x; const float* shift;
-    const float* A; const float* B; const float* c;
-    int T, K, D;
-    float* lse;                 // likelihood pass: written; accumulate pass: read
-    float* post;                // [T][K] or nullptr
-    float* slabs;               // [tiles_k][n_ranges][128][2 D + 1]
-    int tiles_k, fblocks, n_ranges, blocks_per_range;
-};
-
-// Column ka of an augmented operand: 0 xc / A, 1 xc^2 / B, 2 the ones column / c, 3 the zero fill up to the k-tile.
-__device__ __forceinline__ int aug_kind(int ka, int D) { return ka < D ? 0 : ka < 2 * D ? 1 : ka == 2 * D ? 2 : 3; }
-__device__ __forceinline__ int aug_col(int ka, int D) { return ka < D ? ka : ka < 2 * D ? ka - D : 0; }
-
-// One element of X~ from the raw value: centred in fp32, squared in fp32, a non-finite value contributes 0 (its
-// frame is BAD: the likelihood pass marks it and nobody uses its scores).
-__device__ __forceinline__ float aug_value(float raw, float sh, int kind, bool row_ok)
-{
-    const float xc = raw - sh, sq = xc * xc;
-    float v = kind == 0 ? xc : kind == 1 ? sq : kind == 2 ? 1.0f : 0.0f;
-    if (kind < 2 && !__builtin_isfinite(sq)) v = 0.0f;
-    return row_ok ? v : 0.0f;
-}
-
-// 128 x 32 tiles, K-contiguous in LDS ([row][36]).  Thread t owns column k0 + (t & 31) of rows (t >> 5) + 8 i.
-// Branch-free issue from clamped addresses, validity applied at commit (gemm_f32.h's tile_issue / tile_commit).
-__device__ __forceinline__ void gmm_x_issue(float* r, const GmmP& p, int m0, int k0)
-{
-    const int t = threadIdx.x, ka = k0 + (t & 31), col = aug_col(ka, p.D);
-    const bool kv = ka < 2 * p.D;
-#pragma unroll
-    for (int i = 0; i < GM_PT; ++i) {
-        const int row = m0 + (t >> 5) + 8 * i;
-        r[i] = p.x[(kv && row < p.T) ? (int64_t)row * p.D + col : 0];
-    }
-}
-__device__ __forceinline__ void gmm_x_commit(const float* r, float* __restrict__ lds, const GmmP& p, int m0, int k0)
-{
-    const int t = threadIdx.x, ka = k0 + (t & 31), kind = aug_kind(ka, p.D);
-    const float sh = p.shift[aug_col(ka, p.D)];
-#pragma unroll
-    for (int i = 0; i < GM_PT; ++i) {
-        const int rl = (t >> 5) + 8 * i;
-        lds[rl * GmTile::stride + (t & 31)] = aug_value(r[i], sh, kind, m0 + rl < p.T);
-    }
-}
-__device__ __forceinline__ void gmm_w_issue(float* r, const GmmP& p, int n0, int k0)
-{
-    const int t = threadIdx.x, ka = k0 + (t & 31), kind = aug_kind(ka, p.D), col = aug_col(ka, p.D);
-    const float* const base = kind == 0 ? p.A : kind == 1 ? p.B : p.c;
-#pragma unroll
-    for (int i = 0; i < GM_PT; ++i) {
-        const int comp = n0 + (t >> 5) + 8 * i;
-        const int64_t off = kind == 2 ? (int64_t)comp : (int64_t)comp * p.D + col;
-        r[i] = base[(kind < 3 && comp < p.K) ? off : 0];
-    }
-}
-__device__ __forceinline__ void gmm_w_commit(const float* r, float* __restrict__ lds, const GmmP& p, int n0, int k0)
-{
-    const int t = threadIdx.x, kind = aug_kind(k0 + (t & 31), p.D);
-#pragma unroll
-    for (int i = 0; i < GM_PT; ++i) {
-        const int rl = (t >> 5) + 8 * i;
-        lds[rl * GmTile::stride + (t & 31)] = (kind < 3 && n0 + rl < p.K) ? r[i] : 0.0f;
-    }
-}
-
-// The 128 x 128 score tile of frames m0 .. and components n0 ..: rows = frames, columns = components, wave w owns
-// the 64 x 64 block ((w >> 1) 64, (w & 1) 64).  The caller guarantees that nobody still reads the operand buffers;
-// on return every wave has passed the last barrier, so the buffers are free again.
-__device__ __forceinline__ void gmm_score_tile(const GmmP& p, int m0, int n0, float* As, float* Bs, f32x16 (&acc)[2][2])
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
-    const int nkt = (2 * p.D + 1 + BK - 1) / BK;
-    float ra[GM_PT], rb[GM_PT];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-    gmm_x_issue(ra, p, m0, 0);
-    gmm_w_issue(rb, p, n0, 0);
-    gmm_x_commit(ra, As, p, m0, 0);
-    gmm_w_commit(rb, Bs, p, n0, 0);
-    __syncthreads();
-    for (int kt = 0; kt < nkt; ++kt) {
-        const int cur = kt & 1;
-        const bool more = kt + 1 < nkt;
-        const float* as = As + cur * GmTile::floats;
-        const float* bs = Bs + cur * GmTile::floats;
-        if (more) {
-            gmm_x_issue(ra, p, m0, (kt + 1) * BK);
-            gmm_w_issue(rb, p, n0, (kt + 1) * BK);
-        }
-#pragma unroll
-        for (int g = 0; g < BK / 8; ++g) {
-            f32x4 fa[2], fb[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) fa[i] = frag_read<GM_B, true>(as, wm0 + 32 * i, g, lane);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) fb[j] = frag_read<GM_B, true>(bs, wn0 + 32 * j, g, lane);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][e], fb[j][e], acc[i][j], 0, 0, 0);
-        }
-        if (more) {
-            gmm_x_commit(ra, As + (cur ^ 1) * GmTile::floats, p, m0, (kt + 1) * BK);
-            gmm_w_commit(rb, Bs + (cur ^ 1) * GmTile::floats, p, n0, (kt + 1) * BK);
-        }
-        __syncthreads();
-    }
-}
 
 __global__ __launch_bounds__(256) void gmm_like_kernel(GmmP p)
 {

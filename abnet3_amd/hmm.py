@@ -1,0 +1,315 @@
+"""Sticky-HMM smoothing of Gaussian posteriorgrams on the MI355X: forward-backward over a fitted mixture's components.
+
+    python -m abnet3_amd.hmm fit-stay GMM.npz FEATURES MODEL.npz [--stay P] [--n-iter N] [--tol T]
+    python -m abnet3_amd.hmm transform MODEL.npz FEATURES OUT [--mode smooth|filter]
+
+``GmmPosteriorgram`` treats every frame on its own, so its posteriors flicker.  An HMM over the mixture's components
+with a single "stay" probability is the smallest acoustic-unit model that has a likelihood: its forward-backward pass
+gives smoothed [rows, K] posteriors for the KL routes (``ABXEvaluator(distance='kl')``, ``QbeSearcher(distance='kl')``),
+a sequence likelihood, and the expected number of stays, from which the stay probability is fitted by EM.  The
+reference has no such model; the definition is the build's own ("parity unpinned") and
+tests/hmm_np.py restates it in numpy.
+
+The definition this module computes, over a fitted mixture (weights w, means, variances, shift of gmm.py):
+
+* States: the K components.  Initial distribution: w.  Transitions: a[j, k] = rho [j == k] + (1 - rho) w[k]: with
+  probability rho the unit stays, otherwise it is redrawn from the weights (and may come back the same).  rho = 0 is
+  the frame-independent mixture exactly; w is the stationary distribution and the chain is reversible.
+* Emissions: logN[t, k] = c0[k] + sum_d xc A + sum_d xc^2 B with gmm.py's xc, A, B (fp32, one GEMM of depth 2D + 1 on the
+  matrix cores) and c0[k] = -0.5 sum_d (log(2 pi v) + m^2 / v): gmm.py's c without log w, rounded once from float64,
+  finite for a component of weight 0.
+* Device inputs: w32 = float32(w), rho as one float32; 1 - rho is taken in fp32.
+* BAD frames (gmm.py's rule: a non-finite value in x or in xc^2): the output row is all zeros, the chain passes over
+  the frame -- the previous good frame is its successor's predecessor --, and it counts neither as a frame nor as a
+  transition.
+* Scaled recursion per utterance over its good frames in order, fp32:
+    m_t = max over {k : w32[k] > 0} of logN[t, k],   bt[t, k] = exp(logN[t, k] - m_t),
+    pred_t = w32 at the first good frame, else rho ahat_prev + (1 - rho) w32,
+    u = bt[t] pred_t,   c_t = sum_k u,   ahat_t = u / c_t,      loglik = sum_t (log c_t + m_t)  (float64 sum).
+  Backward from the last good frame with bhat = 1:  gamma_t = ahat_t bhat;  entering frame t from its predecessor p,
+    stays += sum_k rho ahat_p[k] bt[t, k] bhat[k] / c_t,   e = bt[t] bhat / c_t,   bhat <- rho e + (1 - rho) sum_k w32[k] e[k].
+  mode 'smooth' gives gamma, mode 'filter' ahat (no backward sweep, stays 0).
+* Range: 0 <= rho < 1 and float32(1 - rho) min{w32 > 0} >= 2^-100 (ValueError otherwise): then c_t >= 2^-100 and
+  e <= 2^100, and nothing in the chain underflows to zero or overflows.
+* EM for rho, the mixture fixed: rho_new = sum_u stays_u / sum_u max(n_good_u - 1, 0), clipped to [0, 0.9999]; the
+  log-likelihood does not decrease from one iteration to the next.
+
+On the device this is one launch for the whole corpus (abn_hmm_forward_backward, csrc/hmm.hip): persistent workgroups,
+one utterance at a time, one sum reduction per frame and sweep.  The output table holds ahat between the sweeps, so
+there is no T x K array beyond it.  Limits: K <= abn_hmm_max_k(), D <= abn_gmm_max_d(), an utterance of at most
+abn_hmm_max_len() frames; utterances must not overlap.  Left out: re-estimating the emissions under the HMM, full
+transition matrices, durations, a max-product path.
+"""
+import argparse
+import sys
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import gmm as _gmm
+
+MODES = {'smooth': 0, 'filter': 1}
+STAY_MAX = 0.9999
+TINY = 2.0 ** -100
+
+
+def max_len():
+    return int(_lib.load().abn_hmm_max_len())
+
+
+def max_k():
+    return int(_lib.load().abn_hmm_max_k())
+
+
+def emission_offsets(m, v):
+    """c0 [K] float32 of float64 centred means and variances [K, D]: gmm.score_tables' c without log w."""
+    m, v = np.asarray(m, dtype=np.float64), np.asarray(v, dtype=np.float64)
+    return (-0.5 * (np.log(2.0 * np.pi * v) + m * m / v).sum(axis=1)).astype(np.float32)
+
+
+def check_stay(who, stay, w32=None):
+    """float32(stay) as a Python float, or ValueError: 0 <= stay < 1 and, with the weights, the range condition."""
+    try:
+        r = np.float32(stay)
+    except (TypeError, ValueError):
+        raise ValueError('%s: stay = %r, a number in [0, 1) is needed' % (who, stay))
+    if not (np.isfinite(r) and 0.0 <= r < 1.0):
+        raise ValueError('%s: stay = %r, a number in [0, 1) is needed' % (who, stay))
+    if w32 is not None:
+        w32 = np.asarray(w32, dtype=np.float32)
+        pos = w32[w32 > 0]
+        if not np.isfinite(w32).all() or (w32 < 0).any() or not len(pos):
+            raise ValueError('%s: the weights must be finite, >= 0 and not all 0' % who)
+        if float(np.float32(1.0) - r) * float(pos.min()) < TINY:
+            raise ValueError('%s: (1 - stay) * min weight = %g is below 2^-100: the scaled recursion would underflow'
+                             % (who, float(np.float32(1.0) - r) * float(pos.min())))
+    return float(r)
+
+
+def forward_backward(table, off, lens, shift, A, B, c0, w, stay, mode='smooth', out=None, want_stays=True):
+    """(post [T, K] fp32, loglik [n_utt] float64, stays [n_utt] float64 or None, n_good [n_utt] int32), device tensors,
+    of the recursion the module docstring defines (abn_hmm_forward_backward, one launch).  off, lens: the utterances'
+    first rows and lengths (host sequences or device tensors); they must not overlap.  Rows outside every utterance
+    keep what `out` held (0 in a fresh table)."""
+    lib = _lib.load()
+    if mode not in MODES:
+        raise ValueError('hmm.forward_backward: mode = %r, one of %s' % (mode, sorted(MODES)))
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
+        raise ValueError('hmm.forward_backward: a [T, D] float32 table is needed')
+    T, D = table.shape
+    K = c0.shape[0]
+    if A.shape != (K, D) or B.shape != (K, D) or shift.shape != (D,) or w.shape != (K,) or any(
+            t.dtype != torch.float32 for t in (shift, A, B, c0, w)):
+        raise ValueError('hmm.forward_backward: shift [D], A [K, D], B [K, D], c0 [K], w [K] float32 are needed')
+    if K < 1 or K > max_k():
+        raise ValueError('hmm.forward_backward: K = %d, the kernel takes 1 .. %d (abn_hmm_max_k)' % (K, max_k()))
+    rho = check_stay('hmm.forward_backward', stay, w.cpu().numpy())
+    host = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    off_h, len_h = host(off).astype(np.int64).ravel(), host(lens).astype(np.int64).ravel()
+    n_utt = len(off_h)
+    if len(len_h) != n_utt:
+        raise ValueError('hmm.forward_backward: %d offsets and %d lengths' % (n_utt, len(len_h)))
+    if n_utt and ((off_h < 0).any() or (len_h < 0).any() or (off_h + len_h > T).any()):
+        raise ValueError('hmm.forward_backward: an utterance lies outside the table\'s %d rows' % T)
+    if n_utt > 1:
+        order = np.argsort(off_h, kind='stable')
+        if (off_h[order][1:] < (off_h + len_h)[order][:-1]).any():
+            raise ValueError('hmm.forward_backward: utterances overlap')
+    longest = int(len_h.max()) if n_utt else 0
+    if longest > max_len():
+        raise ValueError('hmm.forward_backward: an utterance of %d frames, the kernel takes up to %d (abn_hmm_max_len)'
+                         % (longest, max_len()))
+    table = _gmm._check_table('hmm.forward_backward', table)
+    _lib.require_device(shift, A, B, c0, w)
+    if out is None:
+        out = torch.zeros((T, K), dtype=torch.float32, device=table.device)
+    if out.shape != (T, K) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError('hmm.forward_backward: out must be a contiguous [T, K] float32 tensor')
+    _lib.require_device(out)
+    ll = torch.zeros(n_utt, dtype=torch.float64, device=table.device)
+    st = torch.zeros(n_utt, dtype=torch.float64, device=table.device) if want_stays else None
+    ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
+    if T and n_utt and longest:
+        need = lib.abn_hmm_ws_bytes(n_utt, longest, K, D)
+        if need < 0:
+            raise ValueError('hmm.forward_backward: %s' % lib.abn_last_error().decode('utf-8', 'replace'))
+        ws = torch.empty(int(need), dtype=torch.uint8, device=table.device)
+        off_d = torch.from_numpy(off_h).to(table.device)
+        len_d = torch.from_numpy(len_h.astype(np.int32)).to(table.device)
+        _lib.check(lib.abn_hmm_forward_backward(_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift),
+                                                _lib.ptr(A), _lib.ptr(B), _lib.ptr(c0), _lib.ptr(w), K, rho, MODES[mode],
+                                                _lib.ptr(out), _lib.ptr(ll), _lib.ptr(st), _lib.ptr(ng), _lib.ptr(ws),
+                                                ws.numel(), _lib.stream()), 'abn_hmm_forward_backward')
+    return out, ll, st, ng
+
+
+def stay_update(stays, n_good):
+    """The EM update of rho from the utterances' expected stays and good-frame counts (host or device arrays)."""
+    host = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    trans = np.maximum(host(n_good).astype(np.int64) - 1, 0).sum()
+    if trans < 1:
+        raise ValueError('hmm: no utterance has two good frames: the stay probability cannot be estimated')
+    return float(min(max(host(stays).astype(np.float64).sum() / float(trans), 0.0), STAY_MAX))
+
+
+class StickyHmmPosteriorgram(object):
+    """transform / score / fit_stay of the sticky HMM the module docstring defines, over a fitted GmmPosteriorgram.
+
+    corpus arguments: a DeviceCorpus, a {name: [T, D]} dict, the path of an h5features file -- each file an utterance --
+    or a [T, D] float32 device table, which is ONE utterance."""
+
+    def __init__(self, gmm, stay=0.9):
+        if not isinstance(gmm, _gmm.GmmPosteriorgram) or gmm.weights_ is None:
+            raise ValueError('StickyHmmPosteriorgram: a fitted GmmPosteriorgram is needed')
+        self.gmm = gmm
+        self.stay_ = check_stay('StickyHmmPosteriorgram', stay, gmm.weights_.astype(np.float32))
+        self.log_likelihoods = []
+        self.n_bad_ = 0
+        self._tables = None
+
+    def whoami(self):
+        return {'params': {'stay': self.stay_, 'gmm': self.gmm.whoami()}, 'class_name': self.__class__.__name__}
+
+    def device_tables(self, device):
+        """(shift, A, B, c0, w32) on the device, rounded once from the mixture's float64 parameters."""
+        if self._tables is None or self._tables[0].device != device:
+            g = self.gmm
+            shift, A, B, _ = g.device_tables(device)
+            m = g.means_ - g.shift_.astype(np.float64)
+            c0 = torch.from_numpy(emission_offsets(m, g.variances_)).to(device)
+            w = torch.from_numpy(g.weights_.astype(np.float32)).to(device)
+            self._tables = (shift, A, B, c0, w)
+        return self._tables
+
+    def _utterances(self, corpus):
+        """(device table, DeviceCorpus or None, lens int64 [n_utt])"""
+        table, dc = _gmm.GmmPosteriorgram._corpus(corpus)
+        if dc is not None:
+            lens = [dc.length[k] for k in dc.names]
+        elif isinstance(corpus, dict):
+            lens = [np.asarray(f).shape[0] for f in corpus.values()]
+        else:
+            lens = [table.shape[0]] if isinstance(table, torch.Tensor) and table.dim() == 2 else []
+        if isinstance(table, torch.Tensor) and table.dim() == 2 and table.dtype == torch.float32:      # (host checks first)
+            if table.shape[1] != self.gmm.shift_.shape[0]:
+                raise ValueError('StickyHmmPosteriorgram: the table has D = %d, the model D = %d'
+                                 % (table.shape[1], self.gmm.shift_.shape[0]))
+            if len(lens) and max(lens) > max_len():
+                raise ValueError('StickyHmmPosteriorgram: an utterance of %d frames, the kernel takes up to %d '
+                                 '(abn_hmm_max_len); pass a corpus of utterances' % (max(lens), max_len()))
+        table = _gmm._check_table('StickyHmmPosteriorgram', table)
+        return table, dc, np.asarray(lens, dtype=np.int64)
+
+    def _run(self, table, lens, mode, stay=None, out=None, want_stays=True):
+        off = np.cumsum(lens) - lens
+        return forward_backward(table, off, lens, *self.device_tables(table.device),
+                                stay=self.stay_ if stay is None else stay, mode=mode, out=out, want_stays=want_stays)
+
+    def transform(self, corpus, mode='smooth'):
+        """The smoothed (mode='filter': filtered) posterior table [rows, K] on the device; for a DeviceCorpus a new
+        DeviceCorpus with the same names, lengths and times."""
+        from .dataloader import DeviceCorpus
+        table, dc, lens = self._utterances(corpus)
+        out = self._run(table, lens, mode, want_stays=False)[0]
+        if dc is None:
+            return out
+        return DeviceCorpus.from_table(out, dc.names, [dc.length[k] for k in dc.names], dc.times)
+
+    def score(self, corpus):
+        """The mean log-likelihood per good frame."""
+        table, _, lens = self._utterances(corpus)
+        _, ll, _, ng = self._run(table, lens, 'filter', want_stays=False)
+        ll_sum, n = torch.stack([ll.sum(), ng.to(torch.float64).sum()]).cpu().tolist()
+        return ll_sum / max(1.0, n)
+
+    def fit_stay(self, corpus, n_iter=10, tol=1e-4):
+        """EM on the stay probability, the mixture fixed, from the current ``stay_``.  Iteration i runs forward-backward
+        under the current stay -- ``log_likelihoods[i]`` is its mean log-likelihood per good frame -- and then applies the
+        update.  After at most n_iter iterations, or as soon as log_likelihoods[i] - log_likelihoods[i - 1] < tol, it stops
+        (the last update is then not applied: ``stay_`` is the stay the last likelihood was computed under, or the
+        update of the n_iter-th).  One T x K scratch table is allocated; one read-back of four numbers per iteration."""
+        table, _, lens = self._utterances(corpus)
+        scratch = torch.zeros((table.shape[0], self.gmm.n_components), dtype=torch.float32, device=table.device)
+        w32 = self.gmm.weights_.astype(np.float32)
+        self.log_likelihoods = []
+        rho = self.stay_
+        for it in range(int(n_iter)):
+            _, ll, st, ng = self._run(table, lens, 'smooth', stay=rho, out=scratch)
+            good = ng.clamp(min=0).to(torch.float64)
+            ll_sum, n, ntr, stays = torch.stack([ll.sum(), good.sum(), (good - 1.0).clamp(min=0.0).sum(), st.sum()]).cpu().tolist()
+            if ntr < 1:
+                raise ValueError('StickyHmmPosteriorgram.fit_stay: no utterance has two good frames')
+            self.log_likelihoods.append(ll_sum / n)
+            self.n_bad_ = int(lens.sum() - n)
+            if it > 0 and self.log_likelihoods[-1] - self.log_likelihoods[-2] < tol:
+                break
+            rho = check_stay('StickyHmmPosteriorgram.fit_stay', min(max(stays / ntr, 0.0), STAY_MAX), w32)
+        self.stay_ = rho
+        return self
+
+    # -- files ----------------------------------------------------------------------------------------------------
+    def save(self, path):
+        g = self.gmm
+        with open(path, 'wb') as f:
+            np.savez(f, weights=g.weights_, means=g.means_, variances=g.variances_, shift=g.shift_, gv=g.gv_,
+                     log_likelihoods=np.asarray(g.log_likelihoods, dtype=np.float64),
+                     n_components=g.n_components, n_iter=g.n_iter, tol=g.tol, var_floor=g.var_floor,
+                     min_count=g.min_count, seed=g.seed, stay=np.float64(self.stay_),
+                     stay_log_likelihoods=np.asarray(self.log_likelihoods, dtype=np.float64))
+
+    @classmethod
+    def load(cls, path):
+        g = _gmm.GmmPosteriorgram.load(path)
+        with np.load(path) as z:
+            if 'stay' not in z.files:
+                raise ValueError('%s: not a StickyHmmPosteriorgram file (no stay)' % path)
+            self = cls(g, float(z['stay']))
+            self.log_likelihoods = [float(v) for v in z['stay_log_likelihoods']]
+        return self
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog='python -m abnet3_amd.hmm', description='Sticky-HMM smoothing of Gaussian posteriorgrams')
+    sub = ap.add_subparsers(dest='cmd', required=True)
+    f = sub.add_parser('fit-stay', help='fit the stay probability of a saved mixture on FEATURES and save the model')
+    f.add_argument('gmm', help='a GmmPosteriorgram .npz (python -m abnet3_amd.gmm fit)')
+    f.add_argument('features', help='h5features file, or an .npz of name -> [T, D]')
+    f.add_argument('model', help='the .npz to write')
+    f.add_argument('--stay', type=float, default=0.9, help='where EM starts')
+    f.add_argument('--n-iter', type=int, default=10)
+    f.add_argument('--tol', type=float, default=1e-4)
+    t = sub.add_parser('transform', help='smoothed posteriorgrams of FEATURES under a saved model')
+    t.add_argument('model')
+    t.add_argument('features', help='h5features file, or an .npz of name -> [T, D]')
+    t.add_argument('out', help='.npz of name -> [T, K], or an h5features file (when the input has times)')
+    t.add_argument('--mode', choices=sorted(MODES), default='smooth')
+    args = ap.parse_args(argv)
+    feats, times = _gmm._read_features(args.features)
+    if args.cmd == 'fit-stay':
+        h = StickyHmmPosteriorgram(_gmm.GmmPosteriorgram.load(args.gmm), args.stay).fit_stay(feats, args.n_iter, args.tol)
+        h.save(args.model)
+        print('stay %.6f after %d iterations, mean log-likelihood %.6f, %d BAD frames'
+              % (h.stay_, len(h.log_likelihoods), h.log_likelihoods[-1], h.n_bad_))
+        return 0
+    h = StickyHmmPosteriorgram.load(args.model)
+    post = h.transform(feats, args.mode).cpu().numpy()
+    out, o = {}, 0
+    for k, v in feats.items():
+        out[k] = post[o:o + v.shape[0]]
+        o += v.shape[0]
+    if args.out.endswith('.npz'):
+        np.savez(args.out, **{str(k): v for k, v in out.items()})
+    else:
+        if times is None:
+            raise ValueError('an h5features output needs the frame times: give an h5features input')
+        import h5features
+        names = list(out)
+        with h5features.Writer(args.out) as wh:
+            wh.write(h5features.Data(names, [np.asarray(times[k]) for k in names], [out[k] for k in names]), 'features')
+    print('%d files, %d frames, K = %d, stay %.4f -> %s' % (len(out), post.shape[0], post.shape[1], h.stay_, args.out))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

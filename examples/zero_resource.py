@@ -5,7 +5,7 @@ Siamese training -> embedding -> ABX.  The corpus' word labels are used twice on
 mined pairs, and the ABX item file ("phones" = word types).
 
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
-                                     [--gmm] [--gmm-components 64] [--no-network] [--terms] [--terms-theta T]
+                                     [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--no-network] [--terms] [--terms-theta T]
                                      [--prefilter] [--alignment FILE]
                                      [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P]
                                      [--eskmeans] [--eskmeans-clusters 24] [--samediff]
@@ -20,7 +20,8 @@ against a stretch of another file ("diff").
 searched in every utterance by subsequence DTW, and the mean average precision of the rankings is printed.
 --gmm adds the untrained baseline (abnet3_amd/gmm.py): a Gaussian mixture fitted on the filterbanks, its posteriorgrams
 under the KL frame distance -- ABX, and with --qbe the search.  No network is trained on this route; --no-network stops
-after it, otherwise its figures are printed again beside the embeddings'.
+after it, otherwise its figures are printed again beside the embeddings'.  --hmm-stay P (or "fit": EM on the stay
+probability) smooths the posteriorgrams with the sticky HMM of abnet3_amd/hmm.py and prints ABX (kl) of both.
 --terms replaces the pair miner by term discovery (abnet3_amd/terms.py): local-alignment DTW of every utterance against
 every other -- over the filterbanks, or with --gmm over the mixture's posteriorgrams under the KL distance -- clustered
 into a .classes file, from which SamplerClusterSiamese draws the train and dev pairs: the reference's canonical route,
@@ -56,6 +57,7 @@ from abnet3_amd.discovery import KnnPairMiner                     # noqa: E402
 from abnet3_amd.embedder import EmbedderSiamese                   # noqa: E402
 from abnet3_amd.features import FeaturesGenerator                 # noqa: E402
 from abnet3_amd.gmm import GmmPosteriorgram                       # noqa: E402
+from abnet3_amd.hmm import StickyHmmPosteriorgram                 # noqa: E402
 from abnet3_amd.kmeans import KMeansQuantizer, bitrate, unit_sequences   # noqa: E402
 from abnet3_amd.loss import KLLoss, coscos2                       # noqa: E402
 from abnet3_amd.model import SiameseNetwork                       # noqa: E402
@@ -178,8 +180,9 @@ def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frame
     return dl
 
 
-def gmm_route(fb, times, tokens, n_components, qbe, want_post=False):
-    """features -> GmmPosteriorgram.fit -> transform -> ABX (kl), and the search: the line main() prints."""
+def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=None):
+    """features -> GmmPosteriorgram.fit -> transform -> ABX (kl), and the search: the line main() prints.  hmm_stay (a
+    number, or 'fit'): the sticky-HMM smoothed posteriorgrams beside the raw ones; they are the ones returned."""
     names = list(fb)
     keep, items = word_items(tokens)
     corpus = DeviceCorpus({k: np.asarray(fb[k], dtype=np.float32) for k in names}, times)
@@ -189,8 +192,19 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False):
     line = ('ABX error on GMM posteriorgrams (K = %d, %d EM iterations, log-likelihood %.3f, %d starved): kl %.2f %% '
             '(%d triplets)' % (n_components, len(g.log_likelihoods), g.log_likelihoods[-1], g.n_starved_, r.error, r.n_triplets))
     print(line)
+    if hmm_stay is not None:
+        h = StickyHmmPosteriorgram(g, 0.9 if hmm_stay == 'fit' else float(hmm_stay))
+        if hmm_stay == 'fit':
+            h.fit_stay(corpus)
+        raw_ll, post = g.score(corpus), h.transform(corpus)
+        rs = ABXEvaluator(items, post, distance='kl').run('within')
+        more = ('ABX error on sticky-HMM smoothed posteriorgrams (stay %.4f%s, log-likelihood per frame %.3f against %.3f): '
+                'kl %.2f %% smoothed, %.2f %% raw (%d triplets)' % (h.stay_, ', fitted' if hmm_stay == 'fit' else '', h.score(corpus),
+                                                                   raw_ll, rs.error, r.error, rs.n_triplets))
+        print(more)
+        line += '\n' + more
     if qbe:
-        qbe_search(post, keep, names, 'GMM posteriorgrams', 'kl')
+        qbe_search(post, keep, names, 'GMM posteriorgrams' + (' (smoothed)' if hmm_stay is not None else ''), 'kl')
     return (line, post) if want_post else line
 
 
@@ -249,6 +263,9 @@ def main():
     ap.add_argument('--qbe', action='store_true', help='after embedding: search a few planted words by example, print MAP')
     ap.add_argument('--gmm', action='store_true', help='the untrained baseline: GMM posteriorgrams of the filterbanks, ABX (kl)')
     ap.add_argument('--gmm-components', type=int, default=64)
+    ap.add_argument('--hmm-stay', default=None, metavar='P|fit',
+                    help='with --gmm: sticky-HMM smoothing of the posteriorgrams (abnet3_amd/hmm.py) with stay probability P, or '
+                         'fitted by EM; ABX (kl) of raw and smoothed side by side')
     ap.add_argument('--no-network', action='store_true', help='with --gmm: stop after the mixture, train nothing')
     ap.add_argument('--terms', action='store_true', help='pairs from term discovery: clusters -> SamplerClusterSiamese')
     ap.add_argument('--terms-theta', type=float, default=None, help='default: a low quantile of random frame distances (untuned)')
@@ -264,6 +281,8 @@ def main():
     args = ap.parse_args()
     if args.eskmeans and not (args.kmeans and args.kmeans_penalty is not None):
         ap.error('--eskmeans takes its landmarks from --kmeans --kmeans-penalty P')
+    if args.hmm_stay is not None and not args.gmm:
+        ap.error('--hmm-stay smooths the posteriorgrams of --gmm')
     esk_k = args.eskmeans_clusters if args.eskmeans else None
     rng = np.random.default_rng(0)
     random.seed(0)
@@ -277,7 +296,7 @@ def main():
 
     gmm_line = post = None
     if args.gmm:
-        gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True)
+        gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True, hmm_stay=args.hmm_stay)
     if args.no_network:
         if not (args.gmm or args.kmeans):
             ap.error('--no-network leaves nothing to do without --gmm or --kmeans')

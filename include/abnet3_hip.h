@@ -1029,6 +1029,31 @@ int abn_kmeans_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off,
                        const float* shift, const float* m, const float* b, int64_t K, float penalty_score,
                        int32_t* ids, double* objective, int32_t* n_switch, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- sticky-HMM posteriorgram smoothing (added within ABI 20) --------------------------------------------------------
+ * Forward-backward of the HMM over a mixture's K components with one stay probability (abnet3_amd/hmm.py states the
+ * recursion): initial distribution w, transitions a[j][k] = rho [j == k] + (1 - rho) w[k], emissions
+ * logN[t][k] = c0[k] + sum_d xc A + sum_d xc^2 B -- abn_gmm_posteriors' score with c0 = c without the log weight.
+ * Utterance u is the len[u] rows from off[u] (off int64, len int32, device arrays; utterances must not overlap).
+ * post [T][K] fp32: mode 0 the smoothed gamma, mode 1 the filtered ahat (no backward sweep); a BAD frame's row is all
+ * zeros and the chain passes over it; rows outside every utterance are not touched.  loglik [n_utt] float64 (the sum
+ * over the good frames), stays [n_utt] float64 (the expected number of stays; may be NULL; 0 in mode 1), n_good [n_utt]
+ * int32.  An utterance that does not lie in 0 .. T, or is longer than the workspace was sized for, is left
+ * untouched: loglik (and stays) NaN, n_good -1.
+ * One launch of persistent workgroups; fp32 recursion with fixed reduction orders, bit-reproducible, no atomics; no
+ * T x K array beyond post, which holds ahat between the sweeps: the workspace holds, per workgroup (at most 256), a
+ * 128-frame slab of scores and one float per frame of the longest utterance.
+ * abn_hmm_ws_bytes: -1 (abn_last_error) for refused sizes; max_len 0 .. abn_hmm_max_len(), K <= abn_hmm_max_k()
+ * (= abn_gmm_max_k()), D <= abn_gmm_max_d().  Null pointers, sizes < 1, rho outside [0, 1) or non-finite, a mode other
+ * than 0 / 1: ABN_E_ARG; limits: ABN_E_UNSUPPORTED; a workspace too small for one frame: ABN_E_WORKSPACE -- all before
+ * any launch.  The caller keeps float32(1 - rho) * min{w > 0} >= 2^-100 (abnet3_amd/hmm.py refuses otherwise). */
+int64_t abn_hmm_max_len(void);             /* host */
+int64_t abn_hmm_max_k(void);               /* host */
+int64_t abn_hmm_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D);
+int abn_hmm_forward_backward(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                             const float* shift, const float* A, const float* B, const float* c0, const float* w,
+                             int64_t K, float rho, int mode, float* post, double* loglik, double* stays,
+                             int32_t* n_good, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- embedded segmental k-means (added within ABI 20) ----------------------------------------------------------------
  * Full-coverage word segmentation (abnet3_amd/eskmeans.py states the definitions).  Landmarks: lm [n_lm] int64 row
  * indices into table [T][D]; utterance u owns lm[lm_off[u] .. lm_off[u + 1]) (lm_off [n_utt + 1] int64), at least two
