@@ -113,33 +113,6 @@ __global__ __launch_bounds__(256) void gmm_like_kernel(GmmP p)
     }
 }
 
-// Second GEMM's B operand: 32 frames x BN columns of X~, k-major in LDS ([frame][BN + 4]); thread t owns column
-// t % BN of frames t / BN + (256 / BN) i.
-template <int BN>
-__device__ __forceinline__ void gmm_xk_issue(float* r, const GmmP& p, int f0)
-{
-    constexpr int PT = 32 * BN / 256, FS = 256 / BN > 0 ? 256 / BN : 1;
-    const int t = threadIdx.x, ka = t % BN, col = aug_col(ka, p.D);
-    const bool kv = ka < 2 * p.D;
-#pragma unroll
-    for (int i = 0; i < PT; ++i) {
-        const int f = f0 + (BN >= 256 ? i : t / BN + FS * i);
-        r[i] = p.x[(kv && f < p.T) ? (int64_t)f * p.D + col : 0];
-    }
-}
-template <int BN>
-__device__ __forceinline__ void gmm_xk_commit(const float* r, float* __restrict__ lds, const GmmP& p, int f0)
-{
-    constexpr int PT = 32 * BN / 256, FS = 256 / BN > 0 ? 256 / BN : 1, ST = TileShape<BN, false>::stride;
-    const int t = threadIdx.x, ka = t % BN, kind = aug_kind(ka, p.D);
-    const float sh = p.shift[aug_col(ka, p.D)];
-#pragma unroll
-    for (int i = 0; i < PT; ++i) {
-        const int fl = BN >= 256 ? i : t / BN + FS * i;
-        lds[fl * ST + ka] = aug_value(r[i], sh, kind, f0 + fl < p.T);
-    }
-}
-
 template <int BN>
 __global__ __launch_bounds__(256) void gmm_accum_kernel(GmmP p)
 {
@@ -255,11 +228,7 @@ __global__ __launch_bounds__(256) void gmm_reduce_kernel(const float* __restrict
     __shared__ double sh[256];
     const int t = threadIdx.x, nc = 2 * D + 1, k = (int)blockIdx.x;
     if (k < K) {
-        if (t >= nc) return;
-        const float* src = slabs + ((int64_t)(k / GM_B) * n_ranges * GM_B + (k % GM_B)) * nc + t;
-        double a = 0.0;
-        for (int r = 0; r < n_ranges; ++r) a += (double)src[(int64_t)r * GM_B * nc];
-        sums[(int64_t)k * nc + t] = a;
+        gmm_sum_slabs(slabs, k, nc, n_ranges, sums);
         return;
     }
     double ll = 0.0, bad = 0.0;
@@ -317,21 +286,6 @@ __global__ __launch_bounds__(256) void gmm_mstep_kernel(const double* __restrict
     }
 }
 
-struct GmmGrid { int tiles_k, fblocks, n_ranges, blocks_per_range; };
-static GmmGrid gmm_grid(int64_t T, int64_t K, int n_ranges)
-{
-    GmmGrid g;
-    g.tiles_k = (int)((K + GM_B - 1) / GM_B);
-    g.fblocks = (int)((T + GM_B - 1) / GM_B);
-    int r = n_ranges;
-    if (r <= 0) r = (1024 + g.tiles_k - 1) / g.tiles_k;      // auto: four workgroups per CU's worth of (tile, range) pairs
-    if (r > GM_MAX_RANGES) r = GM_MAX_RANGES;
-    if (r > g.fblocks) r = g.fblocks;
-    g.blocks_per_range = (g.fblocks + r - 1) / r;
-    g.n_ranges = (g.fblocks + g.blocks_per_range - 1) / g.blocks_per_range;
-    return g;
-}
-
 static int gmm_check_sizes(int64_t T, int64_t K, int64_t D, int n_ranges, const char* what)
 {
     ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "%s: T = %lld out of range", what, (long long)T);
@@ -344,20 +298,6 @@ static int gmm_check_sizes(int64_t T, int64_t K, int64_t D, int n_ranges, const 
         return ABN_E_UNSUPPORTED;
     }
     return ABN_OK;
-}
-
-// Workspace: one slab per (component tile, range).  Sized by a bound on the pairs that does not shrink when T or K grow
-// (the ranges themselves do, where one more frame block tips blocks_per_range over).
-static int64_t gmm_slab_bytes(const GmmGrid& g, int64_t D, int n_ranges)
-{
-    int64_t pairs;
-    if (n_ranges > 0) pairs = (int64_t)g.tiles_k * (n_ranges < g.fblocks ? n_ranges : g.fblocks);
-    else {
-        pairs = 1024 + g.tiles_k;
-        if (pairs > (int64_t)g.tiles_k * GM_MAX_RANGES) pairs = (int64_t)g.tiles_k * GM_MAX_RANGES;
-        if (pairs > (int64_t)g.tiles_k * g.fblocks) pairs = (int64_t)g.tiles_k * g.fblocks;
-    }
-    return pairs * GM_B * (2 * D + 1) * (int64_t)sizeof(float);
 }
 
 static void gmm_fill(GmmP& p, const float* x, int64_t T, int64_t D, const float* shift, const float* A, const float* B,

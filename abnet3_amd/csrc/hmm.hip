@@ -1,4 +1,5 @@
-// hmm.hip -- forward-backward of the sticky HMM over a mixture's components (abn_hmm_forward_backward).
+// hmm.hip -- forward-backward of the sticky HMM over a mixture's components (abn_hmm_forward_backward, and with the
+// per-component stays abn_hmm_forward_backward_stats) and the statistics of its Baum-Welch step (abn_hmm_accumulate).
 // abnet3_amd/hmm.py states the definition; DESIGN.md section 3.4c2 the shape.
 //
 // The sum-product twin of km_viterbi_kernel (kmeans.hip): one launch for the corpus, persistent workgroups that loop
@@ -37,6 +38,7 @@ struct HmmP {
     int n_utt, mode;
     float rho;
     float* post; double* loglik; double* stays; int* n_good;
+    double* stay_k;                         // [n_utt][K], the SK instantiations only
     char* ws; int64_t per_wg;               // bytes of a workgroup's region
     int ks, cap;                            // slab row stride (floats), frames the region holds
 };
@@ -137,7 +139,11 @@ __device__ __forceinline__ void hmm_block_scores(const HmmP& p, int m0, int nf, 
     __syncthreads();
 }
 
-template <int NQ>
+// SK: the per-component stays as well (abn_hmm_forward_backward_stats).  The chain, `post`, loglik, stays and n_good are
+// the same instructions in the same order either way.  A thread adds its own components' terms ah e in fp32 over a block
+// of 128 frames and then into stay_k[u][k] in float64: the row is the store of the float64 sums, every element is read and
+// written by the one thread that owns it, and the factor rho is applied at the utterance's end.
+template <int NQ, bool SK>
 __global__ __launch_bounds__(256) void hmm_fb_kernel(HmmP p)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -167,8 +173,13 @@ __global__ __launch_bounds__(256) void hmm_fb_kernel(HmmP p)
                 p.n_good[u] = -1;
                 if (p.stays) p.stays[u] = NAN;
             }
+            if constexpr (SK)
+                for (int k = t; k < K; k += 256) p.stay_k[(int64_t)u * K + k] = NAN;
             continue;
         }
+        double* const skrow = SK ? p.stay_k + (int64_t)u * K : nullptr;
+        if constexpr (SK)
+            for (int k = t; k < K; k += 256) skrow[k] = 0.0;          // (mode 1, fewer than two good frames: it stays 0)
         float* const post = p.post + o * K;
         float a[NQ], e[NQ];                                           // forward: ahat; backward: bhat and the later frame's e
 #pragma unroll
@@ -241,6 +252,11 @@ __global__ __launch_bounds__(256) void hmm_fb_kernel(HmmP p)
                 ll += hmm_block_sum(v, red_d);
             } else {
                 float bn[NQ], an[NQ];
+                float sk[SK ? NQ : 1];
+                if constexpr (SK) {
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) sk[q] = 0.0f;
+                }
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) {
                     const bool in = 256 * q + t < K;
@@ -268,6 +284,10 @@ __global__ __launch_bounds__(256) void hmm_fb_kernel(HmmP p)
                         if (256 * q + t < K) prow[256 * q + t] = ah[q] * a[q];
                     }
                     st += (double)sp;
+                    if constexpr (SK) {
+#pragma unroll
+                        for (int q = 0; q < NQ; ++q) sk[q] += ah[q] * e[q];
+                    }
                     if (--remaining == 0) break;                      // (uniform) the first good frame has no predecessor
                     const float inv = 1.0f / c_s[f];
                     float s = 0.0f;
@@ -284,6 +304,11 @@ __global__ __launch_bounds__(256) void hmm_fb_kernel(HmmP p)
 #pragma unroll
                     for (int q = 0; q < NQ; ++q) a[q] = rho * e[q] + tot;
                 }
+                if constexpr (SK) {
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q)
+                        if (256 * q + t < K) skrow[256 * q + t] += (double)sk[q];
+                }
                 __syncthreads();                                      // before the next block's scores replace these
                 if (remaining == 0) break;                            // (uniform)
             }
@@ -292,12 +317,161 @@ __global__ __launch_bounds__(256) void hmm_fb_kernel(HmmP p)
             const double tot = hmm_block_sum(st, red_d);
             if (t == 0) p.stays[u] = (double)rho * tot;
         }
+        if constexpr (SK)
+            for (int k = t; k < K; k += 256) skrow[k] *= (double)rho;
         if (t == 0) {
             p.loglik[u] = ll;
             p.n_good[u] = ngood;
         }
         __syncthreads();
     }
+}
+
+// ---- abn_hmm_accumulate: sufficient statistics from a responsibility table ---------------------------------------------
+// gmm_accum_kernel's second GEMM with the A operand LOADED: a workgroup owns a tile of 128 components and a range of
+// frame blocks, [S1 | S2 | N][k][.] += sum_t post[t][k] X~[t][.] on the fp32 matrix cores, accumulators in registers for the
+// whole range, one slab per workgroup.  The 128 x 128 tile of `post` (64 elements per thread: column t % 128 of rows
+// t / 128 + 2 i, so a wave reads 64 consecutive components of a frame) is the launch's whole memory traffic, T K 4 bytes
+// once: it is fetched one block ahead into registers, a quarter behind each of the four 32-frame steps of the block
+// before, and committed k-major ([frame][132], zero past T and past K) once that block's last step has been read.  The
+// X~ tiles stream in two LDS stages across the blocks.  LDS: 66 KiB + 2 x 32 x (BN + 4) floats, one workgroup per CU.
+// gmm_xk_issue for a step whose 32 frames lie inside the table (uniform; every step but the table's last few): the same
+// elements as ONE per-thread 32-bit offset on a uniform pointer per frame -- the clamped 64-bit form costs a dozen VALU
+// instructions per element, and with one wave per SIMD they are not hidden behind anybody's MFMAs.
+template <int BN>
+__device__ __forceinline__ void hmm_xk_issue(float* r, const GmmP& p, int f0)
+{
+    if (f0 + BK > p.T) {
+        gmm_xk_issue<BN>(r, p, f0);
+        return;
+    }
+    constexpr int PT = 32 * BN / 256, FS = 256 / BN > 0 ? 256 / BN : 1;
+    const int t = threadIdx.x, ka = t % BN, col = aug_col(ka, p.D);
+    const bool kv = ka < 2 * p.D;
+    const float* const base = p.x + (int64_t)f0 * p.D;
+    const uint32_t toff = kv ? (uint32_t)((BN >= 256 ? 0 : t / BN) * p.D + col) : 0u;      // (a column of the fill: element 0)
+#pragma unroll
+    for (int i = 0; i < PT; ++i) r[i] = (base + (BN >= 256 ? i : FS * i) * p.D)[toff];
+}
+
+template <int BN> constexpr size_t hmm_accum_lds() { return sizeof(float) * (GM_B * GM_GST + 2 * TileShape<BN, false>::floats); }
+
+template <int BN>
+__global__ __launch_bounds__(256) void hmm_accum_kernel(GmmP p, const float* __restrict__ gamma)
+{
+    constexpr int TN = BN / 64, XPT = 32 * BN / 256, NS = GM_B / BK, GPT = GM_B * GM_B / 256, GPS = GPT / NS;
+    using XT = TileShape<BN, false>;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const G = smem;                                  // [128 frames][132]
+    float* const Xk = smem + GM_B * GM_GST;                 // two stages of [32][BN + 4]
+
+    const int total = p.tiles_k * p.n_ranges;               // (gmm_accum_kernel's order: a tile's ranges on one XCD)
+    const int w = xcd_tile_index((int)blockIdx.x, total);
+    const int ct = w / p.n_ranges, rg = w % p.n_ranges;
+    const int n0 = ct * GM_B;
+    const int b0 = rg * p.blocks_per_range, b1 = min(p.fblocks, b0 + p.blocks_per_range);
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wc0 = (wave >> 1) * 64, wx0 = (wave & 1) * (BN / 2);   // statistics tile: components x columns
+    const int col_l = lane & 31, rsub = 4 * (lane >> 5);
+    const int gcl = t & (GM_B - 1), grl = t >> 7;
+    const bool gcol = n0 + gcl < p.K;
+    const int gcc = min(n0 + gcl, p.K - 1);                 // (past K: a valid address, the value is dropped at the commit)
+    const uint32_t voff = (uint32_t)(grl * p.K + gcc);      // row t / 128 of a block; + 2 K per element
+
+    f32x16 st[2][TN];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) st[i][j][r] = 0.0f;
+
+    // Elements i0 .. i0 + GPS - 1 of this thread's share of the block at frame mb.  A block inside the table (uniform; all
+    // but the table's last): one per-thread 32-bit offset on a uniform pointer per row.  The last block: clamped addresses; validity is applied
+    // at the commit either way.
+    float rp[GPT], rx[XPT];
+    const auto g_fetch = [&](int mb, int i0) {
+        if (mb + GM_B <= p.T) {
+            const float* const base = gamma + (int64_t)mb * p.K;
+#pragma unroll
+            for (int i = 0; i < GPS; ++i) rp[i0 + i] = (base + 2 * (i0 + i) * p.K)[voff];
+        } else {
+#pragma unroll
+            for (int i = 0; i < GPS; ++i) {
+                const int64_t fr = (int64_t)mb + grl + 2 * (i0 + i);
+                rp[i0 + i] = gamma[fr < p.T ? fr * p.K + gcc : 0];
+            }
+        }
+    };
+    const auto frags = [&](const float* gs, const float* xs, int g, f32x4 (&fa)[2], f32x4 (&fx)[TN]) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) fa[i] = frag_read<GM_B, false>(gs, wc0 + 32 * i, g, lane);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) fx[j] = frag_read<BN, false>(xs, wx0 + 32 * j, g, lane);
+    };
+    hmm_xk_issue<BN>(rx, p, b0 * GM_B);
+#pragma unroll
+    for (int q = 0; q < NS; ++q) g_fetch(b0 * GM_B, q * GPS);
+    gmm_xk_commit<BN>(rx, Xk, p, b0 * GM_B);
+
+    for (int fb = b0; fb < b1; ++fb) {
+        const int m0 = fb * GM_B;
+        const bool nextb = fb + 1 < b1;
+#pragma unroll
+        for (int i = 0; i < GPT; ++i) {                     // (every wave is behind the barrier of the last block's last step)
+            const int rl = grl + 2 * i;
+            G[rl * GM_GST + gcl] = (gcol && m0 + rl < p.T) ? rp[i] : 0.0f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < NS; ++q) {
+            const float* const gs = G + q * BK * GM_GST;
+            const float* const xs = Xk + (q & 1) * XT::floats;
+            const bool more = q + 1 < NS || nextb;
+            const int fnext = m0 + (q + 1) * BK;            // (q = NS - 1: the next block's first step)
+            if (more) hmm_xk_issue<BN>(rx, p, fnext);
+            if (nextb) g_fetch(m0 + GM_B, q * GPS);          // (uniform)
+            // the fragments of k-group g + 1 are read before the MFMAs of group g are issued: with one wave per SIMD
+            // nothing else covers the LDS latency
+            f32x4 fa[2][2], fx[2][TN];
+            frags(gs, xs, 0, fa[0], fx[0]);
+#pragma unroll
+            for (int g = 0; g < BK / 8; ++g) {
+                if (g + 1 < BK / 8) frags(gs, xs, g + 1, fa[(g + 1) & 1], fx[(g + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < TN; ++j)
+                            st[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[g & 1][i][e], fx[g & 1][j][e], st[i][j], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (more) gmm_xk_commit<BN>(rx, Xk + ((q + 1) & 1) * XT::floats, p, fnext);
+            __syncthreads();
+        }
+    }
+
+    const int nc = 2 * p.D + 1;
+    float* const slab = p.slabs + ((int64_t)ct * p.n_ranges + rg) * GM_B * nc;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int kl = wc0 + 32 * i + (r & 3) + 8 * (r >> 2) + rsub, col = wx0 + 32 * j + col_l;
+                if (col < nc) slab[kl * nc + col] = st[i][j][r];
+            }
+}
+
+// One workgroup per component: its slabs in range order, in float64 (gmm_reduce_kernel's component blocks).
+__global__ __launch_bounds__(256) void hmm_sums_kernel(const float* __restrict__ slabs, int nc, int n_ranges,
+                                                        double* __restrict__ sums)
+{
+    gmm_sum_slabs(slabs, (int)blockIdx.x, nc, n_ranges, sums);
 }
 
 static int hmm_check_sizes(int64_t n_utt, int64_t K, int64_t D, const char* what)
@@ -330,35 +504,40 @@ extern "C" int64_t abn_hmm_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, i
     return w.per_wg * w.grid;
 }
 
-extern "C" int abn_hmm_forward_backward(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len,
-                                        int64_t n_utt, const float* shift, const float* A, const float* B, const float* c0,
-                                        const float* w, int64_t K, float rho, int mode, float* post, double* loglik,
-                                        double* stays, int32_t* n_good, void* ws, int64_t ws_bytes, void* stream)
+// Both forward-backward entries: `what` names the caller in the messages, stay_k != nullptr picks the SK kernels.
+static int hmm_fb_launch(const char* what, const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len,
+                         int64_t n_utt, const float* shift, const float* A, const float* B, const float* c0, const float* w,
+                         int64_t K, float rho, int mode, float* post, double* loglik, double* stays, int32_t* n_good,
+                         double* stay_k, void* ws, int64_t ws_bytes, void* stream)
 {
-    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "abn_hmm_forward_backward: T = %lld out of range", (long long)T);
-    const int rc = hmm_check_sizes(n_utt, K, D, "abn_hmm_forward_backward");
+    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "%s: T = %lld out of range", what, (long long)T);
+    const int rc = hmm_check_sizes(n_utt, K, D, what);
     if (rc != ABN_OK) return rc;
-    ABN_REQUIRE(x && off && len && shift && A && B && c0 && w && post && loglik && n_good,
-                "abn_hmm_forward_backward: null pointer");
-    ABN_REQUIRE(rho >= 0.0f && rho < 1.0f, "abn_hmm_forward_backward: rho = %g, 0 <= rho < 1 is needed", (double)rho);
-    ABN_REQUIRE(mode == 0 || mode == 1, "abn_hmm_forward_backward: mode = %d, 0 (smoothed) or 1 (filtered)", mode);
+    ABN_REQUIRE(x && off && len && shift && A && B && c0 && w && post && loglik && n_good, "%s: null pointer", what);
+    ABN_REQUIRE(rho >= 0.0f && rho < 1.0f, "%s: rho = %g, 0 <= rho < 1 is needed", what, (double)rho);
+    ABN_REQUIRE(mode == 0 || mode == 1, "%s: mode = %d, 0 (smoothed) or 1 (filtered)", what, mode);
     const HmmWs hw = hmm_ws(n_utt, 0, K);
     const int64_t per_wg = ws_bytes > 0 ? (ws_bytes / hw.grid) & ~255LL : 0;
     int64_t cap = (per_wg - hw.slab_bytes) / (int64_t)sizeof(float);
     if (!ws || cap < 1) {
-        set_error("abn_hmm_forward_backward: workspace of %lld bytes holds no frame (abn_hmm_ws_bytes)", (long long)ws_bytes);
+        set_error("%s: workspace of %lld bytes holds no frame (abn_hmm_ws_bytes)", what, (long long)ws_bytes);
         return ABN_E_WORKSPACE;
     }
-    ABN_REQUIRE(aligned16(ws), "abn_hmm_forward_backward: the workspace must be 16-byte aligned");
+    ABN_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", what);
     if (cap > HM_MAX_LEN) cap = HM_MAX_LEN;
     static bool attr_set[16] = {};
     if (first_use_on_device(attr_set)) {
         const auto opt_in = [](const void* k) { (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GM_TILE_BYTES); };
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<1>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<2>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<4>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<8>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<16>));
+        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<1, false>));
+        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<2, false>));
+        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<4, false>));
+        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<8, false>));
+        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<16, false>));
+        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<1, true>));
+        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<2, true>));
+        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<4, true>));
+        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<8, true>));
+        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<16, true>));
     }
     HmmP p;
     p.g.x = x; p.g.shift = shift; p.g.A = A; p.g.B = B; p.g.c = c0;
@@ -367,20 +546,109 @@ extern "C" int abn_hmm_forward_backward(const float* x, int64_t T, int64_t D, co
     p.g.tiles_k = (int)((K + GM_B - 1) / GM_B); p.g.fblocks = 0; p.g.n_ranges = 0; p.g.blocks_per_range = 0;
     p.w = w; p.off = off; p.len = len; p.n_utt = (int)n_utt;
     p.mode = mode; p.rho = rho;
-    p.post = post; p.loglik = loglik; p.stays = stays; p.n_good = n_good;
+    p.post = post; p.loglik = loglik; p.stays = stays; p.n_good = n_good; p.stay_k = stay_k;
     p.ws = static_cast<char*>(ws); p.per_wg = per_wg;
     p.ks = hw.ks; p.cap = (int)cap;
     const dim3 grid((unsigned)hw.grid);
     hipStream_t st = static_cast<hipStream_t>(stream);
     int nq = 1;
     while (nq * 256 < K) nq <<= 1;
-    switch (nq) {
-    case 1: hipLaunchKernelGGL(hmm_fb_kernel<1>, grid, dim3(256), GM_TILE_BYTES, st, p); break;
-    case 2: hipLaunchKernelGGL(hmm_fb_kernel<2>, grid, dim3(256), GM_TILE_BYTES, st, p); break;
-    case 4: hipLaunchKernelGGL(hmm_fb_kernel<4>, grid, dim3(256), GM_TILE_BYTES, st, p); break;
-    case 8: hipLaunchKernelGGL(hmm_fb_kernel<8>, grid, dim3(256), GM_TILE_BYTES, st, p); break;
-    default: hipLaunchKernelGGL(hmm_fb_kernel<16>, grid, dim3(256), GM_TILE_BYTES, st, p); break;
+    if (stay_k) {
+        switch (nq) {
+        case 1: hipLaunchKernelGGL((hmm_fb_kernel<1, true>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+        case 2: hipLaunchKernelGGL((hmm_fb_kernel<2, true>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+        case 4: hipLaunchKernelGGL((hmm_fb_kernel<4, true>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+        case 8: hipLaunchKernelGGL((hmm_fb_kernel<8, true>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+        default: hipLaunchKernelGGL((hmm_fb_kernel<16, true>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+        }
+    } else {
+        switch (nq) {
+        case 1: hipLaunchKernelGGL((hmm_fb_kernel<1, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+        case 2: hipLaunchKernelGGL((hmm_fb_kernel<2, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+        case 4: hipLaunchKernelGGL((hmm_fb_kernel<4, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+        case 8: hipLaunchKernelGGL((hmm_fb_kernel<8, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+        default: hipLaunchKernelGGL((hmm_fb_kernel<16, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+        }
     }
-    ABN_CHECK_LAUNCH("abn_hmm_forward_backward");
+    ABN_CHECK_LAUNCH(what);
+    return ABN_OK;
+}
+
+extern "C" int abn_hmm_forward_backward(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len,
+                                        int64_t n_utt, const float* shift, const float* A, const float* B, const float* c0,
+                                        const float* w, int64_t K, float rho, int mode, float* post, double* loglik,
+                                        double* stays, int32_t* n_good, void* ws, int64_t ws_bytes, void* stream)
+{
+    return hmm_fb_launch("abn_hmm_forward_backward", x, T, D, off, len, n_utt, shift, A, B, c0, w, K, rho, mode, post, loglik,
+                         stays, n_good, nullptr, ws, ws_bytes, stream);
+}
+
+extern "C" int abn_hmm_forward_backward_stats(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len,
+                                              int64_t n_utt, const float* shift, const float* A, const float* B,
+                                              const float* c0, const float* w, int64_t K, float rho, int mode, float* post,
+                                              double* loglik, double* stays, int32_t* n_good, double* stay_k, void* ws,
+                                              int64_t ws_bytes, void* stream)
+{
+    ABN_REQUIRE(stay_k, "abn_hmm_forward_backward_stats: null pointer (stay_k)");
+    return hmm_fb_launch("abn_hmm_forward_backward_stats", x, T, D, off, len, n_utt, shift, A, B, c0, w, K, rho, mode, post,
+                         loglik, stays, n_good, stay_k, ws, ws_bytes, stream);
+}
+
+static int hmm_acc_check(int64_t T, int64_t K, int64_t D, int n_ranges, const char* what)
+{
+    ABN_REQUIRE(T >= 1 && K >= 1 && D >= 1, "%s: T = %lld, K = %lld, D = %lld out of range", what, (long long)T, (long long)K,
+                (long long)D);
+    ABN_REQUIRE(n_ranges >= 0 && n_ranges <= GM_MAX_RANGES, "%s: n_ranges = %d, supported 0 (by the grid) .. %d", what, n_ranges,
+                GM_MAX_RANGES);
+    if (D > GM_MAX_D || K > GM_MAX_K || T >= (1LL << 31) - GM_B) {
+        set_error("%s: T = %lld, D = %lld, K = %lld, supported T < 2^31 - %d, D <= %d (abn_gmm_max_d), K <= %d (abn_hmm_max_k)",
+                  what, (long long)T, (long long)D, (long long)K, GM_B, GM_MAX_D, GM_MAX_K);
+        return ABN_E_UNSUPPORTED;
+    }
+    return ABN_OK;
+}
+
+extern "C" int64_t abn_hmm_accumulate_ws_bytes(int64_t T, int64_t K, int64_t D, int n_ranges)
+{
+    if (hmm_acc_check(T, K, D, n_ranges, "abn_hmm_accumulate_ws_bytes") != ABN_OK) return -1;
+    return gmm_slab_bytes(gmm_grid(T, K, n_ranges), D, n_ranges);
+}
+
+extern "C" int abn_hmm_accumulate(const float* x, int64_t T, int64_t D, const float* shift, const float* post, int64_t K,
+                                  int n_ranges, double* sums, void* ws, int64_t ws_bytes, void* stream)
+{
+    const int rc = hmm_acc_check(T, K, D, n_ranges, "abn_hmm_accumulate");
+    if (rc != ABN_OK) return rc;
+    ABN_REQUIRE(x && shift && post && sums, "abn_hmm_accumulate: null pointer");
+    const GmmGrid g = gmm_grid(T, K, n_ranges);
+    const int64_t need = gmm_slab_bytes(g, D, n_ranges);
+    if (!ws || ws_bytes < need) {
+        set_error("abn_hmm_accumulate: workspace of %lld bytes, %lld needed (abn_hmm_accumulate_ws_bytes)", (long long)ws_bytes,
+                  (long long)need);
+        return ABN_E_WORKSPACE;
+    }
+    static bool attr_set[16] = {};
+    if (first_use_on_device(attr_set)) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hmm_accum_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)hmm_accum_lds<64>());
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hmm_accum_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)hmm_accum_lds<128>());
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hmm_accum_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)hmm_accum_lds<256>());
+    }
+    GmmP p;
+    p.x = x; p.shift = shift; p.A = nullptr; p.B = nullptr; p.c = nullptr;
+    p.T = (int)T; p.K = (int)K; p.D = (int)D;
+    p.lse = nullptr; p.post = nullptr; p.slabs = static_cast<float*>(ws);
+    p.tiles_k = g.tiles_k; p.fblocks = g.fblocks; p.n_ranges = g.n_ranges; p.blocks_per_range = g.blocks_per_range;
+    const dim3 grid((unsigned)(g.tiles_k * g.n_ranges));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nc = 2 * (int)D + 1;
+    if (nc <= 64) hipLaunchKernelGGL(hmm_accum_kernel<64>, grid, dim3(256), hmm_accum_lds<64>(), st, p, post);
+    else if (nc <= 128) hipLaunchKernelGGL(hmm_accum_kernel<128>, grid, dim3(256), hmm_accum_lds<128>(), st, p, post);
+    else hipLaunchKernelGGL(hmm_accum_kernel<256>, grid, dim3(256), hmm_accum_lds<256>(), st, p, post);
+    ABN_CHECK_LAUNCH("abn_hmm_accumulate");
+    hipLaunchKernelGGL(hmm_sums_kernel, dim3((unsigned)K), dim3(256), 0, st, static_cast<const float*>(ws), nc, g.n_ranges, sums);
+    ABN_CHECK_LAUNCH("abn_hmm_accumulate (sum)");
     return ABN_OK;
 }

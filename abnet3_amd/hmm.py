@@ -1,14 +1,16 @@
 """Sticky-HMM smoothing of Gaussian posteriorgrams on the MI355X: forward-backward over a fitted mixture's components.
 
     python -m abnet3_amd.hmm fit-stay GMM.npz FEATURES MODEL.npz [--stay P] [--n-iter N] [--tol T]
+    python -m abnet3_amd.hmm fit GMM.npz FEATURES MODEL.npz [--stay P] [--n-iter N] [--tol T] [--params mvws]
     python -m abnet3_amd.hmm transform MODEL.npz FEATURES OUT [--mode smooth|filter]
 
 ``GmmPosteriorgram`` treats every frame on its own, so its posteriors flicker.  An HMM over the mixture's components
 with a single "stay" probability is the smallest acoustic-unit model that has a likelihood: its forward-backward pass
 gives smoothed [rows, K] posteriors for the KL routes (``ABXEvaluator(distance='kl')``, ``QbeSearcher(distance='kl')``),
-a sequence likelihood, and the expected number of stays, from which the stay probability is fitted by EM.  The
+a sequence likelihood, and the expected number of stays, from which the stay probability is fitted by EM
+(``fit_stay``); ``fit`` re-estimates the means, variances and weights under the HMM as well (Baum-Welch).  The
 reference has no such model; the definition is the build's own ("parity unpinned") and
-tests/hmm_np.py restates it in numpy.
+tests/hmm_np.py and tests/hmm_bw_np.py restate it in numpy.
 
 The definition this module computes, over a fitted mixture (weights w, means, variances, shift of gmm.py):
 
@@ -33,14 +35,34 @@ The definition this module computes, over a fitted mixture (weights w, means, va
   e <= 2^100, and nothing in the chain underflows to zero or overflows.
 * EM for rho, the mixture fixed: rho_new = sum_u stays_u / sum_u max(n_good_u - 1, 0), clipped to [0, 0.9999]; the
   log-likelihood does not decrease from one iteration to the next.
+* Baum-Welch (``fit``).  The model as a generative story: z_first ~ w; at every later good frame the unit stays with
+  probability rho, otherwise it is redrawn from w; emissions are diagonal Gaussians.  The complete data hold the
+  switch variable, so the E-step needs, per component k, over all good frames and with gamma the smoothed posteriors,
+    N[k] = sum_t gamma_t(k),   S1[k][d] = sum_t gamma_t(k) xc,   S2[k][d] = sum_t gamma_t(k) xc^2
+  (xc = fl32(x - shift) and xc^2 taken in fp32, as gmm.py does; the sums on the fp32 matrix cores, then float64), and
+    stay_k[k] = sum over the transitions (p -> t) of rho ahat_p[k] e_t[k]
+  with the e of the backward sweep above: the per-component terms of `stays`.  The M-step, host float64:
+    means, variances:  m = S1 / N,  v = max(S2 / N - m^2, var_floor gv[d]); a component with N < min_count keeps its mean
+      and variance (gmm.py's rule, with the mixture's var_floor, min_count and gv_).  With the means held fixed the
+      variance is the second moment about the mean in force, S2 / N - 2 m S1 / N + m^2, floored the same way.
+    weights:  draws[k] = max(N[k] - stay_k[k], 0), the expected number of times k was drawn from w, as a first frame or
+      as a redraw (one that lands on the same unit counts);  w = draws / sum draws.  A weight below WEIGHT_MIN = 2^-80
+      is set to exactly 0 and the rest are renormalised, so the range condition above cannot fail in the middle of a
+      fit; such a component is retired for good (its gamma is 0 from then on), ``n_retired_`` counts the weights of 0.
+    stay:  rho = sum_k stay_k / sum_u max(n_good_u - 1, 0), clipped to [0, 0.9999], as ``fit_stay`` does.
+  Any subset of the four may be held fixed (params): each update maximises the expected complete-data log-likelihood
+  in its own parameters, so the likelihood still does not decrease (a generalised EM).
 
-On the device this is one launch for the whole corpus (abn_hmm_forward_backward, csrc/hmm.hip): persistent workgroups,
-one utterance at a time, one sum reduction per frame and sweep.  The output table holds ahat between the sweeps, so
-there is no T x K array beyond it.  Limits: K <= abn_hmm_max_k(), D <= abn_gmm_max_d(), an utterance of at most
-abn_hmm_max_len() frames; utterances must not overlap.  Left out: re-estimating the emissions under the HMM, full
-transition matrices, durations, a max-product path.
+On the device the recursion is one launch for the whole corpus (abn_hmm_forward_backward, csrc/hmm.hip): persistent
+workgroups, one utterance at a time, one sum reduction per frame and sweep.  The output table holds ahat between the
+sweeps, so there is no T x K array beyond it.  A Baum-Welch iteration is that launch with the per-component stays
+(abn_hmm_forward_backward_stats) and abn_hmm_accumulate, which reads the gamma table once as the A operand of
+abn_gmm_accumulate's statistics GEMM.  Limits: K <= abn_hmm_max_k(), D <= abn_gmm_max_d(), an utterance of at most
+abn_hmm_max_len() frames; utterances must not overlap.  Left out: full transition matrices, durations, a max-product
+path.
 """
 import argparse
+import copy
 import sys
 
 import numpy as np
@@ -52,6 +74,8 @@ from . import gmm as _gmm
 MODES = {'smooth': 0, 'filter': 1}
 STAY_MAX = 0.9999
 TINY = 2.0 ** -100
+WEIGHT_MIN = 2.0 ** -80
+PARAMS = 'mvws'
 
 
 def max_len():
@@ -87,11 +111,20 @@ def check_stay(who, stay, w32=None):
     return float(r)
 
 
-def forward_backward(table, off, lens, shift, A, B, c0, w, stay, mode='smooth', out=None, want_stays=True):
+def check_params(who, params):
+    """The letters of `params` as a set, or ValueError: a non-empty string over 'mvws' without a repeat."""
+    if not isinstance(params, str) or not params or len(set(params)) != len(params) or not set(params) <= set(PARAMS):
+        raise ValueError('%s: params = %r, a non-empty choice of the letters of %r is needed '
+                         '(m means, v variances, w weights, s stay)' % (who, params, PARAMS))
+    return set(params)
+
+
+def forward_backward(table, off, lens, shift, A, B, c0, w, stay, mode='smooth', out=None, want_stays=True, want_stay_k=False):
     """(post [T, K] fp32, loglik [n_utt] float64, stays [n_utt] float64 or None, n_good [n_utt] int32), device tensors,
     of the recursion the module docstring defines (abn_hmm_forward_backward, one launch).  off, lens: the utterances'
     first rows and lengths (host sequences or device tensors); they must not overlap.  Rows outside every utterance
-    keep what `out` held (0 in a fresh table)."""
+    keep what `out` held (0 in a fresh table).  want_stay_k: a fifth element, stay_k [n_utt, K] float64, the
+    per-component terms of stays (abn_hmm_forward_backward_stats; the four others are the same bits)."""
     lib = _lib.load()
     if mode not in MODES:
         raise ValueError('hmm.forward_backward: mode = %r, one of %s' % (mode, sorted(MODES)))
@@ -130,6 +163,7 @@ def forward_backward(table, off, lens, shift, A, B, c0, w, stay, mode='smooth', 
     ll = torch.zeros(n_utt, dtype=torch.float64, device=table.device)
     st = torch.zeros(n_utt, dtype=torch.float64, device=table.device) if want_stays else None
     ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
+    sk = torch.zeros((n_utt, K), dtype=torch.float64, device=table.device) if want_stay_k else None
     if T and n_utt and longest:
         need = lib.abn_hmm_ws_bytes(n_utt, longest, K, D)
         if need < 0:
@@ -137,11 +171,92 @@ def forward_backward(table, off, lens, shift, A, B, c0, w, stay, mode='smooth', 
         ws = torch.empty(int(need), dtype=torch.uint8, device=table.device)
         off_d = torch.from_numpy(off_h).to(table.device)
         len_d = torch.from_numpy(len_h.astype(np.int32)).to(table.device)
-        _lib.check(lib.abn_hmm_forward_backward(_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift),
-                                                _lib.ptr(A), _lib.ptr(B), _lib.ptr(c0), _lib.ptr(w), K, rho, MODES[mode],
-                                                _lib.ptr(out), _lib.ptr(ll), _lib.ptr(st), _lib.ptr(ng), _lib.ptr(ws),
-                                                ws.numel(), _lib.stream()), 'abn_hmm_forward_backward')
-    return out, ll, st, ng
+        head = [_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B),
+                _lib.ptr(c0), _lib.ptr(w), K, rho, MODES[mode], _lib.ptr(out), _lib.ptr(ll), _lib.ptr(st), _lib.ptr(ng)]
+        tail = [_lib.ptr(ws), ws.numel(), _lib.stream()]
+        if want_stay_k:
+            _lib.check(lib.abn_hmm_forward_backward_stats(*(head + [_lib.ptr(sk)] + tail)), 'abn_hmm_forward_backward_stats')
+        else:
+            _lib.check(lib.abn_hmm_forward_backward(*(head + tail)), 'abn_hmm_forward_backward')
+    return (out, ll, st, ng, sk) if want_stay_k else (out, ll, st, ng)
+
+
+def accumulate(table, post, shift, n_ranges=0):
+    """sums [K, 2D + 1] float64 = [S1 | S2 | N] on the device: the sum over the rows of post[t, k] [xc | xc^2 | 1]
+    (abn_hmm_accumulate: `post` is read once; fp32 slabs per frame range, then float64 in range order; the same bits for
+    the same n_ranges).  A non-finite entry of the table contributes 0; forward_backward leaves zero rows at BAD frames."""
+    lib = _lib.load()
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
+        raise ValueError('hmm.accumulate: a [T, D] float32 table is needed')
+    T, D = table.shape
+    if not isinstance(post, torch.Tensor) or post.dim() != 2 or post.dtype != torch.float32 or post.shape[0] != T or \
+            not post.is_contiguous():
+        raise ValueError('hmm.accumulate: post must be a contiguous [T, K] float32 tensor with the table\'s %d rows' % T)
+    K = post.shape[1]
+    if not isinstance(shift, torch.Tensor) or shift.shape != (D,) or shift.dtype != torch.float32:
+        raise ValueError('hmm.accumulate: shift [D] float32 is needed')
+    if K < 1 or K > max_k():
+        raise ValueError('hmm.accumulate: K = %d, the kernel takes 1 .. %d (abn_hmm_max_k)' % (K, max_k()))
+    if not 0 <= int(n_ranges) <= 256:
+        raise ValueError('hmm.accumulate: n_ranges = %r, 0 (chosen from the grid) .. 256' % (n_ranges,))
+    table = _gmm._check_table('hmm.accumulate', table)
+    _lib.require_device(post, shift)
+    sums = torch.zeros((K, 2 * D + 1), dtype=torch.float64, device=table.device)
+    if T:
+        need = lib.abn_hmm_accumulate_ws_bytes(T, K, D, int(n_ranges))
+        if need < 0:
+            raise ValueError('hmm.accumulate: %s' % lib.abn_last_error().decode('utf-8', 'replace'))
+        ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=table.device)
+        _lib.check(lib.abn_hmm_accumulate(_lib.ptr(table), T, D, _lib.ptr(shift), _lib.ptr(post), K, int(n_ranges),
+                                          _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.stream()), 'abn_hmm_accumulate')
+    return sums
+
+
+def baum_welch_update(sums, stay_k_total, n_trans, means, variances, gv, var_floor=0.01, min_count=1.0, params=PARAMS,
+                      weights=None, stay=None, stays_total=None):
+    """The M-step of the module docstring on the host, float64: (weights, means, variances, stay, n_retired).
+    sums [K, 2D + 1] = [S1 | S2 | N] and stay_k_total [K] are the corpus totals, n_trans = sum_u max(n_good_u - 1, 0);
+    means are centred (mean - shift), as the statistics are.  A parameter whose letter is not in `params` comes back
+    as given: `weights` and `stay` are the current ones (needed when held fixed).  stays_total: the kernel's own sum of
+    the stays, used for the stay instead of sum_k stay_k when given (``fit_stay``'s number).  The returned stay is a
+    float32 value that passes check_stay with the returned weights, or ValueError."""
+    who = 'hmm.baum_welch_update'
+    p = check_params(who, params)
+    sums = np.asarray(sums, dtype=np.float64)
+    m, v = np.array(means, dtype=np.float64), np.array(variances, dtype=np.float64)
+    K, D = m.shape
+    sk = np.asarray(stay_k_total, dtype=np.float64)
+    if sums.shape != (K, 2 * D + 1) or v.shape != (K, D) or sk.shape != (K,) or np.shape(gv) != (D,):
+        raise ValueError('%s: sums [K, 2D + 1], stay_k_total [K], means and variances [K, D], gv [D] are needed' % who)
+    N, S1, S2 = sums[:, 2 * D], sums[:, :D], sums[:, D:2 * D]
+    keep = (N < min_count)[:, None]                      # a starved component keeps its mean and variance
+    floor = float(var_floor) * np.asarray(gv, dtype=np.float64)[None, :]
+    with np.errstate(all='ignore'):
+        m1 = S1 / N[:, None]
+        if 'v' in p:
+            raw = S2 / N[:, None] - m1 * m1 if 'm' in p else S2 / N[:, None] - 2.0 * m * m1 + m * m
+            v = np.where(keep, v, np.maximum(raw, floor))
+        if 'm' in p:
+            m = np.where(keep, m, m1)
+    if 'w' in p:
+        draws = np.maximum(N - sk, 0.0)
+        if not np.isfinite(draws).all() or not draws.sum() > 0:
+            raise ValueError('%s: the expected draws are not finite or all 0' % who)
+        w = draws / draws.sum()
+        w[w < WEIGHT_MIN] = 0.0
+        w = w / w.sum()
+    else:
+        if weights is None:
+            raise ValueError('%s: the current weights are needed when params has no w' % who)
+        w = np.array(weights, dtype=np.float64)
+    if 's' in p:
+        if n_trans < 1:
+            raise ValueError('%s: no utterance has two good frames: the stay probability cannot be estimated' % who)
+        num = float(sk.sum()) if stays_total is None else float(stays_total)
+        stay = min(max(num / float(n_trans), 0.0), STAY_MAX)
+    elif stay is None:
+        raise ValueError('%s: the current stay is needed when params has no s' % who)
+    return w, m, v, check_stay(who, stay, w.astype(np.float32)), int((w == 0).sum())
 
 
 def stay_update(stays, n_good):
@@ -165,7 +280,7 @@ class StickyHmmPosteriorgram(object):
         self.gmm = gmm
         self.stay_ = check_stay('StickyHmmPosteriorgram', stay, gmm.weights_.astype(np.float32))
         self.log_likelihoods = []
-        self.n_bad_ = 0
+        self.n_bad_ = self.n_retired_ = self.n_starved_ = 0
         self._tables = None
 
     def whoami(self):
@@ -248,6 +363,58 @@ class StickyHmmPosteriorgram(object):
         self.stay_ = rho
         return self
 
+    def fit(self, corpus, n_iter=10, tol=1e-4, params=PARAMS, n_ranges=0):
+        """Baum-Welch from the current mixture and ``stay_``: any subset of the `m`eans, `v`ariances, `w`eights and the
+        `s`tay (params) by the M-step of the module docstring.  The mixture is COPIED first: the GmmPosteriorgram this
+        object was made from is untouched, ``self.gmm`` is the trained copy.  Iteration i runs forward-backward with the
+        per-component stays and the statistics GEMM under the current parameters -- ``log_likelihoods[i]`` is their mean
+        log-likelihood per good frame --, reads the sums, the summed stays, the likelihood and the counts back once, and
+        applies the update; the stopping rule is ``fit_stay``'s (the parameters are those of the last likelihood, or the
+        update of the n_iter-th).  One T x K scratch table is allocated."""
+        p = check_params('StickyHmmPosteriorgram.fit', params)                    # (host checks first)
+        table, _, lens = self._utterances(corpus)
+        g = copy.copy(self.gmm)
+        g.weights_, g.means_, g.variances_ = (np.array(a, dtype=np.float64) for a in (g.weights_, g.means_, g.variances_))
+        g.log_likelihoods, g._tables = list(g.log_likelihoods), None
+        K, D = g.means_.shape
+        shift64 = g.shift_.astype(np.float64)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(table.device)
+        shift = dev(g.shift_)
+        scratch = torch.zeros((table.shape[0], K), dtype=torch.float32, device=table.device)
+        off = np.cumsum(lens) - lens
+        w, m, v, rho = g.weights_, g.means_ - shift64, g.variances_, self.stay_
+        need_sums = bool(p & set('mvw'))
+        self.log_likelihoods = []
+        for it in range(int(n_iter)):
+            A, B, _ = _gmm.score_tables(w, m, v)
+            _, ll, st, ng, sk = forward_backward(table, off, lens, shift, dev(A), dev(B), dev(emission_offsets(m, v)), dev(w), rho,
+                                                 'smooth', out=scratch, want_stay_k=True)
+            good = ng.clamp(min=0).to(torch.float64)
+            head = torch.stack([ll.sum(), good.sum(), (good - 1.0).clamp(min=0.0).sum(), st.sum()])
+            sums = accumulate(table, scratch, shift, n_ranges) if need_sums else torch.zeros((K, 2 * D + 1), dtype=torch.float64,
+                                                                                            device=table.device)
+            back = torch.cat([head, sk.sum(dim=0), sums.flatten()]).cpu().numpy()      # the iteration's one read-back
+            ll_sum, n, ntr, stays = back[:4].tolist()
+            if ntr < 1:
+                raise ValueError('StickyHmmPosteriorgram.fit: no utterance has two good frames')
+            self.log_likelihoods.append(ll_sum / n)
+            self.n_bad_ = int(lens.sum() - n)
+            if it > 0 and self.log_likelihoods[-1] - self.log_likelihoods[-2] < tol:
+                break
+            sums_h = back[4 + K:].reshape(K, 2 * D + 1)
+            if need_sums:
+                self.n_starved_ = int((sums_h[:, 2 * D] < g.min_count).sum())
+            w, m, v, rho, self.n_retired_ = baum_welch_update(sums_h, back[4:4 + K], ntr, m, v, g.gv_, g.var_floor, g.min_count,
+                                                              params, weights=w, stay=rho, stays_total=stays)
+        if 'w' in p:
+            g.weights_ = w
+        if 'm' in p:
+            g.means_ = m + shift64
+        if 'v' in p:
+            g.variances_ = v
+        self.gmm, self.stay_, self._tables = g, rho, None
+        return self
+
     # -- files ----------------------------------------------------------------------------------------------------
     def save(self, path):
         g = self.gmm
@@ -279,13 +446,29 @@ def main(argv=None):
     f.add_argument('--stay', type=float, default=0.9, help='where EM starts')
     f.add_argument('--n-iter', type=int, default=10)
     f.add_argument('--tol', type=float, default=1e-4)
+    b = sub.add_parser('fit', help='Baum-Welch from a saved mixture on FEATURES: means, variances, weights and the stay')
+    b.add_argument('gmm', help='a GmmPosteriorgram .npz (python -m abnet3_amd.gmm fit)')
+    b.add_argument('features', help='h5features file, or an .npz of name -> [T, D]')
+    b.add_argument('model', help='the .npz to write')
+    b.add_argument('--stay', type=float, default=0.9, help='where EM starts')
+    b.add_argument('--n-iter', type=int, default=10)
+    b.add_argument('--tol', type=float, default=1e-4)
+    b.add_argument('--params', default=PARAMS, help='the letters of what is re-estimated: m means, v variances, w weights, s stay')
     t = sub.add_parser('transform', help='smoothed posteriorgrams of FEATURES under a saved model')
     t.add_argument('model')
     t.add_argument('features', help='h5features file, or an .npz of name -> [T, D]')
     t.add_argument('out', help='.npz of name -> [T, K], or an h5features file (when the input has times)')
     t.add_argument('--mode', choices=sorted(MODES), default='smooth')
     args = ap.parse_args(argv)
+    if args.cmd == 'fit':
+        check_params('python -m abnet3_amd.hmm fit', args.params)
     feats, times = _gmm._read_features(args.features)
+    if args.cmd == 'fit':
+        h = StickyHmmPosteriorgram(_gmm.GmmPosteriorgram.load(args.gmm), args.stay).fit(feats, args.n_iter, args.tol, args.params)
+        h.save(args.model)
+        print('stay %.6f after %d iterations (params %s), mean log-likelihood %.6f, %d BAD frames, %d starved, %d retired'
+              % (h.stay_, len(h.log_likelihoods), args.params, h.log_likelihoods[-1], h.n_bad_, h.n_starved_, h.n_retired_))
+        return 0
     if args.cmd == 'fit-stay':
         h = StickyHmmPosteriorgram(_gmm.GmmPosteriorgram.load(args.gmm), args.stay).fit_stay(feats, args.n_iter, args.tol)
         h.save(args.model)

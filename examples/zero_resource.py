@@ -5,7 +5,7 @@ Siamese training -> embedding -> ABX.  The corpus' word labels are used twice on
 mined pairs, and the ABX item file ("phones" = word types).
 
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
-                                     [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--no-network] [--terms] [--terms-theta T]
+                                     [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--hmm-fit N] [--no-network] [--terms] [--terms-theta T]
                                      [--prefilter] [--alignment FILE]
                                      [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P]
                                      [--eskmeans] [--eskmeans-clusters 24] [--samediff]
@@ -22,6 +22,8 @@ searched in every utterance by subsequence DTW, and the mean average precision o
 under the KL frame distance -- ABX, and with --qbe the search.  No network is trained on this route; --no-network stops
 after it, otherwise its figures are printed again beside the embeddings'.  --hmm-stay P (or "fit": EM on the stay
 probability) smooths the posteriorgrams with the sticky HMM of abnet3_amd/hmm.py and prints ABX (kl) of both.
+--hmm-fit N trains that HMM by N iterations of Baum-Welch from the mixture (means, variances, weights and the stay)
+and prints ABX (kl) of raw, smoothed and Baum-Welch-trained posteriorgrams side by side.
 --terms replaces the pair miner by term discovery (abnet3_amd/terms.py): local-alignment DTW of every utterance against
 every other -- over the filterbanks, or with --gmm over the mixture's posteriorgrams under the KL distance -- clustered
 into a .classes file, from which SamplerClusterSiamese draws the train and dev pairs: the reference's canonical route,
@@ -180,9 +182,10 @@ def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frame
     return dl
 
 
-def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=None):
+def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=None, hmm_fit=0):
     """features -> GmmPosteriorgram.fit -> transform -> ABX (kl), and the search: the line main() prints.  hmm_stay (a
-    number, or 'fit'): the sticky-HMM smoothed posteriorgrams beside the raw ones; they are the ones returned."""
+    number, or 'fit'): the sticky-HMM smoothed posteriorgrams beside the raw ones; they are the ones returned.  hmm_fit
+    (iterations): the posteriorgrams of the Baum-Welch-trained HMM beside both; then those are returned."""
     names = list(fb)
     keep, items = word_items(tokens)
     corpus = DeviceCorpus({k: np.asarray(fb[k], dtype=np.float32) for k in names}, times)
@@ -192,6 +195,8 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
     line = ('ABX error on GMM posteriorgrams (K = %d, %d EM iterations, log-likelihood %.3f, %d starved): kl %.2f %% '
             '(%d triplets)' % (n_components, len(g.log_likelihoods), g.log_likelihoods[-1], g.n_starved_, r.error, r.n_triplets))
     print(line)
+    if hmm_fit and hmm_stay is None:
+        hmm_stay = 0.9
     if hmm_stay is not None:
         h = StickyHmmPosteriorgram(g, 0.9 if hmm_stay == 'fit' else float(hmm_stay))
         if hmm_stay == 'fit':
@@ -203,8 +208,18 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
                                                                    raw_ll, rs.error, r.error, rs.n_triplets))
         print(more)
         line += '\n' + more
+        if hmm_fit:
+            t = StickyHmmPosteriorgram(g, h.stay_).fit(corpus, n_iter=int(hmm_fit), tol=-np.inf)
+            post = t.transform(corpus)
+            rt = ABXEvaluator(items, post, distance='kl').run('within')
+            more = ('ABX error on Baum-Welch-trained posteriorgrams (%d iterations, stay %.4f, log-likelihood per frame %.3f -> %.3f, '
+                    '%d starved, %d retired): kl %.2f %% trained, %.2f %% smoothed, %.2f %% raw (%d triplets)'
+                    % (len(t.log_likelihoods), t.stay_, t.log_likelihoods[0], t.score(corpus), t.n_starved_, t.n_retired_, rt.error,
+                       rs.error, r.error, rt.n_triplets))
+            print(more)
+            line += '\n' + more
     if qbe:
-        qbe_search(post, keep, names, 'GMM posteriorgrams' + (' (smoothed)' if hmm_stay is not None else ''), 'kl')
+        qbe_search(post, keep, names, 'GMM posteriorgrams' + (' (Baum-Welch-trained)' if hmm_fit else ' (smoothed)' if hmm_stay is not None else ''), 'kl')
     return (line, post) if want_post else line
 
 
@@ -266,6 +281,9 @@ def main():
     ap.add_argument('--hmm-stay', default=None, metavar='P|fit',
                     help='with --gmm: sticky-HMM smoothing of the posteriorgrams (abnet3_amd/hmm.py) with stay probability P, or '
                          'fitted by EM; ABX (kl) of raw and smoothed side by side')
+    ap.add_argument('--hmm-fit', type=int, default=0, metavar='N',
+                    help='with --gmm: N iterations of Baum-Welch on the sticky HMM (from --hmm-stay, default 0.9); ABX (kl) of raw, '
+                         'smoothed and trained posteriorgrams')
     ap.add_argument('--no-network', action='store_true', help='with --gmm: stop after the mixture, train nothing')
     ap.add_argument('--terms', action='store_true', help='pairs from term discovery: clusters -> SamplerClusterSiamese')
     ap.add_argument('--terms-theta', type=float, default=None, help='default: a low quantile of random frame distances (untuned)')
@@ -283,6 +301,8 @@ def main():
         ap.error('--eskmeans takes its landmarks from --kmeans --kmeans-penalty P')
     if args.hmm_stay is not None and not args.gmm:
         ap.error('--hmm-stay smooths the posteriorgrams of --gmm')
+    if args.hmm_fit and not args.gmm:
+        ap.error('--hmm-fit trains the HMM over the mixture of --gmm')
     esk_k = args.eskmeans_clusters if args.eskmeans else None
     rng = np.random.default_rng(0)
     random.seed(0)
@@ -296,7 +316,7 @@ def main():
 
     gmm_line = post = None
     if args.gmm:
-        gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True, hmm_stay=args.hmm_stay)
+        gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True, hmm_stay=args.hmm_stay, hmm_fit=args.hmm_fit)
     if args.no_network:
         if not (args.gmm or args.kmeans):
             ap.error('--no-network leaves nothing to do without --gmm or --kmeans')

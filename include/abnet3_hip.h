@@ -1054,6 +1054,30 @@ int abn_hmm_forward_backward(const float* x, int64_t T, int64_t D, const int64_t
                              int64_t K, float rho, int mode, float* post, double* loglik, double* stays,
                              int32_t* n_good, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- Baum-Welch statistics of the sticky HMM (added within ABI 20) ----------------------------------------------------
+ * abn_hmm_forward_backward_stats: abn_hmm_forward_backward with one more output.  post, loglik, stays and n_good are the
+ * same bits for the same inputs; stay_k [n_utt][K] float64 holds the per-component terms of stays,
+ *   stay_k[u][k] = sum over the transitions (p -> t) of utterance u of rho ahat_p[k] e_t[k]
+ * (fp32 sums over a block of 128 frames, float64 across the blocks, in one fixed order: per utterance, independent of the
+ * grid and of the other utterances, no atomics).  Mode 1, an utterance with fewer than two good frames and a component of
+ * weight 0 give zeros; a refused utterance a row of NaN.  stay_k must not be null; everything else as above.
+ * abn_hmm_accumulate: sums [K][2 D + 1] float64 = [S1 | S2 | N], sum over the rows t of post[t][k] [xc | xc^2 | 1] with
+ * abn_gmm_accumulate's fp32 xc = x - shift and xc^2 -- the second GEMM of that kernel on the fp32 matrix cores, its A
+ * operand read from post [T][K] (fp32, once: T K 4 bytes) instead of recomputed.  A non-finite x entry contributes 0
+ * (never 0 x NaN); the caller's table has zero rows at BAD frames (abn_hmm_forward_backward writes them).  One fp32 slab
+ * [128][2 D + 1] per (128-component tile, frame range) in ws, then summed in range order in float64: two launches, no
+ * atomics, bit-reproducible for a given n_ranges (0: chosen from the grid).  ws: abn_hmm_accumulate_ws_bytes (-1 for
+ * refused sizes).  Null pointers, sizes < 1, n_ranges outside 0 .. 256: ABN_E_ARG; K > abn_hmm_max_k(),
+ * D > abn_gmm_max_d(), T >= 2^31 - 128: ABN_E_UNSUPPORTED; a short workspace: ABN_E_WORKSPACE -- all before any launch. */
+int abn_hmm_forward_backward_stats(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len,
+                                   int64_t n_utt, const float* shift, const float* A, const float* B, const float* c0,
+                                   const float* w, int64_t K, float rho, int mode, float* post, double* loglik,
+                                   double* stays, int32_t* n_good, double* stay_k, void* ws, int64_t ws_bytes,
+                                   void* stream);
+int64_t abn_hmm_accumulate_ws_bytes(int64_t T, int64_t K, int64_t D, int n_ranges);
+int abn_hmm_accumulate(const float* x, int64_t T, int64_t D, const float* shift, const float* post, int64_t K,
+                       int n_ranges, double* sums, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- embedded segmental k-means (added within ABI 20) ----------------------------------------------------------------
  * Full-coverage word segmentation (abnet3_amd/eskmeans.py states the definitions).  Landmarks: lm [n_lm] int64 row
  * indices into table [T][D]; utterance u owns lm[lm_off[u] .. lm_off[u + 1]) (lm_off [n_utt + 1] int64), at least two
