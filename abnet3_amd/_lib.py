@@ -155,6 +155,9 @@ SYMBOLS = {
                                                  _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'abn_hmm_accumulate_ws_bytes': (_i64, [_i64, _i64, _i64, C.c_int]),
     'abn_hmm_accumulate': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, C.c_int, _vp, _vp, _i64, _vp]),
+    'abn_hmm_viterbi_ws_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'abn_hmm_viterbi': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                  _vp, _i64, _vp]),
     'abn_esk_max_span': (_i64, []),
     'abn_esk_score': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, C.c_int, C.c_int, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     'abn_esk_segment': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),

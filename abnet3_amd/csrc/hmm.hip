@@ -1,5 +1,6 @@
 // hmm.hip -- forward-backward of the sticky HMM over a mixture's components (abn_hmm_forward_backward, and with the
-// per-component stays abn_hmm_forward_backward_stats) and the statistics of its Baum-Welch step (abn_hmm_accumulate).
+// per-component stays abn_hmm_forward_backward_stats), the statistics of its Baum-Welch step (abn_hmm_accumulate) and
+// its max-product path (abn_hmm_viterbi, above hmm_viterbi_kernel).
 // abnet3_amd/hmm.py states the definition; DESIGN.md section 3.4c2 the shape.
 //
 // The sum-product twin of km_viterbi_kernel (kmeans.hip): one launch for the corpus, persistent workgroups that loop
@@ -22,6 +23,7 @@
 #include "common.h"
 #include "gemm_f32.h"
 #include "gmm_tile.h"
+#include "vit_wave.h"
 
 #include <math.h>
 
@@ -474,6 +476,191 @@ __global__ __launch_bounds__(256) void hmm_sums_kernel(const float* __restrict__
     gmm_sum_slabs(slabs, (int)blockIdx.x, nc, n_ranges, sums);
 }
 
+// ---- max-product path (abn_hmm_viterbi) ----------------------------------------------------------------------------------
+// The max-product twin of hmm_fb_kernel and the HMM twin of km_viterbi_kernel (kmeans.hip), whose shape it takes over:
+// persistent workgroups, utterance u = blockIdx.x, + gridDim.x, ...  Per block of 128 frames the score tiles logN (the
+// score phase of hmm_block_scores without the max / exp rewrite) go into the workgroup's own slab [128][ks] -- in LDS
+// behind the operand tiles where K <= 128, otherwise in the workspace --, then one sequential step per frame: component
+// k = 256 q + thread, W and the three log tables in registers, every operation one rounded add or a compare,
+//   a = W + ls,  st = a > lr,  u = s + (st ? a : lr)   (first good frame: u = s + lw),   M = max u,  W = u - M,
+// the max and its lowest index as ONE 64-bit max-reduction (vit_wave.h) and one LDS exchange, one ballot word of stay
+// bits per 64 components, and the previous good frame's j* as an int32 (-1: the first good frame, -2: a BAD frame).
+// Wave 0 then walks the stay bits backwards 64 frames at a time.  The slab, the stay bits and prevj are written and read
+// by this workgroup alone with a workgroup barrier between, in 256-byte aligned regions: the comment above KM_VIT_GRID
+// (kmeans.hip) says why that is enough.
+constexpr int HM_VIT_LDS_KS = GM_B + 8;    // K <= 128: slab rows 136 floats apart (the two half-waves of a deposit on different banks)
+constexpr size_t HM_VIT_LDS_BYTES = GM_TILE_BYTES + sizeof(float) * GM_B * HM_VIT_LDS_KS;       // 140 KiB of the CU's 160
+static_assert(HM_VIT_LDS_BYTES + 1024 <= 160 * 1024, "the LDS slab fits beside the operand tiles and the static arrays");
+
+struct HmmVitP {
+    GmmP g;                                 // x, shift, A, B, c = c0, T, K, D, tiles_k (a kernel argument, as in HmmP)
+    const float* lw; const float* ls; const float* lr;
+    const int64_t* off; const int* len;
+    int n_utt;
+    int* ids; double* log_prob; int* n_switch; int* n_good;
+    char* ws; int64_t per_wg;               // bytes of a workgroup's region
+    int ks, kw, cap;                        // slab row stride (floats), stay words per frame, frames the region holds
+};
+
+struct HmmVitWs { int64_t slab_bytes, per_frame, per_wg; int grid, ks, kw; };
+static HmmVitWs hmm_vit_ws(int64_t n_utt, int64_t max_len, int64_t K)
+{
+    HmmVitWs w;
+    w.grid = (int)(n_utt < HM_GRID ? n_utt : HM_GRID);
+    w.ks = (int)((K + GM_B - 1) / GM_B) * GM_B;
+    int nq = 1;
+    while (nq * 256 < K) nq <<= 1;
+    w.kw = 4 * nq;
+    w.slab_bytes = (int64_t)sizeof(float) * GM_B * w.ks;
+    w.per_frame = 8LL * w.kw + 4;           // the stay words and prevj
+    w.per_wg = align_up(w.slab_bytes + max_len * w.per_frame, 256);
+    return w;
+}
+
+// The block of frames m0 .. m0 + nf - 1: BAD flags and the score tiles logN into the slab.  Ends behind a barrier.
+// (hmm_block_scores' first half, restated: sharing it moved hmm_fb_kernel's register allocation.)
+__device__ __forceinline__ void hmm_vit_scores(const GmmP& gp, int m0, int nf, float* smem, float* slab, int ks, int* bad_s)
+{
+    float* const As = smem;
+    float* const Bs = smem + 2 * GmTile::floats;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
+    if (t < GM_B) {
+        bool bad = false;
+        if (t < nf)
+            for (int d = 0; d < gp.D; ++d) {
+                const float xc = gp.x[(int64_t)(m0 + t) * gp.D + d] - gp.shift[d];
+                bad |= !__builtin_isfinite(xc * xc);
+            }
+        bad_s[t] = bad;
+    }
+    for (int ct = 0; ct < gp.tiles_k; ++ct) {
+        const int n0 = ct * GM_B;
+        f32x16 acc[2][2];
+        gmm_score_tile(gp, m0, n0, As, Bs, acc);
+        const int col_l = lane & 31, rsub = 4 * (lane >> 5);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    slab[(int64_t)(wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + rsub) * ks + n0 + wn0 + 32 * j + col_l] = acc[i][j][r];
+    }
+    __syncthreads();                                                  // the slab and bad_s are this workgroup's own
+}
+
+template <int NQ, bool LDSS>
+__global__ __launch_bounds__(256) void hmm_viterbi_kernel(HmmVitP p)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ int bad_s[GM_B];
+    __shared__ unsigned long long red_k[2][4];
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    char* const base = p.ws + (int64_t)blockIdx.x * p.per_wg;
+    float* const slab = LDSS ? smem + 4 * GmTile::floats : reinterpret_cast<float*>(base);
+    const int ks = LDSS ? HM_VIT_LDS_KS : p.ks;
+    unsigned long long* const stay = reinterpret_cast<unsigned long long*>(base + (int64_t)sizeof(float) * GM_B * p.ks);
+    int* const prevj = reinterpret_cast<int*>(stay + (int64_t)p.cap * p.kw);
+    const int K = p.g.K;
+
+    float lw[NQ], ls[NQ], lr[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int k = 256 * q + t;
+        lw[q] = k < K ? p.lw[k] : 0.0f;
+        ls[q] = k < K ? p.ls[k] : 0.0f;
+        lr[q] = k < K ? p.lr[k] : 0.0f;
+    }
+
+    for (int u = (int)blockIdx.x; u < p.n_utt; u += (int)gridDim.x) {
+        const int64_t o = p.off[u];
+        const int L = p.len[u];
+        if (o < 0 || L < 0 || o + L > p.g.T || L > p.cap) {          // (uniform) nothing of this utterance is touched
+            if (t == 0) {
+                if (p.log_prob) p.log_prob[u] = NAN;
+                if (p.n_switch) p.n_switch[u] = -1;
+                if (p.n_good) p.n_good[u] = -1;
+            }
+            continue;
+        }
+        float W[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) W[q] = 0.0f;
+        bool started = false;
+        int jprev = -1, par = 0, ngood = 0;
+        double lp = 0.0;
+
+        for (int f0 = 0; f0 < L; f0 += GM_B) {
+            const int nf = min(GM_B, L - f0);
+            hmm_vit_scores(p.g, (int)o + f0, nf, smem, slab, ks, bad_s);
+
+            float sn[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) sn[q] = 256 * q + t < K ? slab[256 * q + t] : 0.0f;
+            for (int f = 0; f < nf; ++f) {
+                const int g = f0 + f;
+                float s[NQ];
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) s[q] = sn[q];
+                if (f + 1 < nf) {
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) sn[q] = 256 * q + t < K ? slab[(int64_t)(f + 1) * ks + 256 * q + t] : 0.0f;
+                }
+                if (bad_s[f]) {                                       // (uniform) the chain passes over it
+                    if (t == 0) prevj[g] = -2;
+                    continue;
+                }
+                unsigned long long key = 0;                           // (below the key of -inf)
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const int k = 256 * q + t;
+                    const float a = W[q] + ls[q];
+                    const bool st = started && a > lr[q];             // strict: a tie goes to the switch
+                    const unsigned long long word = __ballot(st);
+                    if (lane == 0) stay[(int64_t)g * p.kw + 4 * q + wave] = word;
+                    float uq = s[q] + (started ? (st ? a : lr[q]) : lw[q]);
+                    if (k >= K) uq = -INFINITY;
+                    W[q] = uq;
+                    const unsigned long long kq = vit_key(uq, k);
+                    key = kq > key ? kq : key;
+                }
+                key = vit_wave_max(key);
+                if (lane == 0) red_k[par][wave] = key;
+                __syncthreads();
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned long long ok = red_k[par][w];
+                    key = ok > key ? ok : key;
+                }
+                par ^= 1;                                             // (the other set is not rewritten before the next barrier)
+                const float bv = vit_key_score(key);
+                int bi = (int)~(unsigned)key;
+                if ((unsigned)bi >= (unsigned)K) bi = 0;              // no score compared greater than -inf: still an id
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) W[q] -= bv;
+                lp += (double)bv;
+                if (t == 0) prevj[g] = jprev;
+                jprev = bi;
+                started = true;
+                ++ngood;
+            }
+            __syncthreads();                                          // before the next block's scores replace these
+        }
+
+        if (wave == 0) {                                              // traceback: jprev is the last good frame's j*
+            const int nsw = vit_traceback(stay, prevj, p.kw, p.ids, o, L, jprev, lane);
+            if (lane == 0) {
+                if (p.log_prob) p.log_prob[u] = lp;
+                if (p.n_switch) p.n_switch[u] = nsw;
+                if (p.n_good) p.n_good[u] = ngood;
+            }
+        }
+        __syncthreads();                                              // the traceback's reads before the next utterance's writes
+    }
+}
+
 static int hmm_check_sizes(int64_t n_utt, int64_t K, int64_t D, const char* what)
 {
     ABN_REQUIRE(n_utt >= 1 && n_utt < (1LL << 31), "%s: n_utt = %lld out of range", what, (long long)n_utt);
@@ -592,6 +779,68 @@ extern "C" int abn_hmm_forward_backward_stats(const float* x, int64_t T, int64_t
     ABN_REQUIRE(stay_k, "abn_hmm_forward_backward_stats: null pointer (stay_k)");
     return hmm_fb_launch("abn_hmm_forward_backward_stats", x, T, D, off, len, n_utt, shift, A, B, c0, w, K, rho, mode, post,
                          loglik, stays, n_good, stay_k, ws, ws_bytes, stream);
+}
+
+extern "C" int64_t abn_hmm_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D)
+{
+    if (hmm_check_sizes(n_utt, K, D, "abn_hmm_viterbi_ws_bytes") != ABN_OK) return -1;
+    if (max_len < 0 || max_len > HM_MAX_LEN) {
+        set_error("abn_hmm_viterbi_ws_bytes: max_len = %lld, supported 0 .. %d (abn_hmm_max_len)", (long long)max_len, HM_MAX_LEN);
+        return -1;
+    }
+    const HmmVitWs w = hmm_vit_ws(n_utt, max_len, K);
+    return w.per_wg * w.grid;
+}
+
+extern "C" int abn_hmm_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                               const float* shift, const float* A, const float* B, const float* c0, const float* lw,
+                               const float* ls, const float* lr, int64_t K, int32_t* ids, double* log_prob, int32_t* n_switch,
+                               int32_t* n_good, void* ws, int64_t ws_bytes, void* stream)
+{
+    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "abn_hmm_viterbi: T = %lld out of range", (long long)T);
+    const int rc = hmm_check_sizes(n_utt, K, D, "abn_hmm_viterbi");
+    if (rc != ABN_OK) return rc;
+    ABN_REQUIRE(x && off && len && shift && A && B && c0 && lw && ls && lr && ids, "abn_hmm_viterbi: null pointer");
+    const HmmVitWs w = hmm_vit_ws(n_utt, 0, K);
+    const int64_t per_wg = ws_bytes > 0 ? (ws_bytes / w.grid) & ~255LL : 0;
+    int64_t cap = (per_wg - w.slab_bytes) / w.per_frame;
+    if (!ws || cap < 1) {
+        set_error("abn_hmm_viterbi: workspace of %lld bytes holds no frame (abn_hmm_viterbi_ws_bytes)", (long long)ws_bytes);
+        return ABN_E_WORKSPACE;
+    }
+    ABN_REQUIRE(aligned16(ws), "abn_hmm_viterbi: the workspace must be 16-byte aligned");
+    if (cap > HM_MAX_LEN) cap = HM_MAX_LEN;
+    static bool attr_set[16] = {};
+    if (first_use_on_device(attr_set)) {
+        const auto opt_in = [](const void* k, size_t bytes) { (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+        opt_in(reinterpret_cast<const void*>(hmm_viterbi_kernel<1, true>), HM_VIT_LDS_BYTES);
+        opt_in(reinterpret_cast<const void*>(hmm_viterbi_kernel<1, false>), GM_TILE_BYTES);
+        opt_in(reinterpret_cast<const void*>(hmm_viterbi_kernel<2, false>), GM_TILE_BYTES);
+        opt_in(reinterpret_cast<const void*>(hmm_viterbi_kernel<4, false>), GM_TILE_BYTES);
+        opt_in(reinterpret_cast<const void*>(hmm_viterbi_kernel<8, false>), GM_TILE_BYTES);
+        opt_in(reinterpret_cast<const void*>(hmm_viterbi_kernel<16, false>), GM_TILE_BYTES);
+    }
+    HmmVitP p;
+    p.g.x = x; p.g.shift = shift; p.g.A = A; p.g.B = B; p.g.c = c0;
+    p.g.T = (int)T; p.g.K = (int)K; p.g.D = (int)D;
+    p.g.lse = nullptr; p.g.post = nullptr; p.g.slabs = nullptr;
+    p.g.tiles_k = (int)((K + GM_B - 1) / GM_B); p.g.fblocks = 0; p.g.n_ranges = 0; p.g.blocks_per_range = 0;
+    p.lw = lw; p.ls = ls; p.lr = lr; p.off = off; p.len = len; p.n_utt = (int)n_utt;
+    p.ids = ids; p.log_prob = log_prob; p.n_switch = n_switch; p.n_good = n_good;
+    p.ws = static_cast<char*>(ws); p.per_wg = per_wg;
+    p.ks = w.ks; p.kw = w.kw; p.cap = (int)cap;
+    const dim3 grid((unsigned)w.grid);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (K <= GM_B) hipLaunchKernelGGL((hmm_viterbi_kernel<1, true>), grid, dim3(256), HM_VIT_LDS_BYTES, st, p);
+    else switch (w.kw / 4) {
+    case 1: hipLaunchKernelGGL((hmm_viterbi_kernel<1, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+    case 2: hipLaunchKernelGGL((hmm_viterbi_kernel<2, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+    case 4: hipLaunchKernelGGL((hmm_viterbi_kernel<4, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+    case 8: hipLaunchKernelGGL((hmm_viterbi_kernel<8, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+    default: hipLaunchKernelGGL((hmm_viterbi_kernel<16, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
+    }
+    ABN_CHECK_LAUNCH("abn_hmm_viterbi");
+    return ABN_OK;
 }
 
 static int hmm_acc_check(int64_t T, int64_t K, int64_t D, int n_ranges, const char* what)

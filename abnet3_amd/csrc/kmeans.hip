@@ -20,6 +20,7 @@
 // No floating-point atomics anywhere: every sum has one fixed order, two calls give the same bits.
 #include "common.h"
 #include "kmeans_tile.h"
+#include "vit_wave.h"
 
 #include <limits.h>
 #include <math.h>
@@ -331,48 +332,7 @@ static KmVitWs km_vit_ws(int64_t n_utt, int64_t max_len, int64_t K)
     return w;
 }
 
-// (score, index) as one integer whose unsigned order is: the greater score first, then the LOWER index -- so that the
-// max and its lowest index are one max-reduction.  -0 is read as +0, as the float comparison reads it.
-__device__ __forceinline__ unsigned long long km_vit_key(float v, int k)
-{
-    unsigned u = __float_as_uint(v == 0.0f ? 0.0f : v);
-    u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
-    return ((unsigned long long)u << 32) | (unsigned)~k;
-}
-__device__ __forceinline__ float km_vit_key_score(unsigned long long key)
-{
-    unsigned u = (unsigned)(key >> 32);
-    u ^= (u >> 31) ? 0x80000000u : 0xffffffffu;
-    return __uint_as_float(u);
-}
-// One DPP exchange inside the rows of 16 lanes (every lane has a source under these controls) and the max of the two.
-template <int CTRL>
-__device__ __forceinline__ unsigned long long km_vit_dpp_max(unsigned long long v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xf, 0xf, false);
-    const unsigned long long o = ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
-    return o > v ? o : v;
-}
-// The max over the wave, in every lane: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror leave the
-// row's max in its 16 lanes; the four rows' values are read with v_readlane.  All 64 lanes must be active.
-__device__ __forceinline__ unsigned long long km_vit_wave_max(unsigned long long v)
-{
-    v = km_vit_dpp_max<0xB1>(v);
-    v = km_vit_dpp_max<0x4E>(v);
-    v = km_vit_dpp_max<0x141>(v);
-    v = km_vit_dpp_max<0x140>(v);
-    unsigned long long r = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 16 * i);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 16 * i);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        r = o > r ? o : r;
-    }
-    return r;
-}
-
+// The (score, index) key, its wave reduction and the traceback: vit_wave.h (shared with hmm.hip's abn_hmm_viterbi).
 template <int NQ, bool LDSS>
 __global__ __launch_bounds__(256) void km_viterbi_kernel(KmVitP p)
 {
@@ -468,10 +428,10 @@ __global__ __launch_bounds__(256) void km_viterbi_kernel(KmVitP p)
                     float uq = started ? s[q] + (st ? W[q] : -pen) : s[q];
                     if (k >= p.K) uq = -INFINITY;
                     W[q] = uq;
-                    const unsigned long long kq = km_vit_key(uq, k);
+                    const unsigned long long kq = vit_key(uq, k);
                     key = kq > key ? kq : key;
                 }
-                key = km_vit_wave_max(key);
+                key = vit_wave_max(key);
                 if (lane == 0) red_k[par][wave] = key;
                 __syncthreads();
 #pragma unroll
@@ -480,7 +440,7 @@ __global__ __launch_bounds__(256) void km_viterbi_kernel(KmVitP p)
                     key = o > key ? o : key;
                 }
                 par ^= 1;                                             // (the other set is not rewritten before the next barrier)
-                const float bv = km_vit_key_score(key);
+                const float bv = vit_key_score(key);
                 int bi = (int)~(unsigned)key;
                 if ((unsigned)bi >= (unsigned)p.K) bi = 0;            // no score compared greater than -inf: still an id
 #pragma unroll
@@ -494,25 +454,7 @@ __global__ __launch_bounds__(256) void km_viterbi_kernel(KmVitP p)
         }
 
         if (wave == 0) {                                              // traceback: jprev is the last good frame's j*
-            int cur = jprev, te = L - 1, nsw = 0;
-            while (te >= 0) {
-                const int g = te - lane;
-                int pj = -2;
-                bool cleared = false;
-                if (g >= 0) {
-                    pj = prevj[g];
-                    if (cur >= 0 && pj != -2) cleared = !((stay[(int64_t)g * p.kw + (cur >> 6)] >> (cur & 63)) & 1ull);
-                }
-                const unsigned long long mask = __ballot(cleared);
-                const int l1 = mask ? __builtin_ctzll(mask) : 63;     // frames te .. te - l1 keep cur
-                if (g >= 0 && lane <= l1) p.ids[o + g] = (pj == -2 || cur < 0) ? -1 : cur;
-                if (mask) {
-                    const int nj = __shfl(pj, l1);                    // -1: that was the first good frame
-                    nsw += nj >= 0 && nj != cur;                      // (equal only with a penalty of 0, where nothing stays)
-                    cur = nj;
-                }
-                te -= l1 + 1;
-            }
+            const int nsw = vit_traceback(stay, prevj, p.kw, p.ids, o, L, jprev, lane);
             if (lane == 0) {
                 if (p.objective) p.objective[u] = obj;
                 if (p.n_switch) p.n_switch[u] = nsw;

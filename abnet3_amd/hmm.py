@@ -3,6 +3,7 @@
     python -m abnet3_amd.hmm fit-stay GMM.npz FEATURES MODEL.npz [--stay P] [--n-iter N] [--tol T]
     python -m abnet3_amd.hmm fit GMM.npz FEATURES MODEL.npz [--stay P] [--n-iter N] [--tol T] [--params mvws]
     python -m abnet3_amd.hmm transform MODEL.npz FEATURES OUT [--mode smooth|filter]
+    python -m abnet3_amd.hmm decode MODEL.npz FEATURES OUT
 
 ``GmmPosteriorgram`` treats every frame on its own, so its posteriors flicker.  An HMM over the mixture's components
 with a single "stay" probability is the smallest acoustic-unit model that has a likelihood: its forward-backward pass
@@ -58,8 +59,33 @@ workgroups, one utterance at a time, one sum reduction per frame and sweep.  The
 sweeps, so there is no T x K array beyond it.  A Baum-Welch iteration is that launch with the per-component stays
 (abn_hmm_forward_backward_stats) and abn_hmm_accumulate, which reads the gamma table once as the A operand of
 abn_gmm_accumulate's statistics GEMM.  Limits: K <= abn_hmm_max_k(), D <= abn_gmm_max_d(), an utterance of at most
-abn_hmm_max_len() frames; utterances must not overlap.  Left out: full transition matrices, durations, a max-product
-path.
+abn_hmm_max_len() frames; utterances must not overlap.  Left out: full transition matrices, durations.
+
+The max-product path (``viterbi``, ``StickyHmmPosteriorgram.decode`` / ``quantize``; abn_hmm_viterbi, one launch;
+tests/hmm_vit_np.py restates it).  The model, the emissions and the BAD-frame rule are the ones above.
+
+* Log tables ``viterbi_tables(w, stay) -> (lw, ls, lr)``, each [K] float32, computed on the host in float64 from
+  w32 = float32(w), r = float32(stay) and omr = float32(1) - r and rounded once:
+    lw = log w32,   ls = log(r + omr w32),   lr = log(omr w32);
+  lw and lr are -inf where w32 == 0 (ls too when stay == 0); check_stay's range condition applies.  The kernel takes no
+  logarithm.
+* Recurrence per utterance over its good frames in order, fp32; every operation is one rounded add or a compare, so
+  contraction cannot change it.  s = logN[t, :] are the score tile's bits.
+    first good frame:  u[k] = s[k] + lw[k]
+    later frames:      a = W[k] + ls[k],  st[k] = a > lr[k]  (strict: a tie goes to the switch),
+                       u[k] = s[k] + (st[k] ? a : lr[k])
+    every good frame:  M = max_k u[k],  j* its lowest index,  W[k] = u[k] - M,  log_prob += M  (float64 sum);
+                       the frame records st[.] and the PREVIOUS good frame's j*.
+  max_j (delta[j] + log a[j, k]) = max(delta[k] + ls[k], max_j delta[j] + lr[k]) because ls >= lr, so this is the exact
+  max-product recursion.  A component of weight 0 has u = -inf throughout and is never chosen.
+* Traceback from the last good frame's j*: a frame keeps cur while st[cur] is set, otherwise cur becomes that frame's
+  recorded predecessor.
+* Outputs: ids [T] int32 (BAD frames -1; rows outside every utterance keep what they held), log_prob [n_utt] float64 (the
+  log joint probability of the best path and the good frames), n_switch [n_utt] int32 (the changes of id between
+  consecutive good frames), n_good [n_utt] int32.  A refused utterance (outside 0 .. T, or longer than the workspace was
+  sized for) is left untouched: log_prob NaN, n_switch and n_good -1.
+* At stay = 0 all three tables are equal and the recurrence is argmax_k fl32(s[k] + lw[k]) frame by frame: the mixture's
+  hard assignment.
 """
 import argparse
 import copy
@@ -181,6 +207,98 @@ def forward_backward(table, off, lens, shift, A, B, c0, w, stay, mode='smooth', 
     return (out, ll, st, ng, sk) if want_stay_k else (out, ll, st, ng)
 
 
+def viterbi_tables(w, stay):
+    """(lw, ls, lr), each [K] float32: the log tables of the max-product path (module docstring), computed on the host in
+    float64 from w32 = float32(w), r = float32(stay) and omr = float32(1) - r and rounded once.  ValueError through
+    check_stay (0 <= stay < 1 and the range condition)."""
+    w32 = np.asarray(w, dtype=np.float32).ravel()
+    r = np.float32(check_stay('hmm.viterbi_tables', stay, w32))
+    omr = np.float32(1.0) - r
+    w64 = w32.astype(np.float64)
+    with np.errstate(divide='ignore'):
+        lw = np.log(w64)
+        ls = np.log(np.float64(r) + np.float64(omr) * w64)
+        lr = np.log(np.float64(omr) * w64)
+    lw[w32 == 0], lr[w32 == 0] = -np.inf, -np.inf
+    return lw.astype(np.float32), ls.astype(np.float32), lr.astype(np.float32)
+
+
+def _check_log_tables(who, lw, ls, lr, K):
+    """The host checks of the three log tables (host arrays come back): [K] float32, lr <= ls, lw and lr -inf at the
+    same places and not everywhere, ls finite wherever lw is, and nothing NaN or +inf."""
+    for t in (lw, ls, lr):
+        if not isinstance(t, torch.Tensor) or t.shape != (K,) or t.dtype != torch.float32:
+            raise ValueError('%s: lw, ls, lr [K] float32 tensors are needed (hmm.viterbi_tables)' % who)
+    a, b, c = (t.detach().cpu().numpy() for t in (lw, ls, lr))
+    if np.isnan(a).any() or np.isnan(b).any() or np.isnan(c).any() or (a == np.inf).any() or (b == np.inf).any() or \
+            (c == np.inf).any():
+        raise ValueError('%s: the log tables must not hold NaN or +inf' % who)
+    dead = np.isneginf(a)
+    if not np.array_equal(dead, np.isneginf(c)):
+        raise ValueError('%s: lw and lr must be -inf at the same components (those of weight 0)' % who)
+    if dead.all():
+        raise ValueError('%s: lw is -inf everywhere: no component has a weight' % who)
+    if not np.isfinite(b[~dead]).all():
+        raise ValueError('%s: ls must be finite at every component of positive weight' % who)
+    if not (c <= b).all():
+        raise ValueError('%s: lr <= ls is needed (a stay is at least as likely as a redraw of the same unit)' % who)
+
+
+def viterbi(table, off, lens, shift, A, B, c0, lw, ls, lr, ids=None, want_log_prob=True):
+    """(ids [T] int32, log_prob [n_utt] float64 or None, n_switch [n_utt] int32 or None, n_good [n_utt] int32), device
+    tensors, of the max-product recurrence the module docstring defines (abn_hmm_viterbi, one launch).  off, lens: the
+    utterances' first rows and lengths (host sequences or device tensors); they must not overlap.  lw, ls, lr: the log
+    tables of ``viterbi_tables``.  Rows outside every utterance keep what `ids` held (-1 in a fresh `ids`)."""
+    lib = _lib.load()
+    who = 'hmm.viterbi'
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
+        raise ValueError('%s: a [T, D] float32 table is needed' % who)
+    T, D = table.shape
+    K = c0.shape[0]
+    if A.shape != (K, D) or B.shape != (K, D) or shift.shape != (D,) or any(t.dtype != torch.float32 for t in (shift, A, B, c0)):
+        raise ValueError('%s: shift [D], A [K, D], B [K, D], c0 [K] float32 are needed' % who)
+    if K < 1 or K > max_k():
+        raise ValueError('%s: K = %d, the kernel takes 1 .. %d (abn_hmm_max_k)' % (who, K, max_k()))
+    _check_log_tables(who, lw, ls, lr, K)
+    host = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    off_h, len_h = host(off).astype(np.int64).ravel(), host(lens).astype(np.int64).ravel()
+    n_utt = len(off_h)
+    if len(len_h) != n_utt:
+        raise ValueError('%s: %d offsets and %d lengths' % (who, n_utt, len(len_h)))
+    if n_utt and ((off_h < 0).any() or (len_h < 0).any() or (off_h + len_h > T).any()):
+        raise ValueError('%s: an utterance lies outside the table\'s %d rows' % (who, T))
+    if n_utt > 1:
+        order = np.argsort(off_h, kind='stable')
+        if (off_h[order][1:] < (off_h + len_h)[order][:-1]).any():
+            raise ValueError('%s: utterances overlap' % who)
+    longest = int(len_h.max()) if n_utt else 0
+    if longest > max_len():
+        raise ValueError('%s: an utterance of %d frames, the kernel takes up to %d (abn_hmm_max_len)' % (who, longest, max_len()))
+    if ids is not None and (not isinstance(ids, torch.Tensor) or ids.shape != (T,) or ids.dtype != torch.int32 or
+                            not ids.is_contiguous()):
+        raise ValueError('%s: ids must be a contiguous [T] int32 tensor' % who)
+    table = _gmm._check_table(who, table)
+    _lib.require_device(shift, A, B, c0, lw, ls, lr)
+    if ids is None:
+        ids = torch.full((T,), -1, dtype=torch.int32, device=table.device)
+    _lib.require_device(ids)
+    lp = torch.zeros(n_utt, dtype=torch.float64, device=table.device) if want_log_prob else None
+    nsw = torch.zeros(n_utt, dtype=torch.int32, device=table.device) if want_log_prob else None
+    ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
+    if T and n_utt and longest:
+        need = lib.abn_hmm_viterbi_ws_bytes(n_utt, longest, K, D)
+        if need < 0:
+            raise ValueError('%s: %s' % (who, lib.abn_last_error().decode('utf-8', 'replace')))
+        ws = torch.empty(int(need), dtype=torch.uint8, device=table.device)
+        off_d = torch.from_numpy(off_h).to(table.device)
+        len_d = torch.from_numpy(len_h.astype(np.int32)).to(table.device)
+        _lib.check(lib.abn_hmm_viterbi(_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A),
+                                       _lib.ptr(B), _lib.ptr(c0), _lib.ptr(lw), _lib.ptr(ls), _lib.ptr(lr), K, _lib.ptr(ids),
+                                       _lib.ptr(lp), _lib.ptr(nsw), _lib.ptr(ng), _lib.ptr(ws), ws.numel(), _lib.stream()),
+                   'abn_hmm_viterbi')
+    return ids, lp, nsw, ng
+
+
 def accumulate(table, post, shift, n_ranges=0):
     """sums [K, 2D + 1] float64 = [S1 | S2 | N] on the device: the sum over the rows of post[t, k] [xc | xc^2 | 1]
     (abn_hmm_accumulate: `post` is read once; fp32 slabs per frame range, then float64 in range order; the same bits for
@@ -269,7 +387,7 @@ def stay_update(stays, n_good):
 
 
 class StickyHmmPosteriorgram(object):
-    """transform / score / fit_stay of the sticky HMM the module docstring defines, over a fitted GmmPosteriorgram.
+    """transform / decode / quantize / score / fit_stay / fit of the sticky HMM the module docstring defines, over a fitted GmmPosteriorgram.
 
     corpus arguments: a DeviceCorpus, a {name: [T, D]} dict, the path of an h5features file -- each file an utterance --
     or a [T, D] float32 device table, which is ONE utterance."""
@@ -281,6 +399,7 @@ class StickyHmmPosteriorgram(object):
         self.stay_ = check_stay('StickyHmmPosteriorgram', stay, gmm.weights_.astype(np.float32))
         self.log_likelihoods = []
         self.n_bad_ = self.n_retired_ = self.n_starved_ = 0
+        self.last_log_prob_ = self.last_n_switch_ = self.last_n_good_ = None
         self._tables = None
 
     def whoami(self):
@@ -327,6 +446,48 @@ class StickyHmmPosteriorgram(object):
         from .dataloader import DeviceCorpus
         table, dc, lens = self._utterances(corpus)
         out = self._run(table, lens, mode, want_stays=False)[0]
+        if dc is None:
+            return out
+        return DeviceCorpus.from_table(out, dc.names, [dc.length[k] for k in dc.names], dc.times)
+
+    def _decode_ids(self, corpus):
+        """(device ids [rows] int32, DeviceCorpus or None, names or None, lens); fills last_log_prob_ / last_n_switch_ /
+        last_n_good_ / n_bad_."""
+        table, dc, lens = self._utterances(corpus)
+        names = list(dc.names) if dc is not None else list(corpus) if isinstance(corpus, dict) else None
+        shift, A, B, c0, w = self.device_tables(table.device)
+        lw, ls, lr = (torch.from_numpy(a).to(table.device) for a in viterbi_tables(self.gmm.weights_, self.stay_))
+        off = np.cumsum(lens) - lens
+        ids, lp, nsw, ng = viterbi(table, off, lens, shift, A, B, c0, lw, ls, lr)
+        self.last_log_prob_, self.last_n_switch_, self.last_n_good_ = lp.cpu().numpy(), nsw.cpu().numpy(), ng.cpu().numpy()
+        self.n_bad_ = int(lens.sum() - self.last_n_good_.sum())
+        return ids, dc, names, lens
+
+    def decode(self, corpus):
+        """The unit ids of the best path (the module docstring's max-product recurrence), int32, -1 for a BAD frame:
+        {name: host array [length]} in corpus order for a DeviceCorpus, a dict or a file -- what KMeansQuantizer.segment
+        returns, so kmeans.unit_sequences / bitrate / segments, eskmeans.landmarks_from_units and tde.unit_boundaries take
+        it as it is --; for a [T, D] table, which is ONE utterance, the device tensor [T].  ``last_log_prob_`` (float64),
+        ``last_n_switch_`` and ``last_n_good_`` (int32) hold the utterances' log joint probabilities, switch counts and
+        good-frame counts; ``n_bad_`` the BAD frames."""
+        ids, _, names, lens = self._decode_ids(corpus)
+        if names is None:
+            return ids
+        host, out, o = ids.cpu().numpy(), {}, 0
+        for k, n in zip(names, lens):
+            out[k] = host[o:o + int(n)]
+            o += int(n)
+        return out
+
+    def quantize(self, corpus):
+        """Each frame replaced by the mean of its decoded component (uncentred: m + shift), [rows, D] float32 on the
+        device, a BAD frame a row of zeros; for a DeviceCorpus a new DeviceCorpus with the same names, lengths and times
+        (what KMeansQuantizer.quantize gives ``ABXEvaluator(parallel='zero')``)."""
+        from .dataloader import DeviceCorpus
+        ids, dc, _, _ = self._decode_ids(corpus)
+        means = torch.from_numpy(self.gmm.means_.astype(np.float32)).to(ids.device)
+        out = means[ids.clamp(min=0).to(torch.int64)]
+        out[ids < 0] = 0.0
         if dc is None:
             return out
         return DeviceCorpus.from_table(out, dc.names, [dc.length[k] for k in dc.names], dc.times)
@@ -459,6 +620,10 @@ def main(argv=None):
     t.add_argument('features', help='h5features file, or an .npz of name -> [T, D]')
     t.add_argument('out', help='.npz of name -> [T, K], or an h5features file (when the input has times)')
     t.add_argument('--mode', choices=sorted(MODES), default='smooth')
+    d = sub.add_parser('decode', help='unit ids of the best path of FEATURES under a saved model')
+    d.add_argument('model')
+    d.add_argument('features', help='h5features file, or an .npz of name -> [T, D]')
+    d.add_argument('out', help='.npz of name -> [T] ids, or an h5features file (when the input has times)')
     args = ap.parse_args(argv)
     if args.cmd == 'fit':
         check_params('python -m abnet3_amd.hmm fit', args.params)
@@ -476,6 +641,29 @@ def main(argv=None):
               % (h.stay_, len(h.log_likelihoods), h.log_likelihoods[-1], h.n_bad_))
         return 0
     h = StickyHmmPosteriorgram.load(args.model)
+    if args.cmd == 'decode':
+        from . import kmeans as _kmeans
+        out = h.decode(feats)
+        if args.out.endswith('.npz'):
+            np.savez(args.out, **{str(k): v for k, v in out.items()})
+        else:
+            if times is None:
+                raise ValueError('an h5features output needs the frame times: give an h5features input')
+            import h5features
+            names = list(out)
+            with h5features.Writer(args.out) as wh:
+                wh.write(h5features.Data(names, [np.asarray(times[k]) for k in names],
+                                         [out[k].astype(np.float32)[:, None] for k in names]), 'features')
+        n_good = int(h.last_n_good_.sum())
+        if times is not None:
+            seconds = sum(float(np.asarray(times[k])[-1] - np.asarray(times[k])[0]) for k in out if len(times[k]) > 1)
+            rate = '%.2f bits/s' % _kmeans.bitrate(_kmeans.unit_sequences(out), seconds) if seconds > 0 else 'n/a (no duration)'
+        else:
+            rate = '%.2f bits/s at 100 frames/s' % _kmeans.bitrate(_kmeans.unit_sequences(out), max(n_good, 1) / 100.0)
+        print('%d files, %d frames (%d BAD), K = %d, stay %.4f, %d switches, bitrate %s, mean log-probability %.6f per good frame -> %s'
+              % (len(out), sum(v.shape[0] for v in out.values()), h.n_bad_, h.gmm.n_components, h.stay_,
+                 int(h.last_n_switch_.sum()), rate, float(h.last_log_prob_.sum()) / max(n_good, 1), args.out))
+        return 0
     post = h.transform(feats, args.mode).cpu().numpy()
     out, o = {}, 0
     for k, v in feats.items():

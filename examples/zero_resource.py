@@ -5,7 +5,7 @@ Siamese training -> embedding -> ABX.  The corpus' word labels are used twice on
 mined pairs, and the ABX item file ("phones" = word types).
 
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
-                                     [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--hmm-fit N] [--no-network] [--terms] [--terms-theta T]
+                                     [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--hmm-fit N] [--hmm-decode] [--no-network] [--terms] [--terms-theta T]
                                      [--prefilter] [--alignment FILE]
                                      [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P]
                                      [--eskmeans] [--eskmeans-clusters 24] [--samediff]
@@ -23,7 +23,10 @@ under the KL frame distance -- ABX, and with --qbe the search.  No network is tr
 after it, otherwise its figures are printed again beside the embeddings'.  --hmm-stay P (or "fit": EM on the stay
 probability) smooths the posteriorgrams with the sticky HMM of abnet3_amd/hmm.py and prints ABX (kl) of both.
 --hmm-fit N trains that HMM by N iterations of Baum-Welch from the mixture (means, variances, weights and the stay)
-and prints ABX (kl) of raw, smoothed and Baum-Welch-trained posteriorgrams side by side.
+and prints ABX (kl) of raw, smoothed and Baum-Welch-trained posteriorgrams side by side.  --hmm-decode adds the
+discrete units of that HMM's best path (StickyHmmPosteriorgram.decode, Viterbi): their bitrate and switch count beside
+those of the frame-wise mixture argmax (stay = 0 through the same call), and ABX over the quantised frames (each frame
+replaced by its unit's mean).  Nothing in it is tuned on real speech.
 --terms replaces the pair miner by term discovery (abnet3_amd/terms.py): local-alignment DTW of every utterance against
 every other -- over the filterbanks, or with --gmm over the mixture's posteriorgrams under the KL distance -- clustered
 into a .classes file, from which SamplerClusterSiamese draws the train and dev pairs: the reference's canonical route,
@@ -182,10 +185,11 @@ def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frame
     return dl
 
 
-def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=None, hmm_fit=0):
+def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=None, hmm_fit=0, hmm_decode=False):
     """features -> GmmPosteriorgram.fit -> transform -> ABX (kl), and the search: the line main() prints.  hmm_stay (a
     number, or 'fit'): the sticky-HMM smoothed posteriorgrams beside the raw ones; they are the ones returned.  hmm_fit
-    (iterations): the posteriorgrams of the Baum-Welch-trained HMM beside both; then those are returned."""
+    (iterations): the posteriorgrams of the Baum-Welch-trained HMM beside both; then those are returned.  hmm_decode: the
+    discrete units of the (trained, else smoothed) HMM's best path beside the frame-wise mixture argmax."""
     names = list(fb)
     keep, items = word_items(tokens)
     corpus = DeviceCorpus({k: np.asarray(fb[k], dtype=np.float32) for k in names}, times)
@@ -218,9 +222,30 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
                        rs.error, r.error, rt.n_triplets))
             print(more)
             line += '\n' + more
+            h = t
+        if hmm_decode:
+            more = hmm_decode_lines(h, corpus, items)
+            print(more)
+            line += '\n' + more
     if qbe:
         qbe_search(post, keep, names, 'GMM posteriorgrams' + (' (Baum-Welch-trained)' if hmm_fit else ' (smoothed)' if hmm_stay is not None else ''), 'kl')
     return (line, post) if want_post else line
+
+
+def hmm_decode_lines(h, corpus, items):
+    """The units of the HMM's best path (StickyHmmPosteriorgram.decode) beside the frame-wise mixture argmax (stay = 0
+    through the same call): bitrate with runs merged, switches, and ABX over the quantised frames."""
+    seconds = 0.01 * corpus.total
+    out = []
+    for label, model in (('sticky-HMM Viterbi units (stay %.4f)' % h.stay_, h),
+                         ('frame-wise mixture argmax (stay 0)', StickyHmmPosteriorgram(h.gmm, 0.0))):
+        ids = model.decode(corpus)
+        r = ABXEvaluator(items, model.quantize(corpus), parallel='zero').run('within')
+        out.append('%s: %.0f bit/s with runs merged, %d switches, log-probability per frame %.3f; ABX error quantised %.2f %% '
+                   '(%d triplets)' % (label, bitrate(unit_sequences(ids), seconds), int(model.last_n_switch_.sum()),
+                                      float(model.last_log_prob_.sum()) / max(1, int(model.last_n_good_.sum())), r.error, r.n_triplets))
+    out.append('(nothing here is tuned on real speech: neither the stay probability nor the number of components)')
+    return '\n'.join(out)
 
 
 def eskmeans_route(corpus, unit_ids, n_clusters, tokens=None, tolerance=0.03):
@@ -284,6 +309,9 @@ def main():
     ap.add_argument('--hmm-fit', type=int, default=0, metavar='N',
                     help='with --gmm: N iterations of Baum-Welch on the sticky HMM (from --hmm-stay, default 0.9); ABX (kl) of raw, '
                          'smoothed and trained posteriorgrams')
+    ap.add_argument('--hmm-decode', action='store_true',
+                    help='with --hmm-stay / --hmm-fit: the discrete units of the HMM\'s best path (Viterbi): bitrate, switches and ABX '
+                         'of the quantised frames, beside the frame-wise mixture argmax; nothing is tuned on real speech')
     ap.add_argument('--no-network', action='store_true', help='with --gmm: stop after the mixture, train nothing')
     ap.add_argument('--terms', action='store_true', help='pairs from term discovery: clusters -> SamplerClusterSiamese')
     ap.add_argument('--terms-theta', type=float, default=None, help='default: a low quantile of random frame distances (untuned)')
@@ -303,6 +331,8 @@ def main():
         ap.error('--hmm-stay smooths the posteriorgrams of --gmm')
     if args.hmm_fit and not args.gmm:
         ap.error('--hmm-fit trains the HMM over the mixture of --gmm')
+    if args.hmm_decode and args.hmm_stay is None and not args.hmm_fit:
+        ap.error('--hmm-decode decodes the HMM of --hmm-stay or --hmm-fit')
     esk_k = args.eskmeans_clusters if args.eskmeans else None
     rng = np.random.default_rng(0)
     random.seed(0)
@@ -316,7 +346,7 @@ def main():
 
     gmm_line = post = None
     if args.gmm:
-        gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True, hmm_stay=args.hmm_stay, hmm_fit=args.hmm_fit)
+        gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True, hmm_stay=args.hmm_stay, hmm_fit=args.hmm_fit, hmm_decode=args.hmm_decode)
     if args.no_network:
         if not (args.gmm or args.kmeans):
             ap.error('--no-network leaves nothing to do without --gmm or --kmeans')

@@ -1078,6 +1078,31 @@ int64_t abn_hmm_accumulate_ws_bytes(int64_t T, int64_t K, int64_t D, int n_range
 int abn_hmm_accumulate(const float* x, int64_t T, int64_t D, const float* shift, const float* post, int64_t K,
                        int n_ranges, double* sums, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- Viterbi decoding of the sticky HMM (added within ABI 20) ----------------------------------------------------------
+ * The max-product path of the same model (abnet3_amd/hmm.py states the recurrence): the best state sequence of every
+ * utterance under initial distribution w, transitions rho [j == k] + (1 - rho) w[k] and abn_hmm_forward_backward's
+ * emissions logN[t][k].  The kernel takes no logarithm: lw = log w, ls = log(rho + (1 - rho) w), lr = log((1 - rho) w),
+ * each [K] fp32 (hmm.viterbi_tables; lw = lr = -inf for a component of weight 0, which is then never chosen; the caller
+ * keeps lr <= ls).  Over the good frames, fp32, every operation one rounded add or a compare:
+ *   first: u = logN + lw;  later: a = W + ls, stay = a > lr (a tie switches), u = logN + (stay ? a : lr);
+ *   M = max_k u at its lowest index j*,  W = u - M,  log_prob += M (float64).
+ * ids [T] int32: the path; a BAD frame gets -1 and the chain passes over it; rows outside every utterance keep what ids
+ * held.  log_prob [n_utt] float64 (the log joint probability of the path and the good frames), n_switch [n_utt] int32
+ * (changes of id between consecutive good frames) and n_good [n_utt] int32 may each be NULL.  An utterance that does not
+ * lie in 0 .. T, or is longer than the workspace was sized for, is left untouched: log_prob NaN, n_switch and n_good -1.
+ * One launch of persistent workgroups, abn_kmeans_viterbi's shape: bit-reproducible, independent of the grid, no atomics,
+ * no T x K array: the workspace holds, per workgroup (at most 256), a 128-frame slab of scores, one stay bit per
+ * (frame, component) and an int32 per frame of the longest utterance.
+ * abn_hmm_viterbi_ws_bytes: -1 (abn_last_error) for refused sizes; max_len 0 .. abn_hmm_max_len(), K <= abn_hmm_max_k(),
+ * D <= abn_gmm_max_d().  Null pointers, sizes < 1: ABN_E_ARG; limits: ABN_E_UNSUPPORTED; a workspace too small for one
+ * frame: ABN_E_WORKSPACE -- all before any launch. */
+int64_t abn_hmm_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D);
+int abn_hmm_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                    const float* shift, const float* A, const float* B, const float* c0,
+                    const float* lw, const float* ls, const float* lr, int64_t K,
+                    int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good,
+                    void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- embedded segmental k-means (added within ABI 20) ----------------------------------------------------------------
  * Full-coverage word segmentation (abnet3_amd/eskmeans.py states the definitions).  Landmarks: lm [n_lm] int64 row
  * indices into table [T][D]; utterance u owns lm[lm_off[u] .. lm_off[u + 1]) (lm_off [n_utt + 1] int64), at least two
