@@ -1,0 +1,43 @@
+"""What the per-utterance entries (kmeans.viterbi, hmm.forward_backward, hmm.viterbi) share on the host: the checks of
+the utterances' offsets and lengths, and the workspace with the offsets and lengths uploaded beside it."""
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def starts(lens):
+    """First rows [n] int64 of utterances of the given lengths laid end to end."""
+    lens = np.asarray(lens, dtype=np.int64)
+    return np.cumsum(lens) - lens
+
+
+def utterance_spans(who, off, lens, T, longest_allowed, limit_name):
+    """(off int64 [n_utt], lens int64 [n_utt], n_utt, longest) as host arrays, or ValueError: as many offsets as lengths,
+    every utterance inside the table's T rows, no two overlapping, none longer than longest_allowed (the value of the
+    library's limit_name).  off, lens: host sequences or device tensors."""
+    host = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    off_h, len_h = host(off).astype(np.int64).ravel(), host(lens).astype(np.int64).ravel()
+    n_utt = len(off_h)
+    if len(len_h) != n_utt:
+        raise ValueError('%s: %d offsets and %d lengths' % (who, n_utt, len(len_h)))
+    if n_utt and ((off_h < 0).any() or (len_h < 0).any() or (off_h + len_h > T).any()):
+        raise ValueError('%s: an utterance lies outside the table\'s %d rows' % (who, T))
+    if n_utt > 1:
+        order = np.argsort(off_h, kind='stable')
+        if (off_h[order][1:] < (off_h + len_h)[order][:-1]).any():
+            raise ValueError('%s: utterances overlap' % who)
+    longest = int(len_h.max()) if n_utt else 0
+    if longest > longest_allowed:
+        raise ValueError('%s: an utterance of %d frames, the kernel takes up to %d (%s)' % (who, longest, longest_allowed, limit_name))
+    return off_h, len_h, n_utt, longest
+
+
+def workspace(who, ws_bytes_fn, off_h, len_h, longest, K, D, device):
+    """(ws uint8, off int64, lens int32) on the device: the workspace ws_bytes_fn (a *_ws_bytes entry of the library) asks
+    for, its refusal as a ValueError, and the utterances uploaded."""
+    need = ws_bytes_fn(len(off_h), longest, K, D)
+    if need < 0:
+        raise ValueError('%s: %s' % (who, _lib.load().abn_last_error().decode('utf-8', 'replace')))
+    ws = torch.empty(int(need), dtype=torch.uint8, device=device)
+    return ws, torch.from_numpy(off_h).to(device), torch.from_numpy(len_h.astype(np.int32)).to(device)

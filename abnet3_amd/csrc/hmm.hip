@@ -1,7 +1,8 @@
 // hmm.hip -- forward-backward of the sticky HMM over a mixture's components (abn_hmm_forward_backward, and with the
 // per-component stays abn_hmm_forward_backward_stats), the statistics of its Baum-Welch step (abn_hmm_accumulate) and
 // its max-product path (abn_hmm_viterbi, above hmm_viterbi_kernel).
-// abnet3_amd/hmm.py states the definition; DESIGN.md section 3.4c2 the shape.
+// abnet3_amd/hmm.py states the definition; DESIGN.md section 3.4c2 the shape.  The host side of the three per-utterance
+// kernels (workspace geometry, checks, NQ dispatch) is utt_chain.h's, shared with kmeans.hip.
 //
 // The sum-product twin of km_viterbi_kernel (kmeans.hip): one launch for the corpus, persistent workgroups that loop
 // over the utterances, a slab of 128 frames x K emission scores from the mixture's own fp32 MFMA tile (gmm_tile.h, with
@@ -23,14 +24,16 @@
 #include "common.h"
 #include "gemm_f32.h"
 #include "gmm_tile.h"
+#include "utt_chain.h"
 #include "vit_wave.h"
 
 #include <math.h>
 
 namespace abn {
 
-constexpr int HM_GRID = 256;               // one workgroup per CU (the score tile keeps the register file to itself)
-constexpr int HM_MAX_LEN = 1 << 20;
+static_assert(GM_B == UC_B, "utt_chain.h's geometry is these kernels'");
+constexpr ChainLimits HM_LIMITS = {GM_MAX_D, "abn_gmm_max_d", GM_MAX_K, "abn_hmm_max_k", "abn_hmm_max_len"};
+constexpr int64_t HM_FB_FRAME_BYTES = sizeof(float);      // forward-backward keeps c_t per frame
 
 struct HmmP {
     GmmP g;                                 // x, shift, A, B, c = c0, T, K, D, tiles_k: a kernel argument, as in gmm.hip (the
@@ -45,15 +48,16 @@ struct HmmP {
     int ks, cap;                            // slab row stride (floats), frames the region holds
 };
 
-struct HmmWs { int64_t slab_bytes, per_wg; int grid, ks; };
-static HmmWs hmm_ws(int64_t n_utt, int64_t max_len, int64_t K)
+// A GmmP for the score tile alone: the likelihood and accumulate passes' fields are unused.
+static GmmP hmm_score_params(const float* x, int64_t T, int64_t D, const float* shift, const float* A, const float* B,
+                             const float* c0, int64_t K)
 {
-    HmmWs w;
-    w.grid = (int)(n_utt < HM_GRID ? n_utt : HM_GRID);
-    w.ks = (int)((K + GM_B - 1) / GM_B) * GM_B;
-    w.slab_bytes = (int64_t)sizeof(float) * GM_B * w.ks;
-    w.per_wg = align_up(w.slab_bytes + max_len * (int64_t)sizeof(float), 256);
-    return w;
+    GmmP g;
+    g.x = x; g.shift = shift; g.A = A; g.B = B; g.c = c0;
+    g.T = (int)T; g.K = (int)K; g.D = (int)D;
+    g.lse = nullptr; g.post = nullptr; g.slabs = nullptr;
+    g.tiles_k = (int)((K + GM_B - 1) / GM_B); g.fblocks = 0; g.n_ranges = 0; g.blocks_per_range = 0;
+    return g;
 }
 
 // One DPP exchange inside the rows of 16 lanes (every lane has a source under these controls) and the sum of the two:
@@ -486,7 +490,7 @@ __global__ __launch_bounds__(256) void hmm_sums_kernel(const float* __restrict__
 // the max and its lowest index as ONE 64-bit max-reduction (vit_wave.h) and one LDS exchange, one ballot word of stay
 // bits per 64 components, and the previous good frame's j* as an int32 (-1: the first good frame, -2: a BAD frame).
 // Wave 0 then walks the stay bits backwards 64 frames at a time.  The slab, the stay bits and prevj are written and read
-// by this workgroup alone with a workgroup barrier between, in 256-byte aligned regions: the comment above KM_VIT_GRID
+// by this workgroup alone with a workgroup barrier between, in 256-byte aligned regions: the comment above KM_VIT_LDS_KS
 // (kmeans.hip) says why that is enough.
 constexpr int HM_VIT_LDS_KS = GM_B + 8;    // K <= 128: slab rows 136 floats apart (the two half-waves of a deposit on different banks)
 constexpr size_t HM_VIT_LDS_BYTES = GM_TILE_BYTES + sizeof(float) * GM_B * HM_VIT_LDS_KS;       // 140 KiB of the CU's 160
@@ -502,23 +506,9 @@ struct HmmVitP {
     int ks, kw, cap;                        // slab row stride (floats), stay words per frame, frames the region holds
 };
 
-struct HmmVitWs { int64_t slab_bytes, per_frame, per_wg; int grid, ks, kw; };
-static HmmVitWs hmm_vit_ws(int64_t n_utt, int64_t max_len, int64_t K)
-{
-    HmmVitWs w;
-    w.grid = (int)(n_utt < HM_GRID ? n_utt : HM_GRID);
-    w.ks = (int)((K + GM_B - 1) / GM_B) * GM_B;
-    int nq = 1;
-    while (nq * 256 < K) nq <<= 1;
-    w.kw = 4 * nq;
-    w.slab_bytes = (int64_t)sizeof(float) * GM_B * w.ks;
-    w.per_frame = 8LL * w.kw + 4;           // the stay words and prevj
-    w.per_wg = align_up(w.slab_bytes + max_len * w.per_frame, 256);
-    return w;
-}
-
 // The block of frames m0 .. m0 + nf - 1: BAD flags and the score tiles logN into the slab.  Ends behind a barrier.
-// (hmm_block_scores' first half, restated: sharing it moved hmm_fb_kernel's register allocation.)
+// (hmm_block_scores' first half, restated: with one shared function hmm_fb_kernel measured 5 to 7 % slower, DESIGN.md
+// section 3.4c2.)
 __device__ __forceinline__ void hmm_vit_scores(const GmmP& gp, int m0, int nf, float* smem, float* slab, int ks, int* bad_s)
 {
     float* const As = smem;
@@ -661,34 +651,20 @@ __global__ __launch_bounds__(256) void hmm_viterbi_kernel(HmmVitP p)
     }
 }
 
-static int hmm_check_sizes(int64_t n_utt, int64_t K, int64_t D, const char* what)
-{
-    ABN_REQUIRE(n_utt >= 1 && n_utt < (1LL << 31), "%s: n_utt = %lld out of range", what, (long long)n_utt);
-    ABN_REQUIRE(K >= 1 && D >= 1, "%s: K = %lld, D = %lld out of range", what, (long long)K, (long long)D);
-    if (D > GM_MAX_D || K > GM_MAX_K) {
-        set_error("%s: D = %lld, K = %lld, supported D <= %d (abn_gmm_max_d), K <= %d (abn_hmm_max_k)", what, (long long)D,
-                  (long long)K, GM_MAX_D, GM_MAX_K);
-        return ABN_E_UNSUPPORTED;
-    }
-    return ABN_OK;
-}
+struct HmmVitKernels {
+    template <int NQ, bool LDSS> static constexpr auto kernel() { return hmm_viterbi_kernel<NQ, LDSS>; }
+};
 
 }  // namespace abn
 
 using namespace abn;
 
-extern "C" int64_t abn_hmm_max_len(void) { return HM_MAX_LEN; }
+extern "C" int64_t abn_hmm_max_len(void) { return UC_MAX_LEN; }
 extern "C" int64_t abn_hmm_max_k(void) { return GM_MAX_K; }
 
 extern "C" int64_t abn_hmm_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D)
 {
-    if (hmm_check_sizes(n_utt, K, D, "abn_hmm_ws_bytes") != ABN_OK) return -1;
-    if (max_len < 0 || max_len > HM_MAX_LEN) {
-        set_error("abn_hmm_ws_bytes: max_len = %lld, supported 0 .. %d (abn_hmm_max_len)", (long long)max_len, HM_MAX_LEN);
-        return -1;
-    }
-    const HmmWs w = hmm_ws(n_utt, max_len, K);
-    return w.per_wg * w.grid;
+    return chain_ws_bytes("abn_hmm_ws_bytes", n_utt, max_len, K, D, HM_LIMITS, HM_FB_FRAME_BYTES, 0);
 }
 
 // Both forward-backward entries: `what` names the caller in the messages, stay_k != nullptr picks the SK kernels.
@@ -698,65 +674,36 @@ static int hmm_fb_launch(const char* what, const float* x, int64_t T, int64_t D,
                          double* stay_k, void* ws, int64_t ws_bytes, void* stream)
 {
     ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "%s: T = %lld out of range", what, (long long)T);
-    const int rc = hmm_check_sizes(n_utt, K, D, what);
+    int rc = chain_check_sizes(what, n_utt, K, D, HM_LIMITS);
     if (rc != ABN_OK) return rc;
     ABN_REQUIRE(x && off && len && shift && A && B && c0 && w && post && loglik && n_good, "%s: null pointer", what);
     ABN_REQUIRE(rho >= 0.0f && rho < 1.0f, "%s: rho = %g, 0 <= rho < 1 is needed", what, (double)rho);
     ABN_REQUIRE(mode == 0 || mode == 1, "%s: mode = %d, 0 (smoothed) or 1 (filtered)", what, mode);
-    const HmmWs hw = hmm_ws(n_utt, 0, K);
-    const int64_t per_wg = ws_bytes > 0 ? (ws_bytes / hw.grid) & ~255LL : 0;
-    int64_t cap = (per_wg - hw.slab_bytes) / (int64_t)sizeof(float);
-    if (!ws || cap < 1) {
-        set_error("%s: workspace of %lld bytes holds no frame (abn_hmm_ws_bytes)", what, (long long)ws_bytes);
-        return ABN_E_WORKSPACE;
-    }
-    ABN_REQUIRE(aligned16(ws), "%s: the workspace must be 16-byte aligned", what);
-    if (cap > HM_MAX_LEN) cap = HM_MAX_LEN;
+    const ChainWs hw = chain_ws(n_utt, 0, K, HM_FB_FRAME_BYTES, 0);
+    ChainRegion a;
+    rc = chain_region(what, "abn_hmm_ws_bytes", ws, ws_bytes, hw, &a);
+    if (rc != ABN_OK) return rc;
     static bool attr_set[16] = {};
-    if (first_use_on_device(attr_set)) {
-        const auto opt_in = [](const void* k) { (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GM_TILE_BYTES); };
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<1, false>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<2, false>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<4, false>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<8, false>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<16, false>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<1, true>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<2, true>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<4, true>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<8, true>));
-        opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<16, true>));
-    }
+    if (first_use_on_device(attr_set))
+        for_each_nq([](auto n) {
+            chain_opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<decltype(n)::value, false>), GM_TILE_BYTES);
+            chain_opt_in(reinterpret_cast<const void*>(hmm_fb_kernel<decltype(n)::value, true>), GM_TILE_BYTES);
+        });
     HmmP p;
-    p.g.x = x; p.g.shift = shift; p.g.A = A; p.g.B = B; p.g.c = c0;
-    p.g.T = (int)T; p.g.K = (int)K; p.g.D = (int)D;
-    p.g.lse = nullptr; p.g.post = nullptr; p.g.slabs = nullptr;
-    p.g.tiles_k = (int)((K + GM_B - 1) / GM_B); p.g.fblocks = 0; p.g.n_ranges = 0; p.g.blocks_per_range = 0;
+    p.g = hmm_score_params(x, T, D, shift, A, B, c0, K);
     p.w = w; p.off = off; p.len = len; p.n_utt = (int)n_utt;
     p.mode = mode; p.rho = rho;
     p.post = post; p.loglik = loglik; p.stays = stays; p.n_good = n_good; p.stay_k = stay_k;
-    p.ws = static_cast<char*>(ws); p.per_wg = per_wg;
-    p.ks = hw.ks; p.cap = (int)cap;
+    p.ws = a.ws; p.per_wg = a.per_wg;
+    p.ks = a.ks; p.cap = a.cap;
     const dim3 grid((unsigned)hw.grid);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int nq = 1;
-    while (nq * 256 < K) nq <<= 1;
-    if (stay_k) {
-        switch (nq) {
-        case 1: hipLaunchKernelGGL((hmm_fb_kernel<1, true>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-        case 2: hipLaunchKernelGGL((hmm_fb_kernel<2, true>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-        case 4: hipLaunchKernelGGL((hmm_fb_kernel<4, true>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-        case 8: hipLaunchKernelGGL((hmm_fb_kernel<8, true>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-        default: hipLaunchKernelGGL((hmm_fb_kernel<16, true>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-        }
-    } else {
-        switch (nq) {
-        case 1: hipLaunchKernelGGL((hmm_fb_kernel<1, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-        case 2: hipLaunchKernelGGL((hmm_fb_kernel<2, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-        case 4: hipLaunchKernelGGL((hmm_fb_kernel<4, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-        case 8: hipLaunchKernelGGL((hmm_fb_kernel<8, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-        default: hipLaunchKernelGGL((hmm_fb_kernel<16, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-        }
-    }
+    const int nq = nq_for(K);
+    for_each_nq([&](auto n) {
+        if (decltype(n)::value != nq) return;
+        if (stay_k) hipLaunchKernelGGL((hmm_fb_kernel<decltype(n)::value, true>), grid, dim3(256), GM_TILE_BYTES, st, p);
+        else hipLaunchKernelGGL((hmm_fb_kernel<decltype(n)::value, false>), grid, dim3(256), GM_TILE_BYTES, st, p);
+    });
     ABN_CHECK_LAUNCH(what);
     return ABN_OK;
 }
@@ -783,13 +730,7 @@ extern "C" int abn_hmm_forward_backward_stats(const float* x, int64_t T, int64_t
 
 extern "C" int64_t abn_hmm_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D)
 {
-    if (hmm_check_sizes(n_utt, K, D, "abn_hmm_viterbi_ws_bytes") != ABN_OK) return -1;
-    if (max_len < 0 || max_len > HM_MAX_LEN) {
-        set_error("abn_hmm_viterbi_ws_bytes: max_len = %lld, supported 0 .. %d (abn_hmm_max_len)", (long long)max_len, HM_MAX_LEN);
-        return -1;
-    }
-    const HmmVitWs w = hmm_vit_ws(n_utt, max_len, K);
-    return w.per_wg * w.grid;
+    return chain_ws_bytes("abn_hmm_viterbi_ws_bytes", n_utt, max_len, K, D, HM_LIMITS, vit_frame_bytes(K), 0);
 }
 
 extern "C" int abn_hmm_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
@@ -798,49 +739,20 @@ extern "C" int abn_hmm_viterbi(const float* x, int64_t T, int64_t D, const int64
                                int32_t* n_good, void* ws, int64_t ws_bytes, void* stream)
 {
     ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "abn_hmm_viterbi: T = %lld out of range", (long long)T);
-    const int rc = hmm_check_sizes(n_utt, K, D, "abn_hmm_viterbi");
+    int rc = chain_check_sizes("abn_hmm_viterbi", n_utt, K, D, HM_LIMITS);
     if (rc != ABN_OK) return rc;
     ABN_REQUIRE(x && off && len && shift && A && B && c0 && lw && ls && lr && ids, "abn_hmm_viterbi: null pointer");
-    const HmmVitWs w = hmm_vit_ws(n_utt, 0, K);
-    const int64_t per_wg = ws_bytes > 0 ? (ws_bytes / w.grid) & ~255LL : 0;
-    int64_t cap = (per_wg - w.slab_bytes) / w.per_frame;
-    if (!ws || cap < 1) {
-        set_error("abn_hmm_viterbi: workspace of %lld bytes holds no frame (abn_hmm_viterbi_ws_bytes)", (long long)ws_bytes);
-        return ABN_E_WORKSPACE;
-    }
-    ABN_REQUIRE(aligned16(ws), "abn_hmm_viterbi: the workspace must be 16-byte aligned");
-    if (cap > HM_MAX_LEN) cap = HM_MAX_LEN;
-    static bool attr_set[16] = {};
-    if (first_use_on_device(attr_set)) {
-        const auto opt_in = [](const void* k, size_t bytes) { (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
-        opt_in(reinterpret_cast<const void*>(hmm_viterbi_kernel<1, true>), HM_VIT_LDS_BYTES);
-        opt_in(reinterpret_cast<const void*>(hmm_viterbi_kernel<1, false>), GM_TILE_BYTES);
-        opt_in(reinterpret_cast<const void*>(hmm_viterbi_kernel<2, false>), GM_TILE_BYTES);
-        opt_in(reinterpret_cast<const void*>(hmm_viterbi_kernel<4, false>), GM_TILE_BYTES);
-        opt_in(reinterpret_cast<const void*>(hmm_viterbi_kernel<8, false>), GM_TILE_BYTES);
-        opt_in(reinterpret_cast<const void*>(hmm_viterbi_kernel<16, false>), GM_TILE_BYTES);
-    }
+    const ChainWs w = chain_ws(n_utt, 0, K, vit_frame_bytes(K), 0);
+    ChainRegion a;
+    rc = chain_region("abn_hmm_viterbi", "abn_hmm_viterbi_ws_bytes", ws, ws_bytes, w, &a);
+    if (rc != ABN_OK) return rc;
     HmmVitP p;
-    p.g.x = x; p.g.shift = shift; p.g.A = A; p.g.B = B; p.g.c = c0;
-    p.g.T = (int)T; p.g.K = (int)K; p.g.D = (int)D;
-    p.g.lse = nullptr; p.g.post = nullptr; p.g.slabs = nullptr;
-    p.g.tiles_k = (int)((K + GM_B - 1) / GM_B); p.g.fblocks = 0; p.g.n_ranges = 0; p.g.blocks_per_range = 0;
+    p.g = hmm_score_params(x, T, D, shift, A, B, c0, K);
     p.lw = lw; p.ls = ls; p.lr = lr; p.off = off; p.len = len; p.n_utt = (int)n_utt;
     p.ids = ids; p.log_prob = log_prob; p.n_switch = n_switch; p.n_good = n_good;
-    p.ws = static_cast<char*>(ws); p.per_wg = per_wg;
-    p.ks = w.ks; p.kw = w.kw; p.cap = (int)cap;
-    const dim3 grid((unsigned)w.grid);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (K <= GM_B) hipLaunchKernelGGL((hmm_viterbi_kernel<1, true>), grid, dim3(256), HM_VIT_LDS_BYTES, st, p);
-    else switch (w.kw / 4) {
-    case 1: hipLaunchKernelGGL((hmm_viterbi_kernel<1, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-    case 2: hipLaunchKernelGGL((hmm_viterbi_kernel<2, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-    case 4: hipLaunchKernelGGL((hmm_viterbi_kernel<4, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-    case 8: hipLaunchKernelGGL((hmm_viterbi_kernel<8, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-    default: hipLaunchKernelGGL((hmm_viterbi_kernel<16, false>), grid, dim3(256), GM_TILE_BYTES, st, p); break;
-    }
-    ABN_CHECK_LAUNCH("abn_hmm_viterbi");
-    return ABN_OK;
+    p.ws = a.ws; p.per_wg = a.per_wg;
+    p.ks = a.ks; p.kw = a.kw; p.cap = a.cap;
+    return vit_launch<HmmVitKernels>("abn_hmm_viterbi", p, K, w, GM_TILE_BYTES, HM_VIT_LDS_BYTES, stream);
 }
 
 static int hmm_acc_check(int64_t T, int64_t K, int64_t D, int n_ranges, const char* what)

@@ -1,6 +1,7 @@
 // kmeans.hip -- k-means vector quantisation: hard assignment and a deterministic update (abn_kmeans_assign,
 // abn_kmeans_accumulate, abn_kmeans_update), and the penalised segmentation of the ids (abn_kmeans_viterbi, at the end
-// of the file).  abnet3_amd/kmeans.py states the definitions; DESIGN.md sections 3.4d and 3.4e the shapes.
+// of the file; its host side is utt_chain.h's).  abnet3_amd/kmeans.py states the definitions; DESIGN.md
+// sections 3.4d and 3.4e the shapes.
 //
 // The score of frame t under centroid k is one row of a GEMM of depth D + 1,
 //   s[t][k] = sum_ka X~[t][ka] W~[k][ka],   X~ = [xc | 1],  W~ = [m | b],  xc = x - shift (fp32),  b = -|m|^2 / 2,
@@ -20,6 +21,7 @@
 // No floating-point atomics anywhere: every sum has one fixed order, two calls give the same bits.
 #include "common.h"
 #include "kmeans_tile.h"
+#include "utt_chain.h"
 #include "vit_wave.h"
 
 #include <limits.h>
@@ -301,8 +303,6 @@ static KmWs km_ws(const KmGrid& g, int64_t K, int64_t D)
 // The slab, the stay bits and prevj are written and read by this workgroup alone, on one CU, with a workgroup barrier
 // between: plain stores and plain loads are ordered there (the stale-line hazard is another CU's stores); the
 // per-workgroup regions are 256-byte aligned so that no cache line is shared between two workgroups.
-constexpr int KM_VIT_GRID = 256;           // one workgroup per CU (the score tile keeps the register file to itself)
-constexpr int KM_VIT_MAX_LEN = 1 << 20;
 constexpr int KM_VIT_LDS_KS = KM_B + 8;    // K <= 128: the slab lives in LDS behind the operand tiles; rows 136 floats apart, so
                                            // that the two half-waves of a deposit (4 rows apart) fall on different banks
 constexpr size_t KM_VIT_LDS_BYTES = KM_TILE_BYTES + sizeof(float) * KM_B * KM_VIT_LDS_KS;     // 140 KiB of the CU's 160
@@ -317,20 +317,9 @@ struct KmVitP {
     int ks, kw, cap;                        // slab row stride (floats), stay words per frame, frames the region holds
 };
 
-struct KmVitWs { int64_t slab_bytes, per_frame, per_wg; int grid, ks, kw; };
-static KmVitWs km_vit_ws(int64_t n_utt, int64_t max_len, int64_t K)
-{
-    KmVitWs w;
-    w.grid = (int)(n_utt < KM_VIT_GRID ? n_utt : KM_VIT_GRID);
-    w.ks = (int)((K + KM_B - 1) / KM_B) * KM_B;
-    int nq = 1;
-    while (nq * 256 < K) nq <<= 1;
-    w.kw = 4 * nq;
-    w.slab_bytes = (int64_t)sizeof(float) * KM_B * w.ks;
-    w.per_frame = 8LL * w.kw + 4;
-    w.per_wg = align_up(w.slab_bytes + max_len * w.per_frame + 8, 256);
-    return w;
-}
+static_assert(KM_B == UC_B, "utt_chain.h's geometry is this kernel's");
+constexpr ChainLimits KM_VIT_LIMITS = {KM_MAX_D, "abn_kmeans_max_d", KM_MAX_K, "abn_kmeans_viterbi_max_k", "abn_kmeans_viterbi_max_len"};
+constexpr int KM_VIT_TAIL = 8;             // bytes behind a region's prevj (part of what abn_kmeans_viterbi_ws_bytes has always returned)
 
 // The (score, index) key, its wave reduction and the traceback: vit_wave.h (shared with hmm.hip's abn_hmm_viterbi).
 template <int NQ, bool LDSS>
@@ -464,35 +453,20 @@ __global__ __launch_bounds__(256) void km_viterbi_kernel(KmVitP p)
     }
 }
 
+struct KmVitKernels {
+    template <int NQ, bool LDSS> static constexpr auto kernel() { return km_viterbi_kernel<NQ, LDSS>; }
+};
+
 }  // namespace abn
 
 using namespace abn;
 
-extern "C" int64_t abn_kmeans_viterbi_max_len(void) { return KM_VIT_MAX_LEN; }
+extern "C" int64_t abn_kmeans_viterbi_max_len(void) { return UC_MAX_LEN; }
 extern "C" int64_t abn_kmeans_viterbi_max_k(void) { return KM_MAX_K; }
-
-static int km_vit_check_sizes(int64_t n_utt, int64_t K, int64_t D, const char* what)
-{
-    ABN_REQUIRE(n_utt >= 1 && n_utt < (1LL << 31), "%s: n_utt = %lld out of range", what, (long long)n_utt);
-    ABN_REQUIRE(K >= 1 && D >= 1, "%s: K = %lld, D = %lld out of range", what, (long long)K, (long long)D);
-    if (D > KM_MAX_D || K > KM_MAX_K) {
-        set_error("%s: D = %lld, K = %lld, supported D <= %d (abn_kmeans_max_d), K <= %d (abn_kmeans_viterbi_max_k)", what,
-                  (long long)D, (long long)K, KM_MAX_D, KM_MAX_K);
-        return ABN_E_UNSUPPORTED;
-    }
-    return ABN_OK;
-}
 
 extern "C" int64_t abn_kmeans_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D)
 {
-    if (km_vit_check_sizes(n_utt, K, D, "abn_kmeans_viterbi_ws_bytes") != ABN_OK) return -1;
-    if (max_len < 0 || max_len > KM_VIT_MAX_LEN) {
-        set_error("abn_kmeans_viterbi_ws_bytes: max_len = %lld, supported 0 .. %d (abn_kmeans_viterbi_max_len)",
-                  (long long)max_len, KM_VIT_MAX_LEN);
-        return -1;
-    }
-    const KmVitWs w = km_vit_ws(n_utt, max_len, K);
-    return w.per_wg * w.grid;
+    return chain_ws_bytes("abn_kmeans_viterbi_ws_bytes", n_utt, max_len, K, D, KM_VIT_LIMITS, vit_frame_bytes(K), KM_VIT_TAIL);
 }
 
 extern "C" int abn_kmeans_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
@@ -500,50 +474,24 @@ extern "C" int abn_kmeans_viterbi(const float* x, int64_t T, int64_t D, const in
                                   int32_t* ids, double* objective, int32_t* n_switch, void* ws, int64_t ws_bytes, void* stream)
 {
     ABN_REQUIRE(T >= 1 && T < (1LL << 31) - KM_B, "abn_kmeans_viterbi: T = %lld out of range", (long long)T);
-    const int rc = km_vit_check_sizes(n_utt, K, D, "abn_kmeans_viterbi");
+    int rc = chain_check_sizes("abn_kmeans_viterbi", n_utt, K, D, KM_VIT_LIMITS);
     if (rc != ABN_OK) return rc;
     ABN_REQUIRE(x && off && len && shift && m && b && ids, "abn_kmeans_viterbi: null pointer");
     ABN_REQUIRE(penalty_score >= 0.0f && __builtin_isfinite(penalty_score),
                 "abn_kmeans_viterbi: penalty_score = %g, a finite value >= 0 is needed", (double)penalty_score);
-    const KmVitWs w = km_vit_ws(n_utt, 0, K);
-    const int64_t per_wg = ws_bytes > 0 ? (ws_bytes / w.grid) & ~255LL : 0;
-    int64_t cap = (per_wg - w.slab_bytes - 8) / w.per_frame;
-    if (!ws || cap < 1) {
-        set_error("abn_kmeans_viterbi: workspace of %lld bytes holds no frame (abn_kmeans_viterbi_ws_bytes)", (long long)ws_bytes);
-        return ABN_E_WORKSPACE;
-    }
-    ABN_REQUIRE(aligned16(ws), "abn_kmeans_viterbi: the workspace must be 16-byte aligned");
-    if (cap > KM_VIT_MAX_LEN) cap = KM_VIT_MAX_LEN;
-    static bool attr_set[16] = {};
-    if (first_use_on_device(attr_set)) {
-        const auto opt_in = [](const void* k, size_t bytes) { (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
-        opt_in(reinterpret_cast<const void*>(km_viterbi_kernel<1, true>), KM_VIT_LDS_BYTES);
-        opt_in(reinterpret_cast<const void*>(km_viterbi_kernel<1, false>), KM_TILE_BYTES);
-        opt_in(reinterpret_cast<const void*>(km_viterbi_kernel<2, false>), KM_TILE_BYTES);
-        opt_in(reinterpret_cast<const void*>(km_viterbi_kernel<4, false>), KM_TILE_BYTES);
-        opt_in(reinterpret_cast<const void*>(km_viterbi_kernel<8, false>), KM_TILE_BYTES);
-        opt_in(reinterpret_cast<const void*>(km_viterbi_kernel<16, false>), KM_TILE_BYTES);
-    }
+    const ChainWs w = chain_ws(n_utt, 0, K, vit_frame_bytes(K), KM_VIT_TAIL);
+    ChainRegion a;
+    rc = chain_region("abn_kmeans_viterbi", "abn_kmeans_viterbi_ws_bytes", ws, ws_bytes, w, &a);
+    if (rc != ABN_OK) return rc;
     KmVitP p;
     p.x = x; p.shift = shift; p.m = m; p.b = b; p.off = off; p.len = len;
     p.T = (int)T; p.K = (int)K; p.D = (int)D; p.n_utt = (int)n_utt;
     p.tiles_k = (int)((K + KM_B - 1) / KM_B);
     p.pen = penalty_score;
     p.ids = ids; p.objective = objective; p.n_switch = n_switch;
-    p.ws = static_cast<char*>(ws); p.per_wg = per_wg;
-    p.ks = w.ks; p.kw = w.kw; p.cap = (int)cap;
-    const dim3 grid((unsigned)w.grid);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (K <= KM_B) hipLaunchKernelGGL((km_viterbi_kernel<1, true>), grid, dim3(256), KM_VIT_LDS_BYTES, st, p);
-    else switch (w.kw / 4) {
-    case 1: hipLaunchKernelGGL((km_viterbi_kernel<1, false>), grid, dim3(256), KM_TILE_BYTES, st, p); break;
-    case 2: hipLaunchKernelGGL((km_viterbi_kernel<2, false>), grid, dim3(256), KM_TILE_BYTES, st, p); break;
-    case 4: hipLaunchKernelGGL((km_viterbi_kernel<4, false>), grid, dim3(256), KM_TILE_BYTES, st, p); break;
-    case 8: hipLaunchKernelGGL((km_viterbi_kernel<8, false>), grid, dim3(256), KM_TILE_BYTES, st, p); break;
-    default: hipLaunchKernelGGL((km_viterbi_kernel<16, false>), grid, dim3(256), KM_TILE_BYTES, st, p); break;
-    }
-    ABN_CHECK_LAUNCH("abn_kmeans_viterbi");
-    return ABN_OK;
+    p.ws = a.ws; p.per_wg = a.per_wg;
+    p.ks = a.ks; p.kw = a.kw; p.cap = a.cap;
+    return vit_launch<KmVitKernels>("abn_kmeans_viterbi", p, K, w, KM_TILE_BYTES, KM_VIT_LDS_BYTES, stream);
 }
 
 extern "C" int64_t abn_kmeans_max_d(void) { return KM_MAX_D; }

@@ -315,6 +315,30 @@ def _read_features(path):
     return {k: np.asarray(v, dtype=np.float32) for k, v in feats.items()}, times
 
 
+def _split_rows(table, names_and_lengths):
+    """{name: its rows of the host array `table`} for (name, length) pairs laid end to end."""
+    out, o = {}, 0
+    for k, n in names_and_lengths:
+        out[k] = table[o:o + int(n)]
+        o += int(n)
+    return out
+
+
+def _write_named(path, out, times, as_column=False):
+    """{name: array} as an .npz of name -> array or, for any other path, as an h5features file with the frame times
+    {name: [T]} (as_column: [T] ids go in as a [T, 1] float32 column)."""
+    if path.endswith('.npz'):
+        np.savez(path, **{str(k): v for k, v in out.items()})
+        return
+    if times is None:
+        raise ValueError('an h5features output needs the frame times: give an h5features input')
+    import h5features
+    names = list(out)
+    items = [out[k].astype(np.float32)[:, None] if as_column else out[k] for k in names]
+    with h5features.Writer(path) as wh:
+        wh.write(h5features.Data(names, [np.asarray(times[k]) for k in names], items), 'features')
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog='python -m abnet3_amd.gmm', description='Gaussian posteriorgrams of a feature file')
     sub = ap.add_subparsers(dest='cmd', required=True)
@@ -341,19 +365,8 @@ def main(argv=None):
         return 0
     g = GmmPosteriorgram.load(args.model)
     post = g.transform(feats).cpu().numpy()
-    out, o = {}, 0
-    for k, v in feats.items():
-        out[k] = post[o:o + v.shape[0]]
-        o += v.shape[0]
-    if args.out.endswith('.npz'):
-        np.savez(args.out, **{str(k): v for k, v in out.items()})
-    else:
-        if times is None:
-            raise ValueError('an h5features output needs the frame times: give an h5features input')
-        import h5features
-        names = list(out)
-        with h5features.Writer(args.out) as wh:
-            wh.write(h5features.Data(names, [np.asarray(times[k]) for k in names], [out[k] for k in names]), 'features')
+    out = _split_rows(post, ((k, v.shape[0]) for k, v in feats.items()))
+    _write_named(args.out, out, times)
     print('%d files, %d frames, K = %d -> %s' % (len(out), post.shape[0], post.shape[1], args.out))
     return 0
 

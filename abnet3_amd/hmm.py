@@ -95,6 +95,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import _utt
 from . import gmm as _gmm
 
 MODES = {'smooth': 0, 'filter': 1}
@@ -164,21 +165,7 @@ def forward_backward(table, off, lens, shift, A, B, c0, w, stay, mode='smooth', 
     if K < 1 or K > max_k():
         raise ValueError('hmm.forward_backward: K = %d, the kernel takes 1 .. %d (abn_hmm_max_k)' % (K, max_k()))
     rho = check_stay('hmm.forward_backward', stay, w.cpu().numpy())
-    host = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    off_h, len_h = host(off).astype(np.int64).ravel(), host(lens).astype(np.int64).ravel()
-    n_utt = len(off_h)
-    if len(len_h) != n_utt:
-        raise ValueError('hmm.forward_backward: %d offsets and %d lengths' % (n_utt, len(len_h)))
-    if n_utt and ((off_h < 0).any() or (len_h < 0).any() or (off_h + len_h > T).any()):
-        raise ValueError('hmm.forward_backward: an utterance lies outside the table\'s %d rows' % T)
-    if n_utt > 1:
-        order = np.argsort(off_h, kind='stable')
-        if (off_h[order][1:] < (off_h + len_h)[order][:-1]).any():
-            raise ValueError('hmm.forward_backward: utterances overlap')
-    longest = int(len_h.max()) if n_utt else 0
-    if longest > max_len():
-        raise ValueError('hmm.forward_backward: an utterance of %d frames, the kernel takes up to %d (abn_hmm_max_len)'
-                         % (longest, max_len()))
+    off_h, len_h, n_utt, longest = _utt.utterance_spans('hmm.forward_backward', off, lens, T, max_len(), 'abn_hmm_max_len')
     table = _gmm._check_table('hmm.forward_backward', table)
     _lib.require_device(shift, A, B, c0, w)
     if out is None:
@@ -191,12 +178,7 @@ def forward_backward(table, off, lens, shift, A, B, c0, w, stay, mode='smooth', 
     ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
     sk = torch.zeros((n_utt, K), dtype=torch.float64, device=table.device) if want_stay_k else None
     if T and n_utt and longest:
-        need = lib.abn_hmm_ws_bytes(n_utt, longest, K, D)
-        if need < 0:
-            raise ValueError('hmm.forward_backward: %s' % lib.abn_last_error().decode('utf-8', 'replace'))
-        ws = torch.empty(int(need), dtype=torch.uint8, device=table.device)
-        off_d = torch.from_numpy(off_h).to(table.device)
-        len_d = torch.from_numpy(len_h.astype(np.int32)).to(table.device)
+        ws, off_d, len_d = _utt.workspace('hmm.forward_backward', lib.abn_hmm_ws_bytes, off_h, len_h, longest, K, D, table.device)
         head = [_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B),
                 _lib.ptr(c0), _lib.ptr(w), K, rho, MODES[mode], _lib.ptr(out), _lib.ptr(ll), _lib.ptr(st), _lib.ptr(ng)]
         tail = [_lib.ptr(ws), ws.numel(), _lib.stream()]
@@ -260,20 +242,7 @@ def viterbi(table, off, lens, shift, A, B, c0, lw, ls, lr, ids=None, want_log_pr
     if K < 1 or K > max_k():
         raise ValueError('%s: K = %d, the kernel takes 1 .. %d (abn_hmm_max_k)' % (who, K, max_k()))
     _check_log_tables(who, lw, ls, lr, K)
-    host = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    off_h, len_h = host(off).astype(np.int64).ravel(), host(lens).astype(np.int64).ravel()
-    n_utt = len(off_h)
-    if len(len_h) != n_utt:
-        raise ValueError('%s: %d offsets and %d lengths' % (who, n_utt, len(len_h)))
-    if n_utt and ((off_h < 0).any() or (len_h < 0).any() or (off_h + len_h > T).any()):
-        raise ValueError('%s: an utterance lies outside the table\'s %d rows' % (who, T))
-    if n_utt > 1:
-        order = np.argsort(off_h, kind='stable')
-        if (off_h[order][1:] < (off_h + len_h)[order][:-1]).any():
-            raise ValueError('%s: utterances overlap' % who)
-    longest = int(len_h.max()) if n_utt else 0
-    if longest > max_len():
-        raise ValueError('%s: an utterance of %d frames, the kernel takes up to %d (abn_hmm_max_len)' % (who, longest, max_len()))
+    off_h, len_h, n_utt, longest = _utt.utterance_spans(who, off, lens, T, max_len(), 'abn_hmm_max_len')
     if ids is not None and (not isinstance(ids, torch.Tensor) or ids.shape != (T,) or ids.dtype != torch.int32 or
                             not ids.is_contiguous()):
         raise ValueError('%s: ids must be a contiguous [T] int32 tensor' % who)
@@ -286,12 +255,7 @@ def viterbi(table, off, lens, shift, A, B, c0, lw, ls, lr, ids=None, want_log_pr
     nsw = torch.zeros(n_utt, dtype=torch.int32, device=table.device) if want_log_prob else None
     ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
     if T and n_utt and longest:
-        need = lib.abn_hmm_viterbi_ws_bytes(n_utt, longest, K, D)
-        if need < 0:
-            raise ValueError('%s: %s' % (who, lib.abn_last_error().decode('utf-8', 'replace')))
-        ws = torch.empty(int(need), dtype=torch.uint8, device=table.device)
-        off_d = torch.from_numpy(off_h).to(table.device)
-        len_d = torch.from_numpy(len_h.astype(np.int32)).to(table.device)
+        ws, off_d, len_d = _utt.workspace(who, lib.abn_hmm_viterbi_ws_bytes, off_h, len_h, longest, K, D, table.device)
         _lib.check(lib.abn_hmm_viterbi(_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A),
                                        _lib.ptr(B), _lib.ptr(c0), _lib.ptr(lw), _lib.ptr(ls), _lib.ptr(lr), K, _lib.ptr(ids),
                                        _lib.ptr(lp), _lib.ptr(nsw), _lib.ptr(ng), _lib.ptr(ws), ws.numel(), _lib.stream()),
@@ -436,7 +400,7 @@ class StickyHmmPosteriorgram(object):
         return table, dc, np.asarray(lens, dtype=np.int64)
 
     def _run(self, table, lens, mode, stay=None, out=None, want_stays=True):
-        off = np.cumsum(lens) - lens
+        off = _utt.starts(lens)
         return forward_backward(table, off, lens, *self.device_tables(table.device),
                                 stay=self.stay_ if stay is None else stay, mode=mode, out=out, want_stays=want_stays)
 
@@ -457,7 +421,7 @@ class StickyHmmPosteriorgram(object):
         names = list(dc.names) if dc is not None else list(corpus) if isinstance(corpus, dict) else None
         shift, A, B, c0, w = self.device_tables(table.device)
         lw, ls, lr = (torch.from_numpy(a).to(table.device) for a in viterbi_tables(self.gmm.weights_, self.stay_))
-        off = np.cumsum(lens) - lens
+        off = _utt.starts(lens)
         ids, lp, nsw, ng = viterbi(table, off, lens, shift, A, B, c0, lw, ls, lr)
         self.last_log_prob_, self.last_n_switch_, self.last_n_good_ = lp.cpu().numpy(), nsw.cpu().numpy(), ng.cpu().numpy()
         self.n_bad_ = int(lens.sum() - self.last_n_good_.sum())
@@ -471,13 +435,7 @@ class StickyHmmPosteriorgram(object):
         ``last_n_switch_`` and ``last_n_good_`` (int32) hold the utterances' log joint probabilities, switch counts and
         good-frame counts; ``n_bad_`` the BAD frames."""
         ids, _, names, lens = self._decode_ids(corpus)
-        if names is None:
-            return ids
-        host, out, o = ids.cpu().numpy(), {}, 0
-        for k, n in zip(names, lens):
-            out[k] = host[o:o + int(n)]
-            o += int(n)
-        return out
+        return ids if names is None else _gmm._split_rows(ids.cpu().numpy(), zip(names, lens))
 
     def quantize(self, corpus):
         """Each frame replaced by the mean of its decoded component (uncentred: m + shift), [rows, D] float32 on the
@@ -542,7 +500,7 @@ class StickyHmmPosteriorgram(object):
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(table.device)
         shift = dev(g.shift_)
         scratch = torch.zeros((table.shape[0], K), dtype=torch.float32, device=table.device)
-        off = np.cumsum(lens) - lens
+        off = _utt.starts(lens)
         w, m, v, rho = g.weights_, g.means_ - shift64, g.variances_, self.stay_
         need_sums = bool(p & set('mvw'))
         self.log_likelihoods = []
@@ -644,16 +602,7 @@ def main(argv=None):
     if args.cmd == 'decode':
         from . import kmeans as _kmeans
         out = h.decode(feats)
-        if args.out.endswith('.npz'):
-            np.savez(args.out, **{str(k): v for k, v in out.items()})
-        else:
-            if times is None:
-                raise ValueError('an h5features output needs the frame times: give an h5features input')
-            import h5features
-            names = list(out)
-            with h5features.Writer(args.out) as wh:
-                wh.write(h5features.Data(names, [np.asarray(times[k]) for k in names],
-                                         [out[k].astype(np.float32)[:, None] for k in names]), 'features')
+        _gmm._write_named(args.out, out, times, as_column=True)
         n_good = int(h.last_n_good_.sum())
         if times is not None:
             seconds = sum(float(np.asarray(times[k])[-1] - np.asarray(times[k])[0]) for k in out if len(times[k]) > 1)
@@ -665,19 +614,8 @@ def main(argv=None):
                  int(h.last_n_switch_.sum()), rate, float(h.last_log_prob_.sum()) / max(n_good, 1), args.out))
         return 0
     post = h.transform(feats, args.mode).cpu().numpy()
-    out, o = {}, 0
-    for k, v in feats.items():
-        out[k] = post[o:o + v.shape[0]]
-        o += v.shape[0]
-    if args.out.endswith('.npz'):
-        np.savez(args.out, **{str(k): v for k, v in out.items()})
-    else:
-        if times is None:
-            raise ValueError('an h5features output needs the frame times: give an h5features input')
-        import h5features
-        names = list(out)
-        with h5features.Writer(args.out) as wh:
-            wh.write(h5features.Data(names, [np.asarray(times[k]) for k in names], [out[k] for k in names]), 'features')
+    out = _gmm._split_rows(post, ((k, v.shape[0]) for k, v in feats.items()))
+    _gmm._write_named(args.out, out, times)
     print('%d files, %d frames, K = %d, stay %.4f -> %s' % (len(out), post.shape[0], post.shape[1], h.stay_, args.out))
     return 0
 

@@ -73,6 +73,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import _utt
+from . import gmm as _gmm
 
 METRICS = ('euclidean', 'cosine')
 
@@ -159,7 +161,8 @@ def check_penalty(who, penalty):
 def viterbi(table, off, lens, shift, m, b, penalty, ids=None, want_objective=False):
     """(ids [T] int32, objective [n_utt] float64 or None, n_switch [n_utt] int32 or None) of the penalised segmentation
     the module docstring defines (abn_kmeans_viterbi, one launch).  off, lens: the utterances' first rows and lengths
-    (host sequences or device tensors).  Rows outside every utterance keep what `ids` held (-1 in a fresh `ids`)."""
+    (host sequences or device tensors); they must not overlap.  Rows outside every utterance keep what `ids` held (-1
+    in a fresh `ids`)."""
     lib = _lib.load()
     penalty = check_penalty('kmeans.viterbi', penalty)
     table = _check_table('kmeans.viterbi', table)
@@ -170,17 +173,7 @@ def viterbi(table, off, lens, shift, m, b, penalty, ids=None, want_objective=Fal
         raise ValueError('kmeans.viterbi: shift [D], m [K, D], b [K] float32 are needed')
     if K < 1 or K > viterbi_max_k():
         raise ValueError('kmeans.viterbi: K = %d, the kernel takes 1 .. %d (abn_kmeans_viterbi_max_k)' % (K, viterbi_max_k()))
-    host = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    off_h, len_h = host(off).astype(np.int64).ravel(), host(lens).astype(np.int64).ravel()
-    n_utt = len(off_h)
-    if len(len_h) != n_utt:
-        raise ValueError('kmeans.viterbi: %d offsets and %d lengths' % (n_utt, len(len_h)))
-    if n_utt and ((off_h < 0).any() or (len_h < 0).any() or (off_h + len_h > T).any()):
-        raise ValueError('kmeans.viterbi: an utterance lies outside the table\'s %d rows' % T)
-    max_len = int(len_h.max()) if n_utt else 0
-    if max_len > viterbi_max_len():
-        raise ValueError('kmeans.viterbi: an utterance of %d frames, the kernel takes up to %d (abn_kmeans_viterbi_max_len)'
-                         % (max_len, viterbi_max_len()))
+    off_h, len_h, n_utt, max_len = _utt.utterance_spans('kmeans.viterbi', off, lens, T, viterbi_max_len(), 'abn_kmeans_viterbi_max_len')
     if ids is None:
         ids = torch.full((T,), -1, dtype=torch.int32, device=table.device)
     if ids.shape != (T,) or ids.dtype != torch.int32 or not ids.is_contiguous():
@@ -189,12 +182,7 @@ def viterbi(table, off, lens, shift, m, b, penalty, ids=None, want_objective=Fal
     obj = torch.zeros(n_utt, dtype=torch.float64, device=table.device) if want_objective else None
     nsw = torch.zeros(n_utt, dtype=torch.int32, device=table.device) if want_objective else None
     if T and n_utt and max_len:
-        need = lib.abn_kmeans_viterbi_ws_bytes(n_utt, max_len, K, D)
-        if need < 0:
-            raise ValueError('kmeans.viterbi: %s' % lib.abn_last_error().decode('utf-8', 'replace'))
-        ws = torch.empty(int(need), dtype=torch.uint8, device=table.device)
-        off_d = torch.from_numpy(off_h).to(table.device)
-        len_d = torch.from_numpy(len_h.astype(np.int32)).to(table.device)
+        ws, off_d, len_d = _utt.workspace('kmeans.viterbi', lib.abn_kmeans_viterbi_ws_bytes, off_h, len_h, max_len, K, D, table.device)
         _lib.check(lib.abn_kmeans_viterbi(_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift),
                                           _lib.ptr(m), _lib.ptr(b), K, float(np.float32(penalty / 2.0)), _lib.ptr(ids),
                                           _lib.ptr(obj), _lib.ptr(nsw), _lib.ptr(ws), ws.numel(), _lib.stream()),
@@ -395,7 +383,7 @@ class KMeansQuantizer(object):
                 raise ValueError('KMeansQuantizer.segment: an utterance of %d frames, the kernel takes up to %d '
                                  '(abn_kmeans_viterbi_max_len); pass a corpus of utterances' % (int(lens.max()), viterbi_max_len()))
         table = _check_table('KMeansQuantizer.segment', table)
-        off = np.cumsum(lens) - lens
+        off = _utt.starts(lens)
         if self.metric == 'cosine':
             table = table / table.norm(dim=1, keepdim=True)
         shift, m, b, _ = self.device_tables(table.device)
@@ -405,13 +393,7 @@ class KMeansQuantizer(object):
 
     @staticmethod
     def _by_name(ids, rows):
-        if rows is None:
-            return ids
-        host, out, o = ids.cpu().numpy(), {}, 0
-        for k, n in rows.items():
-            out[k] = host[o:o + n]
-            o += n
-        return out
+        return ids if rows is None else _gmm._split_rows(ids.cpu().numpy(), rows.items())
 
     def segment(self, corpus, penalty):
         """The unit ids of the penalised segmentation (module docstring), in predict's forms.  Each file of a corpus is
@@ -537,9 +519,8 @@ def parser():
 
 
 def main(argv=None):
-    from .gmm import _read_features
     args = parser().parse_args(argv)
-    feats, times = _read_features(args.features)
+    feats, times = _gmm._read_features(args.features)
     if args.cmd == 'fit':
         q = KMeansQuantizer(args.n_clusters, args.n_iter, args.tol, args.metric, args.seed).fit(feats)
         q.save(args.model)
@@ -548,22 +529,10 @@ def main(argv=None):
         return 0
     q = KMeansQuantizer.load(args.model)
     if args.quantize:
-        table, out, o = q.quantize(feats, penalty=args.penalty).cpu().numpy(), {}, 0
-        for k, v in feats.items():
-            out[k] = table[o:o + v.shape[0]]
-            o += v.shape[0]
+        out = _gmm._split_rows(q.quantize(feats, penalty=args.penalty).cpu().numpy(), ((k, v.shape[0]) for k, v in feats.items()))
     else:
         out = q.predict(feats, penalty=args.penalty)
-    if args.out.endswith('.npz'):
-        np.savez(args.out, **{str(k): v for k, v in out.items()})
-    else:
-        if times is None:
-            raise ValueError('an h5features output needs the frame times: give an h5features input')
-        import h5features
-        names = list(out)
-        items = [out[k] if args.quantize else out[k].astype(np.float32)[:, None] for k in names]
-        with h5features.Writer(args.out) as wh:
-            wh.write(h5features.Data(names, [np.asarray(times[k]) for k in names], items), 'features')
+    _gmm._write_named(args.out, out, times, as_column=not args.quantize)
     print('%d files, %d frames, K = %d -> %s' % (len(out), sum(v.shape[0] for v in out.values()), q.n_clusters, args.out))
     return 0
 

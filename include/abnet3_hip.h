@@ -1010,7 +1010,8 @@ int abn_kmeans_update(const void* ws, int64_t ws_bytes, const int32_t* ids, int6
 
 /* ---- penalised unit segmentation (added within ABI 20) ---------------------------------------------------------------
  * The same scores s[t][k], smoothed by a constant cost per change of unit (abnet3_amd/kmeans.py states the recurrence):
- * utterance u is the len[u] rows from off[u] (off int64, len int32, device arrays); over its good frames the ids
+ * utterance u is the len[u] rows from off[u] (off int64, len int32, device arrays; utterances must not overlap: each
+ * is written by a workgroup of its own); over its good frames the ids
  * maximise  sum_t s[t][a_t] - penalty_score * #{changes}, penalty_score = penalty / 2 for a penalty in units of the
  * distortion |xc - m|^2.  BAD frames keep id -1 and cost nothing; rows outside every utterance keep what ids held.
  * objective [n_utt] float64 and n_switch [n_utt] int32 may be NULL.  penalty_score = 0 gives abn_kmeans_assign's ids.

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gmm_np  # noqa: E402
 import hmm_np  # noqa: E402
 import hmm_vit_np  # noqa: E402
+import units_np  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -117,6 +118,36 @@ def test_exact_inputs_with_components_of_weight_zero(K):
     c['s'] = (c['s'].astype(np.float64) + np.where(np.isneginf(c['lw']), 64.0, 0.0)).astype(np.float32)
     ids, lp, _, _ = check_exact(c, off, lens)
     assert np.isfinite(lp).all() and not np.isneginf(c['lw'])[ids[ids >= 0]].any()
+
+
+def test_both_max_product_chains_back_to_back_equal_their_restatements():
+    """The k-means and the HMM max-product chain (one workspace geometry, utt_chain.h's) on one corpus, launched back to
+    back on one stream with no synchronisation between: K = 130 puts both slabs in the workspace (ks = 256) with the same stay words per
+    frame, the k-means regions carry 8 bytes of tail and the HMM's none, 600 utterances are more than the workgroups, and
+    some are exactly 128 and 129 frames long.  Each must equal its numpy restatement bit for bit."""
+    from abnet3_amd import hmm, kmeans
+    K, D = 130, 8
+    rng = np.random.default_rng(130)
+    lens = np.concatenate([[1, 128, 129, 300, 128, 129], rng.integers(1, 48, size=590), [300, 257, 128, 129]])
+    rng.shuffle(lens)
+    off, T = layout(lens)
+    c = exact_case(T, K, D, seed=100 * K + D)
+    x, m, b, s = units_np.exact_case(T, K, D, seed=100 * K + D)
+    good = np.ones(T, dtype=bool)
+    ref_k = units_np.viterbi(s, good, off, lens, units_np.score_penalty(3.0))
+    ref_h = hmm_vit_np.viterbi(c['s'], good, off, lens, c['lw'], c['ls'], c['lr'])
+    shift = dev(np.zeros(D, dtype=np.float32))
+    args_k = (dev(x), off, lens, shift, dev(m), dev(b), 3.0)
+    args_h = (dev(c['x']), off, lens, shift) + tuple(dev(c[k]) for k in ('A', 'B', 'c0', 'lw', 'ls', 'lr'))
+    torch.cuda.synchronize()
+    for _ in range(2):                                                     # (the second round: each after the other's launch)
+        got_k = kmeans.viterbi(*args_k, ids=prefilled(T), want_objective=True)
+        got_h = hmm.viterbi(*args_h, ids=prefilled(T))
+        torch.cuda.synchronize()
+        for got, ref in ((got_k, ref_k), (got_h, ref_h)):
+            assert len(got) == len(ref)
+            for g, r in zip(got, ref):
+                assert np.array_equal(host(g), r), np.flatnonzero(host(g) != r)[:10]
 
 
 # ---- 2: stay = 0 against the mixture -------------------------------------------------------------------------------------

@@ -30,16 +30,7 @@ def host(t):
     return t.detach().cpu().numpy()
 
 
-def exact_case(T, K, D, seed):
-    """Integer frames in runs around integer centroids: (x [T, D], m [K, D], b [K], s [T, K] float32, all exact)."""
-    rng = np.random.default_rng(seed)
-    m = rng.integers(-2, 3, size=(K, D)).astype(np.float32)
-    lab = np.repeat(rng.integers(0, K, size=T // 3 + 1), 3)[:T]
-    x = (m[lab] + rng.integers(-1, 2, size=(T, D))).astype(np.float32)
-    b = (-0.5 * (m.astype(np.float64) ** 2).sum(axis=1)).astype(np.float32)
-    s = (x.astype(np.float64) @ m.astype(np.float64).T + b.astype(np.float64)).astype(np.float32)
-    assert np.array_equal(s.astype(np.float64), x.astype(np.float64) @ m.astype(np.float64).T + b.astype(np.float64))
-    return x, m, b, s
+exact_case = units_np.exact_case
 
 
 def layout(lengths, gap=2):
@@ -263,3 +254,5 @@ def test_corpus_through_segment_and_quantize_keeps_names_lengths_and_times():
         q.segment(torch.zeros(10, 5, device='cuda'), 1.0)
     with pytest.raises(ValueError, match='outside the table'):
         kmeans.viterbi(corpus.table, [0], [corpus.total + 1], *q.device_tables(corpus.table.device)[:3], 1.0)
+    with pytest.raises(ValueError, match='kmeans.viterbi: utterances overlap'):
+        kmeans.viterbi(corpus.table, [0, 2], [3, 2], *q.device_tables(corpus.table.device)[:3], 1.0)

@@ -268,6 +268,19 @@ def test_python_layer_refuses_on_the_host(lib):
     with pytest.raises(ValueError, match='abn_kmeans_viterbi_max_len'):
         q.segment(torch.zeros(kmeans.viterbi_max_len() + 1, 3), 1.0)
     assert q.last_objective_ is None and q.last_n_switch_ is None
+    # the refusal table of kmeans.viterbi's utterances (5 rows; the checks it shares with both HMM entries)
+    from abnet3_amd import _utt
+    spans = lambda off=(0, 3), lens=(3, 2), longest=kmeans.viterbi_max_len(): _utt.utterance_spans(
+        'kmeans.viterbi', off, lens, 5, longest, 'abn_kmeans_viterbi_max_len')
+    for kw, match in ((dict(lens=[3]), '2 offsets and 1 lengths'), (dict(lens=[3, 4]), 'outside the table\'s 5 rows'),
+                      (dict(off=[-1, 3]), 'outside the table'), (dict(off=[0, 2]), 'kmeans.viterbi: utterances overlap'),
+                      (dict(off=[2, 0], lens=[3, 3]), 'kmeans.viterbi: utterances overlap'),
+                      (dict(longest=2), 'of 3 frames, the kernel takes up to 2 \\(abn_kmeans_viterbi_max_len\\)')):
+        with pytest.raises(ValueError, match=match):
+            spans(**kw)
+    off_h, len_h, n_utt, longest = spans(off=torch.tensor([3, 0]), lens=[2, 3])          # touching, in any order: not an overlap
+    assert off_h.tolist() == [3, 0] and len_h.tolist() == [2, 3] and off_h.dtype == len_h.dtype == np.int64 and (n_utt, longest) == (2, 3)
+    assert spans(off=[], lens=[])[2:] == (0, 0) and _utt.starts([3, 0, 2]).tolist() == [0, 3, 3]
     ap = kmeans.parser()
     assert ap.parse_args(['transform', 'm.npz', 'f.npz', 'o.npz']).penalty is None
     assert ap.parse_args(['transform', 'm.npz', 'f.npz', 'o.npz', '--penalty', '2.5']).penalty == 2.5

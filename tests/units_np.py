@@ -181,3 +181,16 @@ def boundary_scores(found, gold, tolerance=0.02):
     r2 = abs((-OS + rec - 1.0) / np.sqrt(2.0))
     return {'precision': prec, 'recall': rec, 'f': F, 'os': OS, 'r_value': 1.0 - (r1 + r2) / 2.0,
             'n_found': n_found, 'n_gold': n_gold, 'n_hit': hits}
+
+
+def exact_case(T, K, D, seed):
+    """Exact inputs for the kernel's tests: integer frames in runs around integer centroids,
+    (x [T, D], m [K, D], b [K], s [T, K] float32), every fp32 operation of the score GEMM exact."""
+    rng = np.random.default_rng(seed)
+    m = rng.integers(-2, 3, size=(K, D)).astype(np.float32)
+    lab = np.repeat(rng.integers(0, K, size=T // 3 + 1), 3)[:T]
+    x = (m[lab] + rng.integers(-1, 2, size=(T, D))).astype(np.float32)
+    b = (-0.5 * (m.astype(np.float64) ** 2).sum(axis=1)).astype(np.float32)
+    s = (x.astype(np.float64) @ m.astype(np.float64).T + b.astype(np.float64)).astype(np.float32)
+    assert np.array_equal(s.astype(np.float64), x.astype(np.float64) @ m.astype(np.float64).T + b.astype(np.float64))
+    return x, m, b, s

@@ -12,9 +12,10 @@ minima and maxima.  Per workload, in the same process:
     torch route                per chunk of utterances the scores as a padded [utterances, max_len, K] torch.mm output, a
                                loop over time of batched torch ops with the same fp32 recurrence and a gather traceback;
                                its ids are compared with the kernel's
-  --parent-lib FILE          abn_hmm_forward_backward (mode 1) and abn_kmeans_viterbi of another build of the library (the
-                             parent commit's) timed alternately with this build's, 4 medians each, outputs compared bit
-                             for bit
+  --parent-lib FILE          abn_hmm_viterbi, abn_hmm_forward_backward (mode 1) and abn_kmeans_viterbi of another build of
+                             the library (the parent commit's) timed alternately with this build's, 4 medians each,
+                             outputs compared bit for bit; the bound on each ratio is 1 + twice the spread of the other
+                             build alternating with itself (hmm_fit_time.versus_parent)
 
 python tools/hmm_decode_time.py [--frames 1140000] [--stay 0.9] [--parent-lib FILE] [--out FILE]"""
 import argparse
@@ -27,7 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
 from gmm_time import median_ms
-from hmm_fit_time import alternate
+from hmm_fit_time import versus_parent
 from units_time import cut
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,9 +101,9 @@ def workload(T, D, K, a, parent):
     res = {'T': T, 'D': D, 'K': K, 'stay': rho, 'utterances': n_utt, 'max_len': max_len, 'workspace_bytes': ws_bytes,
            'score_matrix_bytes_never_formed': 4 * T * K}
 
-    def vit():
-        _lib.check(lib.abn_hmm_viterbi(p(table), T, D, p(off), p(lens), n_utt, p(shift), p(A), p(B), p(c0), p(lw), p(ls), p(lr), K,
-                                       p(ids), p(lp), p(nsw), p(ng), p(ws), ws.numel(), _lib.stream()), 'abn_hmm_viterbi')
+    def vit(which=lib, out=ids):
+        _lib.check(which.abn_hmm_viterbi(p(table), T, D, p(off), p(lens), n_utt, p(shift), p(A), p(B), p(c0), p(lw), p(ls), p(lr), K,
+                                         p(out), p(lp), p(nsw), p(ng), p(ws), ws.numel(), _lib.stream()), 'abn_hmm_viterbi')
 
     # ---- the sum-product twin (filter) and the floor: both write a [T][K] table --------------------------------------------
     fws = torch.empty(int(lib.abn_hmm_ws_bytes(n_utt, max_len, K, D)), dtype=torch.uint8, device='cuda')
@@ -151,25 +152,25 @@ def workload(T, D, K, a, parent):
     res['us_per_frame_step_upper_bound'] = round(ms * 1e3 / (T / float(groups)), 3)
 
     if parent is not None:
+        def same(fn, out, other, rest):
+            """`out` and the per-utterance outputs `rest` of fn under both builds"""
+            fn()
+            torch.cuda.synchronize()
+            mine = [t.clone() for t in rest]
+            fn(parent, other)
+            torch.cuda.synchronize()
+            return torch.equal(out, other) and all(torch.equal(m, t) for m, t in zip(mine, rest))
+
         other = torch.zeros((T, K), dtype=torch.float32, device='cuda')
-        blk = alternate(fb, lambda: fb(parent, other))
-        fb(), fb(parent, other)
-        torch.cuda.synchronize()
-        blk.update(first='this build', second='parent build', outputs_bit_identical=bool(torch.equal(post, other)),
-                   within_the_spread=bool(blk['ratio_of_medians'] <= 1.0 + blk['second_relative_spread']))
-        res['abn_hmm_forward_backward_vs_parent_build'] = blk
+        res['abn_hmm_forward_backward_vs_parent_build'] = versus_parent(fb, lambda: fb(parent, other),
+                                                                        lambda: same(fb, post, other, (ll, fng)))
         del other
-        okids = torch.full((T,), -1, dtype=torch.int32, device='cuda')
-        blk = alternate(kvit, lambda: kvit(parent, okids))
-        kvit()
-        torch.cuda.synchronize()
-        mine = (kobj.clone(), knsw.clone())
-        kvit(parent, okids)
-        torch.cuda.synchronize()
-        same = bool(torch.equal(kids, okids) and torch.equal(mine[0], kobj) and torch.equal(mine[1], knsw))
-        blk.update(first='this build', second='parent build', outputs_bit_identical=same,
-                   within_the_spread=bool(blk['ratio_of_medians'] <= 1.0 + blk['second_relative_spread']))
-        res['abn_kmeans_viterbi_vs_parent_build'] = blk
+        oids = torch.full((T,), -1, dtype=torch.int32, device='cuda')
+        res['abn_hmm_viterbi_vs_parent_build'] = versus_parent(vit, lambda: vit(parent, oids),
+                                                               lambda: same(vit, ids, oids, (lp, nsw, ng)))
+        res['abn_kmeans_viterbi_vs_parent_build'] = versus_parent(kvit, lambda: kvit(parent, oids),
+                                                                  lambda: same(kvit, kids, oids, (kobj, knsw)))
+        del oids
     del post, plain
     torch.cuda.empty_cache()
 
@@ -216,7 +217,7 @@ def main():
     if a.parent_lib:
         lib = _lib.load()
         parent = ctypes.CDLL(os.path.abspath(a.parent_lib))
-        for name in ('abn_hmm_forward_backward', 'abn_kmeans_viterbi'):
+        for name in ('abn_hmm_forward_backward', 'abn_hmm_viterbi', 'abn_kmeans_viterbi'):
             fn, own = getattr(parent, name), getattr(lib, name)
             fn.restype, fn.argtypes = own.restype, own.argtypes
     res = {'device': torch.cuda.get_device_name(0), 'calls_per_median': 15,

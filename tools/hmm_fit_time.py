@@ -12,8 +12,10 @@ same seeded utterances and mixture); every route settles the clock (untimed call
   stats entry                abn_hmm_forward_backward_stats against abn_hmm_forward_backward (mode 0), alternating
   fit iteration              one iteration of StickyHmmPosteriorgram.fit, read-back and host M-step included (wall clock),
                              against the forward-backward launch alone
-  --parent-lib FILE          abn_hmm_forward_backward of another build of the library (the parent commit's) timed
-                             alternately with this build's, `repeats` medians each, outputs compared bit for bit
+  --parent-lib FILE          abn_hmm_forward_backward (mode 0) and abn_hmm_forward_backward_stats of another build of the
+                             library (the parent commit's) timed alternately with this build's, `repeats` medians each,
+                             outputs compared bit for bit; the other build alternating with itself gives the spread, and
+                             the bound on the ratio is 1 + twice that spread
 
 python tools/hmm_fit_time.py [--frames 1140000] [--stay 0.9] [--parent-lib FILE] [--out FILE]"""
 import argparse
@@ -43,6 +45,20 @@ def alternate(this_fn, other_fn, repeats=4):
     spread = (max(b) - min(b)) / float(np.median(b))
     return {'first_ms': a, 'second_ms': b, 'ratio_of_medians': round(float(np.median(a) / np.median(b)), 4),
             'second_relative_spread': round(spread, 4)}
+
+
+def versus_parent(this_fn, parent_fn, same):
+    """This build against the parent build, alternating, and the parent build against itself the same way: its spread is
+    (max - min) / median over the 2 x `repeats` medians of that second run, the bound on the ratio 1 + twice the spread.
+    same(): whether the two builds' outputs are bit-identical (it runs both once more)."""
+    blk = alternate(this_fn, parent_fn)
+    own = alternate(parent_fn, parent_fn)
+    ms = own['first_ms'] + own['second_ms']
+    spread = (max(ms) - min(ms)) / float(np.median(ms))
+    blk.update(first='this build', second='parent build', parent_against_itself_ms=ms, parent_spread=round(spread, 4),
+               bound=round(1.0 + 2.0 * spread, 4), outputs_bit_identical=bool(same()))
+    blk['within_the_bound'] = bool(blk['ratio_of_medians'] <= blk['bound'])
+    return blk
 
 
 def workload(T, D, K, a, parent):
@@ -75,20 +91,29 @@ def workload(T, D, K, a, parent):
     def fb(which=lib, out=post):
         _lib.check(which.abn_hmm_forward_backward(*(head(out) + tail)), 'abn_hmm_forward_backward')
 
-    def fb_stats():
-        _lib.check(lib.abn_hmm_forward_backward_stats(*(head(post) + [p(sk)] + tail)), 'abn_hmm_forward_backward_stats')
+    def fb_stats(which=lib, out=post):
+        _lib.check(which.abn_hmm_forward_backward_stats(*(head(out) + [p(sk)] + tail)), 'abn_hmm_forward_backward_stats')
 
     # ---- the stats entry against the plain one ------------------------------------------------------------------------
     fb(), fb_stats()
     res['stats_entry_vs_plain'] = dict(alternate(fb_stats, fb), first='abn_hmm_forward_backward_stats', second='abn_hmm_forward_backward')
     if parent is not None:
         other = torch.zeros((T, K), dtype=torch.float32, device='cuda')
-        blk = alternate(fb, lambda: fb(parent, other))
-        fb(), fb(parent, other)
-        torch.cuda.synchronize()
-        blk.update(first='this build', second='parent build', outputs_bit_identical=bool(torch.equal(post, other)),
-                   within_the_spread=bool(blk['ratio_of_medians'] <= 1.0 + blk['second_relative_spread']))
-        res['abn_hmm_forward_backward_vs_parent_build'] = blk
+
+        def same(fn):
+            """post, loglik, stays, n_good and stay_k of fn under both builds"""
+            sk.zero_()
+            fn()
+            torch.cuda.synchronize()
+            mine = [t.clone() for t in (ll, st, ng, sk)]
+            sk.zero_()
+            fn(parent, other)
+            torch.cuda.synchronize()
+            return torch.equal(post, other) and all(torch.equal(m, t) for m, t in zip(mine, (ll, st, ng, sk)))
+
+        res['abn_hmm_forward_backward_vs_parent_build'] = versus_parent(fb, lambda: fb(parent, other), lambda: same(fb))
+        res['abn_hmm_forward_backward_stats_vs_parent_build'] = versus_parent(fb_stats, lambda: fb_stats(parent, other),
+                                                                              lambda: same(fb_stats))
         del other
 
     # ---- abn_hmm_accumulate -------------------------------------------------------------------------------------------
@@ -178,8 +203,9 @@ def main():
     if a.parent_lib:
         lib = _lib.load()
         parent = ctypes.CDLL(os.path.abspath(a.parent_lib))
-        fn, own = parent.abn_hmm_forward_backward, lib.abn_hmm_forward_backward
-        fn.restype, fn.argtypes = own.restype, own.argtypes
+        for name in ('abn_hmm_forward_backward', 'abn_hmm_forward_backward_stats'):
+            fn, own = getattr(parent, name), getattr(lib, name)
+            fn.restype, fn.argtypes = own.restype, own.argtypes
     res = {'device': torch.cuda.get_device_name(0), 'calls_per_median': 15, 'hbm_peak_bytes_per_s': HBM_PEAK,
            'protocol': 'settle 0.3 s of untimed calls, then the median of 15 device-event timings per route; alternating routes '
                        'take 4 medians each in one process',
