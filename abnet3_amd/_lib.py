@@ -1,4 +1,4 @@
-"""ctypes binding of libabnet3_hip.so (include/abnet3_hip.h).
+"""ctypes binding of libabnet3_hip.so (include/abnet3_hip.h, include/abnet3_hip_next.h).
 
 There is no CPU fallback: if the shared object is missing or a tensor is not
 on a HIP device the call fails loudly.  torch is imported first so that the
@@ -165,6 +165,13 @@ SYMBOLS = {
     'abn_sd_collect': (C.c_int, [_vp, _i64, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'abn_sd_count': (C.c_int, [_vp, _i64, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _i64, _vp, _vp, _vp]),
 }
+# every symbol include/abnet3_hip_next.h declares (prefix abnx_: entries that are not part of the numbered ABI yet; a later
+# change folds them into abnet3_hip.h and SYMBOLS): the twins' arguments plus int32 min_duration at the end
+NEXT_SYMBOLS = {
+    'abnx_viterbi_dur_max': (_i32, []),
+    'abnx_kmeans_viterbi_dur': (C.c_int, SYMBOLS['abn_kmeans_viterbi'][1] + [_i32]),
+    'abnx_hmm_viterbi_dur': (C.c_int, SYMBOLS['abn_hmm_viterbi'][1] + [_i32]),
+}
 # abn_sd_count's conditions and the limits of abn_sd_collect / abn_sd_count (include/abnet3_hip.h)
 SD_CONDITION = {'all': 0, 'swdp': 1, 'swsp': 2}
 SD_MAX_N, SD_MAX_THR, SD_MAX_D = 1 << 22, 1 << 30, 4096
@@ -228,7 +235,7 @@ def load():
             'abnet3_amd: %s is missing. Build it with `python -m abnet3_amd.build` '
             '(hipcc, gfx950). There is no CPU fallback.' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(NEXT_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -1,5 +1,6 @@
 """What the per-utterance entries (kmeans.viterbi, hmm.forward_backward, hmm.viterbi) share on the host: the checks of
-the utterances' offsets and lengths, and the workspace with the offsets and lengths uploaded beside it."""
+the utterances' offsets and lengths and of a minimum duration, and the workspace with the offsets and lengths uploaded
+beside it."""
 import numpy as np
 import torch
 
@@ -31,6 +32,20 @@ def utterance_spans(who, off, lens, T, longest_allowed, limit_name):
     if longest > longest_allowed:
         raise ValueError('%s: an utterance of %d frames, the kernel takes up to %d (%s)' % (who, longest, longest_allowed, limit_name))
     return off_h, len_h, n_utt, longest
+
+
+def viterbi_dur_max():
+    """The largest minimum duration the max-product kernels take (abnx_viterbi_dur_max)."""
+    return int(_lib.load().abnx_viterbi_dur_max())
+
+
+def check_min_duration(who, min_duration):
+    """min_duration as an int, or ValueError: an integer 1 .. viterbi_dur_max()."""
+    if isinstance(min_duration, bool) or not isinstance(min_duration, (int, np.integer)) or \
+            not 1 <= int(min_duration) <= viterbi_dur_max():
+        raise ValueError('%s: min_duration = %r, an integer 1 .. %d is needed (abnx_viterbi_dur_max)'
+                         % (who, min_duration, viterbi_dur_max()))
+    return int(min_duration)
 
 
 def workspace(who, ws_bytes_fn, off_h, len_h, longest, K, D, device):

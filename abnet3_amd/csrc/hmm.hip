@@ -26,6 +26,7 @@
 #include "gmm_tile.h"
 #include "utt_chain.h"
 #include "vit_wave.h"
+#include "../../include/abnet3_hip_next.h"
 
 #include <math.h>
 
@@ -655,6 +656,172 @@ struct HmmVitKernels {
     template <int NQ, bool LDSS> static constexpr auto kernel() { return hmm_viterbi_kernel<NQ, LDSS>; }
 };
 
+// ---- max-product path with a minimum duration (abnx_hmm_viterbi_dur) -----------------------------------------------------
+// hmm_viterbi_kernel's twin for the minimum-duration topology (vit_wave.h: every component a left-to-right chain of S
+// states with tied emissions): the same persistent workgroups, score slab, stay words and prevj, and so the same
+// workspace.  Thread t keeps the chains of its components in V[NQ][SC] registers, SC the capacity the kernel is
+// instantiated with (the smallest of 1, 2, 4, 8 that holds S).  A frame needs two reductions before its one barrier: the
+// keyed max over the exit states (E and the exit j*, which prevj records) and the max over all states (N_t).  After the
+// last frame one more keyed max finds the final state, and wave 0 walks back with vit_traceback_dur.
+struct HmmVitDurP { HmmVitP v; int S; };
+
+template <int NQ, bool LDSS, int SC>
+__global__ __launch_bounds__(256) void hmm_viterbi_dur_kernel(HmmVitDurP pd)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ int bad_s[GM_B];
+    __shared__ unsigned long long red_k[2][4];
+    __shared__ float red_n[2][4];
+
+    const HmmVitP& p = pd.v;
+    const int S = pd.S, e0 = SC - S;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    char* const base = p.ws + (int64_t)blockIdx.x * p.per_wg;
+    float* const slab = LDSS ? smem + 4 * GmTile::floats : reinterpret_cast<float*>(base);
+    const int ks = LDSS ? HM_VIT_LDS_KS : p.ks;
+    unsigned long long* const stay = reinterpret_cast<unsigned long long*>(base + (int64_t)sizeof(float) * GM_B * p.ks);
+    int* const prevj = reinterpret_cast<int*>(stay + (int64_t)p.cap * p.kw);
+    const int K = p.g.K;
+    constexpr int PARK = vit_dur_parked<NQ, SC>(LDSS);
+    float* const park = smem + 4 * GmTile::floats;                    // behind the operand tiles (where the LDS slab would be)
+
+    for (int u = (int)blockIdx.x; u < p.n_utt; u += (int)gridDim.x) {
+        const int64_t o = p.off[u];
+        const int L = p.len[u];
+        if (o < 0 || L < 0 || o + L > p.g.T || L > p.cap) {          // (uniform) nothing of this utterance is touched
+            if (t == 0) {
+                if (p.log_prob) p.log_prob[u] = NAN;
+                if (p.n_switch) p.n_switch[u] = -1;
+                if (p.n_good) p.n_good[u] = -1;
+            }
+            continue;
+        }
+        float V[NQ][SC];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+#pragma unroll
+            for (int j = 0; j < SC; ++j) V[q][j] = -INFINITY;
+        bool started = false;
+        float E = 0.0f;
+        int jprev = -1, par = 0, ngood = 0;
+        double lp = 0.0;
+
+        for (int f0 = 0; f0 < L; f0 += GM_B) {
+            const int nf = min(GM_B, L - f0);
+            vit_dur_park<PARK>(V, park, t);
+            hmm_vit_scores(p.g, (int)o + f0, nf, smem, slab, ks, bad_s);
+            vit_dur_unpark<PARK>(V, park, t);
+
+            // The tables are read again per block, not kept across the score tile, and neither are the 4 NQ addresses of these
+            // loads: tb is t behind an empty asm, so the compiler cannot hoist them out of the loops as invariants (it did,
+            // and spilled them to scratch).
+            int tb = t;
+            asm volatile("" : "+v"(tb));
+            float lw[NQ], ls[NQ], lr[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int k = 256 * q + tb;
+                lw[q] = k < K ? p.lw[k] : 0.0f;
+                ls[q] = k < K ? p.ls[k] : 0.0f;
+                lr[q] = k < K ? p.lr[k] : 0.0f;
+            }
+            float sn[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) sn[q] = 256 * q + tb < K ? slab[256 * q + tb] : -INFINITY;
+            for (int f = 0; f < nf; ++f) {
+                const int g = f0 + f;
+                float s[NQ];
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) s[q] = sn[q];
+                if (f + 1 < nf) {
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) sn[q] = 256 * q + t < K ? slab[(int64_t)(f + 1) * ks + 256 * q + t] : -INFINITY;
+                }
+                if (bad_s[f]) {                                       // (uniform) the chain passes over it
+                    if (t == 0) prevj[g] = -2;
+                    continue;
+                }
+                unsigned long long key = 0;                           // (below the key of -inf)
+                float nmax = -INFINITY;
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {                        // (k >= K: s = -inf, so every state stays -inf)
+                    const int k = 256 * q + t;
+                    const float ent = started ? E + lr[q] : lw[q];
+                    bool st;
+                    const float m = vit_dur_step<SC>(V[q], s[q], ent, ls[q], e0, &st);
+                    const unsigned long long word = __ballot(st);
+                    if (lane == 0) stay[(int64_t)g * p.kw + 4 * q + wave] = word;
+                    nmax = fmaxf(nmax, m);
+                    const unsigned long long kq = vit_key(V[q][SC - 1], k);
+                    key = kq > key ? kq : key;
+                }
+                key = vit_wave_max(key);
+                if (SC > 1) nmax = vit_wave_fmax(nmax);
+                if (lane == 0) {
+                    red_k[par][wave] = key;
+                    if (SC > 1) red_n[par][wave] = nmax;
+                }
+                __syncthreads();
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned long long ok = red_k[par][w];
+                    key = ok > key ? ok : key;
+                    if (SC > 1) nmax = fmaxf(nmax, red_n[par][w]);
+                }
+                par ^= 1;                                             // (the other set is not rewritten before the next barrier)
+                const float xv = vit_key_score(key);
+                const float nv = SC > 1 ? nmax : xv;                  // (one state per component: the exit max is the max)
+                int bi = (int)~(unsigned)key;
+                if ((unsigned)bi >= (unsigned)K) bi = 0;              // no score compared greater than -inf: still an id
+#pragma unroll
+                for (int q = 0; q < NQ; ++q)
+#pragma unroll
+                    for (int j = 0; j < SC; ++j) V[q][j] -= nv;
+                E = xv - nv;
+                lp += (double)nv;
+                if (t == 0) prevj[g] = jprev;
+                jprev = bi;
+                started = true;
+                ++ngood;
+            }
+            __syncthreads();                                          // before the next block's scores replace these
+        }
+
+        int fcode = -1;                                               // the final state: the lowest k, then the largest slot, at 0
+#pragma unroll
+        for (int q = NQ - 1; q >= 0; --q) fcode = vit_dur_final_code<SC>(V[q], q, fcode);
+        unsigned long long fkey = vit_wave_max(vit_dur_final_key<SC>(fcode, t));
+        if (lane == 0) red_k[par][wave] = fkey;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const unsigned long long ok = red_k[par][w];
+            fkey = ok > fkey ? ok : fkey;
+        }
+
+        if (wave == 0) {                                              // traceback from the final state
+            int cur = -1, forced = 0;
+            if (started && fkey) {
+                cur = vit_dur_final_k(fkey);
+                const int i = vit_dur_final_slot(fkey) - e0;
+                forced = i == S - 1 ? 0 : i + 1;
+            }
+            const int nsw = vit_traceback_dur(stay, prevj, p.kw, p.ids, o, L, S, cur, forced, lane);
+            if (lane == 0) {
+                if (p.log_prob) p.log_prob[u] = lp;
+                if (p.n_switch) p.n_switch[u] = nsw;
+                if (p.n_good) p.n_good[u] = ngood;
+            }
+        }
+        __syncthreads();                                              // the traceback's reads before the next utterance's writes
+    }
+}
+
+template <int SC>
+struct HmmVitDurKernels {
+    template <int NQ, bool LDSS> static constexpr auto kernel() { return hmm_viterbi_dur_kernel<NQ, LDSS, SC>; }
+};
+
 }  // namespace abn
 
 using namespace abn;
@@ -753,6 +920,37 @@ extern "C" int abn_hmm_viterbi(const float* x, int64_t T, int64_t D, const int64
     p.ws = a.ws; p.per_wg = a.per_wg;
     p.ks = a.ks; p.kw = a.kw; p.cap = a.cap;
     return vit_launch<HmmVitKernels>("abn_hmm_viterbi", p, K, w, GM_TILE_BYTES, HM_VIT_LDS_BYTES, stream);
+}
+
+// abn_hmm_viterbi with a minimum duration (include/abnet3_hip_next.h): its checks in its order, then min_duration; the
+// workspace is abn_hmm_viterbi_ws_bytes'.
+extern "C" int abnx_hmm_viterbi_dur(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                                    const float* shift, const float* A, const float* B, const float* c0, const float* lw,
+                                    const float* ls, const float* lr, int64_t K, int32_t* ids, double* log_prob,
+                                    int32_t* n_switch, int32_t* n_good, void* ws, int64_t ws_bytes, void* stream, int32_t min_duration)
+{
+    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "abnx_hmm_viterbi_dur: T = %lld out of range", (long long)T);
+    int rc = chain_check_sizes("abnx_hmm_viterbi_dur", n_utt, K, D, HM_LIMITS);
+    if (rc != ABN_OK) return rc;
+    ABN_REQUIRE(x && off && len && shift && A && B && c0 && lw && ls && lr && ids, "abnx_hmm_viterbi_dur: null pointer");
+    ABN_REQUIRE(min_duration >= 1 && min_duration <= VIT_DUR_MAX, "abnx_hmm_viterbi_dur: min_duration = %d, 1 .. %d (abnx_viterbi_dur_max)",
+                (int)min_duration, VIT_DUR_MAX);
+    const ChainWs w = chain_ws(n_utt, 0, K, vit_frame_bytes(K), 0);
+    ChainRegion a;
+    rc = chain_region("abnx_hmm_viterbi_dur", "abn_hmm_viterbi_ws_bytes", ws, ws_bytes, w, &a);
+    if (rc != ABN_OK) return rc;
+    HmmVitDurP p;
+    p.v.g = hmm_score_params(x, T, D, shift, A, B, c0, K);
+    p.v.lw = lw; p.v.ls = ls; p.v.lr = lr; p.v.off = off; p.v.len = len; p.v.n_utt = (int)n_utt;
+    p.v.ids = ids; p.v.log_prob = log_prob; p.v.n_switch = n_switch; p.v.n_good = n_good;
+    p.v.ws = a.ws; p.v.per_wg = a.per_wg;
+    p.v.ks = a.ks; p.v.kw = a.kw; p.v.cap = a.cap;
+    p.S = min_duration;
+    const char* what = "abnx_hmm_viterbi_dur";
+    if (min_duration == 1) return vit_launch<HmmVitDurKernels<1>>(what, p, K, w, GM_TILE_BYTES + VIT_DUR_PARK_BYTES, HM_VIT_LDS_BYTES, stream);
+    if (min_duration == 2) return vit_launch<HmmVitDurKernels<2>>(what, p, K, w, GM_TILE_BYTES + VIT_DUR_PARK_BYTES, HM_VIT_LDS_BYTES, stream);
+    if (min_duration <= 4) return vit_launch<HmmVitDurKernels<4>>(what, p, K, w, GM_TILE_BYTES + VIT_DUR_PARK_BYTES, HM_VIT_LDS_BYTES, stream);
+    return vit_launch<HmmVitDurKernels<8>>(what, p, K, w, GM_TILE_BYTES + VIT_DUR_PARK_BYTES, HM_VIT_LDS_BYTES, stream);
 }
 
 static int hmm_acc_check(int64_t T, int64_t K, int64_t D, int n_ranges, const char* what)

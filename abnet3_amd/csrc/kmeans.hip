@@ -23,6 +23,7 @@
 #include "kmeans_tile.h"
 #include "utt_chain.h"
 #include "vit_wave.h"
+#include "../../include/abnet3_hip_next.h"
 
 #include <limits.h>
 #include <math.h>
@@ -457,6 +458,194 @@ struct KmVitKernels {
     template <int NQ, bool LDSS> static constexpr auto kernel() { return km_viterbi_kernel<NQ, LDSS>; }
 };
 
+// ---- penalised segmentation with a minimum duration (abnx_kmeans_viterbi_dur) ------------------------------------------
+// km_viterbi_kernel's twin for the minimum-duration topology (vit_wave.h: every centroid a left-to-right chain of S
+// states over the same score), with the tables lw = 0, ls = 0, lr = -pen: the same persistent workgroups, score slab,
+// stay words and prevj, and so the same workspace.  Thread t keeps the chains of its centroids in V[NQ][SC] registers,
+// SC the capacity the kernel is instantiated with (the smallest of 1, 2, 4, 8 that holds S).  A frame needs two
+// reductions before its one barrier: the keyed max over the exit states (E and the exit j*, which prevj records) and the
+// max over all states (N_t).  After the last frame one more keyed max finds the final state, and wave 0 walks back with
+// vit_traceback_dur.
+struct KmVitDurP { KmVitP v; int S; };
+
+template <int NQ, bool LDSS, int SC>
+__global__ __launch_bounds__(256) void km_viterbi_dur_kernel(KmVitDurP pd)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const As = smem;
+    float* const Bs = smem + 2 * KmTile::floats;
+    __shared__ int bad_s[KM_B];
+    __shared__ unsigned long long red_k[2][4];
+    __shared__ float red_n[2][4];
+
+    const KmVitP& p = pd.v;
+    const int S = pd.S, e0 = SC - S;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
+    char* const base = p.ws + (int64_t)blockIdx.x * p.per_wg;
+    float* const slab = LDSS ? smem + 4 * KmTile::floats : reinterpret_cast<float*>(base);
+    const int ks = LDSS ? KM_VIT_LDS_KS : p.ks;
+    unsigned long long* const stay = reinterpret_cast<unsigned long long*>(base + (int64_t)sizeof(float) * KM_B * p.ks);
+    int* const prevj = reinterpret_cast<int*>(stay + (int64_t)p.cap * p.kw);
+    const float lr = -p.pen;
+    constexpr int PARK = vit_dur_parked<NQ, SC>(LDSS);
+    float* const park = smem + 4 * KmTile::floats;                    // behind the operand tiles (where the LDS slab would be)
+
+    KmP kp;
+    kp.x = p.x; kp.shift = p.shift; kp.m = p.m; kp.b = p.b;
+    kp.T = p.T; kp.K = p.K; kp.D = p.D;
+    kp.ids = nullptr; kp.prev = nullptr; kp.best = nullptr; kp.changed = nullptr;
+    kp.tiles_k = p.tiles_k;
+
+    for (int u = (int)blockIdx.x; u < p.n_utt; u += (int)gridDim.x) {
+        const int64_t o = p.off[u];
+        const int L = p.len[u];
+        if (o < 0 || L < 0 || o + L > p.T || L > p.cap) {            // (uniform) nothing of this utterance is touched
+            if (t == 0) {
+                if (p.objective) p.objective[u] = NAN;
+                if (p.n_switch) p.n_switch[u] = -1;
+            }
+            continue;
+        }
+        float V[NQ][SC];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+#pragma unroll
+            for (int j = 0; j < SC; ++j) V[q][j] = -INFINITY;
+        bool started = false;
+        float E = 0.0f;
+        int jprev = -1, par = 0;
+        double obj = 0.0;
+
+        for (int f0 = 0; f0 < L; f0 += KM_B) {
+            const int m0 = (int)o + f0;
+            const int nf = min(KM_B, L - f0);
+            vit_dur_park<PARK>(V, park, t);
+            if (t < KM_B) {
+                bool bad = false;
+                if (t < nf)
+                    for (int d = 0; d < p.D; ++d) {
+                        const float xc = p.x[(int64_t)(m0 + t) * p.D + d] - p.shift[d];
+                        bad |= !__builtin_isfinite(xc * xc);
+                    }
+                bad_s[t] = bad;
+            }
+            for (int ct = 0; ct < p.tiles_k; ++ct) {
+                const int n0 = ct * KM_B;
+                f32x16 acc[2][2];
+                km_score_tile(kp, m0, n0, As, Bs, acc);
+                const int col_l = lane & 31, rsub = 4 * (lane >> 5);
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            slab[(int64_t)(wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + rsub) * ks + n0 + wn0 + 32 * j + col_l] =
+                                acc[i][j][r];
+            }
+            __syncthreads();                                          // the slab and bad_s are this workgroup's own
+            vit_dur_unpark<PARK>(V, park, t);
+
+            // tb is t behind an empty asm: the NQ addresses of these loads are then no loop invariants, which the compiler
+            // would keep for the whole kernel (it did, and spilled them to scratch).
+            int tb = t;
+            asm volatile("" : "+v"(tb));
+            float sn[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) sn[q] = 256 * q + tb < p.K ? slab[256 * q + tb] : -INFINITY;
+            for (int f = 0; f < nf; ++f) {
+                const int g = f0 + f;
+                float s[NQ];
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) s[q] = sn[q];
+                if (f + 1 < nf) {
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) sn[q] = 256 * q + t < p.K ? slab[(int64_t)(f + 1) * ks + 256 * q + t] : -INFINITY;
+                }
+                if (bad_s[f]) {                                       // (uniform) the state passes through
+                    if (t == 0) prevj[g] = -2;
+                    continue;
+                }
+                const float ent = started ? E + lr : 0.0f;            // (uniform: the tables are the same for every centroid)
+                unsigned long long key = 0;                           // (below the key of -inf)
+                float nmax = -INFINITY;
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {                        // (k >= K: s = -inf, so every state stays -inf)
+                    const int k = 256 * q + t;
+                    bool st;
+                    const float m = vit_dur_step<SC>(V[q], s[q], ent, 0.0f, e0, &st);
+                    const unsigned long long word = __ballot(st);
+                    if (lane == 0) stay[(int64_t)g * p.kw + 4 * q + wave] = word;
+                    nmax = fmaxf(nmax, m);
+                    const unsigned long long kq = vit_key(V[q][SC - 1], k);
+                    key = kq > key ? kq : key;
+                }
+                key = vit_wave_max(key);
+                if (SC > 1) nmax = vit_wave_fmax(nmax);
+                if (lane == 0) {
+                    red_k[par][wave] = key;
+                    if (SC > 1) red_n[par][wave] = nmax;
+                }
+                __syncthreads();
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned long long ok = red_k[par][w];
+                    key = ok > key ? ok : key;
+                    if (SC > 1) nmax = fmaxf(nmax, red_n[par][w]);
+                }
+                par ^= 1;                                             // (the other set is not rewritten before the next barrier)
+                const float xv = vit_key_score(key);
+                const float nv = SC > 1 ? nmax : xv;                  // (one state per centroid: the exit max is the max)
+                int bi = (int)~(unsigned)key;
+                if ((unsigned)bi >= (unsigned)p.K) bi = 0;            // no score compared greater than -inf: still an id
+#pragma unroll
+                for (int q = 0; q < NQ; ++q)
+#pragma unroll
+                    for (int j = 0; j < SC; ++j) V[q][j] -= nv;
+                E = xv - nv;
+                obj += (double)nv;
+                if (t == 0) prevj[g] = jprev;
+                jprev = bi;
+                started = true;
+            }
+            __syncthreads();                                          // before the next block's scores replace these
+        }
+
+        int fcode = -1;                                               // the final state: the lowest k, then the largest slot, at 0
+#pragma unroll
+        for (int q = NQ - 1; q >= 0; --q) fcode = vit_dur_final_code<SC>(V[q], q, fcode);
+        unsigned long long fkey = vit_wave_max(vit_dur_final_key<SC>(fcode, t));
+        if (lane == 0) red_k[par][wave] = fkey;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const unsigned long long ok = red_k[par][w];
+            fkey = ok > fkey ? ok : fkey;
+        }
+
+        if (wave == 0) {                                              // traceback from the final state
+            int cur = -1, forced = 0;
+            if (started && fkey) {
+                cur = vit_dur_final_k(fkey);
+                const int i = vit_dur_final_slot(fkey) - e0;
+                forced = i == S - 1 ? 0 : i + 1;
+            }
+            const int nsw = vit_traceback_dur(stay, prevj, p.kw, p.ids, o, L, S, cur, forced, lane);
+            if (lane == 0) {
+                if (p.objective) p.objective[u] = obj;
+                if (p.n_switch) p.n_switch[u] = nsw;
+            }
+        }
+        __syncthreads();                                              // the traceback's reads before the next utterance's writes
+    }
+}
+
+template <int SC>
+struct KmVitDurKernels {
+    template <int NQ, bool LDSS> static constexpr auto kernel() { return km_viterbi_dur_kernel<NQ, LDSS, SC>; }
+};
+
 }  // namespace abn
 
 using namespace abn;
@@ -492,6 +681,43 @@ extern "C" int abn_kmeans_viterbi(const float* x, int64_t T, int64_t D, const in
     p.ws = a.ws; p.per_wg = a.per_wg;
     p.ks = a.ks; p.kw = a.kw; p.cap = a.cap;
     return vit_launch<KmVitKernels>("abn_kmeans_viterbi", p, K, w, KM_TILE_BYTES, KM_VIT_LDS_BYTES, stream);
+}
+
+extern "C" int32_t abnx_viterbi_dur_max(void) { return VIT_DUR_MAX; }
+
+// abn_kmeans_viterbi with a minimum duration (include/abnet3_hip_next.h): its checks in its order, then min_duration; the
+// workspace is abn_kmeans_viterbi_ws_bytes'.
+extern "C" int abnx_kmeans_viterbi_dur(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len,
+                                       int64_t n_utt, const float* shift, const float* m, const float* b, int64_t K,
+                                       float penalty_score, int32_t* ids, double* objective, int32_t* n_switch, void* ws,
+                                       int64_t ws_bytes, void* stream, int32_t min_duration)
+{
+    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - KM_B, "abnx_kmeans_viterbi_dur: T = %lld out of range", (long long)T);
+    int rc = chain_check_sizes("abnx_kmeans_viterbi_dur", n_utt, K, D, KM_VIT_LIMITS);
+    if (rc != ABN_OK) return rc;
+    ABN_REQUIRE(x && off && len && shift && m && b && ids, "abnx_kmeans_viterbi_dur: null pointer");
+    ABN_REQUIRE(penalty_score >= 0.0f && __builtin_isfinite(penalty_score),
+                "abnx_kmeans_viterbi_dur: penalty_score = %g, a finite value >= 0 is needed", (double)penalty_score);
+    ABN_REQUIRE(min_duration >= 1 && min_duration <= VIT_DUR_MAX,
+                "abnx_kmeans_viterbi_dur: min_duration = %d, 1 .. %d (abnx_viterbi_dur_max)", (int)min_duration, VIT_DUR_MAX);
+    const ChainWs w = chain_ws(n_utt, 0, K, vit_frame_bytes(K), KM_VIT_TAIL);
+    ChainRegion a;
+    rc = chain_region("abnx_kmeans_viterbi_dur", "abn_kmeans_viterbi_ws_bytes", ws, ws_bytes, w, &a);
+    if (rc != ABN_OK) return rc;
+    KmVitDurP p;
+    p.v.x = x; p.v.shift = shift; p.v.m = m; p.v.b = b; p.v.off = off; p.v.len = len;
+    p.v.T = (int)T; p.v.K = (int)K; p.v.D = (int)D; p.v.n_utt = (int)n_utt;
+    p.v.tiles_k = (int)((K + KM_B - 1) / KM_B);
+    p.v.pen = penalty_score;
+    p.v.ids = ids; p.v.objective = objective; p.v.n_switch = n_switch;
+    p.v.ws = a.ws; p.v.per_wg = a.per_wg;
+    p.v.ks = a.ks; p.v.kw = a.kw; p.v.cap = a.cap;
+    p.S = min_duration;
+    const char* what = "abnx_kmeans_viterbi_dur";
+    if (min_duration == 1) return vit_launch<KmVitDurKernels<1>>(what, p, K, w, KM_TILE_BYTES + VIT_DUR_PARK_BYTES, KM_VIT_LDS_BYTES, stream);
+    if (min_duration == 2) return vit_launch<KmVitDurKernels<2>>(what, p, K, w, KM_TILE_BYTES + VIT_DUR_PARK_BYTES, KM_VIT_LDS_BYTES, stream);
+    if (min_duration <= 4) return vit_launch<KmVitDurKernels<4>>(what, p, K, w, KM_TILE_BYTES + VIT_DUR_PARK_BYTES, KM_VIT_LDS_BYTES, stream);
+    return vit_launch<KmVitDurKernels<8>>(what, p, K, w, KM_TILE_BYTES + VIT_DUR_PARK_BYTES, KM_VIT_LDS_BYTES, stream);
 }
 
 extern "C" int64_t abn_kmeans_max_d(void) { return KM_MAX_D; }

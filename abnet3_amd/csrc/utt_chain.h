@@ -4,7 +4,9 @@
 // 256-byte aligned region of the workspace: a slab [128][ks] of scores, then so many bytes per frame of the longest
 // utterance, then a tail.  Here: that geometry (chain_ws), its split of a caller's workspace (chain_region), the size
 // checks with the callers' limits in their messages (chain_check_sizes, chain_ws_bytes), the NQ list (nq_for,
-// for_each_nq) and the launch of a max-product kernel (vit_launch).  The kernels themselves stay in their files: shared
+// for_each_nq) and the launch of a max-product kernel (vit_launch; km_viterbi_dur_kernel and hmm_viterbi_dur_kernel, the
+// two with a minimum unit duration, go through it with one kernel set per register capacity and the same workspace
+// geometry).  The kernels themselves stay in their files: shared
 // device code (one slab phase, one max-product kernel over a model type) gave the same bits but measured 5 to 11 %
 // slower for hmm_fb_kernel and km_viterbi_kernel (profiles/hmm_*_time_shared_chain.json).
 #pragma once

@@ -3,7 +3,7 @@
     python -m abnet3_amd.hmm fit-stay GMM.npz FEATURES MODEL.npz [--stay P] [--n-iter N] [--tol T]
     python -m abnet3_amd.hmm fit GMM.npz FEATURES MODEL.npz [--stay P] [--n-iter N] [--tol T] [--params mvws]
     python -m abnet3_amd.hmm transform MODEL.npz FEATURES OUT [--mode smooth|filter]
-    python -m abnet3_amd.hmm decode MODEL.npz FEATURES OUT
+    python -m abnet3_amd.hmm decode MODEL.npz FEATURES OUT [--min-duration S]
 
 ``GmmPosteriorgram`` treats every frame on its own, so its posteriors flicker.  An HMM over the mixture's components
 with a single "stay" probability is the smallest acoustic-unit model that has a likelihood: its forward-backward pass
@@ -59,7 +59,8 @@ workgroups, one utterance at a time, one sum reduction per frame and sweep.  The
 sweeps, so there is no T x K array beyond it.  A Baum-Welch iteration is that launch with the per-component stays
 (abn_hmm_forward_backward_stats) and abn_hmm_accumulate, which reads the gamma table once as the A operand of
 abn_gmm_accumulate's statistics GEMM.  Limits: K <= abn_hmm_max_k(), D <= abn_gmm_max_d(), an utterance of at most
-abn_hmm_max_len() frames; utterances must not overlap.  Left out: full transition matrices, durations.
+abn_hmm_max_len() frames; utterances must not overlap.  Left out: full transition matrices, duration distributions (the
+max-product path has a minimum duration, below).
 
 The max-product path (``viterbi``, ``StickyHmmPosteriorgram.decode`` / ``quantize``; abn_hmm_viterbi, one launch;
 tests/hmm_vit_np.py restates it).  The model, the emissions and the BAD-frame rule are the ones above.
@@ -84,6 +85,26 @@ tests/hmm_vit_np.py restates it).  The model, the emissions and the BAD-frame ru
   log joint probability of the best path and the good frames), n_switch [n_utt] int32 (the changes of id between
   consecutive good frames), n_good [n_utt] int32.  A refused utterance (outside 0 .. T, or longer than the workspace was
   sized for) is left untouched: log_prob NaN, n_switch and n_good -1.
+* Minimum duration (``min_duration`` = S, an integer 1 .. 8, default 1 = the recurrence above; abnx_hmm_viterbi_dur,
+  csrc/vit_wave.h; tests/vit_dur_np.py restates it): the minimum-duration topology of HMM acoustic-unit discovery.  Every
+  component becomes a left-to-right chain of S states with tied emissions of which only the last may repeat.  Good frames
+  only (durations count good frames): a path is a sequence of segments (k_i, n_i), every segment but the utterance's last
+  has n_i >= S (the end of the utterance may cut the last one short), and its score is the sum of the frames' scores
+  + lw[k_1] + lr[k_i] for each later segment + max(n_i - S, 0) ls[k_i]: forced advances cost nothing, only the frames
+  beyond the S-th pay the stay term.  Recurrence, fp32, one rounded add or a compare per operation; V[k][0 .. S-1] the
+  normalised previous values, E = max_k V[k][S-1], exitj the lowest k whose U[k][S-1] was the largest (0 if all -inf):
+    first good frame:   U[k][0] = s + lw[k], every other state -inf
+    later good frames:  U[k][0] = s + (E + lr[k]);   U[k][i] = s + V[k][i-1] for 0 < i < S-1;
+                        a = V[k][S-1] + ls[k],  st = a > V[k][S-2]  (strict: a tie goes to the advance),
+                        U[k][S-1] = s + (st ? a : V[k][S-2])
+    every good frame:   N_t = max over all (k, i) of U,  V = U - N_t,  log_prob = the sum of the N_t in float64.
+  The final state is the lowest k, then the largest i, with V[k][i] == 0.  Stored per frame: the st bits and the previous
+  good frame's exitj.  Going backwards: in state S-1 a set bit keeps (k, S-1) and a clear bit goes to (k, S-2); from state
+  i, 0 < i < S-1, to (k, i-1); from state 0 to (exitj, S-1).  n_switch = the changes of id.  Where S ls[k] < lr[k] (a
+  small stay and a large S) closing a unit and entering it again beats staying; the ids do not show such a boundary, and
+  every run of ids but the last is >= S either way.  log_prob is then the score above, not a log joint probability of
+  the sticky chain.  Left out: a duration distribution, a maximum duration, untied emission states; S is untuned on real
+  speech.
 * At stay = 0 all three tables are equal and the recurrence is argmax_k fl32(s[k] + lw[k]) frame by frame: the mixture's
   hard assignment.
 """
@@ -226,13 +247,16 @@ def _check_log_tables(who, lw, ls, lr, K):
         raise ValueError('%s: lr <= ls is needed (a stay is at least as likely as a redraw of the same unit)' % who)
 
 
-def viterbi(table, off, lens, shift, A, B, c0, lw, ls, lr, ids=None, want_log_prob=True):
+def viterbi(table, off, lens, shift, A, B, c0, lw, ls, lr, ids=None, want_log_prob=True, min_duration=1):
     """(ids [T] int32, log_prob [n_utt] float64 or None, n_switch [n_utt] int32 or None, n_good [n_utt] int32), device
     tensors, of the max-product recurrence the module docstring defines (abn_hmm_viterbi, one launch).  off, lens: the
     utterances' first rows and lengths (host sequences or device tensors); they must not overlap.  lw, ls, lr: the log
-    tables of ``viterbi_tables``.  Rows outside every utterance keep what `ids` held (-1 in a fresh `ids`)."""
+    tables of ``viterbi_tables``.  Rows outside every utterance keep what `ids` held (-1 in a fresh `ids`).
+    min_duration = S > 1: every unit lasts at least S good frames (abnx_hmm_viterbi_dur, the same workspace); 1 is
+    abn_hmm_viterbi itself."""
     lib = _lib.load()
     who = 'hmm.viterbi'
+    min_duration = _utt.check_min_duration(who, min_duration)
     if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
         raise ValueError('%s: a [T, D] float32 table is needed' % who)
     T, D = table.shape
@@ -256,10 +280,13 @@ def viterbi(table, off, lens, shift, A, B, c0, lw, ls, lr, ids=None, want_log_pr
     ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
     if T and n_utt and longest:
         ws, off_d, len_d = _utt.workspace(who, lib.abn_hmm_viterbi_ws_bytes, off_h, len_h, longest, K, D, table.device)
-        _lib.check(lib.abn_hmm_viterbi(_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A),
-                                       _lib.ptr(B), _lib.ptr(c0), _lib.ptr(lw), _lib.ptr(ls), _lib.ptr(lr), K, _lib.ptr(ids),
-                                       _lib.ptr(lp), _lib.ptr(nsw), _lib.ptr(ng), _lib.ptr(ws), ws.numel(), _lib.stream()),
-                   'abn_hmm_viterbi')
+        args = (_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B),
+                _lib.ptr(c0), _lib.ptr(lw), _lib.ptr(ls), _lib.ptr(lr), K, _lib.ptr(ids), _lib.ptr(lp), _lib.ptr(nsw), _lib.ptr(ng),
+                _lib.ptr(ws), ws.numel(), _lib.stream())
+        if min_duration == 1:
+            _lib.check(lib.abn_hmm_viterbi(*args), 'abn_hmm_viterbi')
+        else:
+            _lib.check(lib.abnx_hmm_viterbi_dur(*(args + (min_duration,))), 'abnx_hmm_viterbi_dur')
     return ids, lp, nsw, ng
 
 
@@ -414,35 +441,37 @@ class StickyHmmPosteriorgram(object):
             return out
         return DeviceCorpus.from_table(out, dc.names, [dc.length[k] for k in dc.names], dc.times)
 
-    def _decode_ids(self, corpus):
+    def _decode_ids(self, corpus, min_duration=1):
         """(device ids [rows] int32, DeviceCorpus or None, names or None, lens); fills last_log_prob_ / last_n_switch_ /
         last_n_good_ / n_bad_."""
+        min_duration = _utt.check_min_duration('StickyHmmPosteriorgram', min_duration)
         table, dc, lens = self._utterances(corpus)
         names = list(dc.names) if dc is not None else list(corpus) if isinstance(corpus, dict) else None
         shift, A, B, c0, w = self.device_tables(table.device)
         lw, ls, lr = (torch.from_numpy(a).to(table.device) for a in viterbi_tables(self.gmm.weights_, self.stay_))
         off = _utt.starts(lens)
-        ids, lp, nsw, ng = viterbi(table, off, lens, shift, A, B, c0, lw, ls, lr)
+        ids, lp, nsw, ng = viterbi(table, off, lens, shift, A, B, c0, lw, ls, lr, min_duration=min_duration)
         self.last_log_prob_, self.last_n_switch_, self.last_n_good_ = lp.cpu().numpy(), nsw.cpu().numpy(), ng.cpu().numpy()
         self.n_bad_ = int(lens.sum() - self.last_n_good_.sum())
         return ids, dc, names, lens
 
-    def decode(self, corpus):
+    def decode(self, corpus, min_duration=1):
         """The unit ids of the best path (the module docstring's max-product recurrence), int32, -1 for a BAD frame:
         {name: host array [length]} in corpus order for a DeviceCorpus, a dict or a file -- what KMeansQuantizer.segment
         returns, so kmeans.unit_sequences / bitrate / segments, eskmeans.landmarks_from_units and tde.unit_boundaries take
         it as it is --; for a [T, D] table, which is ONE utterance, the device tensor [T].  ``last_log_prob_`` (float64),
         ``last_n_switch_`` and ``last_n_good_`` (int32) hold the utterances' log joint probabilities, switch counts and
-        good-frame counts; ``n_bad_`` the BAD frames."""
-        ids, _, names, lens = self._decode_ids(corpus)
+        good-frame counts; ``n_bad_`` the BAD frames.  min_duration = S (an integer 1 .. 8): every unit but an
+        utterance's last lasts at least S good frames (the module docstring's minimum-duration recurrence)."""
+        ids, _, names, lens = self._decode_ids(corpus, min_duration)
         return ids if names is None else _gmm._split_rows(ids.cpu().numpy(), zip(names, lens))
 
-    def quantize(self, corpus):
+    def quantize(self, corpus, min_duration=1):
         """Each frame replaced by the mean of its decoded component (uncentred: m + shift), [rows, D] float32 on the
         device, a BAD frame a row of zeros; for a DeviceCorpus a new DeviceCorpus with the same names, lengths and times
-        (what KMeansQuantizer.quantize gives ``ABXEvaluator(parallel='zero')``)."""
+        (what KMeansQuantizer.quantize gives ``ABXEvaluator(parallel='zero')``).  min_duration: as in ``decode``."""
         from .dataloader import DeviceCorpus
-        ids, dc, _, _ = self._decode_ids(corpus)
+        ids, dc, _, _ = self._decode_ids(corpus, min_duration)
         means = torch.from_numpy(self.gmm.means_.astype(np.float32)).to(ids.device)
         out = means[ids.clamp(min=0).to(torch.int64)]
         out[ids < 0] = 0.0
@@ -582,6 +611,8 @@ def main(argv=None):
     d.add_argument('model')
     d.add_argument('features', help='h5features file, or an .npz of name -> [T, D]')
     d.add_argument('out', help='.npz of name -> [T] ids, or an h5features file (when the input has times)')
+    d.add_argument('--min-duration', type=int, default=1, metavar='S',
+                   help='every unit lasts at least S frames (1 .. 8; default 1, no minimum)')
     args = ap.parse_args(argv)
     if args.cmd == 'fit':
         check_params('python -m abnet3_amd.hmm fit', args.params)
@@ -601,7 +632,7 @@ def main(argv=None):
     h = StickyHmmPosteriorgram.load(args.model)
     if args.cmd == 'decode':
         from . import kmeans as _kmeans
-        out = h.decode(feats)
+        out = h.decode(feats, min_duration=args.min_duration)
         _gmm._write_named(args.out, out, times, as_column=True)
         n_good = int(h.last_n_good_.sum())
         if times is not None:

@@ -1,7 +1,7 @@
 """K-means discrete units on the MI355X: vector quantisation of frames or embeddings with no labels.
 
     python -m abnet3_amd.kmeans fit FEATURES MODEL.npz [-k K] [--n-iter N] [--tol T] [--metric M] [--seed S]
-    python -m abnet3_amd.kmeans transform MODEL.npz FEATURES OUT [--quantize] [--penalty P]
+    python -m abnet3_amd.kmeans transform MODEL.npz FEATURES OUT [--quantize] [--penalty P] [--min-duration S]
 
 Unit ids are how the ZeroSpeech 2019 / 2020 / 2021 systems are scored: the ids give the bitrate (``unit_sequences``,
 ``bitrate``), and ABX is run over the quantised frames (``quantize`` gives the corpus that ``ABXEvaluator`` and
@@ -58,6 +58,26 @@ Niekerk 2021, "DPDP"), an HMM Viterbi with a uniform switching cost over the sam
   abn_kmeans_assign's ids bit for bit.
 * An utterance with no good frame gives all ids -1, objective 0 and 0 switches; len[u] = 0 is allowed.  Rows outside
   every utterance keep what ``ids`` held.
+* Minimum duration (``min_duration`` = S, an integer 1 .. 8, default 1 = everything above; abnx_kmeans_viterbi_dur,
+  csrc/vit_wave.h; tests/vit_dur_np.py restates it).  The penalty alone cannot remove one-frame units without smoothing
+  real boundaries away; with S > 1 every unit becomes a left-to-right chain of S states over the same score, of which
+  only the last may repeat.  Good frames only (BAD frames get -1 and are passed over; durations count good frames): a
+  path is a sequence of segments (k_i, n_i), every segment but the utterance's last has n_i >= S (the end of the
+  utterance may cut the last one short, so every length has a path), and its score is the sum of the frames' scores
+  + lw[k_1] + lr[k_i] for each later segment + max(n_i - S, 0) ls[k_i], here with lw = 0, ls = 0, lr = -p: the
+  objective J above, maximised over the labellings whose runs are long enough.  Recurrence, fp32, one rounded add or a
+  compare per operation; V[k][0 .. S-1] the normalised previous values, E = max_k V[k][S-1], exitj the lowest k whose
+  U[k][S-1] was the largest (0 if all are -inf):
+    first good frame:   U[k][0] = s + lw[k], every other state -inf
+    later good frames:  U[k][0] = s + (E + lr[k]);   U[k][i] = s + V[k][i-1] for 0 < i < S-1;
+                        a = V[k][S-1] + ls[k],  st = a > V[k][S-2]  (strict: a tie goes to the advance),
+                        U[k][S-1] = s + (st ? a : V[k][S-2])
+    every good frame:   N_t = max over all (k, i) of U,  V = U - N_t,  objective = the sum of the N_t in float64.
+  The final state is the lowest k, then the largest i, with V[k][i] == 0.  Stored per frame: the st bits and the previous
+  good frame's exitj.  Going backwards: in state S-1 a set bit keeps (k, S-1) and a clear bit goes to (k, S-2); from state
+  i, 0 < i < S-1, to (k, i-1); from state 0 to (exitj, S-1).  n_switch = the changes of id along the path.  The same
+  workspace, still no T x K x S array: the S states of a centroid live in S registers of the lane that owns it.  No
+  duration distribution, no maximum duration, and S is untuned on real speech.
 * Limits: K <= abn_kmeans_viterbi_max_k() (4096), D <= abn_kmeans_max_d(), an utterance of at most
   abn_kmeans_viterbi_max_len() frames (2^20).  One launch (abn_kmeans_viterbi) for the whole corpus; no T x K array:
   the workspace is, per workgroup (at most 256), 128 x K scores, one stay bit per (frame of the longest utterance,
@@ -158,13 +178,15 @@ def check_penalty(who, penalty):
     return p
 
 
-def viterbi(table, off, lens, shift, m, b, penalty, ids=None, want_objective=False):
+def viterbi(table, off, lens, shift, m, b, penalty, ids=None, want_objective=False, min_duration=1):
     """(ids [T] int32, objective [n_utt] float64 or None, n_switch [n_utt] int32 or None) of the penalised segmentation
     the module docstring defines (abn_kmeans_viterbi, one launch).  off, lens: the utterances' first rows and lengths
     (host sequences or device tensors); they must not overlap.  Rows outside every utterance keep what `ids` held (-1
-    in a fresh `ids`)."""
+    in a fresh `ids`).  min_duration = S > 1: every unit lasts at least S good frames (abnx_kmeans_viterbi_dur, the same
+    workspace); 1 is abn_kmeans_viterbi itself."""
     lib = _lib.load()
     penalty = check_penalty('kmeans.viterbi', penalty)
+    min_duration = _utt.check_min_duration('kmeans.viterbi', min_duration)
     table = _check_table('kmeans.viterbi', table)
     T, D = table.shape
     K = b.shape[0]
@@ -183,10 +205,12 @@ def viterbi(table, off, lens, shift, m, b, penalty, ids=None, want_objective=Fal
     nsw = torch.zeros(n_utt, dtype=torch.int32, device=table.device) if want_objective else None
     if T and n_utt and max_len:
         ws, off_d, len_d = _utt.workspace('kmeans.viterbi', lib.abn_kmeans_viterbi_ws_bytes, off_h, len_h, max_len, K, D, table.device)
-        _lib.check(lib.abn_kmeans_viterbi(_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift),
-                                          _lib.ptr(m), _lib.ptr(b), K, float(np.float32(penalty / 2.0)), _lib.ptr(ids),
-                                          _lib.ptr(obj), _lib.ptr(nsw), _lib.ptr(ws), ws.numel(), _lib.stream()),
-                   'abn_kmeans_viterbi')
+        args = (_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(m), _lib.ptr(b), K,
+                float(np.float32(penalty / 2.0)), _lib.ptr(ids), _lib.ptr(obj), _lib.ptr(nsw), _lib.ptr(ws), ws.numel(), _lib.stream())
+        if min_duration == 1:
+            _lib.check(lib.abn_kmeans_viterbi(*args), 'abn_kmeans_viterbi')
+        else:
+            _lib.check(lib.abnx_kmeans_viterbi_dur(*(args + (min_duration,))), 'abnx_kmeans_viterbi_dur')
     return ids, obj, nsw
 
 
@@ -367,9 +391,10 @@ class KMeansQuantizer(object):
             accumulate(table, shift, st, n_ranges, update=False)
         return st
 
-    def _segment_ids(self, table, rows, penalty):
+    def _segment_ids(self, table, rows, penalty, min_duration=1):
         """Device ids of the penalised segmentation; fills last_objective_ / last_n_switch_."""
         penalty = check_penalty('KMeansQuantizer.segment', penalty)
+        min_duration = _utt.check_min_duration('KMeansQuantizer.segment', min_duration)
         if self.centroids_ is None:
             raise ValueError('KMeansQuantizer: fit or load first')
         lens = np.array([table.shape[0]] if rows is None else list(rows.values()), dtype=np.int64)
@@ -387,36 +412,50 @@ class KMeansQuantizer(object):
         if self.metric == 'cosine':
             table = table / table.norm(dim=1, keepdim=True)
         shift, m, b, _ = self.device_tables(table.device)
-        ids, obj, nsw = viterbi(table, off, lens, shift, m, b, penalty, want_objective=True)
+        ids, obj, nsw = viterbi(table, off, lens, shift, m, b, penalty, want_objective=True, min_duration=min_duration)
         self.last_objective_, self.last_n_switch_ = obj.cpu().numpy(), nsw.cpu().numpy()
         return ids
+
+    @staticmethod
+    def _duration(who, min_duration):
+        """The keyword that hands a checked min_duration on: none at 1, where every call is the one it was without it."""
+        min_duration = _utt.check_min_duration(who, min_duration)
+        return {} if min_duration == 1 else {'min_duration': min_duration}
 
     @staticmethod
     def _by_name(ids, rows):
         return ids if rows is None else _gmm._split_rows(ids.cpu().numpy(), rows.items())
 
-    def segment(self, corpus, penalty):
+    def segment(self, corpus, penalty, min_duration=1):
         """The unit ids of the penalised segmentation (module docstring), in predict's forms.  Each file of a corpus is
         an utterance; a [T, D] table is ONE utterance (ValueError beyond abn_kmeans_viterbi_max_len frames).
-        ``last_objective_`` (float64) and ``last_n_switch_`` (int32) hold the utterances' objectives and switch counts."""
+        ``last_objective_`` (float64) and ``last_n_switch_`` (int32) hold the utterances' objectives and switch counts.
+        min_duration = S (an integer 1 .. 8): every unit but an utterance's last lasts at least S good frames."""
+        extra = self._duration('KMeansQuantizer.segment', min_duration)
         table, _, rows = self._corpus(corpus)
-        return self._by_name(self._segment_ids(table, rows, penalty), rows)
+        return self._by_name(self._segment_ids(table, rows, penalty, **extra), rows)
 
-    def predict(self, corpus, penalty=None):
+    def predict(self, corpus, penalty=None, min_duration=1):
         """The unit ids, int32, -1 for a BAD frame: a device tensor [rows] for a table, {name: host array} in corpus
-        order for a DeviceCorpus, a dict or a file.  penalty=None: the frame-wise ids; a number: ``segment``."""
+        order for a DeviceCorpus, a dict or a file.  penalty=None: the frame-wise ids; a number: ``segment`` (with its
+        min_duration; without a penalty min_duration must be 1)."""
         if penalty is not None:
-            return self.segment(corpus, penalty)
+            return self.segment(corpus, penalty, min_duration)
+        if self._duration('KMeansQuantizer.predict', min_duration):
+            raise ValueError('KMeansQuantizer.predict: min_duration = %d needs a penalty (0 is one)' % min_duration)
         table, _, rows = self._corpus(corpus)
         return self._by_name(self._assign(table), rows)
 
-    def quantize(self, corpus, penalty=None):
+    def quantize(self, corpus, penalty=None, min_duration=1):
         """Each frame replaced by its centroid, [rows, D] float32 on the device (a BAD frame: zeros); for a DeviceCorpus
-        a new DeviceCorpus with the same names, lengths and times.  penalty: the ids of ``segment`` instead of the
-        frame-wise ones."""
+        a new DeviceCorpus with the same names, lengths and times.  penalty: the ids of ``segment`` (with its
+        min_duration) instead of the frame-wise ones; without a penalty min_duration must be 1."""
         from .dataloader import DeviceCorpus
+        extra = self._duration('KMeansQuantizer.quantize', min_duration)
+        if penalty is None and extra:
+            raise ValueError('KMeansQuantizer.quantize: min_duration = %d needs a penalty (0 is one)' % min_duration)
         table, dc, rows = self._corpus(corpus)
-        ids = self._assign(table) if penalty is None else self._segment_ids(table, rows, penalty)
+        ids = self._assign(table) if penalty is None else self._segment_ids(table, rows, penalty, **extra)
         cent = self.device_tables(ids.device)[3]
         out = cent[ids.clamp(min=0).to(torch.int64)]
         out[ids < 0] = 0.0
@@ -515,6 +554,8 @@ def parser():
     t.add_argument('--quantize', action='store_true', help='write each frame\'s centroid instead of its id')
     t.add_argument('--penalty', type=float, default=None, metavar='P',
                    help='penalised segmentation: cost of a new segment, in units of the distortion (no tuned default)')
+    t.add_argument('--min-duration', type=int, default=1, metavar='S',
+                   help='with --penalty: every unit lasts at least S frames (1 .. 8; default 1, no minimum)')
     return ap
 
 
@@ -529,9 +570,10 @@ def main(argv=None):
         return 0
     q = KMeansQuantizer.load(args.model)
     if args.quantize:
-        out = _gmm._split_rows(q.quantize(feats, penalty=args.penalty).cpu().numpy(), ((k, v.shape[0]) for k, v in feats.items()))
+        out = _gmm._split_rows(q.quantize(feats, penalty=args.penalty, min_duration=args.min_duration).cpu().numpy(),
+                               ((k, v.shape[0]) for k, v in feats.items()))
     else:
-        out = q.predict(feats, penalty=args.penalty)
+        out = q.predict(feats, penalty=args.penalty, min_duration=args.min_duration)
     _gmm._write_named(args.out, out, times, as_column=not args.quantize)
     print('%d files, %d frames, K = %d -> %s' % (len(out), sum(v.shape[0] for v in out.values()), q.n_clusters, args.out))
     return 0

@@ -7,7 +7,8 @@ mined pairs, and the ABX item file ("phones" = word types).
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
                                      [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--hmm-fit N] [--hmm-decode] [--no-network] [--terms] [--terms-theta T]
                                      [--prefilter] [--alignment FILE]
-                                     [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P]
+                                     [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P] [--kmeans-min-duration S]
+                                     [--hmm-min-duration S]
                                      [--eskmeans] [--eskmeans-clusters 24] [--samediff]
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
@@ -185,11 +186,12 @@ def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frame
     return dl
 
 
-def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=None, hmm_fit=0, hmm_decode=False):
+def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=None, hmm_fit=0, hmm_decode=False, hmm_min_duration=1):
     """features -> GmmPosteriorgram.fit -> transform -> ABX (kl), and the search: the line main() prints.  hmm_stay (a
     number, or 'fit'): the sticky-HMM smoothed posteriorgrams beside the raw ones; they are the ones returned.  hmm_fit
     (iterations): the posteriorgrams of the Baum-Welch-trained HMM beside both; then those are returned.  hmm_decode: the
-    discrete units of the (trained, else smoothed) HMM's best path beside the frame-wise mixture argmax."""
+    discrete units of the (trained, else smoothed) HMM's best path beside the frame-wise mixture argmax; hmm_min_duration > 1:
+    and those of the best path whose units last at least that many frames."""
     names = list(fb)
     keep, items = word_items(tokens)
     corpus = DeviceCorpus({k: np.asarray(fb[k], dtype=np.float32) for k in names}, times)
@@ -224,7 +226,7 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
             line += '\n' + more
             h = t
         if hmm_decode:
-            more = hmm_decode_lines(h, corpus, items)
+            more = hmm_decode_lines(h, corpus, items, hmm_min_duration)
             print(more)
             line += '\n' + more
     if qbe:
@@ -232,15 +234,19 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
     return (line, post) if want_post else line
 
 
-def hmm_decode_lines(h, corpus, items):
+def hmm_decode_lines(h, corpus, items, min_duration=1):
     """The units of the HMM's best path (StickyHmmPosteriorgram.decode) beside the frame-wise mixture argmax (stay = 0
-    through the same call): bitrate with runs merged, switches, and ABX over the quantised frames."""
+    through the same call): bitrate with runs merged, switches, and ABX over the quantised frames.  min_duration > 1 adds
+    the best path whose units last at least that many frames."""
     seconds = 0.01 * corpus.total
     out = []
-    for label, model in (('sticky-HMM Viterbi units (stay %.4f)' % h.stay_, h),
-                         ('frame-wise mixture argmax (stay 0)', StickyHmmPosteriorgram(h.gmm, 0.0))):
-        ids = model.decode(corpus)
-        r = ABXEvaluator(items, model.quantize(corpus), parallel='zero').run('within')
+    routes = [('sticky-HMM Viterbi units (stay %.4f)' % h.stay_, h, 1),
+              ('frame-wise mixture argmax (stay 0)', StickyHmmPosteriorgram(h.gmm, 0.0), 1)]
+    if min_duration > 1:
+        routes.insert(1, ('sticky-HMM Viterbi units (stay %.4f, at least %d frames per unit)' % (h.stay_, min_duration), h, min_duration))
+    for label, model, S in routes:
+        ids = model.decode(corpus, min_duration=S)
+        r = ABXEvaluator(items, model.quantize(corpus, min_duration=S), parallel='zero').run('within')
         out.append('%s: %.0f bit/s with runs merged, %d switches, log-probability per frame %.3f; ABX error quantised %.2f %% '
                    '(%d triplets)' % (label, bitrate(unit_sequences(ids), seconds), int(model.last_n_switch_.sum()),
                                       float(model.last_log_prob_.sum()) / max(1, int(model.last_n_good_.sum())), r.error, r.n_triplets))
@@ -266,9 +272,10 @@ def eskmeans_route(corpus, unit_ids, n_clusters, tokens=None, tolerance=0.03):
     return esk
 
 
-def kmeans_route(corpus, items, label, n_clusters, penalty=None, esk_clusters=None, tokens=None):
+def kmeans_route(corpus, items, label, n_clusters, penalty=None, esk_clusters=None, tokens=None, min_duration=1):
     """frames -> KMeansQuantizer.fit -> unit ids (bitrate) and quantised frames (ABX) beside the continuous ones; with a
-    penalty the same for the penalised segmentation, and with esk_clusters ES-KMeans over its landmarks."""
+    penalty the same for the penalised segmentation (min_duration: its units last at least that many frames), and with
+    esk_clusters ES-KMeans over its landmarks."""
     q = KMeansQuantizer(n_clusters).fit(corpus)
     seconds = 0.01 * corpus.total
     rate = bitrate(unit_sequences(q.predict(corpus), collapse=False), seconds)
@@ -281,11 +288,12 @@ def kmeans_route(corpus, items, label, n_clusters, penalty=None, esk_clusters=No
           'ABX error continuous %.2f %%, %s (%d triplets)'
           % (label, n_clusters, len(q.inertias), q.inertias[-1], q.n_empty_, rate, merged, cont.error, quant, cont.n_triplets))
     if penalty is not None:
-        ids = q.segment(corpus, penalty)
-        pen_abx = ABXEvaluator(items, q.quantize(corpus, penalty=penalty), parallel='zero').run('within').error
-        print('  with penalty %g: %.0f bit/s with runs merged (%.0f without the penalty), %d switches (%d without); '
+        ids = q.segment(corpus, penalty, min_duration=min_duration)
+        pen_abx = ABXEvaluator(items, q.quantize(corpus, penalty=penalty, min_duration=min_duration), parallel='zero').run('within').error
+        print('  with penalty %g%s: %.0f bit/s with runs merged (%.0f without the penalty), %d switches (%d without); '
               'ABX error quantised %.2f %% (%s without)'
-              % (penalty, bitrate(unit_sequences(ids), seconds), merged, int(q.last_n_switch_.sum()),
+              % (penalty, ' and at least %d frames per unit' % min_duration if min_duration > 1 else '',
+                 bitrate(unit_sequences(ids), seconds), merged, int(q.last_n_switch_.sum()),
                  sum(len(v) - 1 for v in unit_sequences(q.predict(corpus)).values() if len(v)), pen_abx, quant[len('quantised '):]))
         if esk_clusters:
             eskmeans_route(corpus, ids, esk_clusters, tokens)
@@ -321,6 +329,10 @@ def main():
     ap.add_argument('--kmeans-clusters', type=int, default=50)
     ap.add_argument('--kmeans-penalty', type=float, default=None, metavar='P',
                     help='with --kmeans: also the penalised segmentation, P per new segment in units of the distortion (untuned)')
+    ap.add_argument('--kmeans-min-duration', type=int, default=1, metavar='S',
+                    help='with --kmeans-penalty: every unit lasts at least S frames (1 .. 8, untuned)')
+    ap.add_argument('--hmm-min-duration', type=int, default=1, metavar='S',
+                    help='with --hmm-decode: also the best path whose units last at least S frames (1 .. 8, untuned)')
     ap.add_argument('--eskmeans', action='store_true', help='with --kmeans --kmeans-penalty P: ES-KMeans word segmentation over the units\' boundaries (untuned)')
     ap.add_argument('--eskmeans-clusters', type=int, default=24)
     ap.add_argument('--samediff', action='store_true', help='same-different AP of the planted words: DTW over filterbanks and embeddings, the embeddings\' segment vectors')
@@ -346,13 +358,15 @@ def main():
 
     gmm_line = post = None
     if args.gmm:
-        gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True, hmm_stay=args.hmm_stay, hmm_fit=args.hmm_fit, hmm_decode=args.hmm_decode)
+        gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True, hmm_stay=args.hmm_stay, hmm_fit=args.hmm_fit, hmm_decode=args.hmm_decode,
+                                   hmm_min_duration=args.hmm_min_duration)
     if args.no_network:
         if not (args.gmm or args.kmeans):
             ap.error('--no-network leaves nothing to do without --gmm or --kmeans')
         if args.kmeans:
             corpus = DeviceCorpus({k: np.asarray(v, dtype=np.float32) for k, v in fb.items()}, times)
-            kmeans_route(corpus, word_items(tokens)[1], 'filterbanks', args.kmeans_clusters, args.kmeans_penalty, esk_k, tokens)
+            kmeans_route(corpus, word_items(tokens)[1], 'filterbanks', args.kmeans_clusters, args.kmeans_penalty, esk_k, tokens,
+                         args.kmeans_min_duration)
         return
 
     if args.tcl:
@@ -406,7 +420,7 @@ def main():
         if args.qbe:
             qbe_search(corpus, keep, names, label, 'kl' if args.softmax and label == 'embeddings' else 'cosine')
         if args.kmeans and label == 'embeddings':
-            kmeans_route(corpus, items, label, args.kmeans_clusters, args.kmeans_penalty, esk_k, tokens)
+            kmeans_route(corpus, items, label, args.kmeans_clusters, args.kmeans_penalty, esk_k, tokens, args.kmeans_min_duration)
     if gmm_line:
         print(gmm_line)
 

@@ -1,0 +1,54 @@
+/* abnet3_hip_next.h -- entries of libabnet3_hip.so that are not part of the numbered ABI yet.
+ *
+ * The entries below carry the prefix abnx_ and are exported beside those of abnet3_hip.h, whose conventions they follow
+ * (extern "C", plain pointers and sizes, the ABN_E_* return codes, abn_last_error, every refusal before any launch).
+ * They do not change ABN_ABI_VERSION.  A later change folds them into abnet3_hip.h under their abn_ names, bumps the
+ * version, and moves their ledger (abnet3_amd._lib.NEXT_SYMBOLS, tests/test_gpu_vit_dur.py) into the main one
+ * (abnet3_amd._lib.SYMBOLS, tests/test_dirty_memory_host.py).
+ */
+#ifndef ABNET3_HIP_NEXT_H
+#define ABNET3_HIP_NEXT_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- Minimum unit duration for the two max-product decoders (csrc/kmeans.hip, csrc/hmm.hip, csrc/vit_wave.h) ----------
+ * abn_kmeans_viterbi and abn_hmm_viterbi with one more argument: min_duration = S, 1 .. abnx_viterbi_dur_max() (8).
+ * Every unit k becomes a left-to-right chain of S states with tied emissions of which only the last may repeat, so every
+ * segment of a path but the utterance's last is at least S good frames long (the end of the utterance may cut the last
+ * one short).  One utterance, good frames only (BAD frames get id -1 and are passed over; durations count good frames):
+ * a path is a sequence of segments (k_i, n_i) and its score is
+ *     sum of the frames' scores s[t, k] + lw[k_1] + lr[k_i] for each later segment + max(n_i - S, 0) ls[k_i]
+ * with lw, ls, lr the caller's tables (abnx_hmm_viterbi_dur) or lw = 0, ls = 0, lr = -penalty_score
+ * (abnx_kmeans_viterbi_dur).  Recurrence, fp32, every operation one rounded add or a compare; V[k][0 .. S-1] the
+ * normalised previous values, E = max_k V[k][S-1] and exitj the lowest k whose U[k][S-1] was the largest (0 if all -inf):
+ *     first good frame:  U[k][0] = s + lw[k], every other state -inf
+ *     later good frames: U[k][0] = s + (E + lr[k]);   U[k][i] = s + V[k][i-1] for 0 < i < S-1;
+ *                        a = V[k][S-1] + ls[k],  st = a > V[k][S-2] (strict; S = 1: a > E + lr[k]),
+ *                        U[k][S-1] = s + (st ? a : V[k][S-2])
+ *     every good frame:  N_t = max U,  V = U - N_t,  log_prob / objective = the float64 sum of the N_t in frame order.
+ * The final state is the lowest k, then the largest i, with V[k][i] == 0; the traceback reads one stay bit per
+ * (frame, unit) and the previous good frame's exitj per frame.  With min_duration = 1 the outputs are those of
+ * abn_kmeans_viterbi / abn_hmm_viterbi bit for bit.
+ *
+ * Arguments, outputs, limits and the treatment of refused utterances are the twins' (abnet3_hip.h).  The workspace has the
+ * twins' geometry: size it with abn_kmeans_viterbi_ws_bytes / abn_hmm_viterbi_ws_bytes.  Refusals are the twins', in the
+ * twins' order; min_duration outside 1 .. abnx_viterbi_dur_max(): ABN_E_ARG -- all before any launch. */
+int32_t abnx_viterbi_dur_max(void);        /* host */
+int abnx_kmeans_viterbi_dur(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                            const float* shift, const float* m, const float* b, int64_t K, float penalty_score,
+                            int32_t* ids, double* objective, int32_t* n_switch, void* ws, int64_t ws_bytes,
+                            void* stream, int32_t min_duration);
+int abnx_hmm_viterbi_dur(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                         const float* shift, const float* A, const float* B, const float* c0,
+                         const float* lw, const float* ls, const float* lr, int64_t K,
+                         int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good,
+                         void* ws, int64_t ws_bytes, void* stream, int32_t min_duration);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* ABNET3_HIP_NEXT_H */
