@@ -14,7 +14,7 @@ def __getattr__(name):
     if name == 'KMeansQuantizer':
         from .kmeans import KMeansQuantizer
         return KMeansQuantizer
-    if name in ('StickyHmmPosteriorgram',):
+    if name in ('StickyHmmPosteriorgram', 'TransitionHmmPosteriorgram'):
         from . import hmm
         return getattr(hmm, name)
     if name in ('TermEvaluator', 'edit_distance_batch', 'read_alignment', 'read_classes', 'transcribe'):

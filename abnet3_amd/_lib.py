@@ -172,6 +172,14 @@ NEXT_SYMBOLS = {
     'abnx_kmeans_viterbi_dur': (C.c_int, SYMBOLS['abn_kmeans_viterbi'][1] + [_i32]),
     'abnx_hmm_viterbi_dur': (C.c_int, SYMBOLS['abn_hmm_viterbi'][1] + [_i32]),
 }
+# the second section of include/abnet3_hip_next.h (prefix abny_: the HMM with a full transition matrix, csrc/hmm_dense.hip),
+# as little part of the numbered ABI as NEXT_SYMBOLS
+NEXT2_SYMBOLS = {
+    'abny_hmm_dense_max_k': (_i64, []),
+    'abny_hmm_dense_ws_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'abny_hmm_dense_forward_backward': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, C.c_int,
+                                                  _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+}
 # abn_sd_count's conditions and the limits of abn_sd_collect / abn_sd_count (include/abnet3_hip.h)
 SD_CONDITION = {'all': 0, 'swdp': 1, 'swsp': 2}
 SD_MAX_N, SD_MAX_THR, SD_MAX_D = 1 << 22, 1 << 30, 4096
@@ -235,7 +243,7 @@ def load():
             'abnet3_amd: %s is missing. Build it with `python -m abnet3_amd.build` '
             '(hipcc, gfx950). There is no CPU fallback.' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(NEXT_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(NEXT_SYMBOLS.items()) + list(NEXT2_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -4,6 +4,7 @@
     python -m abnet3_amd.hmm fit GMM.npz FEATURES MODEL.npz [--stay P] [--n-iter N] [--tol T] [--params mvws]
     python -m abnet3_amd.hmm transform MODEL.npz FEATURES OUT [--mode smooth|filter]
     python -m abnet3_amd.hmm decode MODEL.npz FEATURES OUT [--min-duration S]
+    python -m abnet3_amd.hmm fit-trans MODEL_OR_GMM.npz FEATURES OUT.npz [--n-iter N] [--params mvti] [--alpha A]
 
 ``GmmPosteriorgram`` treats every frame on its own, so its posteriors flicker.  An HMM over the mixture's components
 with a single "stay" probability is the smallest acoustic-unit model that has a likelihood: its forward-backward pass
@@ -59,8 +60,8 @@ workgroups, one utterance at a time, one sum reduction per frame and sweep.  The
 sweeps, so there is no T x K array beyond it.  A Baum-Welch iteration is that launch with the per-component stays
 (abn_hmm_forward_backward_stats) and abn_hmm_accumulate, which reads the gamma table once as the A operand of
 abn_gmm_accumulate's statistics GEMM.  Limits: K <= abn_hmm_max_k(), D <= abn_gmm_max_d(), an utterance of at most
-abn_hmm_max_len() frames; utterances must not overlap.  Left out: full transition matrices, duration distributions (the
-max-product path has a minimum duration, below).
+abn_hmm_max_len() frames; utterances must not overlap.  Left out: the max-product path of the full-transition model
+below, duration distributions (the sticky max-product path has a minimum duration, below).
 
 The max-product path (``viterbi``, ``StickyHmmPosteriorgram.decode`` / ``quantize``; abn_hmm_viterbi, one launch;
 tests/hmm_vit_np.py restates it).  The model, the emissions and the BAD-frame rule are the ones above.
@@ -107,6 +108,36 @@ tests/hmm_vit_np.py restates it).  The model, the emissions and the BAD-frame ru
   speech.
 * At stay = 0 all three tables are equal and the recurrence is argmax_k fl32(s[k] + lw[k]) frame by frame: the mixture's
   hard assignment.
+
+The full-transition model (``dense_forward_backward``, ``TransitionHmmPosteriorgram``; abny_hmm_dense_forward_backward,
+csrc/hmm_dense.hip; tests/hmm_dense_np.py restates it).  Over a fitted mixture (means, variances, shift; the mixture
+weights play no part):
+
+* States: the K components.  init [K] float32; trans [K][K] float32, row-stochastic,
+  trans[j][k] = P(k at t | j at the previous good frame).
+* Range: every entry of init and trans is at least 2^-100 (ValueError otherwise, as check_stay does).
+* Emissions: the sticky model's logN[t, k] from c0, A, B: the same score tile, the same bits.  m_t = max_k logN[t, k],
+  bt = exp(logN - m_t).  With the range: c_t >= 2^-100 and e <= 2^100, as in the sticky chain.
+* BAD frames follow the sticky rule exactly: the output row is zero, the chain passes over the frame, and it counts
+  neither as a frame nor as a transition.
+* Forward, fp32, per utterance over its good frames:
+    pred = init at the first good frame, else pred[k] = sum_j ahat_prev[j] trans[j][k],
+    u = bt pred,   c_t = sum_k u,   ahat = u / c_t,      loglik = sum_t (log c_t + m_t)  (float64 sum).
+* Backward from the last good frame with bhat = 1:  gamma_t = ahat_t bhat;  entering frame t from its predecessor p,
+    e = bt[t] bhat / c_t,   G[j][k] += ahat_p[j] e[k],   bhat[j] <- sum_k trans[j][k] e[k].
+  The expected transition counts are xi[j][k] = trans[j][k] G[j][k]; first[k] += gamma at the utterance's first good frame.
+* mode 'smooth' gives gamma, mode 'filter' ahat (no backward sweep, the statistics zero).
+* M-step on the host, float64, with a pseudo-count alpha >= 0 (``transition_update``):
+    trans[j][k] = (xi[j][k] + alpha) / (sum_k xi[j][k] + K alpha),   init[k] = (first[k] + alpha) / (sum first + K alpha);
+  a row of trans with no mass and alpha = 0 keeps its old values.  After the update every entry below
+  TRANS_MIN = 2^-80 is raised to it and the row is renormalised once, so the range condition cannot fail in the middle
+  of a fit.  Means and variances follow ``fit``'s rule above, from abn_hmm_accumulate on the gamma table.  alpha is untuned.
+* The K-term dot products run in the kernel's own fixed order: thread t of 256 takes own = t mod K' (K' = K rounded up to
+  16, 32, 64 or 128) and the slice t div K' of K'^2 / 256 consecutive indices of the other side, adds its products in
+  ascending order with fused multiply-adds, and the 256 / K' partial sums are added slice 0 first.
+* Limits: K <= abny_hmm_dense_max_k() (128: the matrix lives in LDS), D <= abn_gmm_max_d(), an utterance of at most
+  abn_hmm_max_len() frames; utterances must not overlap.  Left out: the max-product path of this model (``decode``),
+  duration states, sparse or banded matrices, K above the LDS limit.  Nothing here is tuned or measured on real speech.
 """
 import argparse
 import copy
@@ -124,6 +155,8 @@ STAY_MAX = 0.9999
 TINY = 2.0 ** -100
 WEIGHT_MIN = 2.0 ** -80
 PARAMS = 'mvws'
+TRANS_MIN = 2.0 ** -80
+DENSE_PARAMS = 'mvti'
 
 
 def max_len():
@@ -377,6 +410,137 @@ def stay_update(stays, n_good):
     return float(min(max(host(stays).astype(np.float64).sum() / float(trans), 0.0), STAY_MAX))
 
 
+def dense_max_k():
+    return int(_lib.load().abny_hmm_dense_max_k())
+
+
+def check_transitions(who, init, trans):
+    """(init [K], trans [K, K]) as float32 host arrays, or ValueError: finite, every entry at least 2^-100 (as float32),
+    and init and every row of trans summing to 1 within 1e-3."""
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    try:
+        i32, t32 = host(init).astype(np.float32), host(trans).astype(np.float32)
+    except (TypeError, ValueError):
+        raise ValueError('%s: init [K] and trans [K, K] arrays of numbers are needed' % who)
+    if i32.ndim != 1 or t32.shape != (len(i32), len(i32)) or not len(i32):
+        raise ValueError('%s: init [K] and trans [K, K] are needed, not %s and %s' % (who, i32.shape, t32.shape))
+    if not (np.isfinite(i32).all() and np.isfinite(t32).all()):
+        raise ValueError('%s: init and trans must be finite' % who)
+    low = min(float(i32.min()), float(t32.min()))
+    if low < TINY:
+        raise ValueError('%s: the smallest entry of init and trans is %g, below 2^-100: the scaled recursion would underflow'
+                         % (who, low))
+    sums = np.concatenate([[i32.astype(np.float64).sum()], t32.astype(np.float64).sum(axis=1)])
+    if np.abs(sums - 1.0).max() > 1e-3:
+        raise ValueError('%s: init and every row of trans must sum to 1 (the worst is off by %g)' % (who, np.abs(sums - 1.0).max()))
+    return i32, t32
+
+
+def sticky_transitions(w, stay):
+    """(init, trans) float32 of the sticky model over weights w: init = float32(w), trans[j][k] = r [j == k] + (1 - r) w32[k]
+    with r = float32(stay) and 1 - r taken in float32, formed in float64 and rounded once.  ValueError naming the
+    components if a weight is 0 (the full-transition model has no retired components), and through check_stay."""
+    w32 = np.asarray(w, dtype=np.float32).ravel()
+    r = np.float32(check_stay('hmm.sticky_transitions', stay, w32))
+    if (w32 <= 0).any():
+        raise ValueError('hmm.sticky_transitions: the components %s have weight 0; a full transition matrix needs every entry '
+                         '>= 2^-100' % np.flatnonzero(w32 <= 0).tolist())
+    omr = np.float32(1.0) - r
+    trans = np.float64(omr) * w32.astype(np.float64)[None, :] + np.float64(r) * np.eye(len(w32))
+    return w32.copy(), trans.astype(np.float32)
+
+
+def dense_forward_backward(table, off, lens, shift, A, B, c0, init, trans, mode='smooth', out=None, want_stats=False):
+    """(post [T, K] fp32, loglik [n_utt] float64, n_good [n_utt] int32[, stats [K + 1, K] float64]), device tensors, of the
+    full-transition recursion the module docstring defines (abny_hmm_dense_forward_backward: one launch, and a second
+    small one for the statistics).  off, lens: the utterances' first rows and lengths (host sequences or device tensors);
+    they must not overlap.  init [K], trans [K, K]: float32 device tensors.  Rows outside every utterance keep what `out`
+    held (0 in a fresh table).  stats: rows 0 .. K - 1 the expected transition counts xi, row K `first`."""
+    lib = _lib.load()
+    who = 'hmm.dense_forward_backward'
+    if mode not in MODES:
+        raise ValueError('%s: mode = %r, one of %s' % (who, mode, sorted(MODES)))
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
+        raise ValueError('%s: a [T, D] float32 table is needed' % who)
+    T, D = table.shape
+    K = c0.shape[0]
+    if A.shape != (K, D) or B.shape != (K, D) or shift.shape != (D,) or any(t.dtype != torch.float32 for t in (shift, A, B, c0)):
+        raise ValueError('%s: shift [D], A [K, D], B [K, D], c0 [K] float32 are needed' % who)
+    if not isinstance(init, torch.Tensor) or not isinstance(trans, torch.Tensor) or init.shape != (K,) or trans.shape != (K, K) or \
+            init.dtype != torch.float32 or trans.dtype != torch.float32:
+        raise ValueError('%s: init [K] and trans [K, K] float32 tensors are needed' % who)
+    if K < 1 or K > dense_max_k():
+        raise ValueError('%s: K = %d, the kernel takes 1 .. %d (abny_hmm_dense_max_k)' % (who, K, dense_max_k()))
+    check_transitions(who, init, trans)
+    off_h, len_h, n_utt, longest = _utt.utterance_spans(who, off, lens, T, max_len(), 'abn_hmm_max_len')
+    table = _gmm._check_table(who, table)
+    _lib.require_device(shift, A, B, c0, init, trans)
+    if out is None:
+        out = torch.zeros((T, K), dtype=torch.float32, device=table.device)
+    if out.shape != (T, K) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError('%s: out must be a contiguous [T, K] float32 tensor' % who)
+    _lib.require_device(out)
+    ll = torch.zeros(n_utt, dtype=torch.float64, device=table.device)
+    ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
+    stats = torch.zeros((K + 1, K), dtype=torch.float64, device=table.device) if want_stats else None
+    if T and n_utt and longest:
+        ws, off_d, len_d = _utt.workspace(who, lib.abny_hmm_dense_ws_bytes, off_h, len_h, longest, K, D, table.device)
+        _lib.check(lib.abny_hmm_dense_forward_backward(
+            _lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B), _lib.ptr(c0),
+            _lib.ptr(init), _lib.ptr(trans), K, MODES[mode], _lib.ptr(out), _lib.ptr(ll), _lib.ptr(ng), _lib.ptr(stats),
+            _lib.ptr(ws), ws.numel(), _lib.stream()), 'abny_hmm_dense_forward_backward')
+    return (out, ll, ng, stats) if want_stats else (out, ll, ng)
+
+
+def floor_rows(p):
+    """float64: every entry below TRANS_MIN raised to it and each row renormalised once (a vector is one row)."""
+    p = np.array(p, dtype=np.float64)
+    p[p < TRANS_MIN] = TRANS_MIN
+    return p / p.sum(axis=-1, keepdims=True)
+
+
+def transition_update(stats, trans, init, alpha=1e-3, params='ti'):
+    """The transition M-step of the module docstring on the host, float64: (trans [K, K], init [K]) from stats [K + 1, K]
+    (rows 0 .. K - 1 xi, row K first) with the pseudo-count alpha >= 0.  A part whose letter (t, i) is not in `params` comes
+    back as given; a row without mass at alpha = 0 keeps its old values; then the floor TRANS_MIN and one renormalisation."""
+    who = 'hmm.transition_update'
+    stats = np.asarray(stats, dtype=np.float64)
+    old_t, old_i = np.array(trans, dtype=np.float64), np.array(init, dtype=np.float64)
+    K = len(old_i)
+    if stats.shape != (K + 1, K) or old_t.shape != (K, K):
+        raise ValueError('%s: stats [K + 1, K], trans [K, K] and init [K] are needed' % who)
+    if not (isinstance(alpha, (int, float, np.floating, np.integer)) and np.isfinite(alpha) and alpha >= 0):
+        raise ValueError('%s: alpha = %r, a number >= 0 is needed' % (who, alpha))
+    if not np.isfinite(stats).all() or (stats < 0).any():
+        raise ValueError('%s: the statistics are not finite or negative' % who)
+    new_t, new_i = old_t, old_i
+    if 't' in params:
+        den = stats[:K].sum(axis=1) + K * alpha
+        with np.errstate(all='ignore'):
+            new_t = np.where((den > 0)[:, None], (stats[:K] + alpha) / den[:, None], old_t)
+        new_t = floor_rows(new_t)
+    if 'i' in params:
+        den = stats[K].sum() + K * alpha
+        new_i = floor_rows((stats[K] + alpha) / den) if den > 0 else floor_rows(old_i)
+    return new_t, new_i
+
+
+def bigram_counts(ids_by_name, K):
+    """int64 [K][K] on the host: the unit bigrams of ``decode`` / ``segment`` output ({name: ids}), BAD frames (-1) passed
+    over.  A data-driven start for TransitionHmmPosteriorgram: trans = counts + alpha, each row normalised."""
+    K = int(K)
+    counts = np.zeros((K, K), dtype=np.int64)
+    seqs = ids_by_name.values() if isinstance(ids_by_name, dict) else ids_by_name
+    for ids in seqs:
+        a = np.asarray(ids).ravel().astype(np.int64)
+        a = a[a >= 0]
+        if len(a) and a.max() >= K:
+            raise ValueError('hmm.bigram_counts: unit id %d with K = %d' % (int(a.max()), K))
+        if len(a) > 1:
+            np.add.at(counts, (a[:-1], a[1:]), 1)
+    return counts
+
+
 class StickyHmmPosteriorgram(object):
     """transform / decode / quantize / score / fit_stay / fit of the sticky HMM the module docstring defines, over a fitted GmmPosteriorgram.
 
@@ -584,6 +748,181 @@ class StickyHmmPosteriorgram(object):
         return self
 
 
+class TransitionHmmPosteriorgram(object):
+    """transform / score / fit of the full-transition HMM the module docstring defines, over a fitted GmmPosteriorgram
+    (its means, variances and shift; its weights only seed the default start).
+
+    trans, init: the start; by default the sticky matrix of the mixture's weights and `stay` (``sticky_transitions``).
+    alpha: the pseudo-count of the transition M-step (untuned).  corpus arguments: as StickyHmmPosteriorgram's."""
+
+    def __init__(self, gmm, trans=None, init=None, stay=0.9, alpha=1e-3):
+        if not isinstance(gmm, _gmm.GmmPosteriorgram) or gmm.weights_ is None:
+            raise ValueError('TransitionHmmPosteriorgram: a fitted GmmPosteriorgram is needed')
+        if not (isinstance(alpha, (int, float, np.floating, np.integer)) and np.isfinite(alpha) and alpha >= 0):
+            raise ValueError('TransitionHmmPosteriorgram: alpha = %r, a number >= 0 is needed' % (alpha,))
+        K = gmm.means_.shape[0]
+        if trans is None or init is None:
+            i0, t0 = sticky_transitions(gmm.weights_, stay)
+            init = i0 if init is None else init
+            trans = t0 if trans is None else trans
+        i32, t32 = check_transitions('TransitionHmmPosteriorgram', init, trans)
+        if len(i32) != K:
+            raise ValueError('TransitionHmmPosteriorgram: init [%d] and trans for a mixture of K = %d components' % (len(i32), K))
+        self.gmm = gmm
+        self.trans_, self.init_ = t32.astype(np.float64), i32.astype(np.float64)
+        self.alpha = float(alpha)
+        self.log_likelihoods = []
+        self.n_bad_ = self.n_starved_ = 0
+        self._tables = None
+
+    @classmethod
+    def from_sticky(cls, h, alpha=1e-3):
+        """The full-transition model that equals a fitted StickyHmmPosteriorgram; ValueError naming the components if a
+        weight is 0."""
+        if not isinstance(h, StickyHmmPosteriorgram):
+            raise ValueError('TransitionHmmPosteriorgram.from_sticky: a StickyHmmPosteriorgram is needed')
+        w = np.asarray(h.gmm.weights_)
+        if (w.astype(np.float32) <= 0).any():
+            raise ValueError('TransitionHmmPosteriorgram.from_sticky: the components %s have weight 0'
+                             % np.flatnonzero(w.astype(np.float32) <= 0).tolist())
+        return cls(h.gmm, stay=h.stay_, alpha=alpha)
+
+    def whoami(self):
+        return {'params': {'alpha': self.alpha, 'gmm': self.gmm.whoami()}, 'class_name': self.__class__.__name__}
+
+    def device_tables(self, device):
+        """(shift, A, B, c0, init32, trans32) on the device, rounded once from the float64 parameters."""
+        if self._tables is None or self._tables[0].device != device:
+            g = self.gmm
+            shift, A, B, _ = g.device_tables(device)
+            m = g.means_ - g.shift_.astype(np.float64)
+            c0 = torch.from_numpy(emission_offsets(m, g.variances_)).to(device)
+            init = torch.from_numpy(self.init_.astype(np.float32)).to(device)
+            trans = torch.from_numpy(np.ascontiguousarray(self.trans_.astype(np.float32))).to(device)
+            self._tables = (shift, A, B, c0, init, trans)
+        return self._tables
+
+    def _utterances(self, corpus):
+        """(device table, DeviceCorpus or None, lens int64 [n_utt])"""
+        table, dc = _gmm.GmmPosteriorgram._corpus(corpus)
+        if dc is not None:
+            lens = [dc.length[k] for k in dc.names]
+        elif isinstance(corpus, dict):
+            lens = [np.asarray(f).shape[0] for f in corpus.values()]
+        else:
+            lens = [table.shape[0]] if isinstance(table, torch.Tensor) and table.dim() == 2 else []
+        if isinstance(table, torch.Tensor) and table.dim() == 2 and table.dtype == torch.float32:      # (host checks first)
+            if table.shape[1] != self.gmm.shift_.shape[0]:
+                raise ValueError('TransitionHmmPosteriorgram: the table has D = %d, the model D = %d'
+                                 % (table.shape[1], self.gmm.shift_.shape[0]))
+            if len(lens) and max(lens) > max_len():
+                raise ValueError('TransitionHmmPosteriorgram: an utterance of %d frames, the kernel takes up to %d '
+                                 '(abn_hmm_max_len); pass a corpus of utterances' % (max(lens), max_len()))
+        table = _gmm._check_table('TransitionHmmPosteriorgram', table)
+        return table, dc, np.asarray(lens, dtype=np.int64)
+
+    def transform(self, corpus, mode='smooth'):
+        """The smoothed (mode='filter': filtered) posterior table [rows, K] on the device; for a DeviceCorpus a new
+        DeviceCorpus with the same names, lengths and times."""
+        from .dataloader import DeviceCorpus
+        table, dc, lens = self._utterances(corpus)
+        out = dense_forward_backward(table, _utt.starts(lens), lens, *self.device_tables(table.device), mode=mode)[0]
+        if dc is None:
+            return out
+        return DeviceCorpus.from_table(out, dc.names, [dc.length[k] for k in dc.names], dc.times)
+
+    def score(self, corpus):
+        """The mean log-likelihood per good frame."""
+        table, _, lens = self._utterances(corpus)
+        _, ll, ng = dense_forward_backward(table, _utt.starts(lens), lens, *self.device_tables(table.device), mode='filter')
+        ll_sum, n = torch.stack([ll.sum(), ng.to(torch.float64).sum()]).cpu().tolist()
+        return ll_sum / max(1.0, n)
+
+    def fit(self, corpus, n_iter=10, tol=1e-4, params=DENSE_PARAMS, n_ranges=0):
+        """Baum-Welch from the current parameters: any subset of the `m`eans, `v`ariances, `t`ransitions and the `i`nit
+        (params).  The mixture is COPIED first: the GmmPosteriorgram this object was made from is untouched, ``self.gmm``
+        is the trained copy.  Iteration i runs forward-backward with the statistics and the statistics GEMM under the
+        current parameters -- ``log_likelihoods[i]`` is their mean log-likelihood per good frame --, reads everything back
+        once, and applies the update; the stopping rule is StickyHmmPosteriorgram.fit's.  Fills ``log_likelihoods``,
+        ``n_bad_``, ``n_starved_``, ``trans_`` and ``init_``.  One T x K scratch table is allocated."""
+        who = 'TransitionHmmPosteriorgram.fit'
+        if not isinstance(params, str) or not params or len(set(params)) != len(params) or not set(params) <= set(DENSE_PARAMS):
+            raise ValueError('%s: params = %r, a non-empty choice of the letters of %r is needed '
+                             '(m means, v variances, t transitions, i init)' % (who, params, DENSE_PARAMS))
+        p = set(params)
+        table, _, lens = self._utterances(corpus)
+        g = copy.copy(self.gmm)
+        g.weights_, g.means_, g.variances_ = (np.array(a, dtype=np.float64) for a in (g.weights_, g.means_, g.variances_))
+        g.log_likelihoods, g._tables = list(g.log_likelihoods), None
+        K, D = g.means_.shape
+        shift64 = g.shift_.astype(np.float64)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(table.device)
+        shift = dev(g.shift_)
+        scratch = torch.zeros((table.shape[0], K), dtype=torch.float32, device=table.device)
+        off = _utt.starts(lens)
+        m, v, trans, init = g.means_ - shift64, g.variances_, self.trans_, self.init_
+        mv = ''.join(c for c in 'mv' if c in p)
+        self.log_likelihoods = []
+        for it in range(int(n_iter)):
+            A, B, _ = _gmm.score_tables(np.full(K, 1.0 / K), m, v)
+            _, ll, ng, stats = dense_forward_backward(table, off, lens, shift, dev(A), dev(B), dev(emission_offsets(m, v)), dev(init),
+                                                      dev(trans), 'smooth', out=scratch, want_stats=True)
+            good = ng.clamp(min=0).to(torch.float64)
+            head = torch.stack([ll.sum(), good.sum(), (good - 1.0).clamp(min=0.0).sum()])
+            sums = accumulate(table, scratch, shift, n_ranges) if mv else torch.zeros((K, 2 * D + 1), dtype=torch.float64,
+                                                                                      device=table.device)
+            back = torch.cat([head, stats.flatten(), sums.flatten()]).cpu().numpy()      # the iteration's one read-back
+            ll_sum, n, ntr = back[:3].tolist()
+            if n < 1:
+                raise ValueError('%s: the corpus has no good frame' % who)
+            if 't' in p and ntr < 1:
+                raise ValueError('%s: no utterance has two good frames: the transitions cannot be estimated' % who)
+            self.log_likelihoods.append(ll_sum / n)
+            self.n_bad_ = int(lens.sum() - n)
+            if it > 0 and self.log_likelihoods[-1] - self.log_likelihoods[-2] < tol:
+                break
+            stats_h = back[3:3 + (K + 1) * K].reshape(K + 1, K)
+            sums_h = back[3 + (K + 1) * K:].reshape(K, 2 * D + 1)
+            if mv:
+                self.n_starved_ = int((sums_h[:, 2 * D] < g.min_count).sum())
+                _, m, v, _, _ = baum_welch_update(sums_h, np.zeros(K), ntr, m, v, g.gv_, g.var_floor, g.min_count, mv,
+                                                  weights=np.full(K, 1.0 / K), stay=0.0)
+            trans, init = transition_update(stats_h, trans, init, self.alpha, ''.join(c for c in 'ti' if c in p))
+        if 'm' in p:
+            g.means_ = m + shift64
+        if 'v' in p:
+            g.variances_ = v
+        self.gmm, self.trans_, self.init_, self._tables = g, np.array(trans, dtype=np.float64), np.array(init, dtype=np.float64), None
+        return self
+
+    # -- files ----------------------------------------------------------------------------------------------------
+    def save(self, path):
+        """The mixture's file (GmmPosteriorgram.load reads it) plus trans, init and alpha."""
+        g = self.gmm
+        with open(path, 'wb') as f:
+            np.savez(f, weights=g.weights_, means=g.means_, variances=g.variances_, shift=g.shift_, gv=g.gv_,
+                     log_likelihoods=np.asarray(g.log_likelihoods, dtype=np.float64),
+                     n_components=g.n_components, n_iter=g.n_iter, tol=g.tol, var_floor=g.var_floor,
+                     min_count=g.min_count, seed=g.seed, trans=self.trans_, init=self.init_, alpha=np.float64(self.alpha),
+                     trans_log_likelihoods=np.asarray(self.log_likelihoods, dtype=np.float64))
+
+    @classmethod
+    def load(cls, path):
+        g = _gmm.GmmPosteriorgram.load(path)
+        with np.load(path) as z:
+            if 'trans' not in z.files or 'init' not in z.files:
+                raise ValueError('%s: not a TransitionHmmPosteriorgram file (no trans)' % path)
+            self = cls(g, z['trans'].astype(np.float64), z['init'].astype(np.float64), alpha=float(z['alpha']))
+            self.trans_, self.init_ = z['trans'].astype(np.float64), z['init'].astype(np.float64)
+            self.log_likelihoods = [float(v) for v in z['trans_log_likelihoods']]
+        return self
+
+
+def _holds(path, key):
+    with np.load(path) as z:
+        return key in z.files
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog='python -m abnet3_amd.hmm', description='Sticky-HMM smoothing of Gaussian posteriorgrams')
     sub = ap.add_subparsers(dest='cmd', required=True)
@@ -613,10 +952,33 @@ def main(argv=None):
     d.add_argument('out', help='.npz of name -> [T] ids, or an h5features file (when the input has times)')
     d.add_argument('--min-duration', type=int, default=1, metavar='S',
                    help='every unit lasts at least S frames (1 .. 8; default 1, no minimum)')
+    ft = sub.add_parser('fit-trans', help='Baum-Welch of the full-transition model on FEATURES, from a saved model or mixture')
+    ft.add_argument('model', help='a TransitionHmmPosteriorgram, StickyHmmPosteriorgram or GmmPosteriorgram .npz: where EM starts')
+    ft.add_argument('features', help='h5features file, or an .npz of name -> [T, D]')
+    ft.add_argument('out', help='the .npz to write')
+    ft.add_argument('--stay', type=float, default=0.9, help='the sticky start over a plain mixture')
+    ft.add_argument('--n-iter', type=int, default=10)
+    ft.add_argument('--tol', type=float, default=1e-4)
+    ft.add_argument('--params', default=DENSE_PARAMS, help='the letters of what is re-estimated: m means, v variances, t transitions, i init')
+    ft.add_argument('--alpha', type=float, default=1e-3, help='pseudo-count of the transition update (untuned)')
     args = ap.parse_args(argv)
     if args.cmd == 'fit':
         check_params('python -m abnet3_amd.hmm fit', args.params)
     feats, times = _gmm._read_features(args.features)
+    if args.cmd == 'fit-trans':
+        if _holds(args.model, 'trans'):
+            h = TransitionHmmPosteriorgram.load(args.model)
+            h.alpha = float(args.alpha)
+        elif _holds(args.model, 'stay'):
+            h = TransitionHmmPosteriorgram.from_sticky(StickyHmmPosteriorgram.load(args.model), alpha=args.alpha)
+        else:
+            h = TransitionHmmPosteriorgram(_gmm.GmmPosteriorgram.load(args.model), stay=args.stay, alpha=args.alpha)
+        h.fit(feats, args.n_iter, args.tol, args.params)
+        h.save(args.out)
+        print('K = %d transitions after %d iterations (params %s, alpha %g), mean log-likelihood %.6f, %d BAD frames, %d starved, '
+              'mean self-transition %.4f' % (h.trans_.shape[0], len(h.log_likelihoods), args.params, h.alpha, h.log_likelihoods[-1],
+                                             h.n_bad_, h.n_starved_, float(np.diag(h.trans_).mean())))
+        return 0
     if args.cmd == 'fit':
         h = StickyHmmPosteriorgram(_gmm.GmmPosteriorgram.load(args.gmm), args.stay).fit(feats, args.n_iter, args.tol, args.params)
         h.save(args.model)
@@ -628,6 +990,16 @@ def main(argv=None):
         h.save(args.model)
         print('stay %.6f after %d iterations, mean log-likelihood %.6f, %d BAD frames'
               % (h.stay_, len(h.log_likelihoods), h.log_likelihoods[-1], h.n_bad_))
+        return 0
+    if _holds(args.model, 'trans'):
+        if args.cmd == 'decode':
+            raise ValueError('python -m abnet3_amd.hmm decode: %s holds a full transition matrix; its max-product path is not '
+                             'built yet' % args.model)
+        h = TransitionHmmPosteriorgram.load(args.model)
+        post = h.transform(feats, args.mode).cpu().numpy()
+        out = _gmm._split_rows(post, ((k, v.shape[0]) for k, v in feats.items()))
+        _gmm._write_named(args.out, out, times)
+        print('%d files, %d frames, K = %d, full transitions -> %s' % (len(out), post.shape[0], post.shape[1], args.out))
         return 0
     h = StickyHmmPosteriorgram.load(args.model)
     if args.cmd == 'decode':

@@ -5,7 +5,7 @@ Siamese training -> embedding -> ABX.  The corpus' word labels are used twice on
 mined pairs, and the ABX item file ("phones" = word types).
 
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
-                                     [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--hmm-fit N] [--hmm-decode] [--no-network] [--terms] [--terms-theta T]
+                                     [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--hmm-fit N] [--hmm-trans N] [--hmm-decode] [--no-network] [--terms] [--terms-theta T]
                                      [--prefilter] [--alignment FILE]
                                      [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P] [--kmeans-min-duration S]
                                      [--hmm-min-duration S]
@@ -24,7 +24,9 @@ under the KL frame distance -- ABX, and with --qbe the search.  No network is tr
 after it, otherwise its figures are printed again beside the embeddings'.  --hmm-stay P (or "fit": EM on the stay
 probability) smooths the posteriorgrams with the sticky HMM of abnet3_amd/hmm.py and prints ABX (kl) of both.
 --hmm-fit N trains that HMM by N iterations of Baum-Welch from the mixture (means, variances, weights and the stay)
-and prints ABX (kl) of raw, smoothed and Baum-Welch-trained posteriorgrams side by side.  --hmm-decode adds the
+and prints ABX (kl) of raw, smoothed and Baum-Welch-trained posteriorgrams side by side.  --hmm-trans N trains the
+full-transition HMM (TransitionHmmPosteriorgram: a K x K transition matrix, K <= 128) by N iterations from the sticky
+matrix and prints ABX (kl) of raw, sticky-smoothed and transition-smoothed posteriorgrams side by side.  --hmm-decode adds the
 discrete units of that HMM's best path (StickyHmmPosteriorgram.decode, Viterbi): their bitrate and switch count beside
 those of the frame-wise mixture argmax (stay = 0 through the same call), and ABX over the quantised frames (each frame
 replaced by its unit's mean).  Nothing in it is tuned on real speech.
@@ -63,7 +65,7 @@ from abnet3_amd.discovery import KnnPairMiner                     # noqa: E402
 from abnet3_amd.embedder import EmbedderSiamese                   # noqa: E402
 from abnet3_amd.features import FeaturesGenerator                 # noqa: E402
 from abnet3_amd.gmm import GmmPosteriorgram                       # noqa: E402
-from abnet3_amd.hmm import StickyHmmPosteriorgram                 # noqa: E402
+from abnet3_amd.hmm import StickyHmmPosteriorgram, TransitionHmmPosteriorgram, sticky_transitions      # noqa: E402
 from abnet3_amd.kmeans import KMeansQuantizer, bitrate, unit_sequences   # noqa: E402
 from abnet3_amd.loss import KLLoss, coscos2                       # noqa: E402
 from abnet3_amd.model import SiameseNetwork                       # noqa: E402
@@ -186,12 +188,14 @@ def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frame
     return dl
 
 
-def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=None, hmm_fit=0, hmm_decode=False, hmm_min_duration=1):
+def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=None, hmm_fit=0, hmm_decode=False, hmm_min_duration=1, hmm_trans=0):
     """features -> GmmPosteriorgram.fit -> transform -> ABX (kl), and the search: the line main() prints.  hmm_stay (a
     number, or 'fit'): the sticky-HMM smoothed posteriorgrams beside the raw ones; they are the ones returned.  hmm_fit
     (iterations): the posteriorgrams of the Baum-Welch-trained HMM beside both; then those are returned.  hmm_decode: the
     discrete units of the (trained, else smoothed) HMM's best path beside the frame-wise mixture argmax; hmm_min_duration > 1:
-    and those of the best path whose units last at least that many frames."""
+    and those of the best path whose units last at least that many frames.  hmm_trans (iterations): the posteriorgrams of
+    the full-transition HMM, trained from the sticky matrix, beside the raw and the sticky-smoothed ones (the returned
+    posteriorgrams stay the sticky route's)."""
     names = list(fb)
     keep, items = word_items(tokens)
     corpus = DeviceCorpus({k: np.asarray(fb[k], dtype=np.float32) for k in names}, times)
@@ -201,7 +205,7 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
     line = ('ABX error on GMM posteriorgrams (K = %d, %d EM iterations, log-likelihood %.3f, %d starved): kl %.2f %% '
             '(%d triplets)' % (n_components, len(g.log_likelihoods), g.log_likelihoods[-1], g.n_starved_, r.error, r.n_triplets))
     print(line)
-    if hmm_fit and hmm_stay is None:
+    if (hmm_fit or hmm_trans) and hmm_stay is None:
         hmm_stay = 0.9
     if hmm_stay is not None:
         h = StickyHmmPosteriorgram(g, 0.9 if hmm_stay == 'fit' else float(hmm_stay))
@@ -214,6 +218,17 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
                                                                    raw_ll, rs.error, r.error, rs.n_triplets))
         print(more)
         line += '\n' + more
+        if hmm_trans:
+            w = np.maximum(g.weights_, 1e-8)                         # (a starved component: the dense model has no retired units)
+            init, trans = sticky_transitions(w / w.sum(), h.stay_)
+            d = TransitionHmmPosteriorgram(g, trans, init).fit(corpus, n_iter=int(hmm_trans), tol=-np.inf)
+            rd = ABXEvaluator(items, d.transform(corpus), distance='kl').run('within')
+            more = ('ABX error on full-transition HMM posteriorgrams (%d iterations, alpha %g untuned, log-likelihood per frame %.3f -> '
+                    '%.3f, mean self-transition %.4f, %d starved): kl %.2f %% transition-smoothed, %.2f %% sticky-smoothed, %.2f %% raw '
+                    '(%d triplets)' % (len(d.log_likelihoods), d.alpha, d.log_likelihoods[0], d.score(corpus),
+                                       float(np.diag(d.trans_).mean()), d.n_starved_, rd.error, rs.error, r.error, rd.n_triplets))
+            print(more)
+            line += '\n' + more
         if hmm_fit:
             t = StickyHmmPosteriorgram(g, h.stay_).fit(corpus, n_iter=int(hmm_fit), tol=-np.inf)
             post = t.transform(corpus)
@@ -317,6 +332,9 @@ def main():
     ap.add_argument('--hmm-fit', type=int, default=0, metavar='N',
                     help='with --gmm: N iterations of Baum-Welch on the sticky HMM (from --hmm-stay, default 0.9); ABX (kl) of raw, '
                          'smoothed and trained posteriorgrams')
+    ap.add_argument('--hmm-trans', type=int, default=0, metavar='N',
+                    help='with --gmm: N iterations of Baum-Welch on the full-transition HMM (K x K matrix, K <= 128) from the sticky '
+                         'matrix of --hmm-stay (default 0.9); ABX (kl) of raw, sticky-smoothed and transition-smoothed posteriorgrams')
     ap.add_argument('--hmm-decode', action='store_true',
                     help='with --hmm-stay / --hmm-fit: the discrete units of the HMM\'s best path (Viterbi): bitrate, switches and ABX '
                          'of the quantised frames, beside the frame-wise mixture argmax; nothing is tuned on real speech')
@@ -343,6 +361,8 @@ def main():
         ap.error('--hmm-stay smooths the posteriorgrams of --gmm')
     if args.hmm_fit and not args.gmm:
         ap.error('--hmm-fit trains the HMM over the mixture of --gmm')
+    if args.hmm_trans and (not args.gmm or args.gmm_components > 128):
+        ap.error('--hmm-trans trains the full-transition HMM over the mixture of --gmm, with --gmm-components <= 128')
     if args.hmm_decode and args.hmm_stay is None and not args.hmm_fit:
         ap.error('--hmm-decode decodes the HMM of --hmm-stay or --hmm-fit')
     esk_k = args.eskmeans_clusters if args.eskmeans else None
@@ -359,7 +379,7 @@ def main():
     gmm_line = post = None
     if args.gmm:
         gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True, hmm_stay=args.hmm_stay, hmm_fit=args.hmm_fit, hmm_decode=args.hmm_decode,
-                                   hmm_min_duration=args.hmm_min_duration)
+                                   hmm_min_duration=args.hmm_min_duration, hmm_trans=args.hmm_trans)
     if args.no_network:
         if not (args.gmm or args.kmeans):
             ap.error('--no-network leaves nothing to do without --gmm or --kmeans')

@@ -1,10 +1,11 @@
 /* abnet3_hip_next.h -- entries of libabnet3_hip.so that are not part of the numbered ABI yet.
  *
- * The entries below carry the prefix abnx_ and are exported beside those of abnet3_hip.h, whose conventions they follow
- * (extern "C", plain pointers and sizes, the ABN_E_* return codes, abn_last_error, every refusal before any launch).
+ * The entries below carry the prefix abnx_ (the minimum unit duration of the max-product decoders) or abny_ (the HMM with
+ * a full transition matrix) and are exported beside those of abnet3_hip.h, whose conventions they follow (extern "C",
+ * plain pointers and sizes, the ABN_E_* return codes, abn_last_error, every refusal before any launch).
  * They do not change ABN_ABI_VERSION.  A later change folds them into abnet3_hip.h under their abn_ names, bumps the
- * version, and moves their ledger (abnet3_amd._lib.NEXT_SYMBOLS, tests/test_gpu_vit_dur.py) into the main one
- * (abnet3_amd._lib.SYMBOLS, tests/test_dirty_memory_host.py).
+ * version, and moves their ledgers (abnet3_amd._lib.NEXT_SYMBOLS with tests/test_gpu_vit_dur.py, abnet3_amd._lib.NEXT2_SYMBOLS
+ * with tests/test_gpu_hmm_dense.py) into the main one (abnet3_amd._lib.SYMBOLS, tests/test_dirty_memory_host.py).
  */
 #ifndef ABNET3_HIP_NEXT_H
 #define ABNET3_HIP_NEXT_H
@@ -47,6 +48,36 @@ int abnx_hmm_viterbi_dur(const float* x, int64_t T, int64_t D, const int64_t* of
                          const float* lw, const float* ls, const float* lr, int64_t K,
                          int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good,
                          void* ws, int64_t ws_bytes, void* stream, int32_t min_duration);
+
+/* ---- The HMM with a full transition matrix over a mixture's components (csrc/hmm_dense.hip) ------------------------------
+ * abn_hmm_forward_backward with init [K] and trans [K][K] (row-stochastic, trans[j][k] = P(k at t | j at the previous good
+ * frame)) in place of the weights and the stay; abnet3_amd/hmm.py states the recursion, tests/hmm_dense_np.py restates it.
+ * x, T, D, off, len, n_utt, shift, A, B, c0, mode, post, loglik, n_good are abn_hmm_forward_backward's: the emissions are
+ * its score tile's bits, BAD frames follow its rule (a zero row, passed over, counted neither as a frame nor as a
+ * transition), `post` holds ahat between the sweeps, and utterances must not overlap.  The caller guarantees that every
+ * entry of init and trans is at least 2^-100 (then c_t >= 2^-100 and e <= 2^100; the library does not read them on the host).
+ *
+ * stats: [K + 1][K] float64 or null.  Rows 0 .. K - 1 are the expected transition counts xi[j][k] = trans[j][k] G[j][k],
+ * G[j][k] = the sum over the transitions (p -> t) of ahat_p[j] e_t[k]; row K is first[k] = gamma summed over the utterances'
+ * first good frames.  All zero in mode 1.  Each workgroup adds its utterances' terms in utterance order into a slab of its
+ * own in the workspace, and a second small launch adds the slabs in workgroup order: the same bits for the same corpus and
+ * the same min(n_utt, 256).  Null: no statistics and no second launch; every other output has the same bits either way.
+ *
+ * K <= abny_hmm_dense_max_k() (a host query: the transition matrix, [K'][K' + 1] fp32 with K' = K rounded up to 16, 32, 64
+ * or 128, lives in LDS beside the score tile's operands; at least 128), D <= abn_gmm_max_d(), an utterance of at most
+ * abn_hmm_max_len() frames.  Workspace: abny_hmm_dense_ws_bytes(n_utt, max_len, K, D) bytes, 16-byte aligned, -1 with
+ * abn_last_error for refused sizes (max_len beyond abn_hmm_max_len() among them); it need not be cleared.
+ * Refusals, all before any launch: null pointers (stats excepted), sizes < 1 and a mode other than 0 or 1: ABN_E_ARG;
+ * K or D beyond the limits: ABN_E_UNSUPPORTED; a workspace that holds no frame: ABN_E_WORKSPACE.  An utterance outside
+ * 0 .. T or longer than the workspace was sized for (and so any longer than abn_hmm_max_len()) is left untouched: loglik NaN,
+ * n_good -1, nothing added to stats. */
+int64_t abny_hmm_dense_max_k(void);        /* host */
+int64_t abny_hmm_dense_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D);      /* host */
+int abny_hmm_dense_forward_backward(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                                    const float* shift, const float* A, const float* B, const float* c0,
+                                    const float* init, const float* trans, int64_t K, int mode,
+                                    float* post, double* loglik, int32_t* n_good, double* stats,
+                                    void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
