@@ -180,6 +180,13 @@ NEXT2_SYMBOLS = {
     'abny_hmm_dense_forward_backward': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, C.c_int,
                                                   _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
+# the third section (prefix abnz_: the max-product path of that model, csrc/hmm_dense_vit.hip): abn_hmm_viterbi's arguments
+# with li, lt in place of lw, ls, lr
+NEXT3_SYMBOLS = {
+    'abnz_hmm_dense_viterbi_ws_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'abnz_hmm_dense_viterbi': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                         _vp, _i64, _vp]),
+}
 # abn_sd_count's conditions and the limits of abn_sd_collect / abn_sd_count (include/abnet3_hip.h)
 SD_CONDITION = {'all': 0, 'swdp': 1, 'swsp': 2}
 SD_MAX_N, SD_MAX_THR, SD_MAX_D = 1 << 22, 1 << 30, 4096
@@ -243,7 +250,8 @@ def load():
             'abnet3_amd: %s is missing. Build it with `python -m abnet3_amd.build` '
             '(hipcc, gfx950). There is no CPU fallback.' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(NEXT_SYMBOLS.items()) + list(NEXT2_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(NEXT_SYMBOLS.items()) + list(NEXT2_SYMBOLS.items()) + \
+            list(NEXT3_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -27,23 +27,15 @@
 #include "gemm_f32.h"
 #include "gmm_tile.h"
 #include "utt_chain.h"
+#include "hmm_dense.h"
 #include "../../include/abnet3_hip_next.h"
 
 #include <math.h>
 
 namespace abn {
 
-static_assert(GM_B == UC_B, "utt_chain.h's geometry is this kernel's");
-constexpr int HD_MAX_K = 128;
-constexpr ChainLimits HD_LIMITS = {GM_MAX_D, "abn_gmm_max_d", HD_MAX_K, "abny_hmm_dense_max_k", "abn_hmm_max_len"};
 constexpr int64_t HD_FRAME_BYTES = sizeof(float);         // c_t per frame
-constexpr size_t hd_trans_bytes(int kc) { return sizeof(float) * kc * (kc + 1); }
-constexpr size_t hd_lds_bytes(int kc) { return GM_TILE_BYTES + hd_trans_bytes(kc); }
 constexpr int64_t hd_stats_bytes(int kc) { return (int64_t)sizeof(double) * (kc * kc + kc); }      // G cells, then `first`
-// 72 KiB of operand tiles + 64.5 KiB of transitions + under 8 KiB of static arrays, of the CU's 160 KiB
-static_assert(hd_lds_bytes(HD_MAX_K) + 8 * 1024 <= 160 * 1024, "the transition matrix fits beside the operand tiles");
-
-static inline int hd_kc_for(int64_t K) { return K <= 16 ? 16 : K <= 32 ? 32 : K <= 64 ? 64 : 128; }
 
 struct HmmDenseP {
     GmmP g;                                 // x, shift, A, B, c = c0, T, K, D, tiles_k: a kernel argument, as in hmm.hip

@@ -1,0 +1,296 @@
+// hmm_dense_vit.hip -- the max-product path of the HMM with a full K x K transition matrix (abnz_hmm_dense_viterbi).
+// abnet3_amd/hmm.py states the definition, tests/hmm_dense_vit_np.py restates it; DESIGN.md section 3.4c7 the shape.  The
+// host side (workspace geometry, checks) is utt_chain.h's.
+//
+// hmm_dense_kernel's launch shape (hmm_dense.hip): one launch for the corpus, persistent workgroups that loop over the
+// utterances (u = blockIdx.x, + gridDim.x, ...: a static assignment), a slab of 128 frames x K raw scores logN from the
+// mixture's fp32 MFMA tile (gmm_tile.h, c0 as the third table; no exp, no m_t) in the workgroup's region of the workspace,
+// then one sequential step per good frame.  The log transitions live in LDS for the whole launch behind the operand tiles:
+// [KC][KC + 1] fp32, -inf past K.  What the sticky decoders (hmm.hip) cannot do and this kernel does:
+//   * a true argmax over j for every (frame, k): thread t has own = t % KC (k) and the slice sl = t / KC of SW = KC^2 / 256
+//     consecutive j; it takes the max of W[j] + lt[j][own] over its slice with a strict compare in ascending j (the lowest
+//     j on ties), the NS = 256 / KC partial (value, j) pairs go through LDS and the threads t < KC combine them slice 0
+//     first, again strictly: the lowest j of the maximum, and its value.
+//   * W is not stored: the previous frame's u[j] stays in LDS and every reader takes W[j] = u[j] - M itself, M in a
+//     register (the same rounded subtraction, the same bits), which saves the frame a third barrier.  u is kept by
+//     parity, so a frame has two barriers: behind the partial pairs and behind the wave keys.
+//   * M and its lowest index -- at the last good frame the final state -- are ONE 64-bit key max-reduction (vit_wave.h).
+//   * a backpointer byte per (frame, k).  A block's bytes [128][KC] are collected in LDS over the dead operand tiles and go
+//     to the workspace as whole dwords from all 256 threads when the block is done (the utterance's last block stays in
+//     LDS).  The traceback takes the blocks last to first, stages each one in LDS the same way, lets one lane chase the
+//     bytes there, and writes the block's ids coalesced.  A BAD frame is marked by 0xFF in its first byte (j < 128); the
+//     first good frame's bytes are bp[k] = k, so the walk counts no switch there.
+// Padding never wins: lt is -inf outside K x K and u is -inf past K (written once, never by an owner), so a padded
+// candidate is -inf + -inf = -inf and loses every strict compare against slice 0's j = 0; threads with own >= K put no
+// key into the reduction (0 is below every key of a float).  No floating-point atomic, fixed orders throughout; nothing of
+// an utterance's results depends on the grid or on its neighbours.
+#include "common.h"
+#include "gemm_f32.h"
+#include "gmm_tile.h"
+#include "utt_chain.h"
+#include "vit_wave.h"
+#include "hmm_dense.h"
+#include "../../include/abnet3_hip_next.h"
+
+#include <math.h>
+
+namespace abn {
+
+constexpr unsigned char HDV_BAD = 0xFF;    // a BAD frame's first backpointer byte (every real one is below HD_MAX_K)
+static_assert(HD_MAX_K <= 128, "a backpointer is one byte and 0xFF marks a BAD frame");
+static_assert((size_t)GM_B * HD_MAX_K <= GM_TILE_BYTES, "a block's backpointers fit over the operand tiles");
+
+struct HmmDenseVitP {
+    GmmP g;                                 // x, shift, A, B, c = c0, T, K, D, tiles_k: a kernel argument, as in hmm.hip
+    const float* li; const float* lt;
+    const int64_t* off; const int* len;
+    int n_utt;
+    int* ids; double* log_prob; int* n_switch; int* n_good;
+    char* ws; int64_t per_wg;               // bytes of a workgroup's region
+    int ks, cap;                            // slab row stride (floats), frames the region holds
+};
+
+// The block of frames m0 .. m0 + nf - 1: BAD flags and the score tile logN into the slab (hmm_vit_scores of hmm.hip with
+// one tile of components).  Ends behind a barrier.
+__device__ __forceinline__ void hdv_block_scores(const GmmP& gp, int m0, int nf, float* smem, float* slab, int ks, int* bad_s)
+{
+    float* const As = smem;
+    float* const Bs = smem + 2 * GmTile::floats;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
+    if (t < GM_B) {
+        bool bad = false;
+        if (t < nf)
+            for (int d = 0; d < gp.D; ++d) {
+                const float xc = gp.x[(int64_t)(m0 + t) * gp.D + d] - gp.shift[d];
+                bad |= !__builtin_isfinite(xc * xc);
+            }
+        bad_s[t] = bad;
+    }
+    {
+        f32x16 acc[2][2];                                             // (K <= 128: one tile of components)
+        gmm_score_tile(gp, m0, 0, As, Bs, acc);
+        const int col_l = lane & 31, rsub = 4 * (lane >> 5);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    slab[(int64_t)(wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + rsub) * ks + wn0 + 32 * j + col_l] = acc[i][j][r];
+    }
+    __syncthreads();                                                  // the slab and bad_s are this workgroup's own
+}
+
+template <int KC>
+__global__ __launch_bounds__(256) void hmm_dense_vit_kernel(HmmDenseVitP p)
+{
+    constexpr int NS = 256 / KC, SW = KC / NS, TS = KC + 1;
+    static_assert(NS * SW == KC && NS * KC == 256, "256 threads cover KC x KC in slices of SW");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ int bad_s[GM_B];
+    __shared__ int ids_s[GM_B];
+    __shared__ unsigned long long red_k[2][4];
+    __shared__ float part_v[256];                                     // [slice][own]
+    __shared__ int part_j[256];
+    __shared__ float u_s[2][KC];                                      // the previous good frame's u, by parity; -inf past K
+
+    float* const lt_s = smem + 4 * GmTile::floats;                    // [KC][TS], behind the operand tiles
+    unsigned char* const bp_s = reinterpret_cast<unsigned char*>(smem);      // [128][KC], over the operand tiles
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int own = t % KC, sl = t / KC;
+    const int K = p.g.K, ks = p.ks;
+    const bool owner = t < K;                                         // state t's chain value is formed by this thread
+    char* const base = p.ws + (int64_t)blockIdx.x * p.per_wg;
+    float* const slab = reinterpret_cast<float*>(base);
+    unsigned char* const bpw = reinterpret_cast<unsigned char*>(base + (int64_t)sizeof(float) * GM_B * ks);
+
+    for (int i = t; i < KC * TS; i += 256) {
+        const int j = i / TS, k = i % TS;
+        lt_s[i] = (j < K && k < K) ? p.lt[j * K + k] : -INFINITY;
+    }
+    if (t < KC) { u_s[0][t] = -INFINITY; u_s[1][t] = -INFINITY; }
+    const float li = owner ? p.li[t] : 0.0f;
+    __syncthreads();
+
+    for (int u = (int)blockIdx.x; u < p.n_utt; u += (int)gridDim.x) {
+        const int64_t o = p.off[u];
+        const int L = p.len[u];
+        if (o < 0 || L < 0 || o + L > p.g.T || L > p.cap) {          // (uniform) nothing of this utterance is touched
+            if (t == 0) {
+                if (p.log_prob) p.log_prob[u] = NAN;
+                if (p.n_switch) p.n_switch[u] = -1;
+                if (p.n_good) p.n_good[u] = -1;
+            }
+            continue;
+        }
+        bool started = false;
+        int par = 0, ngood = 0, jlast = -1;
+        float M = 0.0f;                                               // the previous good frame's max
+        double lp = 0.0;
+        const int nblk = (L + GM_B - 1) / GM_B;
+
+        for (int b = 0; b < nblk; ++b) {
+            const int f0 = b * GM_B;
+            const int nf = min(GM_B, L - f0);
+            hdv_block_scores(p.g, (int)o + f0, nf, smem, slab, ks, bad_s);
+
+            float sn = owner ? slab[t] : 0.0f;
+            for (int f = 0; f < nf; ++f) {
+                const float s = sn;
+                if (f + 1 < nf) sn = owner ? slab[(int64_t)(f + 1) * ks + t] : 0.0f;
+                if (bad_s[f]) {                                       // (uniform) the chain passes over it
+                    if (t == 0) bp_s[f * KC] = HDV_BAD;
+                    continue;
+                }
+                float c = li;
+                int bj = t;                                           // the first good frame: bp[k] = k
+                if (started) {                                        // (uniform) c[own] = max_j (u[j] - M) + lt[j][own]
+                    const float* const ltc = lt_s + (sl * SW) * TS + own;
+                    const float* const uv = u_s[par] + sl * SW;
+                    float best = (uv[0] - M) + ltc[0];
+                    int bc = 0;
+#pragma unroll
+                    for (int q = 1; q < SW; ++q) {
+                        const float v = (uv[q] - M) + ltc[q * TS];
+                        if (v > best) { best = v; bc = q; }           // strict: the lowest j on ties
+                    }
+                    part_v[t] = best;
+                    part_j[t] = sl * SW + bc;
+                    __syncthreads();
+                    if (t < KC) {                                     // (sl == 0, own == t) slice 0 first, strictly
+                        c = part_v[t];
+                        bj = part_j[t];
+#pragma unroll
+                        for (int q = 1; q < NS; ++q) {
+                            const float v = part_v[q * KC + t];
+                            if (v > c) { c = v; bj = part_j[q * KC + t]; }
+                        }
+                    }
+                }
+                const float uu = s + c;
+                unsigned long long key = 0;                           // (below the key of -inf: the padding never wins)
+                if (owner) {
+                    u_s[par ^ 1][t] = uu;
+                    bp_s[f * KC + t] = (unsigned char)bj;
+                    key = vit_key(uu, t);
+                }
+                key = vit_wave_max(key);
+                if (lane == 0) red_k[par][wave] = key;
+                __syncthreads();
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned long long ok = red_k[par][w];
+                    key = ok > key ? ok : key;
+                }
+                M = vit_key_score(key);
+                int bi = (int)~(unsigned)key;
+                if ((unsigned)bi >= (unsigned)K) bi = 0;              // no score compared greater than -inf: still an id
+                jlast = bi;
+                lp += (double)M;
+                par ^= 1;                                             // (the other sets are not rewritten before the next barrier)
+                started = true;
+                ++ngood;
+            }
+            __syncthreads();                                          // the block's backpointers are complete; the slab's readers are done
+            if (b + 1 < nblk) {                                       // (uniform; nf == 128) the last block stays in LDS
+                const unsigned* const src = reinterpret_cast<const unsigned*>(bp_s);
+                unsigned* const dst = reinterpret_cast<unsigned*>(bpw + (int64_t)f0 * KC);
+                for (int i = t; i < GM_B * KC / 4; i += 256) dst[i] = src[i];
+                __syncthreads();                                      // before the next block's operands replace them
+            }
+        }
+
+        // The traceback, last block first: jlast is the final state.  cur and nsw live in thread 0.
+        // (HDV_NO_TRACEBACK: a timing-only variant without it -- tools/variants.sh, tools/hmm_dense_decode_time.py; ids stay
+        // unwritten and n_switch 0.  Never defined in the library's build.)
+        int cur = ngood > 0 ? jlast : -1, nsw = 0;
+#ifndef HDV_NO_TRACEBACK
+        for (int b = nblk - 1; b >= 0; --b) {
+            const int f0 = b * GM_B;
+            const int nf = min(GM_B, L - f0);
+            if (b + 1 < nblk) {                                       // (uniform; nf == 128)
+                const unsigned* const src = reinterpret_cast<const unsigned*>(bpw + (int64_t)f0 * KC);
+                unsigned* const dst = reinterpret_cast<unsigned*>(bp_s);
+                for (int i = t; i < GM_B * KC / 4; i += 256) dst[i] = src[i];
+                __syncthreads();
+            }
+            if (t == 0) {
+                for (int f = nf - 1; f >= 0; --f) {
+                    const unsigned char* const row = bp_s + f * KC;
+                    if (row[0] == HDV_BAD || cur < 0) {
+                        ids_s[f] = -1;
+                        continue;
+                    }
+                    ids_s[f] = cur;
+                    const int pj = row[cur];
+                    nsw += pj != cur;
+                    cur = pj;
+                }
+            }
+            __syncthreads();
+            if (t < nf) p.ids[o + f0 + t] = ids_s[t];
+        }
+#else
+        (void)cur;
+#endif
+        if (t == 0) {
+            if (p.log_prob) p.log_prob[u] = lp;
+            if (p.n_switch) p.n_switch[u] = nsw;
+            if (p.n_good) p.n_good[u] = ngood;
+        }
+        __syncthreads();                                              // the traceback's reads before the next utterance's writes
+    }
+}
+
+}  // namespace abn
+
+using namespace abn;
+
+extern "C" int64_t abnz_hmm_dense_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D)
+{
+    return chain_ws_bytes("abnz_hmm_dense_viterbi_ws_bytes", n_utt, max_len, K, D, HD_LIMITS,
+                          K >= 1 && K <= HD_MAX_K ? hd_kc_for(K) : HD_MAX_K, 0);
+}
+
+template <int KC>
+static void hdv_launch(const HmmDenseVitP& p, int grid, hipStream_t st)
+{
+    static bool attr_set[16] = {};
+    if (first_use_on_device(attr_set)) chain_opt_in(reinterpret_cast<const void*>(hmm_dense_vit_kernel<KC>), hd_lds_bytes(KC));
+    hipLaunchKernelGGL(hmm_dense_vit_kernel<KC>, dim3((unsigned)grid), dim3(256), hd_lds_bytes(KC), st, p);
+}
+
+extern "C" int abnz_hmm_dense_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                                      const float* shift, const float* A, const float* B, const float* c0,
+                                      const float* li, const float* lt, int64_t K,
+                                      int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good,
+                                      void* ws, int64_t ws_bytes, void* stream)
+{
+    const char* what = "abnz_hmm_dense_viterbi";
+    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "%s: T = %lld out of range", what, (long long)T);
+    int rc = chain_check_sizes(what, n_utt, K, D, HD_LIMITS);
+    if (rc != ABN_OK) return rc;
+    ABN_REQUIRE(x && off && len && shift && A && B && c0 && li && lt && ids, "%s: null pointer", what);
+    const int kc = hd_kc_for(K);
+    const ChainWs hw = chain_ws(n_utt, 0, K, kc, 0);
+    ChainRegion a;
+    rc = chain_region(what, "abnz_hmm_dense_viterbi_ws_bytes", ws, ws_bytes, hw, &a);
+    if (rc != ABN_OK) return rc;
+    HmmDenseVitP p;
+    p.g.x = x; p.g.shift = shift; p.g.A = A; p.g.B = B; p.g.c = c0;
+    p.g.T = (int)T; p.g.K = (int)K; p.g.D = (int)D;
+    p.g.lse = nullptr; p.g.post = nullptr; p.g.slabs = nullptr;
+    p.g.tiles_k = 1; p.g.fblocks = 0; p.g.n_ranges = 0; p.g.blocks_per_range = 0;
+    p.li = li; p.lt = lt; p.off = off; p.len = len; p.n_utt = (int)n_utt;
+    p.ids = ids; p.log_prob = log_prob; p.n_switch = n_switch; p.n_good = n_good;
+    p.ws = a.ws; p.per_wg = a.per_wg;
+    p.ks = a.ks; p.cap = a.cap;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (kc == 16) hdv_launch<16>(p, hw.grid, st);
+    else if (kc == 32) hdv_launch<32>(p, hw.grid, st);
+    else if (kc == 64) hdv_launch<64>(p, hw.grid, st);
+    else hdv_launch<128>(p, hw.grid, st);
+    ABN_CHECK_LAUNCH(what);
+    return ABN_OK;
+}

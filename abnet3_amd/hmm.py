@@ -3,7 +3,7 @@
     python -m abnet3_amd.hmm fit-stay GMM.npz FEATURES MODEL.npz [--stay P] [--n-iter N] [--tol T]
     python -m abnet3_amd.hmm fit GMM.npz FEATURES MODEL.npz [--stay P] [--n-iter N] [--tol T] [--params mvws]
     python -m abnet3_amd.hmm transform MODEL.npz FEATURES OUT [--mode smooth|filter]
-    python -m abnet3_amd.hmm decode MODEL.npz FEATURES OUT [--min-duration S]
+    python -m abnet3_amd.hmm decode MODEL.npz FEATURES OUT [--min-duration S]      (a full-transition MODEL: no minimum)
     python -m abnet3_amd.hmm fit-trans MODEL_OR_GMM.npz FEATURES OUT.npz [--n-iter N] [--params mvti] [--alpha A]
 
 ``GmmPosteriorgram`` treats every frame on its own, so its posteriors flicker.  An HMM over the mixture's components
@@ -60,8 +60,8 @@ workgroups, one utterance at a time, one sum reduction per frame and sweep.  The
 sweeps, so there is no T x K array beyond it.  A Baum-Welch iteration is that launch with the per-component stays
 (abn_hmm_forward_backward_stats) and abn_hmm_accumulate, which reads the gamma table once as the A operand of
 abn_gmm_accumulate's statistics GEMM.  Limits: K <= abn_hmm_max_k(), D <= abn_gmm_max_d(), an utterance of at most
-abn_hmm_max_len() frames; utterances must not overlap.  Left out: the max-product path of the full-transition model
-below, duration distributions (the sticky max-product path has a minimum duration, below).
+abn_hmm_max_len() frames; utterances must not overlap.  Left out: duration distributions (the sticky max-product path has
+a minimum duration, below; the full-transition model's has none).
 
 The max-product path (``viterbi``, ``StickyHmmPosteriorgram.decode`` / ``quantize``; abn_hmm_viterbi, one launch;
 tests/hmm_vit_np.py restates it).  The model, the emissions and the BAD-frame rule are the ones above.
@@ -136,8 +136,31 @@ weights play no part):
   16, 32, 64 or 128) and the slice t div K' of K'^2 / 256 consecutive indices of the other side, adds its products in
   ascending order with fused multiply-adds, and the 256 / K' partial sums are added slice 0 first.
 * Limits: K <= abny_hmm_dense_max_k() (128: the matrix lives in LDS), D <= abn_gmm_max_d(), an utterance of at most
-  abn_hmm_max_len() frames; utterances must not overlap.  Left out: the max-product path of this model (``decode``),
-  duration states, sparse or banded matrices, K above the LDS limit.  Nothing here is tuned or measured on real speech.
+  abn_hmm_max_len() frames; utterances must not overlap.  Left out: duration states, sparse or banded matrices, K above
+  the LDS limit.  Nothing here is tuned or measured on real speech.
+
+The max-product path of the full-transition model (``dense_viterbi``, ``TransitionHmmPosteriorgram.decode`` / ``quantize``;
+abnz_hmm_dense_viterbi, csrc/hmm_dense_vit.hip, one launch; tests/hmm_dense_vit_np.py restates it).  Model, emissions and
+BAD-frame rule are those of the full-transition model: s = logN[t, :] are the score tile's bits; a BAD frame gets id -1, the
+chain passes over it, and it counts neither as a frame nor as a transition.
+
+* Log tables ``log_transitions(init, trans) -> (li [K], lt [K][K])``, float32, computed on the host in float64 from the
+  float32 init / trans and rounded once.  check_transitions' range applies (every entry >= 2^-100), so every logarithm is
+  finite; ``dense_viterbi`` refuses tables that hold NaN, +inf or -inf (ValueError).  The kernel takes no logarithm.
+* Recurrence per utterance over its good frames in order, fp32; every operation is one rounded add or a compare, so
+  contraction cannot change it.
+    first good frame:   u[k] = s[k] + li[k]
+    later good frames:  c[k] = max_j (W[j] + lt[j][k]),  bp[k] = the lowest j that attains the max,  u[k] = s[k] + c[k]
+    every good frame:   M = max_k u[k],  W = u - M,  log_prob += M  (a float64 sum in frame order)
+  The final state is the lowest k with W[k] == 0.
+* Traceback from the final state over the good frames backwards: ids[t] = cur, then cur = bp_t[cur].  Among all optimal
+  paths this is the smallest one when read from the last frame to the first.
+* Outputs (abn_hmm_viterbi's): ids [T] int32 (BAD frames -1; rows outside every utterance keep what they held), log_prob
+  [n_utt] float64, n_switch [n_utt] int32 (the changes of id between consecutive good frames), n_good [n_utt] int32.  An
+  utterance with no good frame gives (0.0, 0, 0) and all -1.  A refused utterance (outside 0 .. T, or longer than the
+  workspace was sized for) is left untouched: log_prob NaN, n_switch and n_good -1.
+* Limits: the full-transition model's.  Left out: a minimum duration for this model, hard-EM / Viterbi training, sparse
+  or banded matrices, K above the LDS limit.  Nothing here is tuned or measured on real speech.
 """
 import argparse
 import copy
@@ -492,6 +515,62 @@ def dense_forward_backward(table, off, lens, shift, A, B, c0, init, trans, mode=
     return (out, ll, ng, stats) if want_stats else (out, ll, ng)
 
 
+def log_transitions(init, trans):
+    """(li [K], lt [K, K]) float32: the log tables of the full-transition model's max-product path (module docstring),
+    computed on the host in float64 from float32(init), float32(trans) and rounded once.  ValueError through
+    check_transitions (finite, every entry >= 2^-100, rows summing to 1): every logarithm is finite."""
+    i32, t32 = check_transitions('hmm.log_transitions', init, trans)
+    return np.log(i32.astype(np.float64)).astype(np.float32), np.log(t32.astype(np.float64)).astype(np.float32)
+
+
+def _check_dense_log_tables(who, li, lt, K):
+    """The host checks of li [K] and lt [K, K]: float32 tensors that hold no NaN and no infinity."""
+    if not isinstance(li, torch.Tensor) or not isinstance(lt, torch.Tensor) or li.shape != (K,) or lt.shape != (K, K) or \
+            li.dtype != torch.float32 or lt.dtype != torch.float32:
+        raise ValueError('%s: li [K] and lt [K, K] float32 tensors are needed (hmm.log_transitions)' % who)
+    a, b = li.detach().cpu().numpy(), lt.detach().cpu().numpy()
+    if not (np.isfinite(a).all() and np.isfinite(b).all()):
+        raise ValueError('%s: the log tables must not hold NaN, +inf or -inf (every entry of init and trans is >= 2^-100)' % who)
+
+
+def dense_viterbi(table, off, lens, shift, A, B, c0, li, lt, ids=None, want_log_prob=True):
+    """(ids [T] int32, log_prob [n_utt] float64 or None, n_switch [n_utt] int32 or None, n_good [n_utt] int32), device
+    tensors, of the full-transition max-product recurrence the module docstring defines (abnz_hmm_dense_viterbi, one
+    launch).  off, lens: the utterances' first rows and lengths (host sequences or device tensors); they must not overlap.
+    li, lt: the log tables of ``log_transitions``.  Rows outside every utterance keep what `ids` held (-1 in a fresh
+    `ids`)."""
+    lib = _lib.load()
+    who = 'hmm.dense_viterbi'
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
+        raise ValueError('%s: a [T, D] float32 table is needed' % who)
+    T, D = table.shape
+    K = c0.shape[0]
+    if A.shape != (K, D) or B.shape != (K, D) or shift.shape != (D,) or any(t.dtype != torch.float32 for t in (shift, A, B, c0)):
+        raise ValueError('%s: shift [D], A [K, D], B [K, D], c0 [K] float32 are needed' % who)
+    if K < 1 or K > dense_max_k():
+        raise ValueError('%s: K = %d, the kernel takes 1 .. %d (abny_hmm_dense_max_k)' % (who, K, dense_max_k()))
+    _check_dense_log_tables(who, li, lt, K)
+    off_h, len_h, n_utt, longest = _utt.utterance_spans(who, off, lens, T, max_len(), 'abn_hmm_max_len')
+    if ids is not None and (not isinstance(ids, torch.Tensor) or ids.shape != (T,) or ids.dtype != torch.int32 or
+                            not ids.is_contiguous()):
+        raise ValueError('%s: ids must be a contiguous [T] int32 tensor' % who)
+    table = _gmm._check_table(who, table)
+    _lib.require_device(shift, A, B, c0, li, lt)
+    if ids is None:
+        ids = torch.full((T,), -1, dtype=torch.int32, device=table.device)
+    _lib.require_device(ids)
+    lp = torch.zeros(n_utt, dtype=torch.float64, device=table.device) if want_log_prob else None
+    nsw = torch.zeros(n_utt, dtype=torch.int32, device=table.device) if want_log_prob else None
+    ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
+    if T and n_utt and longest:
+        ws, off_d, len_d = _utt.workspace(who, lib.abnz_hmm_dense_viterbi_ws_bytes, off_h, len_h, longest, K, D, table.device)
+        _lib.check(lib.abnz_hmm_dense_viterbi(
+            _lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B), _lib.ptr(c0),
+            _lib.ptr(li), _lib.ptr(lt), K, _lib.ptr(ids), _lib.ptr(lp), _lib.ptr(nsw), _lib.ptr(ng),
+            _lib.ptr(ws), ws.numel(), _lib.stream()), 'abnz_hmm_dense_viterbi')
+    return ids, lp, nsw, ng
+
+
 def floor_rows(p):
     """float64: every entry below TRANS_MIN raised to it and each row renormalised once (a vector is one row)."""
     p = np.array(p, dtype=np.float64)
@@ -749,7 +828,7 @@ class StickyHmmPosteriorgram(object):
 
 
 class TransitionHmmPosteriorgram(object):
-    """transform / score / fit of the full-transition HMM the module docstring defines, over a fitted GmmPosteriorgram
+    """transform / decode / quantize / score / fit of the full-transition HMM the module docstring defines, over a fitted GmmPosteriorgram
     (its means, variances and shift; its weights only seed the default start).
 
     trans, init: the start; by default the sticky matrix of the mixture's weights and `stay` (``sticky_transitions``).
@@ -773,6 +852,7 @@ class TransitionHmmPosteriorgram(object):
         self.alpha = float(alpha)
         self.log_likelihoods = []
         self.n_bad_ = self.n_starved_ = 0
+        self.last_log_prob_ = self.last_n_switch_ = self.last_n_good_ = None
         self._tables = None
 
     @classmethod
@@ -837,6 +917,42 @@ class TransitionHmmPosteriorgram(object):
         _, ll, ng = dense_forward_backward(table, _utt.starts(lens), lens, *self.device_tables(table.device), mode='filter')
         ll_sum, n = torch.stack([ll.sum(), ng.to(torch.float64).sum()]).cpu().tolist()
         return ll_sum / max(1.0, n)
+
+    def _decode_ids(self, corpus):
+        """(device ids [rows] int32, DeviceCorpus or None, names or None, lens); fills last_log_prob_ / last_n_switch_ /
+        last_n_good_ / n_bad_."""
+        table, dc, lens = self._utterances(corpus)
+        names = list(dc.names) if dc is not None else list(corpus) if isinstance(corpus, dict) else None
+        shift, A, B, c0, _, _ = self.device_tables(table.device)
+        li, lt = (torch.from_numpy(np.ascontiguousarray(a)).to(table.device) for a in log_transitions(self.init_, self.trans_))
+        ids, lp, nsw, ng = dense_viterbi(table, _utt.starts(lens), lens, shift, A, B, c0, li, lt)
+        self.last_log_prob_, self.last_n_switch_, self.last_n_good_ = lp.cpu().numpy(), nsw.cpu().numpy(), ng.cpu().numpy()
+        self.n_bad_ = int(lens.sum() - self.last_n_good_.sum())
+        return ids, dc, names, lens
+
+    def decode(self, corpus):
+        """The unit ids of the best path (the module docstring's full-transition max-product recurrence), int32, -1 for a
+        BAD frame: {name: host array [length]} in corpus order for a DeviceCorpus, a dict or a file -- what
+        KMeansQuantizer.segment and StickyHmmPosteriorgram.decode return, so kmeans.unit_sequences / bitrate / segments,
+        eskmeans.landmarks_from_units, tde.unit_boundaries and hmm.bigram_counts take it as it is --; for a [T, D] table,
+        which is ONE utterance, the device tensor [T].  ``last_log_prob_`` (float64), ``last_n_switch_`` and
+        ``last_n_good_`` (int32) hold the utterances' log joint probabilities, switch counts and good-frame counts;
+        ``n_bad_`` the BAD frames.  There is no minimum duration for this model."""
+        ids, _, names, lens = self._decode_ids(corpus)
+        return ids if names is None else _gmm._split_rows(ids.cpu().numpy(), zip(names, lens))
+
+    def quantize(self, corpus):
+        """Each frame replaced by the mean of its decoded component (uncentred: m + shift), [rows, D] float32 on the
+        device, a BAD frame a row of zeros; for a DeviceCorpus a new DeviceCorpus with the same names, lengths and times
+        (as StickyHmmPosteriorgram.quantize)."""
+        from .dataloader import DeviceCorpus
+        ids, dc, _, _ = self._decode_ids(corpus)
+        means = torch.from_numpy(self.gmm.means_.astype(np.float32)).to(ids.device)
+        out = means[ids.clamp(min=0).to(torch.int64)]
+        out[ids < 0] = 0.0
+        if dc is None:
+            return out
+        return DeviceCorpus.from_table(out, dc.names, [dc.length[k] for k in dc.names], dc.times)
 
     def fit(self, corpus, n_iter=10, tol=1e-4, params=DENSE_PARAMS, n_ranges=0):
         """Baum-Welch from the current parameters: any subset of the `m`eans, `v`ariances, `t`ransitions and the `i`nit
@@ -992,10 +1108,24 @@ def main(argv=None):
               % (h.stay_, len(h.log_likelihoods), h.log_likelihoods[-1], h.n_bad_))
         return 0
     if _holds(args.model, 'trans'):
-        if args.cmd == 'decode':
-            raise ValueError('python -m abnet3_amd.hmm decode: %s holds a full transition matrix; its max-product path is not '
-                             'built yet' % args.model)
         h = TransitionHmmPosteriorgram.load(args.model)
+        if args.cmd == 'decode':
+            from . import kmeans as _kmeans
+            if args.min_duration != 1:
+                raise ValueError('python -m abnet3_amd.hmm decode: %s holds a full transition matrix, whose max-product path '
+                                 'has no minimum duration; --min-duration %d needs a sticky model' % (args.model, args.min_duration))
+            out = h.decode(feats)
+            _gmm._write_named(args.out, out, times, as_column=True)
+            n_good = int(h.last_n_good_.sum())
+            if times is not None:
+                seconds = sum(float(np.asarray(times[k])[-1] - np.asarray(times[k])[0]) for k in out if len(times[k]) > 1)
+                rate = '%.2f bits/s' % _kmeans.bitrate(_kmeans.unit_sequences(out), seconds) if seconds > 0 else 'n/a (no duration)'
+            else:
+                rate = '%.2f bits/s at 100 frames/s' % _kmeans.bitrate(_kmeans.unit_sequences(out), max(n_good, 1) / 100.0)
+            print('%d files, %d frames (%d BAD), K = %d, full transitions, %d switches, bitrate %s, mean log-probability %.6f per '
+                  'good frame -> %s' % (len(out), sum(v.shape[0] for v in out.values()), h.n_bad_, h.gmm.n_components,
+                                        int(h.last_n_switch_.sum()), rate, float(h.last_log_prob_.sum()) / max(n_good, 1), args.out))
+            return 0
         post = h.transform(feats, args.mode).cpu().numpy()
         out = _gmm._split_rows(post, ((k, v.shape[0]) for k, v in feats.items()))
         _gmm._write_named(args.out, out, times)

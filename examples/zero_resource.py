@@ -29,7 +29,8 @@ full-transition HMM (TransitionHmmPosteriorgram: a K x K transition matrix, K <=
 matrix and prints ABX (kl) of raw, sticky-smoothed and transition-smoothed posteriorgrams side by side.  --hmm-decode adds the
 discrete units of that HMM's best path (StickyHmmPosteriorgram.decode, Viterbi): their bitrate and switch count beside
 those of the frame-wise mixture argmax (stay = 0 through the same call), and ABX over the quantised frames (each frame
-replaced by its unit's mean).  Nothing in it is tuned on real speech.
+replaced by its unit's mean); with --hmm-trans N also the units of the full-transition HMM's best path
+(TransitionHmmPosteriorgram.decode).  Nothing in it is tuned on real speech.
 --terms replaces the pair miner by term discovery (abnet3_amd/terms.py): local-alignment DTW of every utterance against
 every other -- over the filterbanks, or with --gmm over the mixture's posteriorgrams under the KL distance -- clustered
 into a .classes file, from which SamplerClusterSiamese draws the train and dev pairs: the reference's canonical route,
@@ -218,6 +219,7 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
                                                                    raw_ll, rs.error, r.error, rs.n_triplets))
         print(more)
         line += '\n' + more
+        dense = None
         if hmm_trans:
             w = np.maximum(g.weights_, 1e-8)                         # (a starved component: the dense model has no retired units)
             init, trans = sticky_transitions(w / w.sum(), h.stay_)
@@ -229,6 +231,7 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
                                        float(np.diag(d.trans_).mean()), d.n_starved_, rd.error, rs.error, r.error, rd.n_triplets))
             print(more)
             line += '\n' + more
+            dense = d
         if hmm_fit:
             t = StickyHmmPosteriorgram(g, h.stay_).fit(corpus, n_iter=int(hmm_fit), tol=-np.inf)
             post = t.transform(corpus)
@@ -241,7 +244,7 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
             line += '\n' + more
             h = t
         if hmm_decode:
-            more = hmm_decode_lines(h, corpus, items, hmm_min_duration)
+            more = hmm_decode_lines(h, corpus, items, hmm_min_duration, dense)
             print(more)
             line += '\n' + more
     if qbe:
@@ -249,19 +252,23 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
     return (line, post) if want_post else line
 
 
-def hmm_decode_lines(h, corpus, items, min_duration=1):
+def hmm_decode_lines(h, corpus, items, min_duration=1, dense=None):
     """The units of the HMM's best path (StickyHmmPosteriorgram.decode) beside the frame-wise mixture argmax (stay = 0
     through the same call): bitrate with runs merged, switches, and ABX over the quantised frames.  min_duration > 1 adds
-    the best path whose units last at least that many frames."""
+    the best path whose units last at least that many frames; dense (a trained TransitionHmmPosteriorgram) the best path
+    under the full transition matrix (TransitionHmmPosteriorgram.decode, which has no minimum duration)."""
     seconds = 0.01 * corpus.total
     out = []
     routes = [('sticky-HMM Viterbi units (stay %.4f)' % h.stay_, h, 1),
               ('frame-wise mixture argmax (stay 0)', StickyHmmPosteriorgram(h.gmm, 0.0), 1)]
     if min_duration > 1:
         routes.insert(1, ('sticky-HMM Viterbi units (stay %.4f, at least %d frames per unit)' % (h.stay_, min_duration), h, min_duration))
+    if dense is not None:
+        routes.insert(1, ('full-transition HMM Viterbi units (mean self-transition %.4f)' % float(np.diag(dense.trans_).mean()), dense, None))
     for label, model, S in routes:
-        ids = model.decode(corpus, min_duration=S)
-        r = ABXEvaluator(items, model.quantize(corpus, min_duration=S), parallel='zero').run('within')
+        kw = {} if S is None else {'min_duration': S}
+        ids = model.decode(corpus, **kw)
+        r = ABXEvaluator(items, model.quantize(corpus, **kw), parallel='zero').run('within')
         out.append('%s: %.0f bit/s with runs merged, %d switches, log-probability per frame %.3f; ABX error quantised %.2f %% '
                    '(%d triplets)' % (label, bitrate(unit_sequences(ids), seconds), int(model.last_n_switch_.sum()),
                                       float(model.last_log_prob_.sum()) / max(1, int(model.last_n_good_.sum())), r.error, r.n_triplets))

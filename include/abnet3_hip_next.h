@@ -1,11 +1,13 @@
 /* abnet3_hip_next.h -- entries of libabnet3_hip.so that are not part of the numbered ABI yet.
  *
- * The entries below carry the prefix abnx_ (the minimum unit duration of the max-product decoders) or abny_ (the HMM with
- * a full transition matrix) and are exported beside those of abnet3_hip.h, whose conventions they follow (extern "C",
- * plain pointers and sizes, the ABN_E_* return codes, abn_last_error, every refusal before any launch).
+ * The entries below carry the prefix abnx_ (the minimum unit duration of the max-product decoders), abny_ (the HMM with
+ * a full transition matrix) or abnz_ (that model's max-product path) and are exported beside those of abnet3_hip.h, whose
+ * conventions they follow (extern "C", plain pointers and sizes, the ABN_E_* return codes, abn_last_error, every refusal
+ * before any launch).
  * They do not change ABN_ABI_VERSION.  A later change folds them into abnet3_hip.h under their abn_ names, bumps the
  * version, and moves their ledgers (abnet3_amd._lib.NEXT_SYMBOLS with tests/test_gpu_vit_dur.py, abnet3_amd._lib.NEXT2_SYMBOLS
- * with tests/test_gpu_hmm_dense.py) into the main one (abnet3_amd._lib.SYMBOLS, tests/test_dirty_memory_host.py).
+ * with tests/test_gpu_hmm_dense.py, abnet3_amd._lib.NEXT3_SYMBOLS with tests/test_gpu_hmm_dense_vit.py) into the main one
+ * (abnet3_amd._lib.SYMBOLS, tests/test_dirty_memory_host.py).
  */
 #ifndef ABNET3_HIP_NEXT_H
 #define ABNET3_HIP_NEXT_H
@@ -78,6 +80,34 @@ int abny_hmm_dense_forward_backward(const float* x, int64_t T, int64_t D, const 
                                     const float* init, const float* trans, int64_t K, int mode,
                                     float* post, double* loglik, int32_t* n_good, double* stats,
                                     void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- The max-product path of the HMM with a full transition matrix (csrc/hmm_dense_vit.hip) ----------------------------
+ * abn_hmm_viterbi with li [K] and lt [K][K] (the float32 logarithms of init and trans, abnet3_amd.hmm.log_transitions: the
+ * kernel takes no logarithm) in place of lw, ls, lr; abnet3_amd/hmm.py states the recurrence, tests/hmm_dense_vit_np.py
+ * restates it.  x, T, D, off, len, n_utt, shift, A, B, c0 and the emissions (the score tile's bits), the BAD-frame rule and
+ * the outputs are abn_hmm_viterbi's: ids [T] int32 (BAD frames -1, rows outside every utterance untouched), log_prob
+ * [n_utt] float64, n_switch [n_utt] int32, n_good [n_utt] int32 -- the last three may be null.  One utterance, good frames
+ * in order, fp32, every operation one rounded add or a compare:
+ *     first good frame:  u[k] = s[k] + li[k]
+ *     later good frames: c[k] = max_j (W[j] + lt[j][k]),  bp[k] = the lowest j that attains it,  u[k] = s[k] + c[k]
+ *     every good frame:  M = max_k u[k],  W = u - M,  log_prob += M (a float64 sum in frame order)
+ * The final state is the lowest k with W[k] == 0; backwards ids[t] = cur, cur = bp_t[cur].  The caller guarantees finite
+ * tables (no NaN, no infinity).  An utterance with no good frame gives (0.0, 0, 0) and all -1.
+ *
+ * K <= abny_hmm_dense_max_k(), D <= abn_gmm_max_d(), an utterance of at most abn_hmm_max_len() frames.  Workspace:
+ * abnz_hmm_dense_viterbi_ws_bytes(n_utt, max_len, K, D) bytes (per workgroup of min(n_utt, 256) the slab of scores and one
+ * backpointer byte per frame and state of the capacity K rounds up to: 16, 32, 64 or 128), 16-byte aligned, -1 with
+ * abn_last_error for refused sizes; it need not be cleared.  Refusals, all before any launch, in
+ * abny_hmm_dense_forward_backward's order: T out of range, sizes < 1: ABN_E_ARG; K or D beyond the limits:
+ * ABN_E_UNSUPPORTED; null pointers (the three optional outputs excepted): ABN_E_ARG; a workspace that holds no frame:
+ * ABN_E_WORKSPACE; a misaligned workspace: ABN_E_ARG.  An utterance outside 0 .. T or longer than the workspace was sized
+ * for is left untouched: log_prob NaN, n_switch and n_good -1. */
+int64_t abnz_hmm_dense_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D);   /* host */
+int abnz_hmm_dense_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                           const float* shift, const float* A, const float* B, const float* c0,
+                           const float* li, const float* lt, int64_t K,
+                           int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good,
+                           void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
