@@ -187,6 +187,12 @@ NEXT3_SYMBOLS = {
     'abnz_hmm_dense_viterbi': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                          _vp, _i64, _vp]),
 }
+# the fourth section (prefix abnw_: that path with a minimum unit duration): the twin's arguments plus int32 min_duration
+# at the end, and a sizing entry of its own
+NEXT4_SYMBOLS = {
+    'abnw_hmm_dense_viterbi_dur_ws_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'abnw_hmm_dense_viterbi_dur': (C.c_int, NEXT3_SYMBOLS['abnz_hmm_dense_viterbi'][1] + [_i32]),
+}
 # abn_sd_count's conditions and the limits of abn_sd_collect / abn_sd_count (include/abnet3_hip.h)
 SD_CONDITION = {'all': 0, 'swdp': 1, 'swsp': 2}
 SD_MAX_N, SD_MAX_THR, SD_MAX_D = 1 << 22, 1 << 30, 4096
@@ -251,7 +257,7 @@ def load():
             '(hipcc, gfx950). There is no CPU fallback.' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SYMBOLS.items()) + list(NEXT_SYMBOLS.items()) + list(NEXT2_SYMBOLS.items()) + \
-            list(NEXT3_SYMBOLS.items()):
+            list(NEXT3_SYMBOLS.items()) + list(NEXT4_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

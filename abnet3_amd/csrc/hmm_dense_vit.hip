@@ -1,6 +1,7 @@
 // hmm_dense_vit.hip -- the max-product path of the HMM with a full K x K transition matrix (abnz_hmm_dense_viterbi).
 // abnet3_amd/hmm.py states the definition, tests/hmm_dense_vit_np.py restates it; DESIGN.md section 3.4c7 the shape.  The
-// host side (workspace geometry, checks) is utt_chain.h's.
+// host side (workspace geometry, checks) is utt_chain.h's.  Behind it the same path with a minimum unit duration
+// (hmm_dense_dur_kernel: abnw_hmm_dense_viterbi_dur), which shares the score phase and the launch shape.
 //
 // hmm_dense_kernel's launch shape (hmm_dense.hip): one launch for the corpus, persistent workgroups that loop over the
 // utterances (u = blockIdx.x, + gridDim.x, ...: a static assignment), a slab of 128 frames x K raw scores logN from the
@@ -243,14 +244,216 @@ __global__ __launch_bounds__(256) void hmm_dense_vit_kernel(HmmDenseVitP p)
     }
 }
 
+// ---- minimum duration (abnw_hmm_dense_viterbi_dur; tests/hmm_dense_dur_np.py restates it) ---------
+// hmm_dense_vit_kernel with every unit a chain of S states (vit_wave.h's vit_dur_step), S >= 2.  What differs:
+//   * the diagonal of lt is -inf in LDS -- a unit is entered from a DIFFERENT unit -- and lt[k][k] is the owner's register ls;
+//   * the owner of unit k keeps the chain's normalised values V in SC >= S registers (slot SC - S + i is state i); u_s holds
+//     the exit states' U[j][S-1], and every reader forms U - N itself, N the previous good frame's maximum over ALL states:
+//     the key reduction runs over each owner's chain maximum.  The same two barriers a frame;
+//   * a byte per (frame, k) holds the backpointer in bits 0 .. 6 and the exit state's stay bit in bit 7, so every value of a
+//     byte is a real one and a BAD frame is marked elsewhere: one byte per frame behind the region's backpointers
+//     (slab | [cap][KC] backpointer bytes | [cap] BAD bytes), bad_s for the block in LDS;
+//   * the chasing lane carries (cur, ci) -- unit and chain state -- across blocks and BAD frames; the final ci is the largest
+//     state of the final unit whose V is 0, which that unit's owner leaves in LDS.
+constexpr unsigned char HDD_STAY = 0x80;
+static_assert(HD_MAX_K <= HDD_STAY, "a backpointer is seven bits beside the stay bit");
+
+struct HmmDenseDurP { HmmDenseVitP v; int S; };
+
+template <int KC, int SC>
+__global__ __launch_bounds__(256) void hmm_dense_dur_kernel(HmmDenseDurP pd)
+{
+    constexpr int NS = 256 / KC, SW = KC / NS, TS = KC + 1;
+    static_assert(NS * SW == KC && NS * KC == 256, "256 threads cover KC x KC in slices of SW");
+    static_assert(SC >= 2 && SC <= VIT_DUR_MAX, "the chain of a unit is held in SC registers");
+    const HmmDenseVitP& p = pd.v;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ int bad_s[GM_B];
+    __shared__ int ids_s[GM_B];
+    __shared__ unsigned long long red_k[2][4];
+    __shared__ float part_v[256];                                     // [slice][own]
+    __shared__ int part_j[256];
+    __shared__ float u_s[2][KC];                                      // the previous good frame's exit U, by parity; -inf past K
+    __shared__ int fin_s;                                             // the final unit's chain state
+
+    float* const lt_s = smem + 4 * GmTile::floats;                    // [KC][TS], behind the operand tiles; the diagonal -inf
+    unsigned char* const bp_s = reinterpret_cast<unsigned char*>(smem);      // [128][KC], over the operand tiles
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int own = t % KC, sl = t / KC;
+    const int K = p.g.K, ks = p.ks, S = pd.S;
+    const int e0 = SC - S;                                            // state i lives in slot e0 + i
+    const bool owner = t < K;                                         // unit t's chain is kept by this thread
+    char* const base = p.ws + (int64_t)blockIdx.x * p.per_wg;
+    float* const slab = reinterpret_cast<float*>(base);
+    unsigned char* const bpw = reinterpret_cast<unsigned char*>(base + (int64_t)sizeof(float) * GM_B * ks);
+    unsigned char* const badw = bpw + (int64_t)p.cap * KC;
+
+    for (int i = t; i < KC * TS; i += 256) {
+        const int j = i / TS, k = i % TS;
+        lt_s[i] = (j < K && k < K && j != k) ? p.lt[j * K + k] : -INFINITY;
+    }
+    if (t < KC) { u_s[0][t] = -INFINITY; u_s[1][t] = -INFINITY; }
+    const float li = owner ? p.li[t] : 0.0f;
+    const float ls = owner ? p.lt[t * K + t] : 0.0f;
+    __syncthreads();
+
+    for (int u = (int)blockIdx.x; u < p.n_utt; u += (int)gridDim.x) {
+        const int64_t o = p.off[u];
+        const int L = p.len[u];
+        if (o < 0 || L < 0 || o + L > p.g.T || L > p.cap) {          // (uniform) nothing of this utterance is touched
+            if (t == 0) {
+                if (p.log_prob) p.log_prob[u] = NAN;
+                if (p.n_switch) p.n_switch[u] = -1;
+                if (p.n_good) p.n_good[u] = -1;
+            }
+            continue;
+        }
+        bool started = false;
+        int par = 0, ngood = 0, jlast = -1;
+        float N = 0.0f;                                               // the previous good frame's max over all states
+        float V[SC];                                                  // the chain of unit t, normalised
+#pragma unroll
+        for (int i = 0; i < SC; ++i) V[i] = -INFINITY;
+        double lp = 0.0;
+        const int nblk = (L + GM_B - 1) / GM_B;
+
+        for (int b = 0; b < nblk; ++b) {
+            const int f0 = b * GM_B;
+            const int nf = min(GM_B, L - f0);
+            hdv_block_scores(p.g, (int)o + f0, nf, smem, slab, ks, bad_s);
+
+            float sn = owner ? slab[t] : 0.0f;
+            for (int f = 0; f < nf; ++f) {
+                const float s = sn;
+                if (f + 1 < nf) sn = owner ? slab[(int64_t)(f + 1) * ks + t] : 0.0f;
+                if (bad_s[f]) continue;                               // (uniform) the chain passes over it
+                float c = li;                                         // what enters state 0
+                int bj = t;                                           // the first good frame: bp[k] = k
+                if (started) {                                        // (uniform) c[own] = max_{j != own} (U[j][S-1] - N) + lt[j][own]
+                    const float* const ltc = lt_s + (sl * SW) * TS + own;
+                    const float* const uv = u_s[par] + sl * SW;
+                    float best = (uv[0] - N) + ltc[0];
+                    int bc = 0;
+#pragma unroll
+                    for (int q = 1; q < SW; ++q) {
+                        const float v = (uv[q] - N) + ltc[q * TS];
+                        if (v > best) { best = v; bc = q; }           // strict: the lowest j on ties
+                    }
+                    part_v[t] = best;
+                    part_j[t] = sl * SW + bc;
+                    __syncthreads();
+                    if (t < KC) {                                     // (sl == 0, own == t) slice 0 first, strictly
+                        c = part_v[t];
+                        bj = part_j[t];
+#pragma unroll
+                        for (int q = 1; q < NS; ++q) {
+                            const float v = part_v[q * KC + t];
+                            if (v > c) { c = v; bj = part_j[q * KC + t]; }
+                        }
+                    }
+                }
+                unsigned long long key = 0;                           // (below the key of -inf: the padding never wins)
+                if (owner) {
+                    bool st;
+                    const float m = vit_dur_step<SC>(V, s, c, ls, e0, &st);
+                    u_s[par ^ 1][t] = V[SC - 1];
+                    bp_s[f * KC + t] = (unsigned char)(bj | (st ? HDD_STAY : 0));
+                    key = vit_key(m, t);
+                }
+                key = vit_wave_max(key);
+                if (lane == 0) red_k[par][wave] = key;
+                __syncthreads();
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned long long ok = red_k[par][w];
+                    key = ok > key ? ok : key;
+                }
+                N = vit_key_score(key);
+                int bi = (int)~(unsigned)key;
+                if ((unsigned)bi >= (unsigned)K) bi = 0;              // no score compared greater than -inf: still an id
+                jlast = bi;                                           // the lowest unit whose chain holds the maximum
+#pragma unroll
+                for (int i = 0; i < SC; ++i) V[i] = V[i] - N;
+                lp += (double)N;
+                par ^= 1;                                             // (the other sets are not rewritten before the next barrier)
+                started = true;
+                ++ngood;
+            }
+            __syncthreads();                                          // the block's backpointers are complete; the slab's readers are done
+            if (b + 1 < nblk) {                                       // (uniform; nf == 128) the last block stays in LDS
+                const unsigned* const src = reinterpret_cast<const unsigned*>(bp_s);
+                unsigned* const dst = reinterpret_cast<unsigned*>(bpw + (int64_t)f0 * KC);
+                for (int i = t; i < GM_B * KC / 4; i += 256) dst[i] = src[i];
+                if (t < GM_B) badw[f0 + t] = (unsigned char)bad_s[t];
+                __syncthreads();                                      // before the next block's operands replace them
+            }
+        }
+
+        // The final state: the largest state of unit jlast at 0, from its owner.  Then the traceback, last block first;
+        // cur, ci and nsw live in thread 0.
+        if (ngood > 0 && t == jlast) {
+            int slot = SC - 1;
+#pragma unroll
+            for (int i = 0; i < SC; ++i) slot = V[i] == 0.0f ? i : slot;
+            fin_s = slot - e0;
+        }
+        __syncthreads();
+        int cur = ngood > 0 ? jlast : -1, ci = 0, nsw = 0;
+        if (t == 0 && ngood > 0) ci = fin_s;
+        for (int b = nblk - 1; b >= 0; --b) {
+            const int f0 = b * GM_B;
+            const int nf = min(GM_B, L - f0);
+            if (b + 1 < nblk) {                                       // (uniform; nf == 128)
+                const unsigned* const src = reinterpret_cast<const unsigned*>(bpw + (int64_t)f0 * KC);
+                unsigned* const dst = reinterpret_cast<unsigned*>(bp_s);
+                for (int i = t; i < GM_B * KC / 4; i += 256) dst[i] = src[i];
+                if (t < GM_B) bad_s[t] = badw[f0 + t];
+                __syncthreads();
+            }
+            if (t == 0) {
+                for (int f = nf - 1; f >= 0; --f) {
+                    if (bad_s[f] || cur < 0) {
+                        ids_s[f] = -1;
+                        continue;
+                    }
+                    ids_s[f] = cur;
+                    const int byte = bp_s[f * KC + cur];
+                    if (ci == S - 1 && (byte & HDD_STAY)) continue;   // the exit state repeats
+                    if (ci > 0) { --ci; continue; }                   // inside the forced advance
+                    const int pj = byte & (HDD_STAY - 1);             // state 0: entered from pj's exit state
+                    nsw += pj != cur;                                 // (the first good frame holds bp[k] = k)
+                    cur = pj;
+                    ci = S - 1;
+                }
+            }
+            __syncthreads();
+            if (t < nf) p.ids[o + f0 + t] = ids_s[t];
+        }
+        if (t == 0) {
+            if (p.log_prob) p.log_prob[u] = lp;
+            if (p.n_switch) p.n_switch[u] = nsw;
+            if (p.n_good) p.n_good[u] = ngood;
+        }
+        __syncthreads();                                              // the traceback's reads before the next utterance's writes
+    }
+}
+
 }  // namespace abn
 
 using namespace abn;
 
+// A region's bytes per frame: the backpointers of the capacity K rounds up to, and with a minimum duration
+// (abnw_hmm_dense_viterbi_dur, whatever S is) one more for the BAD flag.
+static inline int64_t hdv_frame_bytes(int64_t K, bool dur) { return (K >= 1 && K <= HD_MAX_K ? hd_kc_for(K) : HD_MAX_K) + (dur ? 1 : 0); }
+
 extern "C" int64_t abnz_hmm_dense_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D)
 {
-    return chain_ws_bytes("abnz_hmm_dense_viterbi_ws_bytes", n_utt, max_len, K, D, HD_LIMITS,
-                          K >= 1 && K <= HD_MAX_K ? hd_kc_for(K) : HD_MAX_K, 0);
+    return chain_ws_bytes("abnz_hmm_dense_viterbi_ws_bytes", n_utt, max_len, K, D, HD_LIMITS, hdv_frame_bytes(K, false), 0);
+}
+
+extern "C" int64_t abnw_hmm_dense_viterbi_dur_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D)
+{
+    return chain_ws_bytes("abnw_hmm_dense_viterbi_dur_ws_bytes", n_utt, max_len, K, D, HD_LIMITS, hdv_frame_bytes(K, true), 0);
 }
 
 template <int KC>
@@ -261,23 +464,44 @@ static void hdv_launch(const HmmDenseVitP& p, int grid, hipStream_t st)
     hipLaunchKernelGGL(hmm_dense_vit_kernel<KC>, dim3((unsigned)grid), dim3(256), hd_lds_bytes(KC), st, p);
 }
 
-extern "C" int abnz_hmm_dense_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
-                                      const float* shift, const float* A, const float* B, const float* c0,
-                                      const float* li, const float* lt, int64_t K,
-                                      int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good,
-                                      void* ws, int64_t ws_bytes, void* stream)
+template <int KC, int SC>
+static void hdd_launch(const HmmDenseDurP& p, int grid, hipStream_t st)
 {
-    const char* what = "abnz_hmm_dense_viterbi";
+    static bool attr_set[16] = {};
+    if (first_use_on_device(attr_set)) chain_opt_in(reinterpret_cast<const void*>(hmm_dense_dur_kernel<KC, SC>), hd_lds_bytes(KC));
+    hipLaunchKernelGGL((hmm_dense_dur_kernel<KC, SC>), dim3((unsigned)grid), dim3(256), hd_lds_bytes(KC), st, p);
+}
+
+template <int SC>
+static void hdd_launch_kc(const HmmDenseDurP& p, int kc, int grid, hipStream_t st)
+{
+    if (kc == 16) hdd_launch<16, SC>(p, grid, st);
+    else if (kc == 32) hdd_launch<32, SC>(p, grid, st);
+    else if (kc == 64) hdd_launch<64, SC>(p, grid, st);
+    else hdd_launch<128, SC>(p, grid, st);
+}
+
+// Both entries: the checks in their order -- min_duration (null: the entry has none) behind the pointers, as in
+// abnx_hmm_viterbi_dur --, the caller's workspace split into regions of the entry's geometry, and the launch.
+// min_duration = 1 launches hmm_dense_vit_kernel itself (the wider regions hold its backpointers and a spare byte a frame).
+static int hdv_run(const char* what, const char* ws_fn, const int32_t* min_duration,
+                   const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                   const float* shift, const float* A, const float* B, const float* c0, const float* li, const float* lt, int64_t K,
+                   int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good, void* ws, int64_t ws_bytes, void* stream)
+{
     ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "%s: T = %lld out of range", what, (long long)T);
     int rc = chain_check_sizes(what, n_utt, K, D, HD_LIMITS);
     if (rc != ABN_OK) return rc;
     ABN_REQUIRE(x && off && len && shift && A && B && c0 && li && lt && ids, "%s: null pointer", what);
+    const int S = min_duration ? *min_duration : 1;
+    ABN_REQUIRE(S >= 1 && S <= VIT_DUR_MAX, "%s: min_duration = %d, 1 .. %d (abnx_viterbi_dur_max)", what, S, VIT_DUR_MAX);
     const int kc = hd_kc_for(K);
-    const ChainWs hw = chain_ws(n_utt, 0, K, kc, 0);
+    const ChainWs hw = chain_ws(n_utt, 0, K, hdv_frame_bytes(K, min_duration != nullptr), 0);
     ChainRegion a;
-    rc = chain_region(what, "abnz_hmm_dense_viterbi_ws_bytes", ws, ws_bytes, hw, &a);
+    rc = chain_region(what, ws_fn, ws, ws_bytes, hw, &a);
     if (rc != ABN_OK) return rc;
-    HmmDenseVitP p;
+    HmmDenseDurP pd;
+    HmmDenseVitP& p = pd.v;
     p.g.x = x; p.g.shift = shift; p.g.A = A; p.g.B = B; p.g.c = c0;
     p.g.T = (int)T; p.g.K = (int)K; p.g.D = (int)D;
     p.g.lse = nullptr; p.g.post = nullptr; p.g.slabs = nullptr;
@@ -286,11 +510,37 @@ extern "C" int abnz_hmm_dense_viterbi(const float* x, int64_t T, int64_t D, cons
     p.ids = ids; p.log_prob = log_prob; p.n_switch = n_switch; p.n_good = n_good;
     p.ws = a.ws; p.per_wg = a.per_wg;
     p.ks = a.ks; p.cap = a.cap;
+    pd.S = S;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (kc == 16) hdv_launch<16>(p, hw.grid, st);
-    else if (kc == 32) hdv_launch<32>(p, hw.grid, st);
-    else if (kc == 64) hdv_launch<64>(p, hw.grid, st);
-    else hdv_launch<128>(p, hw.grid, st);
+    if (S == 1) {
+        if (kc == 16) hdv_launch<16>(p, hw.grid, st);
+        else if (kc == 32) hdv_launch<32>(p, hw.grid, st);
+        else if (kc == 64) hdv_launch<64>(p, hw.grid, st);
+        else hdv_launch<128>(p, hw.grid, st);
+    } else if (S == 2) hdd_launch_kc<2>(pd, kc, hw.grid, st);
+    else if (S <= 4) hdd_launch_kc<4>(pd, kc, hw.grid, st);
+    else hdd_launch_kc<8>(pd, kc, hw.grid, st);
     ABN_CHECK_LAUNCH(what);
     return ABN_OK;
+}
+
+extern "C" int abnz_hmm_dense_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                                      const float* shift, const float* A, const float* B, const float* c0,
+                                      const float* li, const float* lt, int64_t K,
+                                      int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good,
+                                      void* ws, int64_t ws_bytes, void* stream)
+{
+    return hdv_run("abnz_hmm_dense_viterbi", "abnz_hmm_dense_viterbi_ws_bytes", nullptr, x, T, D, off, len, n_utt, shift, A, B, c0, li, lt, K,
+                   ids, log_prob, n_switch, n_good, ws, ws_bytes, stream);
+}
+
+// abnz_hmm_dense_viterbi with a minimum duration (include/abnet3_hip_next.h).
+extern "C" int abnw_hmm_dense_viterbi_dur(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                                          const float* shift, const float* A, const float* B, const float* c0,
+                                          const float* li, const float* lt, int64_t K,
+                                          int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good,
+                                          void* ws, int64_t ws_bytes, void* stream, int32_t min_duration)
+{
+    return hdv_run("abnw_hmm_dense_viterbi_dur", "abnw_hmm_dense_viterbi_dur_ws_bytes", &min_duration, x, T, D, off, len, n_utt, shift, A, B,
+                   c0, li, lt, K, ids, log_prob, n_switch, n_good, ws, ws_bytes, stream);
 }

@@ -159,8 +159,29 @@ chain passes over it, and it counts neither as a frame nor as a transition.
   [n_utt] float64, n_switch [n_utt] int32 (the changes of id between consecutive good frames), n_good [n_utt] int32.  An
   utterance with no good frame gives (0.0, 0, 0) and all -1.  A refused utterance (outside 0 .. T, or longer than the
   workspace was sized for) is left untouched: log_prob NaN, n_switch and n_good -1.
-* Limits: the full-transition model's.  Left out: a minimum duration for this model, hard-EM / Viterbi training, sparse
-  or banded matrices, K above the LDS limit.  Nothing here is tuned or measured on real speech.
+* Minimum duration (``min_duration`` = S, an integer 1 .. 8, default 1 = the recurrence above; abnw_hmm_dense_viterbi_dur,
+  csrc/hmm_dense_vit.hip with csrc/vit_wave.h's chain step; tests/hmm_dense_dur_np.py restates it).  Every unit k becomes a
+  left-to-right chain of S states with tied emissions of which only the last may repeat; a unit is left only from its last
+  state and only for a DIFFERENT unit.  Good frames only (durations count good frames): a path is a sequence of segments
+  (k_i, n_i) with k_i != k_{i+1}, every segment but the utterance's last has n_i >= S, and its score is the sum of the
+  frames' scores + li[k_1] + lt[k_{i-1}][k_i] for each later segment + max(n_i - S, 0) lt[k_i][k_i].  Adjacent segments
+  differ, so the maximal runs of the ids ARE the segments and n_switch = segments - 1 (the sticky model's "re-entering the
+  same unit" cannot happen).  Recurrence for S >= 2, fp32, one rounded add or a compare per operation; V[k][0 .. S-1] the
+  normalised previous values:
+    first good frame:   U[k][0] = s + li[k], every other state -inf
+    later good frames:  ent[k] = max over j != k of (V[j][S-1] + lt[j][k]),  bp[k] = the lowest such j
+                        (strict compares in ascending j; K = 1: ent = -inf, bp irrelevant)
+                        U[k][0] = s + ent[k];   U[k][i] = s + V[k][i-1] for 0 < i < S-1
+                        a = V[k][S-1] + lt[k][k],  st = a > V[k][S-2]  (strict: a tie goes to the advance)
+                        U[k][S-1] = s + (st ? a : V[k][S-2])
+    every good frame:   N_t = max over all (k, i) of U,  V = U - N_t,  log_prob += N_t  (float64, frame order)
+  The final state is the lowest k, then the largest i, with V[k][i] == 0.  Going backwards from (k, i): i == S-1 and st set
+  -> (k, S-1); else i > 0 -> (k, i-1); else -> (bp[k], S-1), one switch.  S = 1 is NOT this recurrence (its diagonal sits
+  inside the argmax): min_duration = 1 makes the call without it, and abnw_hmm_dense_viterbi_dur launches that kernel.
+  log_prob is the score above, not a log joint probability of the K-state chain.  Left out: a duration distribution, a
+  maximum duration, untied emission states; S is untuned on real speech.
+* Limits: the full-transition model's.  Left out: hard-EM / Viterbi training, sparse or banded matrices, K above the LDS
+  limit.  Nothing here is tuned or measured on real speech.
 """
 import argparse
 import copy
@@ -533,14 +554,16 @@ def _check_dense_log_tables(who, li, lt, K):
         raise ValueError('%s: the log tables must not hold NaN, +inf or -inf (every entry of init and trans is >= 2^-100)' % who)
 
 
-def dense_viterbi(table, off, lens, shift, A, B, c0, li, lt, ids=None, want_log_prob=True):
+def dense_viterbi(table, off, lens, shift, A, B, c0, li, lt, ids=None, want_log_prob=True, min_duration=1):
     """(ids [T] int32, log_prob [n_utt] float64 or None, n_switch [n_utt] int32 or None, n_good [n_utt] int32), device
     tensors, of the full-transition max-product recurrence the module docstring defines (abnz_hmm_dense_viterbi, one
     launch).  off, lens: the utterances' first rows and lengths (host sequences or device tensors); they must not overlap.
     li, lt: the log tables of ``log_transitions``.  Rows outside every utterance keep what `ids` held (-1 in a fresh
-    `ids`)."""
+    `ids`).  min_duration = S > 1: every unit lasts at least S good frames (abnw_hmm_dense_viterbi_dur, a workspace of its
+    own geometry); 1 is exactly the call without it."""
     lib = _lib.load()
     who = 'hmm.dense_viterbi'
+    min_duration = _utt.check_min_duration(who, min_duration)
     if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
         raise ValueError('%s: a [T, D] float32 table is needed' % who)
     T, D = table.shape
@@ -563,11 +586,15 @@ def dense_viterbi(table, off, lens, shift, A, B, c0, li, lt, ids=None, want_log_
     nsw = torch.zeros(n_utt, dtype=torch.int32, device=table.device) if want_log_prob else None
     ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
     if T and n_utt and longest:
-        ws, off_d, len_d = _utt.workspace(who, lib.abnz_hmm_dense_viterbi_ws_bytes, off_h, len_h, longest, K, D, table.device)
-        _lib.check(lib.abnz_hmm_dense_viterbi(
-            _lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B), _lib.ptr(c0),
-            _lib.ptr(li), _lib.ptr(lt), K, _lib.ptr(ids), _lib.ptr(lp), _lib.ptr(nsw), _lib.ptr(ng),
-            _lib.ptr(ws), ws.numel(), _lib.stream()), 'abnz_hmm_dense_viterbi')
+        sizing = lib.abnz_hmm_dense_viterbi_ws_bytes if min_duration == 1 else lib.abnw_hmm_dense_viterbi_dur_ws_bytes
+        ws, off_d, len_d = _utt.workspace(who, sizing, off_h, len_h, longest, K, D, table.device)
+        args = (_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B),
+                _lib.ptr(c0), _lib.ptr(li), _lib.ptr(lt), K, _lib.ptr(ids), _lib.ptr(lp), _lib.ptr(nsw), _lib.ptr(ng),
+                _lib.ptr(ws), ws.numel(), _lib.stream())
+        if min_duration == 1:
+            _lib.check(lib.abnz_hmm_dense_viterbi(*args), 'abnz_hmm_dense_viterbi')
+        else:
+            _lib.check(lib.abnw_hmm_dense_viterbi_dur(*(args + (min_duration,))), 'abnw_hmm_dense_viterbi_dur')
     return ids, lp, nsw, ng
 
 
@@ -918,35 +945,38 @@ class TransitionHmmPosteriorgram(object):
         ll_sum, n = torch.stack([ll.sum(), ng.to(torch.float64).sum()]).cpu().tolist()
         return ll_sum / max(1.0, n)
 
-    def _decode_ids(self, corpus):
+    def _decode_ids(self, corpus, min_duration=1):
         """(device ids [rows] int32, DeviceCorpus or None, names or None, lens); fills last_log_prob_ / last_n_switch_ /
         last_n_good_ / n_bad_."""
+        min_duration = _utt.check_min_duration('TransitionHmmPosteriorgram', min_duration)
         table, dc, lens = self._utterances(corpus)
         names = list(dc.names) if dc is not None else list(corpus) if isinstance(corpus, dict) else None
         shift, A, B, c0, _, _ = self.device_tables(table.device)
         li, lt = (torch.from_numpy(np.ascontiguousarray(a)).to(table.device) for a in log_transitions(self.init_, self.trans_))
-        ids, lp, nsw, ng = dense_viterbi(table, _utt.starts(lens), lens, shift, A, B, c0, li, lt)
+        ids, lp, nsw, ng = dense_viterbi(table, _utt.starts(lens), lens, shift, A, B, c0, li, lt, min_duration=min_duration)
         self.last_log_prob_, self.last_n_switch_, self.last_n_good_ = lp.cpu().numpy(), nsw.cpu().numpy(), ng.cpu().numpy()
         self.n_bad_ = int(lens.sum() - self.last_n_good_.sum())
         return ids, dc, names, lens
 
-    def decode(self, corpus):
+    def decode(self, corpus, min_duration=1):
         """The unit ids of the best path (the module docstring's full-transition max-product recurrence), int32, -1 for a
         BAD frame: {name: host array [length]} in corpus order for a DeviceCorpus, a dict or a file -- what
         KMeansQuantizer.segment and StickyHmmPosteriorgram.decode return, so kmeans.unit_sequences / bitrate / segments,
         eskmeans.landmarks_from_units, tde.unit_boundaries and hmm.bigram_counts take it as it is --; for a [T, D] table,
         which is ONE utterance, the device tensor [T].  ``last_log_prob_`` (float64), ``last_n_switch_`` and
         ``last_n_good_`` (int32) hold the utterances' log joint probabilities, switch counts and good-frame counts;
-        ``n_bad_`` the BAD frames.  There is no minimum duration for this model."""
-        ids, _, names, lens = self._decode_ids(corpus)
+        ``n_bad_`` the BAD frames.  min_duration = S (an integer 1 .. 8): every unit but an utterance's last lasts at least
+        S good frames (the module docstring's minimum duration of this model; with S > 1 ``last_log_prob_`` is that
+        definition's score); 1 is the recurrence without it."""
+        ids, _, names, lens = self._decode_ids(corpus, min_duration)
         return ids if names is None else _gmm._split_rows(ids.cpu().numpy(), zip(names, lens))
 
-    def quantize(self, corpus):
+    def quantize(self, corpus, min_duration=1):
         """Each frame replaced by the mean of its decoded component (uncentred: m + shift), [rows, D] float32 on the
         device, a BAD frame a row of zeros; for a DeviceCorpus a new DeviceCorpus with the same names, lengths and times
-        (as StickyHmmPosteriorgram.quantize)."""
+        (as StickyHmmPosteriorgram.quantize).  min_duration: as in ``decode``."""
         from .dataloader import DeviceCorpus
-        ids, dc, _, _ = self._decode_ids(corpus)
+        ids, dc, _, _ = self._decode_ids(corpus, min_duration)
         means = torch.from_numpy(self.gmm.means_.astype(np.float32)).to(ids.device)
         out = means[ids.clamp(min=0).to(torch.int64)]
         out[ids < 0] = 0.0

@@ -30,7 +30,8 @@ matrix and prints ABX (kl) of raw, sticky-smoothed and transition-smoothed poste
 discrete units of that HMM's best path (StickyHmmPosteriorgram.decode, Viterbi): their bitrate and switch count beside
 those of the frame-wise mixture argmax (stay = 0 through the same call), and ABX over the quantised frames (each frame
 replaced by its unit's mean); with --hmm-trans N also the units of the full-transition HMM's best path
-(TransitionHmmPosteriorgram.decode).  Nothing in it is tuned on real speech.
+(TransitionHmmPosteriorgram.decode), and with --hmm-min-duration S those whose units last at least S frames under either
+model.  Nothing in it is tuned on real speech.
 --terms replaces the pair miner by term discovery (abnet3_amd/terms.py): local-alignment DTW of every utterance against
 every other -- over the filterbanks, or with --gmm over the mixture's posteriorgrams under the KL distance -- clustered
 into a .classes file, from which SamplerClusterSiamese draws the train and dev pairs: the reference's canonical route,
@@ -256,7 +257,8 @@ def hmm_decode_lines(h, corpus, items, min_duration=1, dense=None):
     """The units of the HMM's best path (StickyHmmPosteriorgram.decode) beside the frame-wise mixture argmax (stay = 0
     through the same call): bitrate with runs merged, switches, and ABX over the quantised frames.  min_duration > 1 adds
     the best path whose units last at least that many frames; dense (a trained TransitionHmmPosteriorgram) the best path
-    under the full transition matrix (TransitionHmmPosteriorgram.decode, which has no minimum duration)."""
+    under the full transition matrix (TransitionHmmPosteriorgram.decode), and with min_duration > 1 that model's best path
+    whose units last at least that many frames as well."""
     seconds = 0.01 * corpus.total
     out = []
     routes = [('sticky-HMM Viterbi units (stay %.4f)' % h.stay_, h, 1),
@@ -264,6 +266,8 @@ def hmm_decode_lines(h, corpus, items, min_duration=1, dense=None):
     if min_duration > 1:
         routes.insert(1, ('sticky-HMM Viterbi units (stay %.4f, at least %d frames per unit)' % (h.stay_, min_duration), h, min_duration))
     if dense is not None:
+        if min_duration > 1:
+            routes.insert(1, ('full-transition HMM Viterbi units, at least %d frames per unit' % min_duration, dense, min_duration))
         routes.insert(1, ('full-transition HMM Viterbi units (mean self-transition %.4f)' % float(np.diag(dense.trans_).mean()), dense, None))
     for label, model, S in routes:
         kw = {} if S is None else {'min_duration': S}

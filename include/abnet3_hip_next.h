@@ -1,12 +1,13 @@
 /* abnet3_hip_next.h -- entries of libabnet3_hip.so that are not part of the numbered ABI yet.
  *
  * The entries below carry the prefix abnx_ (the minimum unit duration of the max-product decoders), abny_ (the HMM with
- * a full transition matrix) or abnz_ (that model's max-product path) and are exported beside those of abnet3_hip.h, whose
- * conventions they follow (extern "C", plain pointers and sizes, the ABN_E_* return codes, abn_last_error, every refusal
- * before any launch).
+ * a full transition matrix), abnz_ (that model's max-product path) or abnw_ (that path with a minimum unit duration) and are
+ * exported beside those of abnet3_hip.h, whose conventions they follow (extern "C", plain pointers and sizes, the ABN_E_*
+ * return codes, abn_last_error, every refusal before any launch).
  * They do not change ABN_ABI_VERSION.  A later change folds them into abnet3_hip.h under their abn_ names, bumps the
  * version, and moves their ledgers (abnet3_amd._lib.NEXT_SYMBOLS with tests/test_gpu_vit_dur.py, abnet3_amd._lib.NEXT2_SYMBOLS
- * with tests/test_gpu_hmm_dense.py, abnet3_amd._lib.NEXT3_SYMBOLS with tests/test_gpu_hmm_dense_vit.py) into the main one
+ * with tests/test_gpu_hmm_dense.py, abnet3_amd._lib.NEXT3_SYMBOLS with tests/test_gpu_hmm_dense_vit.py,
+ * abnet3_amd._lib.NEXT4_SYMBOLS with tests/test_gpu_hmm_dense_dur.py) into the main one
  * (abnet3_amd._lib.SYMBOLS, tests/test_dirty_memory_host.py).
  */
 #ifndef ABNET3_HIP_NEXT_H
@@ -108,6 +109,39 @@ int abnz_hmm_dense_viterbi(const float* x, int64_t T, int64_t D, const int64_t* 
                            const float* li, const float* lt, int64_t K,
                            int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good,
                            void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- A minimum unit duration for that path (csrc/hmm_dense_vit.hip, csrc/vit_wave.h) ---------------------------------------
+ * abnz_hmm_dense_viterbi with one more argument: min_duration = S, 1 .. abnx_viterbi_dur_max() (8); abnet3_amd/hmm.py
+ * states the definition, tests/hmm_dense_dur_np.py restates it.  Every unit k becomes a left-to-right chain of S states with
+ * tied emissions of which only the last may repeat; a unit is left only from its last state and only for a DIFFERENT unit.
+ * One utterance, good frames only (BAD frames get id -1 and are passed over; durations count good frames): a path is a
+ * sequence of segments (k_i, n_i), k_i != k_{i+1}, every segment but the utterance's last at least S good frames long, and
+ * its score is
+ *     sum of the frames' scores s[t, k] + li[k_1] + lt[k_{i-1}][k_i] for each later segment + max(n_i - S, 0) lt[k_i][k_i].
+ * The maximal runs of the ids are the segments and n_switch = segments - 1.  Recurrence for S >= 2, fp32, every operation
+ * one rounded add or a compare; V[k][0 .. S-1] the normalised previous values:
+ *     first good frame:  U[k][0] = s + li[k], every other state -inf
+ *     later good frames: ent[k] = max over j != k of (V[j][S-1] + lt[j][k]),  bp[k] = the lowest such j (strict compares in
+ *                        ascending j);   U[k][0] = s + ent[k];   U[k][i] = s + V[k][i-1] for 0 < i < S-1;
+ *                        a = V[k][S-1] + lt[k][k],  st = a > V[k][S-2] (strict),  U[k][S-1] = s + (st ? a : V[k][S-2])
+ *     every good frame:  N_t = max U,  V = U - N_t,  log_prob = the float64 sum of the N_t in frame order.
+ * The final state is the lowest k, then the largest i, with V[k][i] == 0; backwards from (k, i): i == S-1 and st set ->
+ * (k, S-1); else i > 0 -> (k, i-1); else -> (bp[k], S-1), one switch.  With min_duration = 1 the entry launches
+ * abnz_hmm_dense_viterbi's kernel and the outputs are that entry's bit for bit.
+ *
+ * Arguments, outputs, limits and the treatment of refused utterances are abnz_hmm_dense_viterbi's.  Workspace:
+ * abnw_hmm_dense_viterbi_dur_ws_bytes(n_utt, max_len, K, D) bytes, the same for every S: min(n_utt, 256) regions of
+ * 128 x 128 x 4 + max_len x (K' + 1) bytes rounded up to 256, K' = K rounded up to 16, 32, 64 or 128 -- the slab of
+ * scores, one byte per frame and state (the backpointer in bits 0 .. 6, the stay bit in bit 7) and one byte per frame (the
+ * BAD flag); 16-byte aligned, -1 with abn_last_error for refused sizes; it need not be cleared.  Refusals are
+ * abnz_hmm_dense_viterbi's, in its order, with min_duration outside 1 .. abnx_viterbi_dur_max(): ABN_E_ARG behind the null
+ * pointers and ahead of the workspace -- all before any launch. */
+int64_t abnw_hmm_dense_viterbi_dur_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D);   /* host */
+int abnw_hmm_dense_viterbi_dur(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                               const float* shift, const float* A, const float* B, const float* c0,
+                               const float* li, const float* lt, int64_t K,
+                               int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good,
+                               void* ws, int64_t ws_bytes, void* stream, int32_t min_duration);
 
 #ifdef __cplusplus
 }
