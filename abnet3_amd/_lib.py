@@ -193,6 +193,11 @@ NEXT4_SYMBOLS = {
     'abnw_hmm_dense_viterbi_dur_ws_bytes': (_i64, [_i64, _i64, _i64, _i64]),
     'abnw_hmm_dense_viterbi_dur': (C.c_int, NEXT3_SYMBOLS['abnz_hmm_dense_viterbi'][1] + [_i32]),
 }
+# the fifth section (prefix abnv_: the hard statistics of that model's Viterbi training, csrc/hmm_hard.hip)
+NEXT5_SYMBOLS = {
+    'abnv_hmm_hard_stats_ws_bytes': (_i64, [_i64, _i64, _i64, _i64, C.c_int]),
+    'abnv_hmm_hard_stats': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, C.c_int, _vp, _vp, _vp, _vp, _i64, _vp]),
+}
 # abn_sd_count's conditions and the limits of abn_sd_collect / abn_sd_count (include/abnet3_hip.h)
 SD_CONDITION = {'all': 0, 'swdp': 1, 'swsp': 2}
 SD_MAX_N, SD_MAX_THR, SD_MAX_D = 1 << 22, 1 << 30, 4096
@@ -257,7 +262,7 @@ def load():
             '(hipcc, gfx950). There is no CPU fallback.' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SYMBOLS.items()) + list(NEXT_SYMBOLS.items()) + list(NEXT2_SYMBOLS.items()) + \
-            list(NEXT3_SYMBOLS.items()) + list(NEXT4_SYMBOLS.items()):
+            list(NEXT3_SYMBOLS.items()) + list(NEXT4_SYMBOLS.items()) + list(NEXT5_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

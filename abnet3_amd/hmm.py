@@ -5,6 +5,7 @@
     python -m abnet3_amd.hmm transform MODEL.npz FEATURES OUT [--mode smooth|filter]
     python -m abnet3_amd.hmm decode MODEL.npz FEATURES OUT [--min-duration S]      (a full-transition MODEL: no minimum)
     python -m abnet3_amd.hmm fit-trans MODEL_OR_GMM.npz FEATURES OUT.npz [--n-iter N] [--params mvti] [--alpha A]
+                                                                         [--viterbi [--min-duration S]]
 
 ``GmmPosteriorgram`` treats every frame on its own, so its posteriors flicker.  An HMM over the mixture's components
 with a single "stay" probability is the smallest acoustic-unit model that has a likelihood: its forward-backward pass
@@ -180,8 +181,38 @@ chain passes over it, and it counts neither as a frame nor as a transition.
   inside the argmax): min_duration = 1 makes the call without it, and abnw_hmm_dense_viterbi_dur launches that kernel.
   log_prob is the score above, not a log joint probability of the K-state chain.  Left out: a duration distribution, a
   maximum duration, untied emission states; S is untuned on real speech.
-* Limits: the full-transition model's.  Left out: hard-EM / Viterbi training, sparse or banded matrices, K above the LDS
-  limit.  Nothing here is tuned or measured on real speech.
+* Limits: the full-transition model's.  Left out: sparse or banded matrices, K above the LDS limit.  Nothing here is tuned
+  or measured on real speech.
+
+Viterbi training of the full-transition model (``hard_stats``, ``TransitionHmmPosteriorgram.fit_viterbi``;
+abnv_hmm_hard_stats, csrc/hmm_hard.hip; tests/hmm_hard_np.py restates it): hard EM on the decoded path itself (segmental
+k-means, Juang & Rabiner 1990), the alternative to ``fit``'s smoothed posteriors and the only one that trains the model
+``decode(min_duration=S)`` runs.
+
+* The hard statistics of unit ids [T] int32.  A frame is good if 0 <= ids[t] < K; every other id is BAD and is passed over
+  (the decoders write -1).  Per utterance u, a_0 .. a_{n-1} the ids of its good frames in order, S = min_duration:
+    n_good[u] = n;   counts[K][a_0] += 1 when n >= 1   (row K is `first`, the layout of dense_forward_backward's stats)
+    i >= 1, a_i != a_{i-1}:  counts[a_{i-1}][a_i] += 1   (a switch)
+    i >= 1, a_i == a_{i-1}:  counts[a_i][a_i] += 1 only if i >= S and a_{i-1} = ... = a_{i-S} = a_i   (a stay in the chain's
+                             last state; otherwise the frame is a forced advance and counts nothing)
+  A run of n frames gives max(n - S, 0) stays: exactly the lt[k][k] terms of the minimum-duration score above, so the counts,
+  normalised by rows, maximise that score of the path over row-stochastic matrices.  At S = 1 rows 0 .. K - 1 are
+  ``bigram_counts``.  Nothing connects two utterances; rows outside every utterance contribute nothing.
+    sums [K, 2D + 1] float64 = [S1 | S2 | N] over the good frames: N[k] the frames with id k, S1 / S2 the sums of xc and
+    xc^2, xc = fl32(x - shift), xc^2 rounded once; an entry whose xc^2 is not finite contributes 0 (``accumulate``'s rule).
+* counts is integer arithmetic throughout: the same for any grid, any n_ranges and any order of the utterances.  sums: per
+  range of whole 128-row blocks and per unit the frames are added in frame order in fp32, the ranges in range order in
+  float64; no floating-point atomics, the same bits for the same inputs and n_ranges.  So the fp32 error of an entry is at
+  most 2^-24 x (the longest partial's frames) x (the sum of the |terms|), the bar tests/test_gpu_hmm_hard.py holds it to.
+* ``fit_viterbi``: iteration i decodes under the current parameters (``dense_viterbi`` with min_duration),
+  viterbi_log_probs[i] = the mean best-path log probability per good frame, then ``hard_stats`` on the decoded ids, ONE
+  read-back, ``baum_welch_update`` on the sums and ``transition_update`` on the counts (both unchanged).  Each half maximises
+  the path score in its own arguments, so viterbi_log_probs does not decrease beyond the decoder's rounding slack (the
+  variance floor, min_count, alpha > 0 and TRANS_MIN are the usual exceptions).  It stops when the gain is below tol or when
+  no id changed (counted on the device).  No T x K table is allocated.
+* Left out: Viterbi training of the sticky model, whose stay and redraw share one log term (use
+  ``TransitionHmmPosteriorgram.from_sticky``); duration distributions; K above the LDS limit.  Nothing here is tuned or
+  measured on real speech.
 """
 import argparse
 import copy
@@ -647,6 +678,74 @@ def bigram_counts(ids_by_name, K):
     return counts
 
 
+def _hard_stats_launch(lib, table, off_d, len_d, n_utt, shift, ids, K, min_duration, n_ranges, ws):
+    """abnv_hmm_hard_stats on checked arguments: (counts, sums, n_good) from torch.empty (the entry clears what it needs)."""
+    T, D = table.shape
+    counts = torch.empty((K + 1, K), dtype=torch.int64, device=table.device)
+    sums = torch.empty((K, 2 * D + 1), dtype=torch.float64, device=table.device)
+    ng = torch.empty(n_utt, dtype=torch.int32, device=table.device)
+    _lib.check(lib.abnv_hmm_hard_stats(_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(ids), K,
+                                       min_duration, n_ranges, _lib.ptr(counts), _lib.ptr(sums), _lib.ptr(ng), _lib.ptr(ws), ws.numel(),
+                                       _lib.stream()), 'abnv_hmm_hard_stats')
+    return counts, sums, ng
+
+
+def _hard_stats_workspace(who, lib, T, n_utt, K, D, n_ranges, device):
+    need = lib.abnv_hmm_hard_stats_ws_bytes(T, n_utt, K, D, n_ranges)
+    if need < 0:
+        raise ValueError('%s: %s' % (who, lib.abn_last_error().decode('utf-8', 'replace')))
+    return torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+
+
+def _check_n_ranges(who, n_ranges):
+    if isinstance(n_ranges, bool) or not isinstance(n_ranges, (int, np.integer)) or not 0 <= int(n_ranges) <= 256:
+        raise ValueError('%s: n_ranges = %r, an integer 0 (chosen from the grid) .. 256 is needed' % (who, n_ranges))
+    return int(n_ranges)
+
+
+def hard_stats(table, off, lens, shift, ids, K, min_duration=1, n_ranges=0):
+    """(counts [K + 1, K] int64, sums [K, 2D + 1] float64, n_good [n_utt] int32), device tensors: the hard statistics the
+    module docstring defines, of the unit ids `ids` ([T] int32 on the device; what ``dense_viterbi`` decodes) over the
+    utterances off, lens of the [T, D] table (abnv_hmm_hard_stats: three launches).  counts: rows 0 .. K - 1 the transition
+    counts of the chain ``dense_viterbi(min_duration=S)`` decodes (at S = 1 ``bigram_counts``), row K the utterances' first
+    units -- ``transition_update``'s stats.  sums = [S1 | S2 | N] -- ``baum_welch_update``'s.  An id outside 0 .. K - 1 is a BAD
+    frame; rows outside every utterance contribute nothing.  n_ranges: as in ``accumulate``."""
+    lib = _lib.load()
+    who = 'hmm.hard_stats'
+    min_duration = _utt.check_min_duration(who, min_duration)
+    n_ranges = _check_n_ranges(who, n_ranges)
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
+        raise ValueError('%s: a [T, D] float32 table is needed' % who)
+    T, D = table.shape
+    if not isinstance(shift, torch.Tensor) or shift.shape != (D,) or shift.dtype != torch.float32:
+        raise ValueError('%s: shift [D] float32 is needed' % who)
+    if not isinstance(ids, torch.Tensor) or ids.shape != (T,) or ids.dtype != torch.int32 or not ids.is_contiguous():
+        raise ValueError('%s: ids must be a contiguous [T] int32 tensor, one id per row of the table' % who)
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= dense_max_k():
+        raise ValueError('%s: K = %r, the kernel takes 1 .. %d (abny_hmm_dense_max_k)' % (who, K, dense_max_k()))
+    K = int(K)
+    if D < 1 or D > int(lib.abn_gmm_max_d()):
+        raise ValueError('%s: D = %d, the kernel takes 1 .. %d (abn_gmm_max_d)' % (who, D, int(lib.abn_gmm_max_d())))
+    off_h, len_h, n_utt, longest = _utt.utterance_spans(who, off, lens, T, max_len(), 'abn_hmm_max_len')
+    table = _gmm._check_table(who, table)
+    _lib.require_device(shift, ids)
+    if not (T and n_utt):
+        return (torch.zeros((K + 1, K), dtype=torch.int64, device=table.device),
+                torch.zeros((K, 2 * D + 1), dtype=torch.float64, device=table.device),
+                torch.zeros(n_utt, dtype=torch.int32, device=table.device))
+    ws = _hard_stats_workspace(who, lib, T, n_utt, K, D, n_ranges, table.device)
+    off_d, len_d = torch.from_numpy(off_h).to(table.device), torch.from_numpy(len_h.astype(np.int32)).to(table.device)
+    return _hard_stats_launch(lib, table, off_d, len_d, n_utt, shift, ids, K, min_duration, n_ranges, ws)
+
+
+def check_dense_params(who, params):
+    """The letters of `params` as a set, or ValueError: a non-empty string over 'mvti' without a repeat."""
+    if not isinstance(params, str) or not params or len(set(params)) != len(params) or not set(params) <= set(DENSE_PARAMS):
+        raise ValueError('%s: params = %r, a non-empty choice of the letters of %r is needed '
+                         '(m means, v variances, t transitions, i init)' % (who, params, DENSE_PARAMS))
+    return set(params)
+
+
 class StickyHmmPosteriorgram(object):
     """transform / decode / quantize / score / fit_stay / fit of the sticky HMM the module docstring defines, over a fitted GmmPosteriorgram.
 
@@ -878,6 +977,8 @@ class TransitionHmmPosteriorgram(object):
         self.trans_, self.init_ = t32.astype(np.float64), i32.astype(np.float64)
         self.alpha = float(alpha)
         self.log_likelihoods = []
+        self.viterbi_log_probs = []
+        self.last_n_changed_ = None
         self.n_bad_ = self.n_starved_ = 0
         self.last_log_prob_ = self.last_n_switch_ = self.last_n_good_ = None
         self._tables = None
@@ -1041,6 +1142,84 @@ class TransitionHmmPosteriorgram(object):
         self.gmm, self.trans_, self.init_, self._tables = g, np.array(trans, dtype=np.float64), np.array(init, dtype=np.float64), None
         return self
 
+    def fit_viterbi(self, corpus, n_iter=10, tol=1e-4, params=DENSE_PARAMS, min_duration=1, n_ranges=0):
+        """Viterbi training (hard EM, segmental k-means) from the current parameters: any subset of the `m`eans,
+        `v`ariances, `t`ransitions and the `i`nit (params), on a COPY of the mixture exactly as ``fit``.  Iteration i decodes
+        the corpus under the current parameters (``dense_viterbi`` with min_duration) -- ``viterbi_log_probs[i]`` is the mean
+        best-path log probability per good frame --, takes the hard statistics of the decoded ids (``hard_stats``, the same
+        min_duration), reads everything back ONCE, and applies ``baum_welch_update`` to the sums and ``transition_update``
+        to the counts.  It stops after n_iter iterations, as soon as viterbi_log_probs[i] - viterbi_log_probs[i - 1] < tol,
+        or when no id changed since the previous iteration (counted on the device; the parameters are then those of the
+        last decoding).  Fills ``viterbi_log_probs``, ``n_bad_``, ``n_starved_``, ``last_n_changed_`` (the ids that
+        differed from the previous iteration's; all rows in the first), ``trans_`` and ``init_``.  No T x K table is
+        allocated: two [T] id buffers and the two workspaces."""
+        who = 'TransitionHmmPosteriorgram.fit_viterbi'
+        p = check_dense_params(who, params)                                        # (host checks first)
+        S = _utt.check_min_duration(who, min_duration)
+        n_ranges = _check_n_ranges(who, n_ranges)
+        table, _, lens = self._utterances(corpus)
+        lib = _lib.load()
+        g = copy.copy(self.gmm)
+        g.weights_, g.means_, g.variances_ = (np.array(a, dtype=np.float64) for a in (g.weights_, g.means_, g.variances_))
+        g.log_likelihoods, g._tables = list(g.log_likelihoods), None
+        K, D = g.means_.shape
+        if K > dense_max_k():
+            raise ValueError('%s: K = %d, the kernel takes 1 .. %d (abny_hmm_dense_max_k)' % (who, K, dense_max_k()))
+        T = table.shape[0]
+        off_h, len_h, n_utt, longest = _utt.utterance_spans(who, _utt.starts(lens), lens, T, max_len(), 'abn_hmm_max_len')
+        if not (T and n_utt and longest):
+            raise ValueError('%s: the corpus has no frame' % who)
+        shift64 = g.shift_.astype(np.float64)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(table.device)
+        shift = dev(g.shift_)
+        sizing = lib.abnz_hmm_dense_viterbi_ws_bytes if S == 1 else lib.abnw_hmm_dense_viterbi_dur_ws_bytes
+        vws, off_d, len_d = _utt.workspace(who, sizing, off_h, len_h, longest, K, D, table.device)
+        hws = _hard_stats_workspace(who, lib, T, n_utt, K, D, n_ranges, table.device)
+        ids = [torch.full((T,), -1, dtype=torch.int32, device=table.device) for _ in range(2)]
+        lp = torch.zeros(n_utt, dtype=torch.float64, device=table.device)
+        nsw = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
+        ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
+        m, v, trans, init = g.means_ - shift64, g.variances_, self.trans_, self.init_
+        mv, ti = ''.join(c for c in 'mv' if c in p), ''.join(c for c in 'ti' if c in p)
+        self.viterbi_log_probs = []
+        for it in range(int(n_iter)):
+            A, B, _ = _gmm.score_tables(np.full(K, 1.0 / K), m, v)
+            li, lt = (dev(a) for a in log_transitions(init, trans))
+            A, B, c0 = dev(A), dev(B), dev(emission_offsets(m, v))
+            cur = ids[it & 1]
+            args = (_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B),
+                    _lib.ptr(c0), _lib.ptr(li), _lib.ptr(lt), K, _lib.ptr(cur), _lib.ptr(lp), _lib.ptr(nsw),
+                    _lib.ptr(ng), _lib.ptr(vws), vws.numel(), _lib.stream())
+            if S == 1:
+                _lib.check(lib.abnz_hmm_dense_viterbi(*args), 'abnz_hmm_dense_viterbi')
+            else:
+                _lib.check(lib.abnw_hmm_dense_viterbi_dur(*(args + (S,))), 'abnw_hmm_dense_viterbi_dur')
+            counts, sums, _ = _hard_stats_launch(lib, table, off_d, len_d, n_utt, shift, cur, K, S, n_ranges, hws)
+            changed = (cur != ids[(it + 1) & 1]).sum().to(torch.float64) if it else torch.tensor(float(T), dtype=torch.float64,
+                                                                                                 device=table.device)
+            head = torch.stack([lp.sum(), ng.clamp(min=0).to(torch.float64).sum(), changed])
+            back = torch.cat([head, counts.flatten().to(torch.float64), sums.flatten()]).cpu().numpy()      # the one read-back
+            lp_sum, n, n_changed = back[:3].tolist()
+            if n < 1:
+                raise ValueError('%s: the corpus has no good frame' % who)
+            self.viterbi_log_probs.append(lp_sum / n)
+            self.n_bad_, self.last_n_changed_ = int(lens.sum() - n), int(n_changed)
+            if it > 0 and (self.viterbi_log_probs[-1] - self.viterbi_log_probs[-2] < tol or n_changed == 0):
+                break
+            counts_h = back[3:3 + (K + 1) * K].reshape(K + 1, K)
+            sums_h = back[3 + (K + 1) * K:].reshape(K, 2 * D + 1)
+            if mv:
+                self.n_starved_ = int((sums_h[:, 2 * D] < g.min_count).sum())
+                _, m, v, _, _ = baum_welch_update(sums_h, np.zeros(K), 0, m, v, g.gv_, g.var_floor, g.min_count, mv,
+                                                  weights=np.full(K, 1.0 / K), stay=0.0)
+            trans, init = transition_update(counts_h, trans, init, self.alpha, ti)
+        if 'm' in p:
+            g.means_ = m + shift64
+        if 'v' in p:
+            g.variances_ = v
+        self.gmm, self.trans_, self.init_, self._tables = g, np.array(trans, dtype=np.float64), np.array(init, dtype=np.float64), None
+        return self
+
     # -- files ----------------------------------------------------------------------------------------------------
     def save(self, path):
         """The mixture's file (GmmPosteriorgram.load reads it) plus trans, init and alpha."""
@@ -1050,7 +1229,8 @@ class TransitionHmmPosteriorgram(object):
                      log_likelihoods=np.asarray(g.log_likelihoods, dtype=np.float64),
                      n_components=g.n_components, n_iter=g.n_iter, tol=g.tol, var_floor=g.var_floor,
                      min_count=g.min_count, seed=g.seed, trans=self.trans_, init=self.init_, alpha=np.float64(self.alpha),
-                     trans_log_likelihoods=np.asarray(self.log_likelihoods, dtype=np.float64))
+                     trans_log_likelihoods=np.asarray(self.log_likelihoods, dtype=np.float64),
+                     viterbi_log_probs=np.asarray(self.viterbi_log_probs, dtype=np.float64))
 
     @classmethod
     def load(cls, path):
@@ -1061,6 +1241,8 @@ class TransitionHmmPosteriorgram(object):
             self = cls(g, z['trans'].astype(np.float64), z['init'].astype(np.float64), alpha=float(z['alpha']))
             self.trans_, self.init_ = z['trans'].astype(np.float64), z['init'].astype(np.float64)
             self.log_likelihoods = [float(v) for v in z['trans_log_likelihoods']]
+            if 'viterbi_log_probs' in z.files:                                 # (files written before fit_viterbi have none)
+                self.viterbi_log_probs = [float(v) for v in z['viterbi_log_probs']]
         return self
 
 
@@ -1107,6 +1289,9 @@ def main(argv=None):
     ft.add_argument('--tol', type=float, default=1e-4)
     ft.add_argument('--params', default=DENSE_PARAMS, help='the letters of what is re-estimated: m means, v variances, t transitions, i init')
     ft.add_argument('--alpha', type=float, default=1e-3, help='pseudo-count of the transition update (untuned)')
+    ft.add_argument('--viterbi', action='store_true', help='Viterbi training (hard EM on the decoded path) instead of Baum-Welch')
+    ft.add_argument('--min-duration', type=int, default=1, metavar='S',
+                    help='with --viterbi: train the model whose every unit lasts at least S frames (1 .. 8; default 1)')
     args = ap.parse_args(argv)
     if args.cmd == 'fit':
         check_params('python -m abnet3_amd.hmm fit', args.params)
@@ -1119,6 +1304,17 @@ def main(argv=None):
             h = TransitionHmmPosteriorgram.from_sticky(StickyHmmPosteriorgram.load(args.model), alpha=args.alpha)
         else:
             h = TransitionHmmPosteriorgram(_gmm.GmmPosteriorgram.load(args.model), stay=args.stay, alpha=args.alpha)
+        if args.viterbi:
+            h.fit_viterbi(feats, args.n_iter, args.tol, args.params, min_duration=args.min_duration)
+            h.save(args.out)
+            print('K = %d transitions after %d iterations of Viterbi training (params %s, alpha %g, min duration %d), mean best-path '
+                  'log-probability %.6f, %d ids changed in the last, %d BAD frames, %d starved, mean self-transition %.4f'
+                  % (h.trans_.shape[0], len(h.viterbi_log_probs), args.params, h.alpha, args.min_duration, h.viterbi_log_probs[-1],
+                     h.last_n_changed_, h.n_bad_, h.n_starved_, float(np.diag(h.trans_).mean())))
+            return 0
+        if args.min_duration != 1:
+            raise ValueError('python -m abnet3_amd.hmm fit-trans: --min-duration %d needs --viterbi (Baum-Welch has no minimum '
+                             'duration)' % args.min_duration)
         h.fit(feats, args.n_iter, args.tol, args.params)
         h.save(args.out)
         print('K = %d transitions after %d iterations (params %s, alpha %g), mean log-likelihood %.6f, %d BAD frames, %d starved, '

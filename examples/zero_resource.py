@@ -8,7 +8,7 @@ mined pairs, and the ABX item file ("phones" = word types).
                                      [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--hmm-fit N] [--hmm-trans N] [--hmm-decode] [--no-network] [--terms] [--terms-theta T]
                                      [--prefilter] [--alignment FILE]
                                      [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P] [--kmeans-min-duration S]
-                                     [--hmm-min-duration S]
+                                     [--hmm-min-duration S] [--hmm-trans-viterbi]
                                      [--eskmeans] [--eskmeans-clusters 24] [--samediff]
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
@@ -32,6 +32,9 @@ those of the frame-wise mixture argmax (stay = 0 through the same call), and ABX
 replaced by its unit's mean); with --hmm-trans N also the units of the full-transition HMM's best path
 (TransitionHmmPosteriorgram.decode), and with --hmm-min-duration S those whose units last at least S frames under either
 model.  Nothing in it is tuned on real speech.
+--hmm-trans-viterbi (with --hmm-trans N) also trains the full-transition HMM by N iterations of Viterbi training
+(TransitionHmmPosteriorgram.fit_viterbi: hard EM on the decoded path, with the minimum duration of --hmm-min-duration)
+from the same start and prints its best-path log probability, changed ids and switches on a line of its own.
 --terms replaces the pair miner by term discovery (abnet3_amd/terms.py): local-alignment DTW of every utterance against
 every other -- over the filterbanks, or with --gmm over the mixture's posteriorgrams under the KL distance -- clustered
 into a .classes file, from which SamplerClusterSiamese draws the train and dev pairs: the reference's canonical route,
@@ -190,14 +193,16 @@ def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frame
     return dl
 
 
-def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=None, hmm_fit=0, hmm_decode=False, hmm_min_duration=1, hmm_trans=0):
+def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=None, hmm_fit=0, hmm_decode=False, hmm_min_duration=1, hmm_trans=0,
+              hmm_trans_viterbi=False):
     """features -> GmmPosteriorgram.fit -> transform -> ABX (kl), and the search: the line main() prints.  hmm_stay (a
     number, or 'fit'): the sticky-HMM smoothed posteriorgrams beside the raw ones; they are the ones returned.  hmm_fit
     (iterations): the posteriorgrams of the Baum-Welch-trained HMM beside both; then those are returned.  hmm_decode: the
     discrete units of the (trained, else smoothed) HMM's best path beside the frame-wise mixture argmax; hmm_min_duration > 1:
     and those of the best path whose units last at least that many frames.  hmm_trans (iterations): the posteriorgrams of
     the full-transition HMM, trained from the sticky matrix, beside the raw and the sticky-smoothed ones (the returned
-    posteriorgrams stay the sticky route's)."""
+    posteriorgrams stay the sticky route's).  hmm_trans_viterbi: as many iterations of Viterbi training
+    (TransitionHmmPosteriorgram.fit_viterbi, with hmm_min_duration) from the same start, beside the Baum-Welch line."""
     names = list(fb)
     keep, items = word_items(tokens)
     corpus = DeviceCorpus({k: np.asarray(fb[k], dtype=np.float32) for k in names}, times)
@@ -233,6 +238,17 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
             print(more)
             line += '\n' + more
             dense = d
+            if hmm_trans_viterbi:
+                hv = TransitionHmmPosteriorgram(g, trans, init).fit_viterbi(corpus, n_iter=int(hmm_trans), tol=-np.inf,
+                                                                            min_duration=hmm_min_duration)
+                hv.decode(corpus, min_duration=hmm_min_duration)
+                more = ('full-transition HMM Viterbi training (%d iterations, at least %d frames per unit, alpha %g untuned): best-path '
+                        'log-probability per frame %.3f -> %.3f, %d ids changed in the last iteration, %d switches, mean self-transition '
+                        '%.4f, %d starved' % (len(hv.viterbi_log_probs), hmm_min_duration, hv.alpha, hv.viterbi_log_probs[0],
+                                              float(hv.last_log_prob_.sum()) / max(int(hv.last_n_good_.sum()), 1), hv.last_n_changed_,
+                                              int(hv.last_n_switch_.sum()), float(np.diag(hv.trans_).mean()), hv.n_starved_))
+                print(more)
+                line += '\n' + more
         if hmm_fit:
             t = StickyHmmPosteriorgram(g, h.stay_).fit(corpus, n_iter=int(hmm_fit), tol=-np.inf)
             post = t.transform(corpus)
@@ -346,6 +362,9 @@ def main():
     ap.add_argument('--hmm-trans', type=int, default=0, metavar='N',
                     help='with --gmm: N iterations of Baum-Welch on the full-transition HMM (K x K matrix, K <= 128) from the sticky '
                          'matrix of --hmm-stay (default 0.9); ABX (kl) of raw, sticky-smoothed and transition-smoothed posteriorgrams')
+    ap.add_argument('--hmm-trans-viterbi', action='store_true',
+                    help='with --hmm-trans N: also N iterations of Viterbi training (hard EM on the decoded path) from the same start, '
+                         'with the minimum duration of --hmm-min-duration; nothing is tuned on real speech')
     ap.add_argument('--hmm-decode', action='store_true',
                     help='with --hmm-stay / --hmm-fit: the discrete units of the HMM\'s best path (Viterbi): bitrate, switches and ABX '
                          'of the quantised frames, beside the frame-wise mixture argmax; nothing is tuned on real speech')
@@ -374,6 +393,8 @@ def main():
         ap.error('--hmm-fit trains the HMM over the mixture of --gmm')
     if args.hmm_trans and (not args.gmm or args.gmm_components > 128):
         ap.error('--hmm-trans trains the full-transition HMM over the mixture of --gmm, with --gmm-components <= 128')
+    if args.hmm_trans_viterbi and not args.hmm_trans:
+        ap.error('--hmm-trans-viterbi trains the model of --hmm-trans N')
     if args.hmm_decode and args.hmm_stay is None and not args.hmm_fit:
         ap.error('--hmm-decode decodes the HMM of --hmm-stay or --hmm-fit')
     esk_k = args.eskmeans_clusters if args.eskmeans else None
@@ -390,7 +411,8 @@ def main():
     gmm_line = post = None
     if args.gmm:
         gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True, hmm_stay=args.hmm_stay, hmm_fit=args.hmm_fit, hmm_decode=args.hmm_decode,
-                                   hmm_min_duration=args.hmm_min_duration, hmm_trans=args.hmm_trans)
+                                   hmm_min_duration=args.hmm_min_duration, hmm_trans=args.hmm_trans,
+                                   hmm_trans_viterbi=args.hmm_trans_viterbi)
     if args.no_network:
         if not (args.gmm or args.kmeans):
             ap.error('--no-network leaves nothing to do without --gmm or --kmeans')

@@ -1,13 +1,15 @@
 /* abnet3_hip_next.h -- entries of libabnet3_hip.so that are not part of the numbered ABI yet.
  *
  * The entries below carry the prefix abnx_ (the minimum unit duration of the max-product decoders), abny_ (the HMM with
- * a full transition matrix), abnz_ (that model's max-product path) or abnw_ (that path with a minimum unit duration) and are
+ * a full transition matrix), abnz_ (that model's max-product path), abnw_ (that path with a minimum unit duration) or abnv_
+ * (the hard statistics of that model's Viterbi training) and are
  * exported beside those of abnet3_hip.h, whose conventions they follow (extern "C", plain pointers and sizes, the ABN_E_*
  * return codes, abn_last_error, every refusal before any launch).
  * They do not change ABN_ABI_VERSION.  A later change folds them into abnet3_hip.h under their abn_ names, bumps the
  * version, and moves their ledgers (abnet3_amd._lib.NEXT_SYMBOLS with tests/test_gpu_vit_dur.py, abnet3_amd._lib.NEXT2_SYMBOLS
  * with tests/test_gpu_hmm_dense.py, abnet3_amd._lib.NEXT3_SYMBOLS with tests/test_gpu_hmm_dense_vit.py,
- * abnet3_amd._lib.NEXT4_SYMBOLS with tests/test_gpu_hmm_dense_dur.py) into the main one
+ * abnet3_amd._lib.NEXT4_SYMBOLS with tests/test_gpu_hmm_dense_dur.py, abnet3_amd._lib.NEXT5_SYMBOLS with
+ * tests/test_gpu_hmm_hard.py) into the main one
  * (abnet3_amd._lib.SYMBOLS, tests/test_dirty_memory_host.py).
  */
 #ifndef ABNET3_HIP_NEXT_H
@@ -142,6 +144,40 @@ int abnw_hmm_dense_viterbi_dur(const float* x, int64_t T, int64_t D, const int64
                                const float* li, const float* lt, int64_t K,
                                int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good,
                                void* ws, int64_t ws_bytes, void* stream, int32_t min_duration);
+
+/* ---- The hard statistics of the full-transition HMM's Viterbi training (csrc/hmm_hard.hip) ------------------------------
+ * From decoded unit ids (abnz_hmm_dense_viterbi, abnw_hmm_dense_viterbi_dur) the statistics of one hard-EM step;
+ * abnet3_amd/hmm.py states the definition, tests/hmm_hard_np.py restates it.  x, T, D, off, len, n_utt, shift are
+ * abnz_hmm_dense_viterbi's; ids [T] int32.  A frame is good if 0 <= ids[t] < K; every other id is BAD and is passed over.
+ * Per utterance u let a_0 .. a_{n-1} be the ids of its good frames in frame order and S = min_duration, 1 ..
+ * abnx_viterbi_dur_max():  n_good[u] = n, and
+ *     counts[K][a_0] += 1 when n >= 1                                  (row K is `first`, abny_hmm_dense_forward_backward's layout)
+ *     i >= 1, a_i != a_{i-1}:  counts[a_{i-1}][a_i] += 1               (a switch)
+ *     i >= 1, a_i == a_{i-1}:  counts[a_i][a_i] += 1 only if i >= S and a_{i-1} = ... = a_{i-S} = a_i
+ *                                                                      (a stay in the chain's last state; otherwise a forced advance)
+ * -- the maximum-likelihood counts of the chain abnw_hmm_dense_viterbi_dur decodes; at S = 1 rows 0 .. K - 1 are the plain
+ * bigram counts.  Durations count good frames only, nothing connects two utterances, rows outside every utterance contribute
+ * nothing, utterances may lie in any order (they must not overlap).
+ * sums [K][2 D + 1] float64 = [S1 | S2 | N] (abn_hmm_accumulate's layout) over the good frames of the utterances: N[k] the
+ * frames with id k, S1 and S2 the sums of xc and xc^2, xc = x - shift in fp32, xc^2 rounded once; an entry whose xc^2 is not
+ * finite contributes 0 to both (abn_hmm_accumulate's rule).
+ *
+ * counts [K + 1][K] int64 is the same for any grid, any n_ranges and any order of the utterances (integer atomics).  sums
+ * uses no floating-point atomics: the frames of a range (n_ranges consecutive ranges of whole 128-row blocks of the table;
+ * 0: chosen from the grid, at most 256) are added in frame order in fp32 per unit, the ranges in range order in float64 --
+ * the same bits from call to call for the same inputs and n_ranges.  counts, sums, n_good and the workspace need not be
+ * cleared.  Two memsets and three launches.
+ *
+ * K <= abny_hmm_dense_max_k(), D <= abn_gmm_max_d(), T < 2^31 - 128.  Workspace: abnv_hmm_hard_stats_ws_bytes(T, n_utt, K, D,
+ * n_ranges) bytes (a copy of the good ids [T] int32 and the ranges' fp32 partials), 16-byte aligned, -1 with abn_last_error
+ * for refused sizes.  Refusals, all before any launch, in this order: T out of range, sizes < 1: ABN_E_ARG; K or D beyond the
+ * limits: ABN_E_UNSUPPORTED; null pointers: ABN_E_ARG; min_duration outside 1 .. abnx_viterbi_dur_max(), n_ranges outside
+ * 0 .. 256: ABN_E_ARG; a short workspace: ABN_E_WORKSPACE; a misaligned one: ABN_E_ARG.  An utterance outside 0 .. T or longer
+ * than abn_hmm_max_len() gets n_good -1 and adds nothing. */
+int64_t abnv_hmm_hard_stats_ws_bytes(int64_t T, int64_t n_utt, int64_t K, int64_t D, int n_ranges);   /* host */
+int abnv_hmm_hard_stats(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                        const float* shift, const int32_t* ids, int64_t K, int32_t min_duration, int n_ranges,
+                        int64_t* counts, double* sums, int32_t* n_good, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
