@@ -1,6 +1,6 @@
-"""What the per-utterance entries (kmeans.viterbi, hmm.forward_backward, hmm.viterbi) share on the host: the checks of
-the utterances' offsets and lengths and of a minimum duration, and the workspace with the offsets and lengths uploaded
-beside it."""
+"""What the per-utterance entries (kmeans.viterbi, hmm.forward_backward, hmm.viterbi and their full-transition twins)
+share on the host: the checks of the table, of the utterances' offsets and lengths, of a minimum duration and of a
+caller's output tensors, the result tensors, and the workspace with the offsets and lengths uploaded beside it."""
 import numpy as np
 import torch
 
@@ -11,6 +11,42 @@ def starts(lens):
     """First rows [n] int64 of utterances of the given lengths laid end to end."""
     lens = np.asarray(lens, dtype=np.int64)
     return np.cumsum(lens) - lens
+
+
+def table_shape(who, table):
+    """(T, D) of a [T, D] float32 tensor, or ValueError: the first host check of every entry of hmm.py."""
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
+        raise ValueError('%s: a [T, D] float32 table is needed' % who)
+    return table.shape
+
+
+def check_ids(who, ids, T):
+    """ValueError unless a caller's `ids` (None: the entry makes its own) is a contiguous [T] int32 tensor."""
+    if ids is not None and (not isinstance(ids, torch.Tensor) or ids.shape != (T,) or ids.dtype != torch.int32 or
+                            not ids.is_contiguous()):
+        raise ValueError('%s: ids must be a contiguous [T] int32 tensor' % who)
+
+
+def path_results(ids, T, n_utt, want_log_prob, device):
+    """(ids, log_prob or None, n_switch or None, n_good) on the device, what a max-product entry fills: a fresh `ids` holds
+    -1, the per-utterance results 0."""
+    if ids is None:
+        ids = torch.full((T,), -1, dtype=torch.int32, device=device)
+    _lib.require_device(ids)
+    lp = torch.zeros(n_utt, dtype=torch.float64, device=device) if want_log_prob else None
+    nsw = torch.zeros(n_utt, dtype=torch.int32, device=device) if want_log_prob else None
+    return ids, lp, nsw, torch.zeros(n_utt, dtype=torch.int32, device=device)
+
+
+def posterior_table(who, out, T, K, device):
+    """A caller's `out`, checked, or a fresh table of zeros: the contiguous [T, K] float32 device tensor a forward-backward
+    entry writes."""
+    if out is None:
+        out = torch.zeros((T, K), dtype=torch.float32, device=device)
+    if out.shape != (T, K) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError('%s: out must be a contiguous [T, K] float32 tensor' % who)
+    _lib.require_device(out)
+    return out
 
 
 def utterance_spans(who, off, lens, T, longest_allowed, limit_name):

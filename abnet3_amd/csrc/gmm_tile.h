@@ -3,7 +3,8 @@
 // ka ascending, and the operand loaders that form the augmented rows on the way into LDS.  A caller that passes another
 // third table for c (hmm.hip: c without the log weight) runs the SAME MFMA sequence and depth order over it.
 // Also shared: the k-major X~ loaders of the statistics GEMM, the float64 slab sum and the (tile, range) grid with its
-// workspace size (gmm.hip's abn_gmm_accumulate / abn_gmm_mstep, hmm.hip's abn_hmm_accumulate).
+// workspace size (gmm.hip's abn_gmm_accumulate / abn_gmm_mstep, hmm.hip's abn_hmm_accumulate), and the score-only GmmP
+// of every HMM entry (hmm_score_params: hmm.hip, hmm_dense.hip, hmm_dense_vit.hip).
 #pragma once
 #include "common.h"
 #include "gemm_f32.h"
@@ -34,6 +35,19 @@ struct GmmP {
     float* slabs;               // [tiles_k][n_ranges][128][2 D + 1]
     int tiles_k, fblocks, n_ranges, blocks_per_range;
 };
+
+// A GmmP for the score tile alone (the HMM kernels' emissions, c = c0): the likelihood and accumulate passes' fields are
+// unused.
+static inline GmmP hmm_score_params(const float* x, int64_t T, int64_t D, const float* shift, const float* A, const float* B,
+                                    const float* c0, int64_t K)
+{
+    GmmP g;
+    g.x = x; g.shift = shift; g.A = A; g.B = B; g.c = c0;
+    g.T = (int)T; g.K = (int)K; g.D = (int)D;
+    g.lse = nullptr; g.post = nullptr; g.slabs = nullptr;
+    g.tiles_k = (int)((K + GM_B - 1) / GM_B); g.fblocks = 0; g.n_ranges = 0; g.blocks_per_range = 0;
+    return g;
+}
 
 // Column ka of an augmented operand: 0 xc / A, 1 xc^2 / B, 2 the ones column / c, 3 the zero fill up to the k-tile.
 __device__ __forceinline__ int aug_kind(int ka, int D) { return ka < D ? 0 : ka < 2 * D ? 1 : ka == 2 * D ? 2 : 3; }

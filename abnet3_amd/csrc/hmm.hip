@@ -24,6 +24,7 @@
 #include "common.h"
 #include "gemm_f32.h"
 #include "gmm_tile.h"
+#include "fixed_sum.h"
 #include "utt_chain.h"
 #include "vit_wave.h"
 #include "../../include/abnet3_hip_next.h"
@@ -48,56 +49,6 @@ struct HmmP {
     char* ws; int64_t per_wg;               // bytes of a workgroup's region
     int ks, cap;                            // slab row stride (floats), frames the region holds
 };
-
-// A GmmP for the score tile alone: the likelihood and accumulate passes' fields are unused.
-static GmmP hmm_score_params(const float* x, int64_t T, int64_t D, const float* shift, const float* A, const float* B,
-                             const float* c0, int64_t K)
-{
-    GmmP g;
-    g.x = x; g.shift = shift; g.A = A; g.B = B; g.c = c0;
-    g.T = (int)T; g.K = (int)K; g.D = (int)D;
-    g.lse = nullptr; g.post = nullptr; g.slabs = nullptr;
-    g.tiles_k = (int)((K + GM_B - 1) / GM_B); g.fblocks = 0; g.n_ranges = 0; g.blocks_per_range = 0;
-    return g;
-}
-
-// One DPP exchange inside the rows of 16 lanes (every lane has a source under these controls) and the sum of the two:
-// both partners add the same two numbers, so they hold the same bits.
-template <int CTRL>
-__device__ __forceinline__ float hmm_dpp_add(float v)
-{
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-// The sum over the wave, in every lane, in one fixed order: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror,
-// row_mirror leave the row's sum in its 16 lanes; the four rows' sums are read with v_readlane and added row 0 first.
-// All 64 lanes must be active.
-__device__ __forceinline__ float hmm_wave_sum(float v)
-{
-    v = hmm_dpp_add<0xB1>(v);
-    v = hmm_dpp_add<0x4E>(v);
-    v = hmm_dpp_add<0x141>(v);
-    v = hmm_dpp_add<0x140>(v);
-    float r = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-#pragma unroll
-    for (int i = 1; i < 4; ++i) r += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16 * i));
-    return r;
-}
-
-// 256 doubles summed in a fixed tree; the result is returned to every thread.
-__device__ __forceinline__ double hmm_block_sum(double v, double* sh)
-{
-    const int t = threadIdx.x;
-    __syncthreads();
-    sh[t] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) sh[t] += sh[t + o];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
 
 // The block of frames m0 .. m0 + nf - 1: BAD flags, the bt slab and m_t.  Ends behind a barrier.
 __device__ __forceinline__ void hmm_block_scores(const HmmP& p, int m0, int nf, float* smem, float* slab,
@@ -238,7 +189,7 @@ __global__ __launch_bounds__(256) void hmm_fb_kernel(HmmP p)
                         b[q] *= started ? rho * a[q] + omr * wk : wk;
                         s += b[q];
                     }
-                    s = hmm_wave_sum(s);
+                    s = fixed_wave_sum(s);
                     if (lane == 0) red_s[par][wave] = s;
                     __syncthreads();
                     const float c = ((red_s[par][0] + red_s[par][1]) + red_s[par][2]) + red_s[par][3];
@@ -256,7 +207,7 @@ __global__ __launch_bounds__(256) void hmm_fb_kernel(HmmP p)
                 __syncthreads();                                      // c_s is complete; the slab's readers are done
                 double v = 0.0;
                 if (t < nf && !bad_s[t]) v = log((double)c_s[t]) + (double)mt_s[t];
-                ll += hmm_block_sum(v, red_d);
+                ll += fixed_block_sum(v, red_d);
             } else {
                 float bn[NQ], an[NQ];
                 float sk[SK ? NQ : 1];
@@ -303,7 +254,7 @@ __global__ __launch_bounds__(256) void hmm_fb_kernel(HmmP p)
                         e[q] = b[q] * a[q] * inv;
                         s += w_s[256 * q + t] * e[q];
                     }
-                    s = hmm_wave_sum(s);
+                    s = fixed_wave_sum(s);
                     if (lane == 0) red_s[par][wave] = s;
                     __syncthreads();
                     const float tot = omr * (((red_s[par][0] + red_s[par][1]) + red_s[par][2]) + red_s[par][3]);
@@ -321,7 +272,7 @@ __global__ __launch_bounds__(256) void hmm_fb_kernel(HmmP p)
             }
         }
         if (p.stays) {                                                // (uniform)
-            const double tot = hmm_block_sum(st, red_d);
+            const double tot = fixed_block_sum(st, red_d);
             if (t == 0) p.stays[u] = (double)rho * tot;
         }
         if constexpr (SK)
@@ -900,44 +851,23 @@ extern "C" int64_t abn_hmm_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int6
     return chain_ws_bytes("abn_hmm_viterbi_ws_bytes", n_utt, max_len, K, D, HM_LIMITS, vit_frame_bytes(K), 0);
 }
 
-extern "C" int abn_hmm_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
-                               const float* shift, const float* A, const float* B, const float* c0, const float* lw,
-                               const float* ls, const float* lr, int64_t K, int32_t* ids, double* log_prob, int32_t* n_switch,
-                               int32_t* n_good, void* ws, int64_t ws_bytes, void* stream)
+// Both max-product entries: the checks in their order -- min_duration (null: the entry has none) behind the pointers --,
+// the caller's workspace split into abn_hmm_viterbi_ws_bytes' regions, and the launch.  A min_duration of 1 launches the
+// <1> instantiation of hmm_viterbi_dur_kernel, not hmm_viterbi_kernel: only abn_hmm_viterbi launches that one.
+static int hmm_vit_run(const char* what, const int32_t* min_duration, const float* x, int64_t T, int64_t D, const int64_t* off,
+                       const int32_t* len, int64_t n_utt, const float* shift, const float* A, const float* B, const float* c0,
+                       const float* lw, const float* ls, const float* lr, int64_t K, int32_t* ids, double* log_prob,
+                       int32_t* n_switch, int32_t* n_good, void* ws, int64_t ws_bytes, void* stream)
 {
-    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "abn_hmm_viterbi: T = %lld out of range", (long long)T);
-    int rc = chain_check_sizes("abn_hmm_viterbi", n_utt, K, D, HM_LIMITS);
+    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "%s: T = %lld out of range", what, (long long)T);
+    int rc = chain_check_sizes(what, n_utt, K, D, HM_LIMITS);
     if (rc != ABN_OK) return rc;
-    ABN_REQUIRE(x && off && len && shift && A && B && c0 && lw && ls && lr && ids, "abn_hmm_viterbi: null pointer");
+    ABN_REQUIRE(x && off && len && shift && A && B && c0 && lw && ls && lr && ids, "%s: null pointer", what);
+    const int S = min_duration ? *min_duration : 1;
+    ABN_REQUIRE(S >= 1 && S <= VIT_DUR_MAX, "%s: min_duration = %d, 1 .. %d (abnx_viterbi_dur_max)", what, S, VIT_DUR_MAX);
     const ChainWs w = chain_ws(n_utt, 0, K, vit_frame_bytes(K), 0);
     ChainRegion a;
-    rc = chain_region("abn_hmm_viterbi", "abn_hmm_viterbi_ws_bytes", ws, ws_bytes, w, &a);
-    if (rc != ABN_OK) return rc;
-    HmmVitP p;
-    p.g = hmm_score_params(x, T, D, shift, A, B, c0, K);
-    p.lw = lw; p.ls = ls; p.lr = lr; p.off = off; p.len = len; p.n_utt = (int)n_utt;
-    p.ids = ids; p.log_prob = log_prob; p.n_switch = n_switch; p.n_good = n_good;
-    p.ws = a.ws; p.per_wg = a.per_wg;
-    p.ks = a.ks; p.kw = a.kw; p.cap = a.cap;
-    return vit_launch<HmmVitKernels>("abn_hmm_viterbi", p, K, w, GM_TILE_BYTES, HM_VIT_LDS_BYTES, stream);
-}
-
-// abn_hmm_viterbi with a minimum duration (include/abnet3_hip_next.h): its checks in its order, then min_duration; the
-// workspace is abn_hmm_viterbi_ws_bytes'.
-extern "C" int abnx_hmm_viterbi_dur(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
-                                    const float* shift, const float* A, const float* B, const float* c0, const float* lw,
-                                    const float* ls, const float* lr, int64_t K, int32_t* ids, double* log_prob,
-                                    int32_t* n_switch, int32_t* n_good, void* ws, int64_t ws_bytes, void* stream, int32_t min_duration)
-{
-    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "abnx_hmm_viterbi_dur: T = %lld out of range", (long long)T);
-    int rc = chain_check_sizes("abnx_hmm_viterbi_dur", n_utt, K, D, HM_LIMITS);
-    if (rc != ABN_OK) return rc;
-    ABN_REQUIRE(x && off && len && shift && A && B && c0 && lw && ls && lr && ids, "abnx_hmm_viterbi_dur: null pointer");
-    ABN_REQUIRE(min_duration >= 1 && min_duration <= VIT_DUR_MAX, "abnx_hmm_viterbi_dur: min_duration = %d, 1 .. %d (abnx_viterbi_dur_max)",
-                (int)min_duration, VIT_DUR_MAX);
-    const ChainWs w = chain_ws(n_utt, 0, K, vit_frame_bytes(K), 0);
-    ChainRegion a;
-    rc = chain_region("abnx_hmm_viterbi_dur", "abn_hmm_viterbi_ws_bytes", ws, ws_bytes, w, &a);
+    rc = chain_region(what, "abn_hmm_viterbi_ws_bytes", ws, ws_bytes, w, &a);
     if (rc != ABN_OK) return rc;
     HmmVitDurP p;
     p.v.g = hmm_score_params(x, T, D, shift, A, B, c0, K);
@@ -945,12 +875,28 @@ extern "C" int abnx_hmm_viterbi_dur(const float* x, int64_t T, int64_t D, const 
     p.v.ids = ids; p.v.log_prob = log_prob; p.v.n_switch = n_switch; p.v.n_good = n_good;
     p.v.ws = a.ws; p.v.per_wg = a.per_wg;
     p.v.ks = a.ks; p.v.kw = a.kw; p.v.cap = a.cap;
-    p.S = min_duration;
-    const char* what = "abnx_hmm_viterbi_dur";
-    if (min_duration == 1) return vit_launch<HmmVitDurKernels<1>>(what, p, K, w, GM_TILE_BYTES + VIT_DUR_PARK_BYTES, HM_VIT_LDS_BYTES, stream);
-    if (min_duration == 2) return vit_launch<HmmVitDurKernels<2>>(what, p, K, w, GM_TILE_BYTES + VIT_DUR_PARK_BYTES, HM_VIT_LDS_BYTES, stream);
-    if (min_duration <= 4) return vit_launch<HmmVitDurKernels<4>>(what, p, K, w, GM_TILE_BYTES + VIT_DUR_PARK_BYTES, HM_VIT_LDS_BYTES, stream);
-    return vit_launch<HmmVitDurKernels<8>>(what, p, K, w, GM_TILE_BYTES + VIT_DUR_PARK_BYTES, HM_VIT_LDS_BYTES, stream);
+    p.S = S;
+    if (!min_duration) return vit_launch<HmmVitKernels>(what, p.v, K, w, GM_TILE_BYTES, HM_VIT_LDS_BYTES, stream);
+    return vit_dur_launch<HmmVitDurKernels>(what, p, S, K, w, GM_TILE_BYTES + VIT_DUR_PARK_BYTES, HM_VIT_LDS_BYTES, stream);
+}
+
+extern "C" int abn_hmm_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                               const float* shift, const float* A, const float* B, const float* c0, const float* lw,
+                               const float* ls, const float* lr, int64_t K, int32_t* ids, double* log_prob, int32_t* n_switch,
+                               int32_t* n_good, void* ws, int64_t ws_bytes, void* stream)
+{
+    return hmm_vit_run("abn_hmm_viterbi", nullptr, x, T, D, off, len, n_utt, shift, A, B, c0, lw, ls, lr, K, ids, log_prob,
+                       n_switch, n_good, ws, ws_bytes, stream);
+}
+
+// abn_hmm_viterbi with a minimum duration (include/abnet3_hip_next.h); the workspace is abn_hmm_viterbi_ws_bytes'.
+extern "C" int abnx_hmm_viterbi_dur(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                                    const float* shift, const float* A, const float* B, const float* c0, const float* lw,
+                                    const float* ls, const float* lr, int64_t K, int32_t* ids, double* log_prob,
+                                    int32_t* n_switch, int32_t* n_good, void* ws, int64_t ws_bytes, void* stream, int32_t min_duration)
+{
+    return hmm_vit_run("abnx_hmm_viterbi_dur", &min_duration, x, T, D, off, len, n_utt, shift, A, B, c0, lw, ls, lr, K, ids,
+                       log_prob, n_switch, n_good, ws, ws_bytes, stream);
 }
 
 static int hmm_acc_check(int64_t T, int64_t K, int64_t D, int n_ranges, const char* what)

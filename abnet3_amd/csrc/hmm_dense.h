@@ -1,6 +1,8 @@
-// hmm_dense.h -- what the two kernels of the HMM with a full transition matrix share: hmm_dense_kernel (hmm_dense.hip:
-// abny_hmm_dense_forward_backward) and hmm_dense_vit_kernel (hmm_dense_vit.hip: abnz_hmm_dense_viterbi).  Both keep a
-// [KC][KC + 1] fp32 matrix in LDS behind the score tile's operands, KC the capacity the kernel is instantiated with.
+// hmm_dense.h -- what the three kernels of the HMM with a full transition matrix share: hmm_dense_kernel (hmm_dense.hip:
+// abny_hmm_dense_forward_backward), hmm_dense_vit_kernel and hmm_dense_dur_kernel (hmm_dense_vit.hip:
+// abnz_hmm_dense_viterbi, abnw_hmm_dense_viterbi_dur).  All keep a [KC][KC + 1] fp32 matrix in LDS behind the score tile's
+// operands, KC the capacity the kernel is instantiated with.  (Their score-only GmmP is gmm_tile.h's hmm_score_params;
+// hmm_dense_kernel's sum reductions are fixed_sum.h's, shared with hmm.hip.)
 #pragma once
 #include "common.h"
 #include "gmm_tile.h"

@@ -26,6 +26,7 @@
 #include "common.h"
 #include "gemm_f32.h"
 #include "gmm_tile.h"
+#include "fixed_sum.h"
 #include "utt_chain.h"
 #include "hmm_dense.h"
 #include "../../include/abnet3_hip_next.h"
@@ -46,40 +47,6 @@ struct HmmDenseP {
     char* ws; int64_t per_wg;               // bytes of a workgroup's region
     int ks, cap;                            // slab row stride (floats), frames the region holds
 };
-
-template <int CTRL>
-__device__ __forceinline__ float hd_dpp_add(float v)
-{
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-// The sum over the wave, in every lane, in one fixed order (hmm.hip's hmm_wave_sum).  All 64 lanes must be active.
-__device__ __forceinline__ float hd_wave_sum(float v)
-{
-    v = hd_dpp_add<0xB1>(v);
-    v = hd_dpp_add<0x4E>(v);
-    v = hd_dpp_add<0x141>(v);
-    v = hd_dpp_add<0x140>(v);
-    float r = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-#pragma unroll
-    for (int i = 1; i < 4; ++i) r += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16 * i));
-    return r;
-}
-
-// 256 doubles summed in a fixed tree; the result is returned to every thread.
-__device__ __forceinline__ double hd_block_sum(double v, double* sh)
-{
-    const int t = threadIdx.x;
-    __syncthreads();
-    sh[t] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) sh[t] += sh[t + o];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
 
 // The block of frames m0 .. m0 + nf - 1: BAD flags, the bt slab and m_t (hmm_block_scores of hmm.hip with every
 // component live: the same tile, the same max, the same expf).  Ends behind a barrier.
@@ -220,7 +187,7 @@ __global__ __launch_bounds__(256) void hmm_dense_kernel(HmmDenseP p)
                         for (int s = 1; s < NS; ++s) pred += part_s[s * KC + own];
                     }
                     const float uu = owner ? b * pred : 0.0f;
-                    const float s = hd_wave_sum(uu);
+                    const float s = fixed_wave_sum(uu);
                     if (lane == 0) red_s[wave] = s;
                     __syncthreads();
                     const float c = ((red_s[0] + red_s[1]) + red_s[2]) + red_s[3];
@@ -237,7 +204,7 @@ __global__ __launch_bounds__(256) void hmm_dense_kernel(HmmDenseP p)
                 __syncthreads();                                      // c_s is complete; the slab's readers are done
                 double v = 0.0;
                 if (t < nf && !bad_s[t]) v = log((double)c_s[t]) + (double)mt_s[t];
-                ll += hd_block_sum(v, red_d);
+                ll += fixed_block_sum(v, red_d);
             } else {
                 float G[SW];
 #pragma unroll
@@ -361,10 +328,7 @@ extern "C" int abny_hmm_dense_forward_backward(const float* x, int64_t T, int64_
     rc = chain_region(what, "abny_hmm_dense_ws_bytes", ws, ws_bytes, hw, &a);
     if (rc != ABN_OK) return rc;
     HmmDenseP p;
-    p.g.x = x; p.g.shift = shift; p.g.A = A; p.g.B = B; p.g.c = c0;
-    p.g.T = (int)T; p.g.K = (int)K; p.g.D = (int)D;
-    p.g.lse = nullptr; p.g.post = nullptr; p.g.slabs = nullptr;
-    p.g.tiles_k = 1; p.g.fblocks = 0; p.g.n_ranges = 0; p.g.blocks_per_range = 0;
+    p.g = hmm_score_params(x, T, D, shift, A, B, c0, K);      // (K <= 128: one tile of components)
     p.init = init; p.trans = trans; p.off = off; p.len = len; p.n_utt = (int)n_utt;
     p.mode = mode; p.want_stats = stats != nullptr;
     p.post = post; p.loglik = loglik; p.n_good = n_good;

@@ -502,10 +502,7 @@ static int hdv_run(const char* what, const char* ws_fn, const int32_t* min_durat
     if (rc != ABN_OK) return rc;
     HmmDenseDurP pd;
     HmmDenseVitP& p = pd.v;
-    p.g.x = x; p.g.shift = shift; p.g.A = A; p.g.B = B; p.g.c = c0;
-    p.g.T = (int)T; p.g.K = (int)K; p.g.D = (int)D;
-    p.g.lse = nullptr; p.g.post = nullptr; p.g.slabs = nullptr;
-    p.g.tiles_k = 1; p.g.fblocks = 0; p.g.n_ranges = 0; p.g.blocks_per_range = 0;
+    p.g = hmm_score_params(x, T, D, shift, A, B, c0, K);      // (K <= 128: one tile of components)
     p.li = li; p.lt = lt; p.off = off; p.len = len; p.n_utt = (int)n_utt;
     p.ids = ids; p.log_prob = log_prob; p.n_switch = n_switch; p.n_good = n_good;
     p.ws = a.ws; p.per_wg = a.per_wg;

@@ -658,51 +658,25 @@ extern "C" int64_t abn_kmeans_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, i
     return chain_ws_bytes("abn_kmeans_viterbi_ws_bytes", n_utt, max_len, K, D, KM_VIT_LIMITS, vit_frame_bytes(K), KM_VIT_TAIL);
 }
 
-extern "C" int abn_kmeans_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
-                                  const float* shift, const float* m, const float* b, int64_t K, float penalty_score,
-                                  int32_t* ids, double* objective, int32_t* n_switch, void* ws, int64_t ws_bytes, void* stream)
+// Both segmentation entries: the checks in their order -- min_duration (null: the entry has none) behind penalty_score --,
+// the caller's workspace split into abn_kmeans_viterbi_ws_bytes' regions, and the launch.  A min_duration of 1 launches
+// the <1> instantiation of km_viterbi_dur_kernel, not km_viterbi_kernel: only abn_kmeans_viterbi launches that one.
+static int km_vit_run(const char* what, const int32_t* min_duration, const float* x, int64_t T, int64_t D, const int64_t* off,
+                      const int32_t* len, int64_t n_utt, const float* shift, const float* m, const float* b, int64_t K,
+                      float penalty_score, int32_t* ids, double* objective, int32_t* n_switch, void* ws, int64_t ws_bytes,
+                      void* stream)
 {
-    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - KM_B, "abn_kmeans_viterbi: T = %lld out of range", (long long)T);
-    int rc = chain_check_sizes("abn_kmeans_viterbi", n_utt, K, D, KM_VIT_LIMITS);
+    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - KM_B, "%s: T = %lld out of range", what, (long long)T);
+    int rc = chain_check_sizes(what, n_utt, K, D, KM_VIT_LIMITS);
     if (rc != ABN_OK) return rc;
-    ABN_REQUIRE(x && off && len && shift && m && b && ids, "abn_kmeans_viterbi: null pointer");
-    ABN_REQUIRE(penalty_score >= 0.0f && __builtin_isfinite(penalty_score),
-                "abn_kmeans_viterbi: penalty_score = %g, a finite value >= 0 is needed", (double)penalty_score);
+    ABN_REQUIRE(x && off && len && shift && m && b && ids, "%s: null pointer", what);
+    ABN_REQUIRE(penalty_score >= 0.0f && __builtin_isfinite(penalty_score), "%s: penalty_score = %g, a finite value >= 0 is needed",
+                what, (double)penalty_score);
+    const int S = min_duration ? *min_duration : 1;
+    ABN_REQUIRE(S >= 1 && S <= VIT_DUR_MAX, "%s: min_duration = %d, 1 .. %d (abnx_viterbi_dur_max)", what, S, VIT_DUR_MAX);
     const ChainWs w = chain_ws(n_utt, 0, K, vit_frame_bytes(K), KM_VIT_TAIL);
     ChainRegion a;
-    rc = chain_region("abn_kmeans_viterbi", "abn_kmeans_viterbi_ws_bytes", ws, ws_bytes, w, &a);
-    if (rc != ABN_OK) return rc;
-    KmVitP p;
-    p.x = x; p.shift = shift; p.m = m; p.b = b; p.off = off; p.len = len;
-    p.T = (int)T; p.K = (int)K; p.D = (int)D; p.n_utt = (int)n_utt;
-    p.tiles_k = (int)((K + KM_B - 1) / KM_B);
-    p.pen = penalty_score;
-    p.ids = ids; p.objective = objective; p.n_switch = n_switch;
-    p.ws = a.ws; p.per_wg = a.per_wg;
-    p.ks = a.ks; p.kw = a.kw; p.cap = a.cap;
-    return vit_launch<KmVitKernels>("abn_kmeans_viterbi", p, K, w, KM_TILE_BYTES, KM_VIT_LDS_BYTES, stream);
-}
-
-extern "C" int32_t abnx_viterbi_dur_max(void) { return VIT_DUR_MAX; }
-
-// abn_kmeans_viterbi with a minimum duration (include/abnet3_hip_next.h): its checks in its order, then min_duration; the
-// workspace is abn_kmeans_viterbi_ws_bytes'.
-extern "C" int abnx_kmeans_viterbi_dur(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len,
-                                       int64_t n_utt, const float* shift, const float* m, const float* b, int64_t K,
-                                       float penalty_score, int32_t* ids, double* objective, int32_t* n_switch, void* ws,
-                                       int64_t ws_bytes, void* stream, int32_t min_duration)
-{
-    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - KM_B, "abnx_kmeans_viterbi_dur: T = %lld out of range", (long long)T);
-    int rc = chain_check_sizes("abnx_kmeans_viterbi_dur", n_utt, K, D, KM_VIT_LIMITS);
-    if (rc != ABN_OK) return rc;
-    ABN_REQUIRE(x && off && len && shift && m && b && ids, "abnx_kmeans_viterbi_dur: null pointer");
-    ABN_REQUIRE(penalty_score >= 0.0f && __builtin_isfinite(penalty_score),
-                "abnx_kmeans_viterbi_dur: penalty_score = %g, a finite value >= 0 is needed", (double)penalty_score);
-    ABN_REQUIRE(min_duration >= 1 && min_duration <= VIT_DUR_MAX,
-                "abnx_kmeans_viterbi_dur: min_duration = %d, 1 .. %d (abnx_viterbi_dur_max)", (int)min_duration, VIT_DUR_MAX);
-    const ChainWs w = chain_ws(n_utt, 0, K, vit_frame_bytes(K), KM_VIT_TAIL);
-    ChainRegion a;
-    rc = chain_region("abnx_kmeans_viterbi_dur", "abn_kmeans_viterbi_ws_bytes", ws, ws_bytes, w, &a);
+    rc = chain_region(what, "abn_kmeans_viterbi_ws_bytes", ws, ws_bytes, w, &a);
     if (rc != ABN_OK) return rc;
     KmVitDurP p;
     p.v.x = x; p.v.shift = shift; p.v.m = m; p.v.b = b; p.v.off = off; p.v.len = len;
@@ -712,12 +686,29 @@ extern "C" int abnx_kmeans_viterbi_dur(const float* x, int64_t T, int64_t D, con
     p.v.ids = ids; p.v.objective = objective; p.v.n_switch = n_switch;
     p.v.ws = a.ws; p.v.per_wg = a.per_wg;
     p.v.ks = a.ks; p.v.kw = a.kw; p.v.cap = a.cap;
-    p.S = min_duration;
-    const char* what = "abnx_kmeans_viterbi_dur";
-    if (min_duration == 1) return vit_launch<KmVitDurKernels<1>>(what, p, K, w, KM_TILE_BYTES + VIT_DUR_PARK_BYTES, KM_VIT_LDS_BYTES, stream);
-    if (min_duration == 2) return vit_launch<KmVitDurKernels<2>>(what, p, K, w, KM_TILE_BYTES + VIT_DUR_PARK_BYTES, KM_VIT_LDS_BYTES, stream);
-    if (min_duration <= 4) return vit_launch<KmVitDurKernels<4>>(what, p, K, w, KM_TILE_BYTES + VIT_DUR_PARK_BYTES, KM_VIT_LDS_BYTES, stream);
-    return vit_launch<KmVitDurKernels<8>>(what, p, K, w, KM_TILE_BYTES + VIT_DUR_PARK_BYTES, KM_VIT_LDS_BYTES, stream);
+    p.S = S;
+    if (!min_duration) return vit_launch<KmVitKernels>(what, p.v, K, w, KM_TILE_BYTES, KM_VIT_LDS_BYTES, stream);
+    return vit_dur_launch<KmVitDurKernels>(what, p, S, K, w, KM_TILE_BYTES + VIT_DUR_PARK_BYTES, KM_VIT_LDS_BYTES, stream);
+}
+
+extern "C" int abn_kmeans_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                                  const float* shift, const float* m, const float* b, int64_t K, float penalty_score,
+                                  int32_t* ids, double* objective, int32_t* n_switch, void* ws, int64_t ws_bytes, void* stream)
+{
+    return km_vit_run("abn_kmeans_viterbi", nullptr, x, T, D, off, len, n_utt, shift, m, b, K, penalty_score, ids, objective,
+                      n_switch, ws, ws_bytes, stream);
+}
+
+extern "C" int32_t abnx_viterbi_dur_max(void) { return VIT_DUR_MAX; }
+
+// abn_kmeans_viterbi with a minimum duration (include/abnet3_hip_next.h); the workspace is abn_kmeans_viterbi_ws_bytes'.
+extern "C" int abnx_kmeans_viterbi_dur(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len,
+                                       int64_t n_utt, const float* shift, const float* m, const float* b, int64_t K,
+                                       float penalty_score, int32_t* ids, double* objective, int32_t* n_switch, void* ws,
+                                       int64_t ws_bytes, void* stream, int32_t min_duration)
+{
+    return km_vit_run("abnx_kmeans_viterbi_dur", &min_duration, x, T, D, off, len, n_utt, shift, m, b, K, penalty_score, ids,
+                      objective, n_switch, ws, ws_bytes, stream);
 }
 
 extern "C" int64_t abn_kmeans_max_d(void) { return KM_MAX_D; }

@@ -1,14 +1,19 @@
 // utt_chain.h -- the host side of the per-utterance chain kernels, written once: km_viterbi_kernel (kmeans.hip:
-// abn_kmeans_viterbi), hmm_viterbi_kernel and hmm_fb_kernel (hmm.hip: abn_hmm_viterbi, abn_hmm_forward_backward[_stats]).
-// All three launch min(n_utt, 256) persistent workgroups that loop over the utterances and give each workgroup a
+// abn_kmeans_viterbi), hmm_viterbi_kernel and hmm_fb_kernel (hmm.hip: abn_hmm_viterbi, abn_hmm_forward_backward[_stats]),
+// hmm_dense_kernel (hmm_dense.hip: abny_hmm_dense_forward_backward), hmm_dense_vit_kernel and hmm_dense_dur_kernel
+// (hmm_dense_vit.hip: abnz_hmm_dense_viterbi, abnw_hmm_dense_viterbi_dur).
+// All of them launch min(n_utt, 256) persistent workgroups that loop over the utterances and give each workgroup a
 // 256-byte aligned region of the workspace: a slab [128][ks] of scores, then so many bytes per frame of the longest
 // utterance, then a tail.  Here: that geometry (chain_ws), its split of a caller's workspace (chain_region), the size
 // checks with the callers' limits in their messages (chain_check_sizes, chain_ws_bytes), the NQ list (nq_for,
-// for_each_nq) and the launch of a max-product kernel (vit_launch; km_viterbi_dur_kernel and hmm_viterbi_dur_kernel, the
-// two with a minimum unit duration, go through it with one kernel set per register capacity and the same workspace
-// geometry).  The kernels themselves stay in their files: shared
+// for_each_nq) and the launch of a sticky max-product kernel (vit_launch; km_viterbi_dur_kernel and
+// hmm_viterbi_dur_kernel, the two with a minimum unit duration, go through vit_dur_launch with one kernel set per
+// register capacity and the same workspace geometry).  The kernels themselves stay in their files: shared
 // device code (one slab phase, one max-product kernel over a model type) gave the same bits but measured 5 to 11 %
 // slower for hmm_fb_kernel and km_viterbi_kernel (profiles/hmm_*_time_shared_chain.json).
+// Nor is a small helper free once it takes a kernel's LDS arrays: moving only the wave-key reduction that the two kernels
+// of hmm_dense_vit.hip share into a __forceinline__ function with red_k[par] as a pointer changed about 29 000 of the
+// translation unit's 65 000 lines of gfx950 assembly.  What takes and returns values (fixed_sum.h) moved byte for byte.
 #pragma once
 #include "common.h"
 
@@ -134,6 +139,18 @@ static int vit_launch(const char* what, const P& p, int64_t K, const ChainWs& w,
     }
     ABN_CHECK_LAUNCH(what);
     return ABN_OK;
+}
+
+// The same for a minimum duration S: KSD<SC> is the kernel set of register capacity SC, the smallest of 1, 2, 4, 8 that
+// holds S.
+template <template <int> class KSD, class P>
+static int vit_dur_launch(const char* what, const P& p, int S, int64_t K, const ChainWs& w, size_t tile_bytes, size_t lds_bytes,
+                          void* stream)
+{
+    if (S == 1) return vit_launch<KSD<1>>(what, p, K, w, tile_bytes, lds_bytes, stream);
+    if (S == 2) return vit_launch<KSD<2>>(what, p, K, w, tile_bytes, lds_bytes, stream);
+    if (S <= 4) return vit_launch<KSD<4>>(what, p, K, w, tile_bytes, lds_bytes, stream);
+    return vit_launch<KSD<8>>(what, p, K, w, tile_bytes, lds_bytes, stream);
 }
 
 }  // namespace abn

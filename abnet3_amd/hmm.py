@@ -284,9 +284,7 @@ def forward_backward(table, off, lens, shift, A, B, c0, w, stay, mode='smooth', 
     lib = _lib.load()
     if mode not in MODES:
         raise ValueError('hmm.forward_backward: mode = %r, one of %s' % (mode, sorted(MODES)))
-    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
-        raise ValueError('hmm.forward_backward: a [T, D] float32 table is needed')
-    T, D = table.shape
+    T, D = _utt.table_shape('hmm.forward_backward', table)
     K = c0.shape[0]
     if A.shape != (K, D) or B.shape != (K, D) or shift.shape != (D,) or w.shape != (K,) or any(
             t.dtype != torch.float32 for t in (shift, A, B, c0, w)):
@@ -297,11 +295,7 @@ def forward_backward(table, off, lens, shift, A, B, c0, w, stay, mode='smooth', 
     off_h, len_h, n_utt, longest = _utt.utterance_spans('hmm.forward_backward', off, lens, T, max_len(), 'abn_hmm_max_len')
     table = _gmm._check_table('hmm.forward_backward', table)
     _lib.require_device(shift, A, B, c0, w)
-    if out is None:
-        out = torch.zeros((T, K), dtype=torch.float32, device=table.device)
-    if out.shape != (T, K) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError('hmm.forward_backward: out must be a contiguous [T, K] float32 tensor')
-    _lib.require_device(out)
+    out = _utt.posterior_table('hmm.forward_backward', out, T, K, table.device)
     ll = torch.zeros(n_utt, dtype=torch.float64, device=table.device)
     st = torch.zeros(n_utt, dtype=torch.float64, device=table.device) if want_stays else None
     ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
@@ -316,6 +310,15 @@ def forward_backward(table, off, lens, shift, A, B, c0, w, stay, mode='smooth', 
         else:
             _lib.check(lib.abn_hmm_forward_backward(*(head + tail)), 'abn_hmm_forward_backward')
     return (out, ll, st, ng, sk) if want_stay_k else (out, ll, st, ng)
+
+
+def _emission_shapes(who, table, shift, A, B, c0):
+    """(T, D, K) of a [T, D] float32 table and the emission tables that fit it, or ValueError."""
+    T, D = _utt.table_shape(who, table)
+    K = c0.shape[0]
+    if A.shape != (K, D) or B.shape != (K, D) or shift.shape != (D,) or any(t.dtype != torch.float32 for t in (shift, A, B, c0)):
+        raise ValueError('%s: shift [D], A [K, D], B [K, D], c0 [K] float32 are needed' % who)
+    return T, D, K
 
 
 def viterbi_tables(w, stay):
@@ -365,27 +368,15 @@ def viterbi(table, off, lens, shift, A, B, c0, lw, ls, lr, ids=None, want_log_pr
     lib = _lib.load()
     who = 'hmm.viterbi'
     min_duration = _utt.check_min_duration(who, min_duration)
-    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
-        raise ValueError('%s: a [T, D] float32 table is needed' % who)
-    T, D = table.shape
-    K = c0.shape[0]
-    if A.shape != (K, D) or B.shape != (K, D) or shift.shape != (D,) or any(t.dtype != torch.float32 for t in (shift, A, B, c0)):
-        raise ValueError('%s: shift [D], A [K, D], B [K, D], c0 [K] float32 are needed' % who)
+    T, D, K = _emission_shapes(who, table, shift, A, B, c0)
     if K < 1 or K > max_k():
         raise ValueError('%s: K = %d, the kernel takes 1 .. %d (abn_hmm_max_k)' % (who, K, max_k()))
     _check_log_tables(who, lw, ls, lr, K)
     off_h, len_h, n_utt, longest = _utt.utterance_spans(who, off, lens, T, max_len(), 'abn_hmm_max_len')
-    if ids is not None and (not isinstance(ids, torch.Tensor) or ids.shape != (T,) or ids.dtype != torch.int32 or
-                            not ids.is_contiguous()):
-        raise ValueError('%s: ids must be a contiguous [T] int32 tensor' % who)
+    _utt.check_ids(who, ids, T)
     table = _gmm._check_table(who, table)
     _lib.require_device(shift, A, B, c0, lw, ls, lr)
-    if ids is None:
-        ids = torch.full((T,), -1, dtype=torch.int32, device=table.device)
-    _lib.require_device(ids)
-    lp = torch.zeros(n_utt, dtype=torch.float64, device=table.device) if want_log_prob else None
-    nsw = torch.zeros(n_utt, dtype=torch.int32, device=table.device) if want_log_prob else None
-    ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
+    ids, lp, nsw, ng = _utt.path_results(ids, T, n_utt, want_log_prob, table.device)
     if T and n_utt and longest:
         ws, off_d, len_d = _utt.workspace(who, lib.abn_hmm_viterbi_ws_bytes, off_h, len_h, longest, K, D, table.device)
         args = (_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B),
@@ -403,9 +394,7 @@ def accumulate(table, post, shift, n_ranges=0):
     (abn_hmm_accumulate: `post` is read once; fp32 slabs per frame range, then float64 in range order; the same bits for
     the same n_ranges).  A non-finite entry of the table contributes 0; forward_backward leaves zero rows at BAD frames."""
     lib = _lib.load()
-    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
-        raise ValueError('hmm.accumulate: a [T, D] float32 table is needed')
-    T, D = table.shape
+    T, D = _utt.table_shape('hmm.accumulate', table)
     if not isinstance(post, torch.Tensor) or post.dim() != 2 or post.dtype != torch.float32 or post.shape[0] != T or \
             not post.is_contiguous():
         raise ValueError('hmm.accumulate: post must be a contiguous [T, K] float32 tensor with the table\'s %d rows' % T)
@@ -535,12 +524,7 @@ def dense_forward_backward(table, off, lens, shift, A, B, c0, init, trans, mode=
     who = 'hmm.dense_forward_backward'
     if mode not in MODES:
         raise ValueError('%s: mode = %r, one of %s' % (who, mode, sorted(MODES)))
-    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
-        raise ValueError('%s: a [T, D] float32 table is needed' % who)
-    T, D = table.shape
-    K = c0.shape[0]
-    if A.shape != (K, D) or B.shape != (K, D) or shift.shape != (D,) or any(t.dtype != torch.float32 for t in (shift, A, B, c0)):
-        raise ValueError('%s: shift [D], A [K, D], B [K, D], c0 [K] float32 are needed' % who)
+    T, D, K = _emission_shapes(who, table, shift, A, B, c0)
     if not isinstance(init, torch.Tensor) or not isinstance(trans, torch.Tensor) or init.shape != (K,) or trans.shape != (K, K) or \
             init.dtype != torch.float32 or trans.dtype != torch.float32:
         raise ValueError('%s: init [K] and trans [K, K] float32 tensors are needed' % who)
@@ -550,11 +534,7 @@ def dense_forward_backward(table, off, lens, shift, A, B, c0, init, trans, mode=
     off_h, len_h, n_utt, longest = _utt.utterance_spans(who, off, lens, T, max_len(), 'abn_hmm_max_len')
     table = _gmm._check_table(who, table)
     _lib.require_device(shift, A, B, c0, init, trans)
-    if out is None:
-        out = torch.zeros((T, K), dtype=torch.float32, device=table.device)
-    if out.shape != (T, K) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError('%s: out must be a contiguous [T, K] float32 tensor' % who)
-    _lib.require_device(out)
+    out = _utt.posterior_table(who, out, T, K, table.device)
     ll = torch.zeros(n_utt, dtype=torch.float64, device=table.device)
     ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
     stats = torch.zeros((K + 1, K), dtype=torch.float64, device=table.device) if want_stats else None
@@ -585,6 +565,24 @@ def _check_dense_log_tables(who, li, lt, K):
         raise ValueError('%s: the log tables must not hold NaN, +inf or -inf (every entry of init and trans is >= 2^-100)' % who)
 
 
+def _dense_viterbi_sizing(lib, min_duration):
+    """The *_ws_bytes entry of the decoder ``_dense_viterbi_launch`` runs for this min_duration."""
+    return lib.abnz_hmm_dense_viterbi_ws_bytes if min_duration == 1 else lib.abnw_hmm_dense_viterbi_dur_ws_bytes
+
+
+def _dense_viterbi_launch(lib, table, off_d, len_d, n_utt, shift, A, B, c0, li, lt, K, ids, lp, nsw, ng, min_duration, ws):
+    """abnz_hmm_dense_viterbi (min_duration 1) or abnw_hmm_dense_viterbi_dur on checked arguments and a workspace of
+    ``_dense_viterbi_sizing``'s entry; fills ids, lp, nsw (either may be None) and ng."""
+    T, D = table.shape
+    args = (_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B),
+            _lib.ptr(c0), _lib.ptr(li), _lib.ptr(lt), K, _lib.ptr(ids), _lib.ptr(lp), _lib.ptr(nsw), _lib.ptr(ng),
+            _lib.ptr(ws), ws.numel(), _lib.stream())
+    if min_duration == 1:
+        _lib.check(lib.abnz_hmm_dense_viterbi(*args), 'abnz_hmm_dense_viterbi')
+    else:
+        _lib.check(lib.abnw_hmm_dense_viterbi_dur(*(args + (min_duration,))), 'abnw_hmm_dense_viterbi_dur')
+
+
 def dense_viterbi(table, off, lens, shift, A, B, c0, li, lt, ids=None, want_log_prob=True, min_duration=1):
     """(ids [T] int32, log_prob [n_utt] float64 or None, n_switch [n_utt] int32 or None, n_good [n_utt] int32), device
     tensors, of the full-transition max-product recurrence the module docstring defines (abnz_hmm_dense_viterbi, one
@@ -595,37 +593,18 @@ def dense_viterbi(table, off, lens, shift, A, B, c0, li, lt, ids=None, want_log_
     lib = _lib.load()
     who = 'hmm.dense_viterbi'
     min_duration = _utt.check_min_duration(who, min_duration)
-    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
-        raise ValueError('%s: a [T, D] float32 table is needed' % who)
-    T, D = table.shape
-    K = c0.shape[0]
-    if A.shape != (K, D) or B.shape != (K, D) or shift.shape != (D,) or any(t.dtype != torch.float32 for t in (shift, A, B, c0)):
-        raise ValueError('%s: shift [D], A [K, D], B [K, D], c0 [K] float32 are needed' % who)
+    T, D, K = _emission_shapes(who, table, shift, A, B, c0)
     if K < 1 or K > dense_max_k():
         raise ValueError('%s: K = %d, the kernel takes 1 .. %d (abny_hmm_dense_max_k)' % (who, K, dense_max_k()))
     _check_dense_log_tables(who, li, lt, K)
     off_h, len_h, n_utt, longest = _utt.utterance_spans(who, off, lens, T, max_len(), 'abn_hmm_max_len')
-    if ids is not None and (not isinstance(ids, torch.Tensor) or ids.shape != (T,) or ids.dtype != torch.int32 or
-                            not ids.is_contiguous()):
-        raise ValueError('%s: ids must be a contiguous [T] int32 tensor' % who)
+    _utt.check_ids(who, ids, T)
     table = _gmm._check_table(who, table)
     _lib.require_device(shift, A, B, c0, li, lt)
-    if ids is None:
-        ids = torch.full((T,), -1, dtype=torch.int32, device=table.device)
-    _lib.require_device(ids)
-    lp = torch.zeros(n_utt, dtype=torch.float64, device=table.device) if want_log_prob else None
-    nsw = torch.zeros(n_utt, dtype=torch.int32, device=table.device) if want_log_prob else None
-    ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
+    ids, lp, nsw, ng = _utt.path_results(ids, T, n_utt, want_log_prob, table.device)
     if T and n_utt and longest:
-        sizing = lib.abnz_hmm_dense_viterbi_ws_bytes if min_duration == 1 else lib.abnw_hmm_dense_viterbi_dur_ws_bytes
-        ws, off_d, len_d = _utt.workspace(who, sizing, off_h, len_h, longest, K, D, table.device)
-        args = (_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B),
-                _lib.ptr(c0), _lib.ptr(li), _lib.ptr(lt), K, _lib.ptr(ids), _lib.ptr(lp), _lib.ptr(nsw), _lib.ptr(ng),
-                _lib.ptr(ws), ws.numel(), _lib.stream())
-        if min_duration == 1:
-            _lib.check(lib.abnz_hmm_dense_viterbi(*args), 'abnz_hmm_dense_viterbi')
-        else:
-            _lib.check(lib.abnw_hmm_dense_viterbi_dur(*(args + (min_duration,))), 'abnw_hmm_dense_viterbi_dur')
+        ws, off_d, len_d = _utt.workspace(who, _dense_viterbi_sizing(lib, min_duration), off_h, len_h, longest, K, D, table.device)
+        _dense_viterbi_launch(lib, table, off_d, len_d, n_utt, shift, A, B, c0, li, lt, K, ids, lp, nsw, ng, min_duration, ws)
     return ids, lp, nsw, ng
 
 
@@ -714,9 +693,7 @@ def hard_stats(table, off, lens, shift, ids, K, min_duration=1, n_ranges=0):
     who = 'hmm.hard_stats'
     min_duration = _utt.check_min_duration(who, min_duration)
     n_ranges = _check_n_ranges(who, n_ranges)
-    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:      # (host checks first)
-        raise ValueError('%s: a [T, D] float32 table is needed' % who)
-    T, D = table.shape
+    T, D = _utt.table_shape(who, table)
     if not isinstance(shift, torch.Tensor) or shift.shape != (D,) or shift.dtype != torch.float32:
         raise ValueError('%s: shift [D] float32 is needed' % who)
     if not isinstance(ids, torch.Tensor) or ids.shape != (T,) or ids.dtype != torch.int32 or not ids.is_contiguous():
@@ -746,38 +723,32 @@ def check_dense_params(who, params):
     return set(params)
 
 
-class StickyHmmPosteriorgram(object):
-    """transform / decode / quantize / score / fit_stay / fit of the sticky HMM the module docstring defines, over a fitted GmmPosteriorgram.
+class _MixtureHmm(object):
+    """What the two models over a fitted GmmPosteriorgram share: the emission tables, the corpus plumbing of transform /
+    score / decode / quantize, the scaffold of the training loops and the mixture's part of the file.  A subclass supplies
+    ``_forward_backward(table, lens, mode) -> (post, loglik, n_good)`` and
+    ``_max_product(table, lens, min_duration) -> (ids, log_prob, n_switch, n_good)``, device tensors of its own chain.
+    The messages name the subclass."""
 
-    corpus arguments: a DeviceCorpus, a {name: [T, D]} dict, the path of an h5features file -- each file an utterance --
-    or a [T, D] float32 device table, which is ONE utterance."""
-
-    def __init__(self, gmm, stay=0.9):
+    def __init__(self, gmm):
         if not isinstance(gmm, _gmm.GmmPosteriorgram) or gmm.weights_ is None:
-            raise ValueError('StickyHmmPosteriorgram: a fitted GmmPosteriorgram is needed')
+            raise ValueError('%s: a fitted GmmPosteriorgram is needed' % type(self).__name__)
         self.gmm = gmm
-        self.stay_ = check_stay('StickyHmmPosteriorgram', stay, gmm.weights_.astype(np.float32))
         self.log_likelihoods = []
-        self.n_bad_ = self.n_retired_ = self.n_starved_ = 0
+        self.n_bad_ = self.n_starved_ = 0
         self.last_log_prob_ = self.last_n_switch_ = self.last_n_good_ = None
         self._tables = None
 
-    def whoami(self):
-        return {'params': {'stay': self.stay_, 'gmm': self.gmm.whoami()}, 'class_name': self.__class__.__name__}
-
-    def device_tables(self, device):
-        """(shift, A, B, c0, w32) on the device, rounded once from the mixture's float64 parameters."""
-        if self._tables is None or self._tables[0].device != device:
-            g = self.gmm
-            shift, A, B, _ = g.device_tables(device)
-            m = g.means_ - g.shift_.astype(np.float64)
-            c0 = torch.from_numpy(emission_offsets(m, g.variances_)).to(device)
-            w = torch.from_numpy(g.weights_.astype(np.float32)).to(device)
-            self._tables = (shift, A, B, c0, w)
-        return self._tables
+    def _emission_tables(self, device):
+        """(shift, A, B, c0) on the device, rounded once from the mixture's float64 parameters."""
+        g = self.gmm
+        shift, A, B, _ = g.device_tables(device)
+        m = g.means_ - g.shift_.astype(np.float64)
+        return shift, A, B, torch.from_numpy(emission_offsets(m, g.variances_)).to(device)
 
     def _utterances(self, corpus):
         """(device table, DeviceCorpus or None, lens int64 [n_utt])"""
+        who = type(self).__name__
         table, dc = _gmm.GmmPosteriorgram._corpus(corpus)
         if dc is not None:
             lens = [dc.length[k] for k in dc.names]
@@ -787,42 +758,125 @@ class StickyHmmPosteriorgram(object):
             lens = [table.shape[0]] if isinstance(table, torch.Tensor) and table.dim() == 2 else []
         if isinstance(table, torch.Tensor) and table.dim() == 2 and table.dtype == torch.float32:      # (host checks first)
             if table.shape[1] != self.gmm.shift_.shape[0]:
-                raise ValueError('StickyHmmPosteriorgram: the table has D = %d, the model D = %d'
-                                 % (table.shape[1], self.gmm.shift_.shape[0]))
+                raise ValueError('%s: the table has D = %d, the model D = %d' % (who, table.shape[1], self.gmm.shift_.shape[0]))
             if len(lens) and max(lens) > max_len():
-                raise ValueError('StickyHmmPosteriorgram: an utterance of %d frames, the kernel takes up to %d '
-                                 '(abn_hmm_max_len); pass a corpus of utterances' % (max(lens), max_len()))
-        table = _gmm._check_table('StickyHmmPosteriorgram', table)
+                raise ValueError('%s: an utterance of %d frames, the kernel takes up to %d '
+                                 '(abn_hmm_max_len); pass a corpus of utterances' % (who, max(lens), max_len()))
+        table = _gmm._check_table(who, table)
         return table, dc, np.asarray(lens, dtype=np.int64)
+
+    @staticmethod
+    def _like(dc, out):
+        """A table of one row per frame as the corpus came: for a DeviceCorpus a new one with its names, lengths and times."""
+        from .dataloader import DeviceCorpus
+        return out if dc is None else DeviceCorpus.from_table(out, dc.names, [dc.length[k] for k in dc.names], dc.times)
+
+    def transform(self, corpus, mode='smooth'):
+        """The smoothed (mode='filter': filtered) posterior table [rows, K] on the device; for a DeviceCorpus a new
+        DeviceCorpus with the same names, lengths and times."""
+        table, dc, lens = self._utterances(corpus)
+        return self._like(dc, self._forward_backward(table, lens, mode)[0])
+
+    def score(self, corpus):
+        """The mean log-likelihood per good frame."""
+        table, _, lens = self._utterances(corpus)
+        _, ll, ng = self._forward_backward(table, lens, 'filter')
+        ll_sum, n = torch.stack([ll.sum(), ng.to(torch.float64).sum()]).cpu().tolist()
+        return ll_sum / max(1.0, n)
+
+    def _decode_ids(self, corpus, min_duration=1):
+        """(device ids [rows] int32, DeviceCorpus or None, names or None, lens); fills last_log_prob_ / last_n_switch_ /
+        last_n_good_ / n_bad_."""
+        min_duration = _utt.check_min_duration(type(self).__name__, min_duration)
+        table, dc, lens = self._utterances(corpus)
+        names = list(dc.names) if dc is not None else list(corpus) if isinstance(corpus, dict) else None
+        ids, lp, nsw, ng = self._max_product(table, lens, min_duration)
+        self.last_log_prob_, self.last_n_switch_, self.last_n_good_ = lp.cpu().numpy(), nsw.cpu().numpy(), ng.cpu().numpy()
+        self.n_bad_ = int(lens.sum() - self.last_n_good_.sum())
+        return ids, dc, names, lens
+
+    def decode(self, corpus, min_duration=1):
+        """The unit ids of the model's best path, int32, -1 for a BAD frame: {name: host array [length]} in corpus order for
+        a DeviceCorpus, a dict or a file; for a [T, D] table, which is ONE utterance, the device tensor [T].  The
+        subclasses' docstrings say what each one's path and ``last_*_`` are."""
+        ids, _, names, lens = self._decode_ids(corpus, min_duration)
+        return ids if names is None else _gmm._split_rows(ids.cpu().numpy(), zip(names, lens))
+
+    def quantize(self, corpus, min_duration=1):
+        """Each frame replaced by the mean of its decoded component (uncentred: m + shift), [rows, D] float32 on the
+        device, a BAD frame a row of zeros; for a DeviceCorpus a new DeviceCorpus with the same names, lengths and times
+        (what KMeansQuantizer.quantize gives ``ABXEvaluator(parallel='zero')``).  min_duration: as in ``decode``."""
+        ids, dc, _, _ = self._decode_ids(corpus, min_duration)
+        means = torch.from_numpy(self.gmm.means_.astype(np.float32)).to(ids.device)
+        out = means[ids.clamp(min=0).to(torch.int64)]
+        out[ids < 0] = 0.0
+        return self._like(dc, out)
+
+    # -- training: the scaffold of the fit loops ------------------------------------------------------------------
+    def _training_copy(self, device):
+        """(g, shift64, dev, shift): a copy of the mixture with float64 parameters of its own (the GmmPosteriorgram this
+        object was made from stays untouched), its shift in float64, the float32 uploader and the shift on the device."""
+        g = copy.copy(self.gmm)
+        g.weights_, g.means_, g.variances_ = (np.array(a, dtype=np.float64) for a in (g.weights_, g.means_, g.variances_))
+        g.log_likelihoods, g._tables = list(g.log_likelihoods), None
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+        return g, g.shift_.astype(np.float64), dev, dev(g.shift_)
+
+    def _adopt(self, g, p, shift64, m, v, w=None):
+        """The trained copy becomes ``self.gmm``, with those of the centred means m, variances v and weights w that the
+        letters p name."""
+        if 'w' in p:
+            g.weights_ = w
+        if 'm' in p:
+            g.means_ = m + shift64
+        if 'v' in p:
+            g.variances_ = v
+        self.gmm, self._tables = g, None
+
+    # -- files ----------------------------------------------------------------------------------------------------
+    def _mixture_fields(self):
+        """The arrays of the mixture's own file (GmmPosteriorgram.load reads them), for ``save``."""
+        g = self.gmm
+        return dict(weights=g.weights_, means=g.means_, variances=g.variances_, shift=g.shift_, gv=g.gv_,
+                    log_likelihoods=np.asarray(g.log_likelihoods, dtype=np.float64),
+                    n_components=g.n_components, n_iter=g.n_iter, tol=g.tol, var_floor=g.var_floor,
+                    min_count=g.min_count, seed=g.seed)
+
+
+class StickyHmmPosteriorgram(_MixtureHmm):
+    """transform / decode / quantize / score / fit_stay / fit of the sticky HMM the module docstring defines, over a fitted GmmPosteriorgram.
+
+    corpus arguments: a DeviceCorpus, a {name: [T, D]} dict, the path of an h5features file -- each file an utterance --
+    or a [T, D] float32 device table, which is ONE utterance."""
+
+    def __init__(self, gmm, stay=0.9):
+        super().__init__(gmm)
+        self.stay_ = check_stay('StickyHmmPosteriorgram', stay, gmm.weights_.astype(np.float32))
+        self.n_retired_ = 0
+
+    def whoami(self):
+        return {'params': {'stay': self.stay_, 'gmm': self.gmm.whoami()}, 'class_name': self.__class__.__name__}
+
+    def device_tables(self, device):
+        """(shift, A, B, c0, w32) on the device, rounded once from the mixture's float64 parameters."""
+        if self._tables is None or self._tables[0].device != device:
+            w = torch.from_numpy(self.gmm.weights_.astype(np.float32)).to(device)
+            self._tables = self._emission_tables(device) + (w,)
+        return self._tables
 
     def _run(self, table, lens, mode, stay=None, out=None, want_stays=True):
         off = _utt.starts(lens)
         return forward_backward(table, off, lens, *self.device_tables(table.device),
                                 stay=self.stay_ if stay is None else stay, mode=mode, out=out, want_stays=want_stays)
 
-    def transform(self, corpus, mode='smooth'):
-        """The smoothed (mode='filter': filtered) posterior table [rows, K] on the device; for a DeviceCorpus a new
-        DeviceCorpus with the same names, lengths and times."""
-        from .dataloader import DeviceCorpus
-        table, dc, lens = self._utterances(corpus)
-        out = self._run(table, lens, mode, want_stays=False)[0]
-        if dc is None:
-            return out
-        return DeviceCorpus.from_table(out, dc.names, [dc.length[k] for k in dc.names], dc.times)
+    def _forward_backward(self, table, lens, mode):
+        post, ll, _, ng = self._run(table, lens, mode, want_stays=False)
+        return post, ll, ng
 
-    def _decode_ids(self, corpus, min_duration=1):
-        """(device ids [rows] int32, DeviceCorpus or None, names or None, lens); fills last_log_prob_ / last_n_switch_ /
-        last_n_good_ / n_bad_."""
-        min_duration = _utt.check_min_duration('StickyHmmPosteriorgram', min_duration)
-        table, dc, lens = self._utterances(corpus)
-        names = list(dc.names) if dc is not None else list(corpus) if isinstance(corpus, dict) else None
+    def _max_product(self, table, lens, min_duration):
         shift, A, B, c0, w = self.device_tables(table.device)
         lw, ls, lr = (torch.from_numpy(a).to(table.device) for a in viterbi_tables(self.gmm.weights_, self.stay_))
-        off = _utt.starts(lens)
-        ids, lp, nsw, ng = viterbi(table, off, lens, shift, A, B, c0, lw, ls, lr, min_duration=min_duration)
-        self.last_log_prob_, self.last_n_switch_, self.last_n_good_ = lp.cpu().numpy(), nsw.cpu().numpy(), ng.cpu().numpy()
-        self.n_bad_ = int(lens.sum() - self.last_n_good_.sum())
-        return ids, dc, names, lens
+        return viterbi(table, _utt.starts(lens), lens, shift, A, B, c0, lw, ls, lr, min_duration=min_duration)
 
     def decode(self, corpus, min_duration=1):
         """The unit ids of the best path (the module docstring's max-product recurrence), int32, -1 for a BAD frame:
@@ -832,28 +886,7 @@ class StickyHmmPosteriorgram(object):
         ``last_n_switch_`` and ``last_n_good_`` (int32) hold the utterances' log joint probabilities, switch counts and
         good-frame counts; ``n_bad_`` the BAD frames.  min_duration = S (an integer 1 .. 8): every unit but an
         utterance's last lasts at least S good frames (the module docstring's minimum-duration recurrence)."""
-        ids, _, names, lens = self._decode_ids(corpus, min_duration)
-        return ids if names is None else _gmm._split_rows(ids.cpu().numpy(), zip(names, lens))
-
-    def quantize(self, corpus, min_duration=1):
-        """Each frame replaced by the mean of its decoded component (uncentred: m + shift), [rows, D] float32 on the
-        device, a BAD frame a row of zeros; for a DeviceCorpus a new DeviceCorpus with the same names, lengths and times
-        (what KMeansQuantizer.quantize gives ``ABXEvaluator(parallel='zero')``).  min_duration: as in ``decode``."""
-        from .dataloader import DeviceCorpus
-        ids, dc, _, _ = self._decode_ids(corpus, min_duration)
-        means = torch.from_numpy(self.gmm.means_.astype(np.float32)).to(ids.device)
-        out = means[ids.clamp(min=0).to(torch.int64)]
-        out[ids < 0] = 0.0
-        if dc is None:
-            return out
-        return DeviceCorpus.from_table(out, dc.names, [dc.length[k] for k in dc.names], dc.times)
-
-    def score(self, corpus):
-        """The mean log-likelihood per good frame."""
-        table, _, lens = self._utterances(corpus)
-        _, ll, _, ng = self._run(table, lens, 'filter', want_stays=False)
-        ll_sum, n = torch.stack([ll.sum(), ng.to(torch.float64).sum()]).cpu().tolist()
-        return ll_sum / max(1.0, n)
+        return super().decode(corpus, min_duration)
 
     def fit_stay(self, corpus, n_iter=10, tol=1e-4):
         """EM on the stay probability, the mixture fixed, from the current ``stay_``.  Iteration i runs forward-backward
@@ -890,13 +923,8 @@ class StickyHmmPosteriorgram(object):
         update of the n_iter-th).  One T x K scratch table is allocated."""
         p = check_params('StickyHmmPosteriorgram.fit', params)                    # (host checks first)
         table, _, lens = self._utterances(corpus)
-        g = copy.copy(self.gmm)
-        g.weights_, g.means_, g.variances_ = (np.array(a, dtype=np.float64) for a in (g.weights_, g.means_, g.variances_))
-        g.log_likelihoods, g._tables = list(g.log_likelihoods), None
+        g, shift64, dev, shift = self._training_copy(table.device)
         K, D = g.means_.shape
-        shift64 = g.shift_.astype(np.float64)
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(table.device)
-        shift = dev(g.shift_)
         scratch = torch.zeros((table.shape[0], K), dtype=torch.float32, device=table.device)
         off = _utt.starts(lens)
         w, m, v, rho = g.weights_, g.means_ - shift64, g.variances_, self.stay_
@@ -923,23 +951,14 @@ class StickyHmmPosteriorgram(object):
                 self.n_starved_ = int((sums_h[:, 2 * D] < g.min_count).sum())
             w, m, v, rho, self.n_retired_ = baum_welch_update(sums_h, back[4:4 + K], ntr, m, v, g.gv_, g.var_floor, g.min_count,
                                                               params, weights=w, stay=rho, stays_total=stays)
-        if 'w' in p:
-            g.weights_ = w
-        if 'm' in p:
-            g.means_ = m + shift64
-        if 'v' in p:
-            g.variances_ = v
-        self.gmm, self.stay_, self._tables = g, rho, None
+        self._adopt(g, p, shift64, m, v, w)
+        self.stay_ = rho
         return self
 
     # -- files ----------------------------------------------------------------------------------------------------
     def save(self, path):
-        g = self.gmm
         with open(path, 'wb') as f:
-            np.savez(f, weights=g.weights_, means=g.means_, variances=g.variances_, shift=g.shift_, gv=g.gv_,
-                     log_likelihoods=np.asarray(g.log_likelihoods, dtype=np.float64),
-                     n_components=g.n_components, n_iter=g.n_iter, tol=g.tol, var_floor=g.var_floor,
-                     min_count=g.min_count, seed=g.seed, stay=np.float64(self.stay_),
+            np.savez(f, **self._mixture_fields(), stay=np.float64(self.stay_),
                      stay_log_likelihoods=np.asarray(self.log_likelihoods, dtype=np.float64))
 
     @classmethod
@@ -953,7 +972,7 @@ class StickyHmmPosteriorgram(object):
         return self
 
 
-class TransitionHmmPosteriorgram(object):
+class TransitionHmmPosteriorgram(_MixtureHmm):
     """transform / decode / quantize / score / fit of the full-transition HMM the module docstring defines, over a fitted GmmPosteriorgram
     (its means, variances and shift; its weights only seed the default start).
 
@@ -961,8 +980,7 @@ class TransitionHmmPosteriorgram(object):
     alpha: the pseudo-count of the transition M-step (untuned).  corpus arguments: as StickyHmmPosteriorgram's."""
 
     def __init__(self, gmm, trans=None, init=None, stay=0.9, alpha=1e-3):
-        if not isinstance(gmm, _gmm.GmmPosteriorgram) or gmm.weights_ is None:
-            raise ValueError('TransitionHmmPosteriorgram: a fitted GmmPosteriorgram is needed')
+        super().__init__(gmm)
         if not (isinstance(alpha, (int, float, np.floating, np.integer)) and np.isfinite(alpha) and alpha >= 0):
             raise ValueError('TransitionHmmPosteriorgram: alpha = %r, a number >= 0 is needed' % (alpha,))
         K = gmm.means_.shape[0]
@@ -973,15 +991,10 @@ class TransitionHmmPosteriorgram(object):
         i32, t32 = check_transitions('TransitionHmmPosteriorgram', init, trans)
         if len(i32) != K:
             raise ValueError('TransitionHmmPosteriorgram: init [%d] and trans for a mixture of K = %d components' % (len(i32), K))
-        self.gmm = gmm
         self.trans_, self.init_ = t32.astype(np.float64), i32.astype(np.float64)
         self.alpha = float(alpha)
-        self.log_likelihoods = []
         self.viterbi_log_probs = []
         self.last_n_changed_ = None
-        self.n_bad_ = self.n_starved_ = 0
-        self.last_log_prob_ = self.last_n_switch_ = self.last_n_good_ = None
-        self._tables = None
 
     @classmethod
     def from_sticky(cls, h, alpha=1e-3):
@@ -1001,63 +1014,18 @@ class TransitionHmmPosteriorgram(object):
     def device_tables(self, device):
         """(shift, A, B, c0, init32, trans32) on the device, rounded once from the float64 parameters."""
         if self._tables is None or self._tables[0].device != device:
-            g = self.gmm
-            shift, A, B, _ = g.device_tables(device)
-            m = g.means_ - g.shift_.astype(np.float64)
-            c0 = torch.from_numpy(emission_offsets(m, g.variances_)).to(device)
             init = torch.from_numpy(self.init_.astype(np.float32)).to(device)
             trans = torch.from_numpy(np.ascontiguousarray(self.trans_.astype(np.float32))).to(device)
-            self._tables = (shift, A, B, c0, init, trans)
+            self._tables = self._emission_tables(device) + (init, trans)
         return self._tables
 
-    def _utterances(self, corpus):
-        """(device table, DeviceCorpus or None, lens int64 [n_utt])"""
-        table, dc = _gmm.GmmPosteriorgram._corpus(corpus)
-        if dc is not None:
-            lens = [dc.length[k] for k in dc.names]
-        elif isinstance(corpus, dict):
-            lens = [np.asarray(f).shape[0] for f in corpus.values()]
-        else:
-            lens = [table.shape[0]] if isinstance(table, torch.Tensor) and table.dim() == 2 else []
-        if isinstance(table, torch.Tensor) and table.dim() == 2 and table.dtype == torch.float32:      # (host checks first)
-            if table.shape[1] != self.gmm.shift_.shape[0]:
-                raise ValueError('TransitionHmmPosteriorgram: the table has D = %d, the model D = %d'
-                                 % (table.shape[1], self.gmm.shift_.shape[0]))
-            if len(lens) and max(lens) > max_len():
-                raise ValueError('TransitionHmmPosteriorgram: an utterance of %d frames, the kernel takes up to %d '
-                                 '(abn_hmm_max_len); pass a corpus of utterances' % (max(lens), max_len()))
-        table = _gmm._check_table('TransitionHmmPosteriorgram', table)
-        return table, dc, np.asarray(lens, dtype=np.int64)
+    def _forward_backward(self, table, lens, mode):
+        return dense_forward_backward(table, _utt.starts(lens), lens, *self.device_tables(table.device), mode=mode)
 
-    def transform(self, corpus, mode='smooth'):
-        """The smoothed (mode='filter': filtered) posterior table [rows, K] on the device; for a DeviceCorpus a new
-        DeviceCorpus with the same names, lengths and times."""
-        from .dataloader import DeviceCorpus
-        table, dc, lens = self._utterances(corpus)
-        out = dense_forward_backward(table, _utt.starts(lens), lens, *self.device_tables(table.device), mode=mode)[0]
-        if dc is None:
-            return out
-        return DeviceCorpus.from_table(out, dc.names, [dc.length[k] for k in dc.names], dc.times)
-
-    def score(self, corpus):
-        """The mean log-likelihood per good frame."""
-        table, _, lens = self._utterances(corpus)
-        _, ll, ng = dense_forward_backward(table, _utt.starts(lens), lens, *self.device_tables(table.device), mode='filter')
-        ll_sum, n = torch.stack([ll.sum(), ng.to(torch.float64).sum()]).cpu().tolist()
-        return ll_sum / max(1.0, n)
-
-    def _decode_ids(self, corpus, min_duration=1):
-        """(device ids [rows] int32, DeviceCorpus or None, names or None, lens); fills last_log_prob_ / last_n_switch_ /
-        last_n_good_ / n_bad_."""
-        min_duration = _utt.check_min_duration('TransitionHmmPosteriorgram', min_duration)
-        table, dc, lens = self._utterances(corpus)
-        names = list(dc.names) if dc is not None else list(corpus) if isinstance(corpus, dict) else None
+    def _max_product(self, table, lens, min_duration):
         shift, A, B, c0, _, _ = self.device_tables(table.device)
         li, lt = (torch.from_numpy(np.ascontiguousarray(a)).to(table.device) for a in log_transitions(self.init_, self.trans_))
-        ids, lp, nsw, ng = dense_viterbi(table, _utt.starts(lens), lens, shift, A, B, c0, li, lt, min_duration=min_duration)
-        self.last_log_prob_, self.last_n_switch_, self.last_n_good_ = lp.cpu().numpy(), nsw.cpu().numpy(), ng.cpu().numpy()
-        self.n_bad_ = int(lens.sum() - self.last_n_good_.sum())
-        return ids, dc, names, lens
+        return dense_viterbi(table, _utt.starts(lens), lens, shift, A, B, c0, li, lt, min_duration=min_duration)
 
     def decode(self, corpus, min_duration=1):
         """The unit ids of the best path (the module docstring's full-transition max-product recurrence), int32, -1 for a
@@ -1069,21 +1037,10 @@ class TransitionHmmPosteriorgram(object):
         ``n_bad_`` the BAD frames.  min_duration = S (an integer 1 .. 8): every unit but an utterance's last lasts at least
         S good frames (the module docstring's minimum duration of this model; with S > 1 ``last_log_prob_`` is that
         definition's score); 1 is the recurrence without it."""
-        ids, _, names, lens = self._decode_ids(corpus, min_duration)
-        return ids if names is None else _gmm._split_rows(ids.cpu().numpy(), zip(names, lens))
+        return super().decode(corpus, min_duration)
 
-    def quantize(self, corpus, min_duration=1):
-        """Each frame replaced by the mean of its decoded component (uncentred: m + shift), [rows, D] float32 on the
-        device, a BAD frame a row of zeros; for a DeviceCorpus a new DeviceCorpus with the same names, lengths and times
-        (as StickyHmmPosteriorgram.quantize).  min_duration: as in ``decode``."""
-        from .dataloader import DeviceCorpus
-        ids, dc, _, _ = self._decode_ids(corpus, min_duration)
-        means = torch.from_numpy(self.gmm.means_.astype(np.float32)).to(ids.device)
-        out = means[ids.clamp(min=0).to(torch.int64)]
-        out[ids < 0] = 0.0
-        if dc is None:
-            return out
-        return DeviceCorpus.from_table(out, dc.names, [dc.length[k] for k in dc.names], dc.times)
+    def _adopt_transitions(self, trans, init):
+        self.trans_, self.init_ = np.array(trans, dtype=np.float64), np.array(init, dtype=np.float64)
 
     def fit(self, corpus, n_iter=10, tol=1e-4, params=DENSE_PARAMS, n_ranges=0):
         """Baum-Welch from the current parameters: any subset of the `m`eans, `v`ariances, `t`ransitions and the `i`nit
@@ -1093,18 +1050,10 @@ class TransitionHmmPosteriorgram(object):
         once, and applies the update; the stopping rule is StickyHmmPosteriorgram.fit's.  Fills ``log_likelihoods``,
         ``n_bad_``, ``n_starved_``, ``trans_`` and ``init_``.  One T x K scratch table is allocated."""
         who = 'TransitionHmmPosteriorgram.fit'
-        if not isinstance(params, str) or not params or len(set(params)) != len(params) or not set(params) <= set(DENSE_PARAMS):
-            raise ValueError('%s: params = %r, a non-empty choice of the letters of %r is needed '
-                             '(m means, v variances, t transitions, i init)' % (who, params, DENSE_PARAMS))
-        p = set(params)
+        p = check_dense_params(who, params)                                        # (host checks first)
         table, _, lens = self._utterances(corpus)
-        g = copy.copy(self.gmm)
-        g.weights_, g.means_, g.variances_ = (np.array(a, dtype=np.float64) for a in (g.weights_, g.means_, g.variances_))
-        g.log_likelihoods, g._tables = list(g.log_likelihoods), None
+        g, shift64, dev, shift = self._training_copy(table.device)
         K, D = g.means_.shape
-        shift64 = g.shift_.astype(np.float64)
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(table.device)
-        shift = dev(g.shift_)
         scratch = torch.zeros((table.shape[0], K), dtype=torch.float32, device=table.device)
         off = _utt.starts(lens)
         m, v, trans, init = g.means_ - shift64, g.variances_, self.trans_, self.init_
@@ -1135,11 +1084,8 @@ class TransitionHmmPosteriorgram(object):
                 _, m, v, _, _ = baum_welch_update(sums_h, np.zeros(K), ntr, m, v, g.gv_, g.var_floor, g.min_count, mv,
                                                   weights=np.full(K, 1.0 / K), stay=0.0)
             trans, init = transition_update(stats_h, trans, init, self.alpha, ''.join(c for c in 'ti' if c in p))
-        if 'm' in p:
-            g.means_ = m + shift64
-        if 'v' in p:
-            g.variances_ = v
-        self.gmm, self.trans_, self.init_, self._tables = g, np.array(trans, dtype=np.float64), np.array(init, dtype=np.float64), None
+        self._adopt(g, p, shift64, m, v)
+        self._adopt_transitions(trans, init)
         return self
 
     def fit_viterbi(self, corpus, n_iter=10, tol=1e-4, params=DENSE_PARAMS, min_duration=1, n_ranges=0):
@@ -1159,26 +1105,18 @@ class TransitionHmmPosteriorgram(object):
         n_ranges = _check_n_ranges(who, n_ranges)
         table, _, lens = self._utterances(corpus)
         lib = _lib.load()
-        g = copy.copy(self.gmm)
-        g.weights_, g.means_, g.variances_ = (np.array(a, dtype=np.float64) for a in (g.weights_, g.means_, g.variances_))
-        g.log_likelihoods, g._tables = list(g.log_likelihoods), None
-        K, D = g.means_.shape
+        K, D = self.gmm.means_.shape
         if K > dense_max_k():
             raise ValueError('%s: K = %d, the kernel takes 1 .. %d (abny_hmm_dense_max_k)' % (who, K, dense_max_k()))
         T = table.shape[0]
         off_h, len_h, n_utt, longest = _utt.utterance_spans(who, _utt.starts(lens), lens, T, max_len(), 'abn_hmm_max_len')
         if not (T and n_utt and longest):
             raise ValueError('%s: the corpus has no frame' % who)
-        shift64 = g.shift_.astype(np.float64)
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(table.device)
-        shift = dev(g.shift_)
-        sizing = lib.abnz_hmm_dense_viterbi_ws_bytes if S == 1 else lib.abnw_hmm_dense_viterbi_dur_ws_bytes
-        vws, off_d, len_d = _utt.workspace(who, sizing, off_h, len_h, longest, K, D, table.device)
+        g, shift64, dev, shift = self._training_copy(table.device)
+        vws, off_d, len_d = _utt.workspace(who, _dense_viterbi_sizing(lib, S), off_h, len_h, longest, K, D, table.device)
         hws = _hard_stats_workspace(who, lib, T, n_utt, K, D, n_ranges, table.device)
-        ids = [torch.full((T,), -1, dtype=torch.int32, device=table.device) for _ in range(2)]
-        lp = torch.zeros(n_utt, dtype=torch.float64, device=table.device)
-        nsw = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
-        ng = torch.zeros(n_utt, dtype=torch.int32, device=table.device)
+        ids, lp, nsw, ng = _utt.path_results(None, T, n_utt, True, table.device)
+        ids = [ids, torch.full_like(ids, -1)]                 # (two buffers: an iteration's ids are compared with the last's)
         m, v, trans, init = g.means_ - shift64, g.variances_, self.trans_, self.init_
         mv, ti = ''.join(c for c in 'mv' if c in p), ''.join(c for c in 'ti' if c in p)
         self.viterbi_log_probs = []
@@ -1187,13 +1125,7 @@ class TransitionHmmPosteriorgram(object):
             li, lt = (dev(a) for a in log_transitions(init, trans))
             A, B, c0 = dev(A), dev(B), dev(emission_offsets(m, v))
             cur = ids[it & 1]
-            args = (_lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B),
-                    _lib.ptr(c0), _lib.ptr(li), _lib.ptr(lt), K, _lib.ptr(cur), _lib.ptr(lp), _lib.ptr(nsw),
-                    _lib.ptr(ng), _lib.ptr(vws), vws.numel(), _lib.stream())
-            if S == 1:
-                _lib.check(lib.abnz_hmm_dense_viterbi(*args), 'abnz_hmm_dense_viterbi')
-            else:
-                _lib.check(lib.abnw_hmm_dense_viterbi_dur(*(args + (S,))), 'abnw_hmm_dense_viterbi_dur')
+            _dense_viterbi_launch(lib, table, off_d, len_d, n_utt, shift, A, B, c0, li, lt, K, cur, lp, nsw, ng, S, vws)
             counts, sums, _ = _hard_stats_launch(lib, table, off_d, len_d, n_utt, shift, cur, K, S, n_ranges, hws)
             changed = (cur != ids[(it + 1) & 1]).sum().to(torch.float64) if it else torch.tensor(float(T), dtype=torch.float64,
                                                                                                  device=table.device)
@@ -1213,22 +1145,15 @@ class TransitionHmmPosteriorgram(object):
                 _, m, v, _, _ = baum_welch_update(sums_h, np.zeros(K), 0, m, v, g.gv_, g.var_floor, g.min_count, mv,
                                                   weights=np.full(K, 1.0 / K), stay=0.0)
             trans, init = transition_update(counts_h, trans, init, self.alpha, ti)
-        if 'm' in p:
-            g.means_ = m + shift64
-        if 'v' in p:
-            g.variances_ = v
-        self.gmm, self.trans_, self.init_, self._tables = g, np.array(trans, dtype=np.float64), np.array(init, dtype=np.float64), None
+        self._adopt(g, p, shift64, m, v)
+        self._adopt_transitions(trans, init)
         return self
 
     # -- files ----------------------------------------------------------------------------------------------------
     def save(self, path):
         """The mixture's file (GmmPosteriorgram.load reads it) plus trans, init and alpha."""
-        g = self.gmm
         with open(path, 'wb') as f:
-            np.savez(f, weights=g.weights_, means=g.means_, variances=g.variances_, shift=g.shift_, gv=g.gv_,
-                     log_likelihoods=np.asarray(g.log_likelihoods, dtype=np.float64),
-                     n_components=g.n_components, n_iter=g.n_iter, tol=g.tol, var_floor=g.var_floor,
-                     min_count=g.min_count, seed=g.seed, trans=self.trans_, init=self.init_, alpha=np.float64(self.alpha),
+            np.savez(f, **self._mixture_fields(), trans=self.trans_, init=self.init_, alpha=np.float64(self.alpha),
                      trans_log_likelihoods=np.asarray(self.log_likelihoods, dtype=np.float64),
                      viterbi_log_probs=np.asarray(self.viterbi_log_probs, dtype=np.float64))
 
@@ -1249,6 +1174,31 @@ class TransitionHmmPosteriorgram(object):
 def _holds(path, key):
     with np.load(path) as z:
         return key in z.files
+
+
+def _report_decode(h, out, times, model, path):
+    """Writes the decoded ids and prints the report; `model` is the fragment that names the chain."""
+    from . import kmeans as _kmeans
+    _gmm._write_named(path, out, times, as_column=True)
+    n_good = int(h.last_n_good_.sum())
+    if times is not None:
+        seconds = sum(float(np.asarray(times[k])[-1] - np.asarray(times[k])[0]) for k in out if len(times[k]) > 1)
+        rate = '%.2f bits/s' % _kmeans.bitrate(_kmeans.unit_sequences(out), seconds) if seconds > 0 else 'n/a (no duration)'
+    else:
+        rate = '%.2f bits/s at 100 frames/s' % _kmeans.bitrate(_kmeans.unit_sequences(out), max(n_good, 1) / 100.0)
+    print('%d files, %d frames (%d BAD), K = %d, %s, %d switches, bitrate %s, mean log-probability %.6f per good frame -> %s'
+          % (len(out), sum(v.shape[0] for v in out.values()), h.n_bad_, h.gmm.n_components, model,
+             int(h.last_n_switch_.sum()), rate, float(h.last_log_prob_.sum()) / max(n_good, 1), path))
+    return 0
+
+
+def _report_transform(h, feats, times, mode, model, path):
+    """Writes the posteriorgrams and prints the report; `model` as in ``_report_decode``."""
+    post = h.transform(feats, mode).cpu().numpy()
+    out = _gmm._split_rows(post, ((k, v.shape[0]) for k, v in feats.items()))
+    _gmm._write_named(path, out, times)
+    print('%d files, %d frames, K = %d, %s -> %s' % (len(out), post.shape[0], post.shape[1], model, path))
+    return 0
 
 
 def main(argv=None):
@@ -1333,50 +1283,16 @@ def main(argv=None):
         print('stay %.6f after %d iterations, mean log-likelihood %.6f, %d BAD frames'
               % (h.stay_, len(h.log_likelihoods), h.log_likelihoods[-1], h.n_bad_))
         return 0
-    if _holds(args.model, 'trans'):
-        h = TransitionHmmPosteriorgram.load(args.model)
-        if args.cmd == 'decode':
-            from . import kmeans as _kmeans
-            if args.min_duration != 1:
-                raise ValueError('python -m abnet3_amd.hmm decode: %s holds a full transition matrix, whose max-product path '
-                                 'has no minimum duration; --min-duration %d needs a sticky model' % (args.model, args.min_duration))
-            out = h.decode(feats)
-            _gmm._write_named(args.out, out, times, as_column=True)
-            n_good = int(h.last_n_good_.sum())
-            if times is not None:
-                seconds = sum(float(np.asarray(times[k])[-1] - np.asarray(times[k])[0]) for k in out if len(times[k]) > 1)
-                rate = '%.2f bits/s' % _kmeans.bitrate(_kmeans.unit_sequences(out), seconds) if seconds > 0 else 'n/a (no duration)'
-            else:
-                rate = '%.2f bits/s at 100 frames/s' % _kmeans.bitrate(_kmeans.unit_sequences(out), max(n_good, 1) / 100.0)
-            print('%d files, %d frames (%d BAD), K = %d, full transitions, %d switches, bitrate %s, mean log-probability %.6f per '
-                  'good frame -> %s' % (len(out), sum(v.shape[0] for v in out.values()), h.n_bad_, h.gmm.n_components,
-                                        int(h.last_n_switch_.sum()), rate, float(h.last_log_prob_.sum()) / max(n_good, 1), args.out))
-            return 0
-        post = h.transform(feats, args.mode).cpu().numpy()
-        out = _gmm._split_rows(post, ((k, v.shape[0]) for k, v in feats.items()))
-        _gmm._write_named(args.out, out, times)
-        print('%d files, %d frames, K = %d, full transitions -> %s' % (len(out), post.shape[0], post.shape[1], args.out))
-        return 0
-    h = StickyHmmPosteriorgram.load(args.model)
+    dense = _holds(args.model, 'trans')
+    h = (TransitionHmmPosteriorgram if dense else StickyHmmPosteriorgram).load(args.model)
+    model = 'full transitions' if dense else 'stay %.4f' % h.stay_
     if args.cmd == 'decode':
-        from . import kmeans as _kmeans
-        out = h.decode(feats, min_duration=args.min_duration)
-        _gmm._write_named(args.out, out, times, as_column=True)
-        n_good = int(h.last_n_good_.sum())
-        if times is not None:
-            seconds = sum(float(np.asarray(times[k])[-1] - np.asarray(times[k])[0]) for k in out if len(times[k]) > 1)
-            rate = '%.2f bits/s' % _kmeans.bitrate(_kmeans.unit_sequences(out), seconds) if seconds > 0 else 'n/a (no duration)'
-        else:
-            rate = '%.2f bits/s at 100 frames/s' % _kmeans.bitrate(_kmeans.unit_sequences(out), max(n_good, 1) / 100.0)
-        print('%d files, %d frames (%d BAD), K = %d, stay %.4f, %d switches, bitrate %s, mean log-probability %.6f per good frame -> %s'
-              % (len(out), sum(v.shape[0] for v in out.values()), h.n_bad_, h.gmm.n_components, h.stay_,
-                 int(h.last_n_switch_.sum()), rate, float(h.last_log_prob_.sum()) / max(n_good, 1), args.out))
-        return 0
-    post = h.transform(feats, args.mode).cpu().numpy()
-    out = _gmm._split_rows(post, ((k, v.shape[0]) for k, v in feats.items()))
-    _gmm._write_named(args.out, out, times)
-    print('%d files, %d frames, K = %d, stay %.4f -> %s' % (len(out), post.shape[0], post.shape[1], h.stay_, args.out))
-    return 0
+        if dense and args.min_duration != 1:
+            raise ValueError('python -m abnet3_amd.hmm decode: %s holds a full transition matrix, whose max-product path '
+                             'has no minimum duration; --min-duration %d needs a sticky model' % (args.model, args.min_duration))
+        out = h.decode(feats) if dense else h.decode(feats, min_duration=args.min_duration)
+        return _report_decode(h, out, times, model, args.out)
+    return _report_transform(h, feats, times, args.mode, model, args.out)
 
 
 if __name__ == '__main__':
