@@ -61,8 +61,8 @@ workgroups, one utterance at a time, one sum reduction per frame and sweep.  The
 sweeps, so there is no T x K array beyond it.  A Baum-Welch iteration is that launch with the per-component stays
 (abn_hmm_forward_backward_stats) and abn_hmm_accumulate, which reads the gamma table once as the A operand of
 abn_gmm_accumulate's statistics GEMM.  Limits: K <= abn_hmm_max_k(), D <= abn_gmm_max_d(), an utterance of at most
-abn_hmm_max_len() frames; utterances must not overlap.  Left out: duration distributions (the sticky max-product path has
-a minimum duration, below; the full-transition model's has none).
+abn_hmm_max_len() frames; utterances must not overlap.  Left out: duration distributions for THIS model (its max-product
+path has a minimum duration, below; the full-transition model's has explicit unit durations, at the end).
 
 The max-product path (``viterbi``, ``StickyHmmPosteriorgram.decode`` / ``quantize``; abn_hmm_viterbi, one launch;
 tests/hmm_vit_np.py restates it).  The model, the emissions and the BAD-frame rule are the ones above.
@@ -105,8 +105,8 @@ tests/hmm_vit_np.py restates it).  The model, the emissions and the BAD-frame ru
   i, 0 < i < S-1, to (k, i-1); from state 0 to (exitj, S-1).  n_switch = the changes of id.  Where S ls[k] < lr[k] (a
   small stay and a large S) closing a unit and entering it again beats staying; the ids do not show such a boundary, and
   every run of ids but the last is >= S either way.  log_prob is then the score above, not a log joint probability of
-  the sticky chain.  Left out: a duration distribution, a maximum duration, untied emission states; S is untuned on real
-  speech.
+  the sticky chain.  Left out: a maximum duration, untied emission states (a duration distribution per unit exists for the
+  full-transition model only, at the end); S is untuned on real speech.
 * At stay = 0 all three tables are equal and the recurrence is argmax_k fl32(s[k] + lw[k]) frame by frame: the mixture's
   hard assignment.
 
@@ -137,8 +137,9 @@ weights play no part):
   16, 32, 64 or 128) and the slice t div K' of K'^2 / 256 consecutive indices of the other side, adds its products in
   ascending order with fused multiply-adds, and the 256 / K' partial sums are added slice 0 first.
 * Limits: K <= abny_hmm_dense_max_k() (128: the matrix lives in LDS), D <= abn_gmm_max_d(), an utterance of at most
-  abn_hmm_max_len() frames; utterances must not overlap.  Left out: duration states, sparse or banded matrices, K above
-  the LDS limit.  Nothing here is tuned or measured on real speech.
+  abn_hmm_max_len() frames; utterances must not overlap.  Left out: sparse or banded matrices, K above the LDS limit
+  (forward-backward itself has no duration states: the explicit durations at the end are the max-product path's alone).
+  Nothing here is tuned or measured on real speech.
 
 The max-product path of the full-transition model (``dense_viterbi``, ``TransitionHmmPosteriorgram.decode`` / ``quantize``;
 abnz_hmm_dense_viterbi, csrc/hmm_dense_vit.hip, one launch; tests/hmm_dense_vit_np.py restates it).  Model, emissions and
@@ -179,8 +180,8 @@ chain passes over it, and it counts neither as a frame nor as a transition.
   The final state is the lowest k, then the largest i, with V[k][i] == 0.  Going backwards from (k, i): i == S-1 and st set
   -> (k, S-1); else i > 0 -> (k, i-1); else -> (bp[k], S-1), one switch.  S = 1 is NOT this recurrence (its diagonal sits
   inside the argmax): min_duration = 1 makes the call without it, and abnw_hmm_dense_viterbi_dur launches that kernel.
-  log_prob is the score above, not a log joint probability of the K-state chain.  Left out: a duration distribution, a
-  maximum duration, untied emission states; S is untuned on real speech.
+  log_prob is the score above, not a log joint probability of the K-state chain.  Left out: a maximum duration, untied
+  emission states; S is untuned on real speech.  (A duration distribution per unit: the explicit durations below.)
 * Limits: the full-transition model's.  Left out: sparse or banded matrices, K above the LDS limit.  Nothing here is tuned
   or measured on real speech.
 
@@ -211,8 +212,53 @@ k-means, Juang & Rabiner 1990), the alternative to ``fit``'s smoothed posteriors
   variance floor, min_count, alpha > 0 and TRANS_MIN are the usual exceptions).  It stops when the gain is below tol or when
   no id changed (counted on the device).  No T x K table is allocated.
 * Left out: Viterbi training of the sticky model, whose stay and redraw share one log term (use
-  ``TransitionHmmPosteriorgram.from_sticky``); duration distributions; K above the LDS limit.  Nothing here is tuned or
-  measured on real speech.
+  ``TransitionHmmPosteriorgram.from_sticky``); K above the LDS limit.  Nothing here is tuned or measured on real speech.
+
+Explicit unit durations: a hidden semi-Markov model (HSMM) over the same units (``hsmm_viterbi``, ``run_stats``,
+``duration_update``, ``TransitionHmmPosteriorgram.set_durations`` / ``decode(durations=True)`` / ``fit_viterbi(params='mvtid',
+max_duration=L)``; abnu_hmm_hsmm_viterbi and abnu_hmm_run_stats, csrc/hmm_hsmm.hip; tests/hmm_hsmm_np.py restates it).
+Emissions, BAD-frame rule, init and trans are the full-transition model's; durations count good frames only (a BAD frame gets
+id -1, the chain passes over it, and it counts as nothing).
+
+* A path is a sequence of segments (k_i, n_i) with k_i != k_{i+1} and n_i >= 1: the maximal runs of the ids are the segments
+  and n_switch = segments - 1.  Unit k has a duration law with a free head of L - 1 values and a geometric tail, L an integer
+  2 .. 32 (``hsmm_max_duration``): with q[k][1..L] summing to 1 and r[k] in (0, 1),
+    p_k(d) = q[k][d] for d < L,     p_k(d) = q[k][L] (1 - r[k]) r[k]^(d - L) for d >= L,
+  so every utterance has a finite-score path for every K >= 1 and a long silence needs no artificial split.
+* Host-made float32 tables, float64 logarithms rounded once: ``duration_tables(q, r) -> (ld [K, L], ls [K])`` with
+  ld[k][i] = log q[k][i] for i < L, ld[k][L] = log(q[k][L] (1 - r[k])), ls[k] = log r[k]; ``switch_log_transitions(init, trans)
+  -> (li, lx)`` with lx[j][k] = log(trans[j][k] / (1 - trans[j][j])) for j != k (the diagonal is never read).  Every q, r and
+  1 - r must be at least 2^-100 (ValueError), so every entry is finite; the kernel takes no logarithm.
+  ``geometric_durations(trans, L)`` is the law under which this model scores a path as the plain one does (r = trans[k][k]),
+  up to log(1 - r) of the LAST unit: the score below closes the utterance's last segment.
+* The score of a path: the sum of the frames' scores + li[k_1] + lx[k_{i-1}][k_i] for each later segment + log p_{k_i}(n_i)
+  for every segment INCLUDING the utterance's last, which is treated as complete, not censored.
+* Recurrence over an utterance's good frames, fp32, every operation one rounded add or one compare.  V[k][1..L] are the
+  normalised previous values; state i = "in unit k, the current segment is i frames long", state L = "L or more":
+    first good frame:   U[k][1] = s[k] + li[k], every other state -inf
+    later good frames:  x[j] = max_i (V[j][i] + ld[j][i]),  xi[j] = the lowest i attaining it  (strict compares, ascending i)
+                        ent[k] = max over j != k of (x[j] + lx[j][k]),  bp[k] = the lowest such j  (strict, ascending j;
+                        K = 1: -inf);   U[k][1] = s[k] + ent[k];   U[k][i] = s[k] + V[k][i-1] for 1 < i < L
+                        a = V[k][L] + ls[k],  st = a > V[k][L-1]  (strict: a tie goes to the advance)
+                        U[k][L] = s[k] + (st ? a : V[k][L-1])
+    every good frame:   N_t = max over (k, i) of U,  V = U - N_t,  log_prob += N_t  (float64, frame order)
+    after the last:     F = max over (k, i) of (V[k][i] + ld[k][i]),  final = the lowest k, then the lowest i, attaining it;
+                        log_prob += F
+  Traceback from (k, i) at frame t: i == L and st set -> (k, L); otherwise i > 1 -> (k, i - 1); otherwise -> (bp[k],
+  xi[bp[k]] as recorded at frame t), one switch.  Outputs are ``dense_viterbi``'s, refused utterances included.
+* ``run_stats(ids, off, lens, K, L) -> (dur [K, L], tail [K])``, int64, one small launch: for every maximal run, over an
+  utterance's good frames (0 <= id < K), of unit k with length n, dur[k][min(n, L) - 1] += 1 and tail[k] += max(n - L, 0).
+  Integer arithmetic: the same for any grid and any order of the utterances.
+* ``duration_update(dur, tail, q, r, alpha)`` on the host, float64: q[k][d] = (dur[k][d] + alpha) / (sum_d dur[k] + L alpha),
+  r[k] = (tail[k] + alpha) / (tail[k] + dur[k][L-1] + 2 alpha) -- at alpha = 0 the maximiser of the duration part of the
+  paths' score; a unit without any run at alpha = 0 keeps its old law; then the floor TRANS_MIN and one renormalisation.
+* ``fit_viterbi(params='mvtid', max_duration=L)``: the letter d (this method only) learns the durations.  Iteration i decodes
+  with ``hsmm_viterbi``, takes ``hard_stats`` at min_duration = 1 and ``run_stats`` on the same ids, reads back once, and
+  applies ``baum_welch_update``, ``transition_update`` (both unchanged: the diagonal of the counts receives the stays, and
+  the off-diagonal ratio of a row is the maximum-likelihood lx) and ``duration_update``.  ``transform``, ``score`` and ``fit``
+  ignore the durations.
+* L and alpha are untuned, and nothing here is measured on real speech.  Left out: K above the LDS limit, L above 32,
+  duration laws in forward-backward.
 """
 import argparse
 import copy
@@ -232,6 +278,9 @@ WEIGHT_MIN = 2.0 ** -80
 PARAMS = 'mvws'
 TRANS_MIN = 2.0 ** -80
 DENSE_PARAMS = 'mvti'
+HSMM_PARAMS = 'mvtid'
+HSMM_MAX_DURATION = 32
+DUR_TAIL_MAX = 1.0 - 2.0 ** -24
 
 
 def max_len():
@@ -723,6 +772,192 @@ def check_dense_params(who, params):
     return set(params)
 
 
+# ---- explicit unit durations (the module docstring's semi-Markov decoder) -------------------------------------------------
+def hsmm_max_duration():
+    return int(_lib.load().abnu_hmm_hsmm_max_duration())
+
+
+def check_max_duration(who, L):
+    """L as an int, or ValueError: an integer 2 .. HSMM_MAX_DURATION."""
+    if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 2 <= int(L) <= HSMM_MAX_DURATION:
+        raise ValueError('%s: max_duration = %r, an integer 2 .. %d is needed (abnu_hmm_hsmm_max_duration)'
+                         % (who, L, HSMM_MAX_DURATION))
+    return int(L)
+
+
+def check_hsmm_params(who, params):
+    """The letters of `params` as a set, or ValueError: a non-empty string over 'mvtid' without a repeat."""
+    if not isinstance(params, str) or not params or len(set(params)) != len(params) or not set(params) <= set(HSMM_PARAMS):
+        raise ValueError('%s: params = %r, a non-empty choice of the letters of %r is needed '
+                         '(m means, v variances, t transitions, i init, d durations)' % (who, params, HSMM_PARAMS))
+    return set(params)
+
+
+def check_durations(who, q, r):
+    """(q [K, L], r [K]) as float64 host arrays, or ValueError: finite, every q, r and 1 - r at least 2^-100, L within
+    2 .. HSMM_MAX_DURATION and every row of q summing to 1 within 1e-3."""
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    try:
+        q64, r64 = host(q).astype(np.float64), host(r).astype(np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('%s: q [K, L] and r [K] arrays of numbers are needed' % who)
+    if q64.ndim != 2 or r64.shape != (q64.shape[0],) or not q64.shape[0]:
+        raise ValueError('%s: q [K, L] and r [K] are needed, not %s and %s' % (who, q64.shape, r64.shape))
+    check_max_duration(who, q64.shape[1])
+    if not (np.isfinite(q64).all() and np.isfinite(r64).all()):
+        raise ValueError('%s: q and r must be finite' % who)
+    low = min(float(q64.min()), float(r64.min()), float((1.0 - r64).min()))
+    if low < TINY:
+        raise ValueError('%s: the smallest of q, r and 1 - r is %g, below 2^-100: a log table would not be finite' % (who, low))
+    off = np.abs(q64.sum(axis=1) - 1.0).max()
+    if off > 1e-3:
+        raise ValueError('%s: every row of q must sum to 1 (the worst is off by %g)' % (who, off))
+    return q64, r64
+
+
+def geometric_durations(trans, L):
+    """(q [K, L], r [K]) float64: the duration law under which the semi-Markov model IS the plain full-transition model
+    (up to the utterance's last segment, which the semi-Markov score closes): r[k] = trans[k][k], q[k][d] = (1 - r) r^(d-1)
+    for d < L and q[k][L] = r^(L-1)."""
+    L = check_max_duration('hmm.geometric_durations', L)
+    t = np.asarray(trans.detach().cpu().numpy() if isinstance(trans, torch.Tensor) else trans, dtype=np.float64)
+    if t.ndim != 2 or t.shape[0] != t.shape[1] or not t.shape[0]:
+        raise ValueError('hmm.geometric_durations: trans [K, K] is needed, not %s' % (t.shape,))
+    r = np.diag(t).copy()
+    if not np.isfinite(r).all() or (r <= 0).any() or (r >= 1).any():
+        raise ValueError('hmm.geometric_durations: every trans[k][k] must lie inside (0, 1)')
+    q = np.empty((len(r), L), dtype=np.float64)
+    q[:, :L - 1] = (1.0 - r)[:, None] * r[:, None] ** np.arange(L - 1)[None, :]
+    q[:, L - 1] = r ** (L - 1)
+    return q, r
+
+
+def duration_tables(q, r):
+    """(ld [K, L], ls [K]) float32: ld[k][i-1] = log q[k][i] for i < L, ld[k][L-1] = log(q[k][L] (1 - r[k])), ls[k] = log r[k],
+    float64 logarithms rounded once.  ValueError through check_durations: every entry is finite."""
+    q64, r64 = check_durations('hmm.duration_tables', q, r)
+    ld = np.log(q64)
+    ld[:, -1] = np.log(q64[:, -1] * (1.0 - r64))
+    return np.ascontiguousarray(ld.astype(np.float32)), np.log(r64).astype(np.float32)
+
+
+def switch_log_transitions(init, trans):
+    """(li [K], lx [K, K]) float32: li as ``log_transitions`` gives it, lx[j][k] = log(trans[j][k] / (1 - trans[j][j])) for
+    j != k -- where the chain goes GIVEN that it leaves j --, float64 from float32(init), float32(trans), rounded once.  The
+    diagonal of lx is never read and holds 0.  Where float32(trans[j][j]) is so near 1 that 1 - trans[j][j] is below 2^-100
+    (a unit the training data never leaves, its other entries at the floor), the row's off-diagonal sum stands for it: the
+    same quantity for a stochastic row, and never 0.  ValueError through check_transitions."""
+    who = 'hmm.switch_log_transitions'
+    i32, t32 = check_transitions(who, init, trans)
+    t = t32.astype(np.float64)
+    K = len(i32)
+    leave = 1.0 - np.diag(t)
+    leave = np.where(leave >= TINY, leave, np.where(np.eye(K, dtype=bool), 0.0, t).sum(axis=1))
+    with np.errstate(all='ignore'):
+        lx = np.log(t / np.where(leave > 0, leave, 1.0)[:, None])        # (leave is 0 only for K = 1, whose lx is all diagonal)
+    lx[np.arange(K), np.arange(K)] = 0.0
+    return np.log(i32.astype(np.float64)).astype(np.float32), np.ascontiguousarray(lx.astype(np.float32))
+
+
+def _check_hsmm_log_tables(who, li, lx, ld, ls, K):
+    """The host checks of the four log tables: float32 tensors of the right shapes that hold no NaN and no infinity.
+    Returns L."""
+    ok = all(isinstance(a, torch.Tensor) and a.dtype == torch.float32 for a in (li, lx, ld, ls))
+    if not ok or li.shape != (K,) or lx.shape != (K, K) or ls.shape != (K,) or ld.dim() != 2 or ld.shape[0] != K:
+        raise ValueError('%s: li [K], lx [K, K], ld [K, L] and ls [K] float32 tensors are needed (hmm.switch_log_transitions, '
+                         'hmm.duration_tables)' % who)
+    L = check_max_duration(who, int(ld.shape[1]))
+    if not all(np.isfinite(a.detach().cpu().numpy()).all() for a in (li, lx, ld, ls)):
+        raise ValueError('%s: the log tables must not hold NaN, +inf or -inf' % who)
+    return L
+
+
+def _hsmm_viterbi_launch(lib, table, off_d, len_d, n_utt, shift, A, B, c0, li, lx, ld, ls, K, L, ids, lp, nsw, ng, ws):
+    """abnu_hmm_hsmm_viterbi on checked arguments and a workspace of abnu_hmm_hsmm_viterbi_ws_bytes."""
+    T, D = table.shape
+    _lib.check(lib.abnu_hmm_hsmm_viterbi(
+        _lib.ptr(table), T, D, _lib.ptr(off_d), _lib.ptr(len_d), n_utt, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B), _lib.ptr(c0),
+        _lib.ptr(li), _lib.ptr(lx), K, _lib.ptr(ids), _lib.ptr(lp), _lib.ptr(nsw), _lib.ptr(ng), _lib.ptr(ws), ws.numel(),
+        _lib.stream(), _lib.ptr(ld), _lib.ptr(ls), L), 'abnu_hmm_hsmm_viterbi')
+
+
+def hsmm_viterbi(table, off, lens, shift, A, B, c0, li, lx, ld, ls, ids=None, want_log_prob=True):
+    """(ids [T] int32, log_prob [n_utt] float64 or None, n_switch [n_utt] int32 or None, n_good [n_utt] int32), device
+    tensors, of the semi-Markov recurrence the module docstring defines (abnu_hmm_hsmm_viterbi, one launch): ``dense_viterbi``
+    with explicit unit durations.  li, lx: ``switch_log_transitions``; ld [K, L], ls [K]: ``duration_tables``; L is ld's width.
+    Everything else as in ``dense_viterbi``."""
+    lib = _lib.load()
+    who = 'hmm.hsmm_viterbi'
+    T, D, K = _emission_shapes(who, table, shift, A, B, c0)
+    if K < 1 or K > dense_max_k():
+        raise ValueError('%s: K = %d, the kernel takes 1 .. %d (abny_hmm_dense_max_k)' % (who, K, dense_max_k()))
+    L = _check_hsmm_log_tables(who, li, lx, ld, ls, K)
+    off_h, len_h, n_utt, longest = _utt.utterance_spans(who, off, lens, T, max_len(), 'abn_hmm_max_len')
+    _utt.check_ids(who, ids, T)
+    table = _gmm._check_table(who, table)
+    _lib.require_device(shift, A, B, c0, li, lx, ld, ls)
+    ids, lp, nsw, ng = _utt.path_results(ids, T, n_utt, want_log_prob, table.device)
+    if T and n_utt and longest:
+        sizing = lambda n, m, k, d: lib.abnu_hmm_hsmm_viterbi_ws_bytes(n, m, k, d, L)
+        ws, off_d, len_d = _utt.workspace(who, sizing, off_h, len_h, longest, K, D, table.device)
+        _hsmm_viterbi_launch(lib, table, off_d, len_d, n_utt, shift, A, B, c0, li, lx, ld, ls, K, L, ids, lp, nsw, ng, ws)
+    return ids, lp, nsw, ng
+
+
+def _run_stats_launch(lib, ids, off_d, len_d, n_utt, K, L):
+    """abnu_hmm_run_stats on checked arguments: (dur, tail) from torch.empty (the entry clears them)."""
+    dur = torch.empty((K, L), dtype=torch.int64, device=ids.device)
+    tail = torch.empty(K, dtype=torch.int64, device=ids.device)
+    _lib.check(lib.abnu_hmm_run_stats(_lib.ptr(ids), ids.shape[0], _lib.ptr(off_d), _lib.ptr(len_d), n_utt, K, L, _lib.ptr(dur),
+                                      _lib.ptr(tail), _lib.stream()), 'abnu_hmm_run_stats')
+    return dur, tail
+
+
+def run_stats(ids, off, lens, K, L):
+    """(dur [K, L] int64, tail [K] int64), device tensors: the run statistics of the unit ids `ids` ([T] int32 on the device)
+    over the utterances off, lens (abnu_hmm_run_stats, one launch).  For every maximal run, over an utterance's good frames,
+    of unit k with length n: dur[k][min(n, L) - 1] += 1 and tail[k] += max(n - L, 0).  An id outside 0 .. K - 1 is a BAD
+    frame and is passed over; rows outside every utterance count nothing."""
+    lib = _lib.load()
+    who = 'hmm.run_stats'
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 1 or ids.dtype != torch.int32 or not ids.is_contiguous():
+        raise ValueError('%s: ids must be a contiguous [T] int32 tensor' % who)
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= dense_max_k():
+        raise ValueError('%s: K = %r, the kernel takes 1 .. %d (abny_hmm_dense_max_k)' % (who, K, dense_max_k()))
+    K, L = int(K), check_max_duration(who, L)
+    T = ids.shape[0]
+    off_h, len_h, n_utt, _ = _utt.utterance_spans(who, off, lens, T, max_len(), 'abn_hmm_max_len')
+    _lib.require_device(ids)
+    if not (T and n_utt):
+        return torch.zeros((K, L), dtype=torch.int64, device=ids.device), torch.zeros(K, dtype=torch.int64, device=ids.device)
+    off_d, len_d = torch.from_numpy(off_h).to(ids.device), torch.from_numpy(len_h.astype(np.int32)).to(ids.device)
+    return _run_stats_launch(lib, ids, off_d, len_d, n_utt, K, L)
+
+
+def duration_update(dur, tail, q, r, alpha=1e-3):
+    """The duration M-step of the module docstring on the host, float64: (q [K, L], r [K]) from the run statistics with the
+    pseudo-count alpha >= 0:  q[k][d] = (dur[k][d] + alpha) / (sum_d dur[k] + L alpha),
+    r[k] = (tail[k] + alpha) / (tail[k] + dur[k][L-1] + 2 alpha).  A unit without any run at alpha = 0 keeps its old law (and a
+    unit without a run of L or more its old r).  Then every q below TRANS_MIN is raised to it and the row renormalised
+    once, and r is kept inside TRANS_MIN .. DUR_TAIL_MAX = 1 - 2^-24 (below 1 as a float32 too)."""
+    who = 'hmm.duration_update'
+    old_q, old_r = check_durations(who, q, r)
+    K, L = old_q.shape
+    dur, tail = np.asarray(dur, dtype=np.float64), np.asarray(tail, dtype=np.float64)
+    if dur.shape != (K, L) or tail.shape != (K,):
+        raise ValueError('%s: dur [K, L] and tail [K] are needed for q [%d, %d]' % (who, K, L))
+    if not (isinstance(alpha, (int, float, np.floating, np.integer)) and np.isfinite(alpha) and alpha >= 0):
+        raise ValueError('%s: alpha = %r, a number >= 0 is needed' % (who, alpha))
+    if not (np.isfinite(dur).all() and np.isfinite(tail).all()) or (dur < 0).any() or (tail < 0).any():
+        raise ValueError('%s: the statistics are not finite or negative' % who)
+    den = dur.sum(axis=1) + L * alpha
+    rden = tail + dur[:, L - 1] + 2.0 * alpha
+    with np.errstate(all='ignore'):
+        new_q = np.where((den > 0)[:, None], (dur + alpha) / den[:, None], old_q)
+        new_r = np.where(rden > 0, (tail + alpha) / rden, old_r)
+    return floor_rows(new_q), np.clip(new_r, TRANS_MIN, DUR_TAIL_MAX)
+
+
 class _MixtureHmm(object):
     """What the two models over a fitted GmmPosteriorgram share: the emission tables, the corpus plumbing of transform /
     score / decode / quantize, the scaffold of the training loops and the mixture's part of the file.  A subclass supplies
@@ -784,29 +1019,30 @@ class _MixtureHmm(object):
         ll_sum, n = torch.stack([ll.sum(), ng.to(torch.float64).sum()]).cpu().tolist()
         return ll_sum / max(1.0, n)
 
-    def _decode_ids(self, corpus, min_duration=1):
+    def _decode_ids(self, corpus, min_duration=1, **how):
         """(device ids [rows] int32, DeviceCorpus or None, names or None, lens); fills last_log_prob_ / last_n_switch_ /
-        last_n_good_ / n_bad_."""
+        last_n_good_ / n_bad_.  `how`: what a subclass's ``_max_product`` takes beside the minimum duration."""
         min_duration = _utt.check_min_duration(type(self).__name__, min_duration)
         table, dc, lens = self._utterances(corpus)
         names = list(dc.names) if dc is not None else list(corpus) if isinstance(corpus, dict) else None
-        ids, lp, nsw, ng = self._max_product(table, lens, min_duration)
+        ids, lp, nsw, ng = self._max_product(table, lens, min_duration, **how)
         self.last_log_prob_, self.last_n_switch_, self.last_n_good_ = lp.cpu().numpy(), nsw.cpu().numpy(), ng.cpu().numpy()
         self.n_bad_ = int(lens.sum() - self.last_n_good_.sum())
         return ids, dc, names, lens
 
-    def decode(self, corpus, min_duration=1):
+    def decode(self, corpus, min_duration=1, **how):
         """The unit ids of the model's best path, int32, -1 for a BAD frame: {name: host array [length]} in corpus order for
         a DeviceCorpus, a dict or a file; for a [T, D] table, which is ONE utterance, the device tensor [T].  The
         subclasses' docstrings say what each one's path and ``last_*_`` are."""
-        ids, _, names, lens = self._decode_ids(corpus, min_duration)
+        ids, _, names, lens = self._decode_ids(corpus, min_duration, **how)
         return ids if names is None else _gmm._split_rows(ids.cpu().numpy(), zip(names, lens))
 
-    def quantize(self, corpus, min_duration=1):
+    def quantize(self, corpus, min_duration=1, **how):
         """Each frame replaced by the mean of its decoded component (uncentred: m + shift), [rows, D] float32 on the
         device, a BAD frame a row of zeros; for a DeviceCorpus a new DeviceCorpus with the same names, lengths and times
-        (what KMeansQuantizer.quantize gives ``ABXEvaluator(parallel='zero')``).  min_duration: as in ``decode``."""
-        ids, dc, _, _ = self._decode_ids(corpus, min_duration)
+        (what KMeansQuantizer.quantize gives ``ABXEvaluator(parallel='zero')``).  min_duration (and, for the full-transition
+        model, durations=True): as in ``decode``."""
+        ids, dc, _, _ = self._decode_ids(corpus, min_duration, **how)
         means = torch.from_numpy(self.gmm.means_.astype(np.float32)).to(ids.device)
         out = means[ids.clamp(min=0).to(torch.int64)]
         out[ids < 0] = 0.0
@@ -995,6 +1231,23 @@ class TransitionHmmPosteriorgram(_MixtureHmm):
         self.alpha = float(alpha)
         self.viterbi_log_probs = []
         self.last_n_changed_ = None
+        self.dur_ = self.dur_tail_ = None                     # q [K, L] and r [K] of the explicit durations; None: the model has none
+
+    def set_durations(self, q=None, r=None, max_duration=None):
+        """Gives the model explicit unit durations (the module docstring's semi-Markov decoder): ``dur_`` = q [K, L] and
+        ``dur_tail_`` = r [K], float64, checked as ``duration_tables`` checks them; or max_duration = L alone for the
+        geometric start ``geometric_durations(trans_, L)``, under which ``decode(durations=True)`` scores what ``decode()``
+        scores (up to the last segment's end).  ``transform``, ``score`` and ``fit`` ignore the durations."""
+        who = 'TransitionHmmPosteriorgram.set_durations'
+        if (q is None) != (r is None) or (q is None) == (max_duration is None):
+            raise ValueError('%s: either q [K, L] and r [K], or max_duration = L, is needed' % who)
+        if q is None:
+            q, r = geometric_durations(self.trans_, check_max_duration(who, max_duration))
+        q64, r64 = check_durations(who, q, r)
+        if q64.shape[0] != self.trans_.shape[0]:
+            raise ValueError('%s: q [%d, L] for a model of K = %d units' % (who, q64.shape[0], self.trans_.shape[0]))
+        self.dur_, self.dur_tail_ = q64.copy(), r64.copy()
+        return self
 
     @classmethod
     def from_sticky(cls, h, alpha=1e-3):
@@ -1022,12 +1275,28 @@ class TransitionHmmPosteriorgram(_MixtureHmm):
     def _forward_backward(self, table, lens, mode):
         return dense_forward_backward(table, _utt.starts(lens), lens, *self.device_tables(table.device), mode=mode)
 
-    def _max_product(self, table, lens, min_duration):
+    def _with_durations(self, min_duration, durations):
+        """`durations` as a bool, or ValueError: the model has none, or a min_duration > 1 came with them (host checks)."""
+        who = type(self).__name__
+        if durations and self.dur_ is None:
+            raise ValueError('%s: durations=True, but the model has no durations (set_durations, or fit_viterbi with the '
+                             'letter d)' % who)
+        if durations and _utt.check_min_duration(who, min_duration) != 1:
+            raise ValueError('%s: durations=True takes no min_duration (%d): the duration law is the model\'s own'
+                             % (who, min_duration))
+        return bool(durations)
+
+    def _max_product(self, table, lens, min_duration, durations=False):
         shift, A, B, c0, _, _ = self.device_tables(table.device)
-        li, lt = (torch.from_numpy(np.ascontiguousarray(a)).to(table.device) for a in log_transitions(self.init_, self.trans_))
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(table.device)
+        if self._with_durations(min_duration, durations):
+            li, lx = switch_log_transitions(self.init_, self.trans_)
+            ld, ls = duration_tables(self.dur_, self.dur_tail_)
+            return hsmm_viterbi(table, _utt.starts(lens), lens, shift, A, B, c0, up(li), up(lx), up(ld), up(ls))
+        li, lt = (up(a) for a in log_transitions(self.init_, self.trans_))
         return dense_viterbi(table, _utt.starts(lens), lens, shift, A, B, c0, li, lt, min_duration=min_duration)
 
-    def decode(self, corpus, min_duration=1):
+    def decode(self, corpus, min_duration=1, durations=False):
         """The unit ids of the best path (the module docstring's full-transition max-product recurrence), int32, -1 for a
         BAD frame: {name: host array [length]} in corpus order for a DeviceCorpus, a dict or a file -- what
         KMeansQuantizer.segment and StickyHmmPosteriorgram.decode return, so kmeans.unit_sequences / bitrate / segments,
@@ -1036,8 +1305,14 @@ class TransitionHmmPosteriorgram(_MixtureHmm):
         ``last_n_good_`` (int32) hold the utterances' log joint probabilities, switch counts and good-frame counts;
         ``n_bad_`` the BAD frames.  min_duration = S (an integer 1 .. 8): every unit but an utterance's last lasts at least
         S good frames (the module docstring's minimum duration of this model; with S > 1 ``last_log_prob_`` is that
-        definition's score); 1 is the recurrence without it."""
-        return super().decode(corpus, min_duration)
+        definition's score); 1 is the recurrence without it.  durations=True: the semi-Markov path under the model's own
+        duration law ``dur_`` / ``dur_tail_`` (``last_log_prob_`` is that definition's score); ValueError if the model has
+        none, or together with min_duration > 1."""
+        return super().decode(corpus, min_duration, durations=self._with_durations(min_duration, durations))
+
+    def quantize(self, corpus, min_duration=1, durations=False):
+        """``_MixtureHmm.quantize`` of the path ``decode`` with the same arguments gives."""
+        return super().quantize(corpus, min_duration, durations=self._with_durations(min_duration, durations))
 
     def _adopt_transitions(self, trans, init):
         self.trans_, self.init_ = np.array(trans, dtype=np.float64), np.array(init, dtype=np.float64)
@@ -1088,7 +1363,7 @@ class TransitionHmmPosteriorgram(_MixtureHmm):
         self._adopt_transitions(trans, init)
         return self
 
-    def fit_viterbi(self, corpus, n_iter=10, tol=1e-4, params=DENSE_PARAMS, min_duration=1, n_ranges=0):
+    def fit_viterbi(self, corpus, n_iter=10, tol=1e-4, params=DENSE_PARAMS, min_duration=1, n_ranges=0, max_duration=None):
         """Viterbi training (hard EM, segmental k-means) from the current parameters: any subset of the `m`eans,
         `v`ariances, `t`ransitions and the `i`nit (params), on a COPY of the mixture exactly as ``fit``.  Iteration i decodes
         the corpus under the current parameters (``dense_viterbi`` with min_duration) -- ``viterbi_log_probs[i]`` is the mean
@@ -1098,10 +1373,30 @@ class TransitionHmmPosteriorgram(_MixtureHmm):
         or when no id changed since the previous iteration (counted on the device; the parameters are then those of the
         last decoding).  Fills ``viterbi_log_probs``, ``n_bad_``, ``n_starved_``, ``last_n_changed_`` (the ids that
         differed from the previous iteration's; all rows in the first), ``trans_`` and ``init_``.  No T x K table is
-        allocated: two [T] id buffers and the two workspaces."""
+        allocated: two [T] id buffers and the two workspaces.
+
+        Explicit durations (the module docstring's semi-Markov decoder): with the letter `d` in params (this method only;
+        ``fit`` refuses it) or with max_duration = L, iteration i decodes with ``hsmm_viterbi``, takes ``hard_stats`` at
+        min_duration = 1 and ``run_stats`` on the same ids, still reads back once, and applies ``duration_update`` beside the
+        two updates above when `d` is named.  The start is the model's own law (``set_durations``) if its width is L or no
+        max_duration is given, otherwise ``geometric_durations(trans_, L)``; ``dur_`` and ``dur_tail_`` are filled.
+        min_duration must then be 1."""
         who = 'TransitionHmmPosteriorgram.fit_viterbi'
-        p = check_dense_params(who, params)                                        # (host checks first)
+        p = check_hsmm_params(who, params)                                         # (host checks first)
         S = _utt.check_min_duration(who, min_duration)
+        hsmm = 'd' in p or max_duration is not None
+        q = r = None
+        if hsmm:
+            if S != 1:
+                raise ValueError('%s: explicit durations take no min_duration (%d)' % (who, S))
+            if max_duration is None and self.dur_ is None:
+                raise ValueError('%s: the letter d needs max_duration = L, or a model that has durations' % who)
+            if max_duration is not None and (self.dur_ is None or self.dur_.shape[1] != check_max_duration(who, max_duration)):
+                q, r = geometric_durations(self.trans_, max_duration)
+            else:
+                q, r = self.dur_, self.dur_tail_
+            q, r = check_durations(who, q, r)
+            L = q.shape[1]
         n_ranges = _check_n_ranges(who, n_ranges)
         table, _, lens = self._utterances(corpus)
         lib = _lib.load()
@@ -1113,7 +1408,8 @@ class TransitionHmmPosteriorgram(_MixtureHmm):
         if not (T and n_utt and longest):
             raise ValueError('%s: the corpus has no frame' % who)
         g, shift64, dev, shift = self._training_copy(table.device)
-        vws, off_d, len_d = _utt.workspace(who, _dense_viterbi_sizing(lib, S), off_h, len_h, longest, K, D, table.device)
+        sizing = (lambda n, m, k, d: lib.abnu_hmm_hsmm_viterbi_ws_bytes(n, m, k, d, L)) if hsmm else _dense_viterbi_sizing(lib, S)
+        vws, off_d, len_d = _utt.workspace(who, sizing, off_h, len_h, longest, K, D, table.device)
         hws = _hard_stats_workspace(who, lib, T, n_utt, K, D, n_ranges, table.device)
         ids, lp, nsw, ng = _utt.path_results(None, T, n_utt, True, table.device)
         ids = [ids, torch.full_like(ids, -1)]                 # (two buffers: an iteration's ids are compared with the last's)
@@ -1122,15 +1418,23 @@ class TransitionHmmPosteriorgram(_MixtureHmm):
         self.viterbi_log_probs = []
         for it in range(int(n_iter)):
             A, B, _ = _gmm.score_tables(np.full(K, 1.0 / K), m, v)
-            li, lt = (dev(a) for a in log_transitions(init, trans))
             A, B, c0 = dev(A), dev(B), dev(emission_offsets(m, v))
             cur = ids[it & 1]
-            _dense_viterbi_launch(lib, table, off_d, len_d, n_utt, shift, A, B, c0, li, lt, K, cur, lp, nsw, ng, S, vws)
+            if hsmm:
+                li, lx = (dev(a) for a in switch_log_transitions(init, trans))
+                ld, ls = (dev(a) for a in duration_tables(q, r))
+                _hsmm_viterbi_launch(lib, table, off_d, len_d, n_utt, shift, A, B, c0, li, lx, ld, ls, K, L, cur, lp, nsw, ng, vws)
+            else:
+                li, lt = (dev(a) for a in log_transitions(init, trans))
+                _dense_viterbi_launch(lib, table, off_d, len_d, n_utt, shift, A, B, c0, li, lt, K, cur, lp, nsw, ng, S, vws)
             counts, sums, _ = _hard_stats_launch(lib, table, off_d, len_d, n_utt, shift, cur, K, S, n_ranges, hws)
+            runs = torch.zeros(0, dtype=torch.float64, device=table.device)
+            if hsmm:                                          # [dur | tail] behind the sums, in the same read-back
+                runs = torch.cat([t.flatten() for t in _run_stats_launch(lib, cur, off_d, len_d, n_utt, K, L)]).to(torch.float64)
             changed = (cur != ids[(it + 1) & 1]).sum().to(torch.float64) if it else torch.tensor(float(T), dtype=torch.float64,
                                                                                                  device=table.device)
             head = torch.stack([lp.sum(), ng.clamp(min=0).to(torch.float64).sum(), changed])
-            back = torch.cat([head, counts.flatten().to(torch.float64), sums.flatten()]).cpu().numpy()      # the one read-back
+            back = torch.cat([head, counts.flatten().to(torch.float64), sums.flatten(), runs]).cpu().numpy()      # the one read-back
             lp_sum, n, n_changed = back[:3].tolist()
             if n < 1:
                 raise ValueError('%s: the corpus has no good frame' % who)
@@ -1139,21 +1443,29 @@ class TransitionHmmPosteriorgram(_MixtureHmm):
             if it > 0 and (self.viterbi_log_probs[-1] - self.viterbi_log_probs[-2] < tol or n_changed == 0):
                 break
             counts_h = back[3:3 + (K + 1) * K].reshape(K + 1, K)
-            sums_h = back[3 + (K + 1) * K:].reshape(K, 2 * D + 1)
+            n_sums = K * (2 * D + 1)
+            sums_h = back[3 + (K + 1) * K:3 + (K + 1) * K + n_sums].reshape(K, 2 * D + 1)
             if mv:
                 self.n_starved_ = int((sums_h[:, 2 * D] < g.min_count).sum())
                 _, m, v, _, _ = baum_welch_update(sums_h, np.zeros(K), 0, m, v, g.gv_, g.var_floor, g.min_count, mv,
                                                   weights=np.full(K, 1.0 / K), stay=0.0)
             trans, init = transition_update(counts_h, trans, init, self.alpha, ti)
+            if 'd' in p:
+                runs_h = back[3 + (K + 1) * K + n_sums:]
+                q, r = duration_update(runs_h[:K * L].reshape(K, L), runs_h[K * L:], q, r, self.alpha)
         self._adopt(g, p, shift64, m, v)
         self._adopt_transitions(trans, init)
+        if hsmm:
+            self.dur_, self.dur_tail_ = np.array(q, dtype=np.float64), np.array(r, dtype=np.float64)
         return self
 
     # -- files ----------------------------------------------------------------------------------------------------
     def save(self, path):
-        """The mixture's file (GmmPosteriorgram.load reads it) plus trans, init and alpha."""
+        """The mixture's file (GmmPosteriorgram.load reads it) plus trans, init and alpha, and dur, dur_tail if the model has
+        durations."""
+        durations = {} if self.dur_ is None else dict(dur=self.dur_, dur_tail=self.dur_tail_)
         with open(path, 'wb') as f:
-            np.savez(f, **self._mixture_fields(), trans=self.trans_, init=self.init_, alpha=np.float64(self.alpha),
+            np.savez(f, **self._mixture_fields(), **durations, trans=self.trans_, init=self.init_, alpha=np.float64(self.alpha),
                      trans_log_likelihoods=np.asarray(self.log_likelihoods, dtype=np.float64),
                      viterbi_log_probs=np.asarray(self.viterbi_log_probs, dtype=np.float64))
 
@@ -1168,6 +1480,8 @@ class TransitionHmmPosteriorgram(_MixtureHmm):
             self.log_likelihoods = [float(v) for v in z['trans_log_likelihoods']]
             if 'viterbi_log_probs' in z.files:                                 # (files written before fit_viterbi have none)
                 self.viterbi_log_probs = [float(v) for v in z['viterbi_log_probs']]
+            if 'dur' in z.files and 'dur_tail' in z.files:                     # (files without durations load as before)
+                self.dur_, self.dur_tail_ = check_durations('%s: dur' % path, z['dur'], z['dur_tail'])
         return self
 
 
@@ -1230,6 +1544,7 @@ def main(argv=None):
     d.add_argument('out', help='.npz of name -> [T] ids, or an h5features file (when the input has times)')
     d.add_argument('--min-duration', type=int, default=1, metavar='S',
                    help='every unit lasts at least S frames (1 .. 8; default 1, no minimum)')
+    d.add_argument('--durations', action='store_true', help='decode under the explicit unit durations a full-transition model holds')
     ft = sub.add_parser('fit-trans', help='Baum-Welch of the full-transition model on FEATURES, from a saved model or mixture')
     ft.add_argument('model', help='a TransitionHmmPosteriorgram, StickyHmmPosteriorgram or GmmPosteriorgram .npz: where EM starts')
     ft.add_argument('features', help='h5features file, or an .npz of name -> [T, D]')
@@ -1242,6 +1557,9 @@ def main(argv=None):
     ft.add_argument('--viterbi', action='store_true', help='Viterbi training (hard EM on the decoded path) instead of Baum-Welch')
     ft.add_argument('--min-duration', type=int, default=1, metavar='S',
                     help='with --viterbi: train the model whose every unit lasts at least S frames (1 .. 8; default 1)')
+    ft.add_argument('--max-duration', type=int, default=None, metavar='L',
+                    help='with --viterbi: train explicit unit durations, a free law up to L frames and a geometric tail '
+                         '(2 .. 32; add the letter d to --params to learn it; untuned)')
     args = ap.parse_args(argv)
     if args.cmd == 'fit':
         check_params('python -m abnet3_amd.hmm fit', args.params)
@@ -1254,9 +1572,15 @@ def main(argv=None):
             h = TransitionHmmPosteriorgram.from_sticky(StickyHmmPosteriorgram.load(args.model), alpha=args.alpha)
         else:
             h = TransitionHmmPosteriorgram(_gmm.GmmPosteriorgram.load(args.model), stay=args.stay, alpha=args.alpha)
+        if args.max_duration is not None and not args.viterbi:
+            raise ValueError('python -m abnet3_amd.hmm fit-trans: --max-duration %d needs --viterbi (Baum-Welch ignores the '
+                             'durations)' % args.max_duration)
         if args.viterbi:
-            h.fit_viterbi(feats, args.n_iter, args.tol, args.params, min_duration=args.min_duration)
+            h.fit_viterbi(feats, args.n_iter, args.tol, args.params, min_duration=args.min_duration, max_duration=args.max_duration)
             h.save(args.out)
+            if h.dur_ is not None:
+                print('explicit durations up to L = %d frames: the modes of the units\' laws %s, mean tail stay %.4f'
+                      % (h.dur_.shape[1], (np.argmax(h.dur_, axis=1) + 1).tolist(), float(h.dur_tail_.mean())))
             print('K = %d transitions after %d iterations of Viterbi training (params %s, alpha %g, min duration %d), mean best-path '
                   'log-probability %.6f, %d ids changed in the last, %d BAD frames, %d starved, mean self-transition %.4f'
                   % (h.trans_.shape[0], len(h.viterbi_log_probs), args.params, h.alpha, args.min_duration, h.viterbi_log_probs[-1],
@@ -1290,6 +1614,12 @@ def main(argv=None):
         if dense and args.min_duration != 1:
             raise ValueError('python -m abnet3_amd.hmm decode: %s holds a full transition matrix, whose max-product path '
                              'has no minimum duration; --min-duration %d needs a sticky model' % (args.model, args.min_duration))
+        if args.durations and not (dense and h.dur_ is not None):
+            raise ValueError('python -m abnet3_amd.hmm decode: --durations needs a full-transition model that holds dur; %s has none'
+                             % args.model)
+        if args.durations:
+            model += ', explicit durations up to %d' % h.dur_.shape[1]
+            return _report_decode(h, h.decode(feats, durations=True), times, model, args.out)
         out = h.decode(feats) if dense else h.decode(feats, min_duration=args.min_duration)
         return _report_decode(h, out, times, model, args.out)
     return _report_transform(h, feats, times, args.mode, model, args.out)

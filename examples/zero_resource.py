@@ -8,7 +8,7 @@ mined pairs, and the ABX item file ("phones" = word types).
                                      [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--hmm-fit N] [--hmm-trans N] [--hmm-decode] [--no-network] [--terms] [--terms-theta T]
                                      [--prefilter] [--alignment FILE]
                                      [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P] [--kmeans-min-duration S]
-                                     [--hmm-min-duration S] [--hmm-trans-viterbi]
+                                     [--hmm-min-duration S] [--hmm-trans-viterbi] [--hmm-max-duration L]
                                      [--eskmeans] [--eskmeans-clusters 24] [--samediff]
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
@@ -194,7 +194,7 @@ def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frame
 
 
 def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=None, hmm_fit=0, hmm_decode=False, hmm_min_duration=1, hmm_trans=0,
-              hmm_trans_viterbi=False):
+              hmm_trans_viterbi=False, hmm_max_duration=None):
     """features -> GmmPosteriorgram.fit -> transform -> ABX (kl), and the search: the line main() prints.  hmm_stay (a
     number, or 'fit'): the sticky-HMM smoothed posteriorgrams beside the raw ones; they are the ones returned.  hmm_fit
     (iterations): the posteriorgrams of the Baum-Welch-trained HMM beside both; then those are returned.  hmm_decode: the
@@ -202,7 +202,9 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
     and those of the best path whose units last at least that many frames.  hmm_trans (iterations): the posteriorgrams of
     the full-transition HMM, trained from the sticky matrix, beside the raw and the sticky-smoothed ones (the returned
     posteriorgrams stay the sticky route's).  hmm_trans_viterbi: as many iterations of Viterbi training
-    (TransitionHmmPosteriorgram.fit_viterbi, with hmm_min_duration) from the same start, beside the Baum-Welch line."""
+    (TransitionHmmPosteriorgram.fit_viterbi, with hmm_min_duration) from the same start, beside the Baum-Welch line;
+    hmm_max_duration = L: that training with explicit unit durations (params 'mvtid', a free law up to L frames and a
+    geometric tail) instead of the minimum duration, and hmm_decode then adds the best path under the learned durations."""
     names = list(fb)
     keep, items = word_items(tokens)
     corpus = DeviceCorpus({k: np.asarray(fb[k], dtype=np.float32) for k in names}, times)
@@ -225,7 +227,7 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
                                                                    raw_ll, rs.error, r.error, rs.n_triplets))
         print(more)
         line += '\n' + more
-        dense = None
+        dense = timed = None
         if hmm_trans:
             w = np.maximum(g.weights_, 1e-8)                         # (a starved component: the dense model has no retired units)
             init, trans = sticky_transitions(w / w.sum(), h.stay_)
@@ -238,7 +240,19 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
             print(more)
             line += '\n' + more
             dense = d
-            if hmm_trans_viterbi:
+            if hmm_trans_viterbi and hmm_max_duration:
+                timed = TransitionHmmPosteriorgram(g, trans, init).fit_viterbi(corpus, n_iter=int(hmm_trans), tol=-np.inf, params='mvtid',
+                                                                               max_duration=int(hmm_max_duration))
+                timed.decode(corpus, durations=True)
+                more = ('full-transition HMM Viterbi training with explicit durations (%d iterations, L = %d and alpha %g untuned): '
+                        'best-path score per frame %.3f -> %.3f, %d ids changed in the last iteration, %d switches, modes of the '
+                        'units\' duration laws %s' % (len(timed.viterbi_log_probs), timed.dur_.shape[1], timed.alpha, timed.viterbi_log_probs[0],
+                                                      float(timed.last_log_prob_.sum()) / max(int(timed.last_n_good_.sum()), 1),
+                                                      timed.last_n_changed_, int(timed.last_n_switch_.sum()),
+                                                      (np.argmax(timed.dur_, axis=1) + 1).tolist()))
+                print(more)
+                line += '\n' + more
+            elif hmm_trans_viterbi:
                 hv = TransitionHmmPosteriorgram(g, trans, init).fit_viterbi(corpus, n_iter=int(hmm_trans), tol=-np.inf,
                                                                             min_duration=hmm_min_duration)
                 hv.decode(corpus, min_duration=hmm_min_duration)
@@ -261,7 +275,7 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
             line += '\n' + more
             h = t
         if hmm_decode:
-            more = hmm_decode_lines(h, corpus, items, hmm_min_duration, dense)
+            more = hmm_decode_lines(h, corpus, items, hmm_min_duration, dense, timed)
             print(more)
             line += '\n' + more
     if qbe:
@@ -269,12 +283,13 @@ def gmm_route(fb, times, tokens, n_components, qbe, want_post=False, hmm_stay=No
     return (line, post) if want_post else line
 
 
-def hmm_decode_lines(h, corpus, items, min_duration=1, dense=None):
+def hmm_decode_lines(h, corpus, items, min_duration=1, dense=None, timed=None):
     """The units of the HMM's best path (StickyHmmPosteriorgram.decode) beside the frame-wise mixture argmax (stay = 0
     through the same call): bitrate with runs merged, switches, and ABX over the quantised frames.  min_duration > 1 adds
     the best path whose units last at least that many frames; dense (a trained TransitionHmmPosteriorgram) the best path
     under the full transition matrix (TransitionHmmPosteriorgram.decode), and with min_duration > 1 that model's best path
-    whose units last at least that many frames as well."""
+    whose units last at least that many frames as well; timed (a TransitionHmmPosteriorgram that has durations) the best
+    path under its explicit unit durations (decode(durations=True))."""
     seconds = 0.01 * corpus.total
     out = []
     routes = [('sticky-HMM Viterbi units (stay %.4f)' % h.stay_, h, 1),
@@ -285,8 +300,10 @@ def hmm_decode_lines(h, corpus, items, min_duration=1, dense=None):
         if min_duration > 1:
             routes.insert(1, ('full-transition HMM Viterbi units, at least %d frames per unit' % min_duration, dense, min_duration))
         routes.insert(1, ('full-transition HMM Viterbi units (mean self-transition %.4f)' % float(np.diag(dense.trans_).mean()), dense, None))
+    if timed is not None and timed.dur_ is not None:
+        routes.insert(1, ('full-transition HMM Viterbi units under explicit durations (L = %d)' % timed.dur_.shape[1], timed, 'durations'))
     for label, model, S in routes:
-        kw = {} if S is None else {'min_duration': S}
+        kw = {} if S is None else {'durations': True} if S == 'durations' else {'min_duration': S}
         ids = model.decode(corpus, **kw)
         r = ABXEvaluator(items, model.quantize(corpus, **kw), parallel='zero').run('within')
         out.append('%s: %.0f bit/s with runs merged, %d switches, log-probability per frame %.3f; ABX error quantised %.2f %% '
@@ -365,6 +382,9 @@ def main():
     ap.add_argument('--hmm-trans-viterbi', action='store_true',
                     help='with --hmm-trans N: also N iterations of Viterbi training (hard EM on the decoded path) from the same start, '
                          'with the minimum duration of --hmm-min-duration; nothing is tuned on real speech')
+    ap.add_argument('--hmm-max-duration', type=int, default=None, metavar='L',
+                    help='with --hmm-trans-viterbi: train explicit unit durations (a free law up to L frames, 2 .. 32, and a geometric '
+                         'tail) instead of the minimum duration; --hmm-decode then decodes under them; L is untuned')
     ap.add_argument('--hmm-decode', action='store_true',
                     help='with --hmm-stay / --hmm-fit: the discrete units of the HMM\'s best path (Viterbi): bitrate, switches and ABX '
                          'of the quantised frames, beside the frame-wise mixture argmax; nothing is tuned on real speech')
@@ -395,6 +415,8 @@ def main():
         ap.error('--hmm-trans trains the full-transition HMM over the mixture of --gmm, with --gmm-components <= 128')
     if args.hmm_trans_viterbi and not args.hmm_trans:
         ap.error('--hmm-trans-viterbi trains the model of --hmm-trans N')
+    if args.hmm_max_duration is not None and not args.hmm_trans_viterbi:
+        ap.error('--hmm-max-duration belongs to --hmm-trans-viterbi')
     if args.hmm_decode and args.hmm_stay is None and not args.hmm_fit:
         ap.error('--hmm-decode decodes the HMM of --hmm-stay or --hmm-fit')
     esk_k = args.eskmeans_clusters if args.eskmeans else None
@@ -412,7 +434,7 @@ def main():
     if args.gmm:
         gmm_line, post = gmm_route(fb, times, tokens, args.gmm_components, args.qbe, want_post=True, hmm_stay=args.hmm_stay, hmm_fit=args.hmm_fit, hmm_decode=args.hmm_decode,
                                    hmm_min_duration=args.hmm_min_duration, hmm_trans=args.hmm_trans,
-                                   hmm_trans_viterbi=args.hmm_trans_viterbi)
+                                   hmm_trans_viterbi=args.hmm_trans_viterbi, hmm_max_duration=args.hmm_max_duration)
     if args.no_network:
         if not (args.gmm or args.kmeans):
             ap.error('--no-network leaves nothing to do without --gmm or --kmeans')

@@ -2,7 +2,8 @@
  *
  * The entries below carry the prefix abnx_ (the minimum unit duration of the max-product decoders), abny_ (the HMM with
  * a full transition matrix), abnz_ (that model's max-product path), abnw_ (that path with a minimum unit duration) or abnv_
- * (the hard statistics of that model's Viterbi training) and are
+ * (the hard statistics of that model's Viterbi training) or abnu_ (explicit unit durations: the semi-Markov decoder and its
+ * run statistics, ledger abnet3_amd._lib.NEXT6_SYMBOLS with tests/test_gpu_hmm_hsmm.py) and are
  * exported beside those of abnet3_hip.h, whose conventions they follow (extern "C", plain pointers and sizes, the ABN_E_*
  * return codes, abn_last_error, every refusal before any launch).
  * They do not change ABN_ABI_VERSION.  A later change folds them into abnet3_hip.h under their abn_ names, bumps the
@@ -178,6 +179,51 @@ int64_t abnv_hmm_hard_stats_ws_bytes(int64_t T, int64_t n_utt, int64_t K, int64_
 int abnv_hmm_hard_stats(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
                         const float* shift, const int32_t* ids, int64_t K, int32_t min_duration, int n_ranges,
                         int64_t* counts, double* sums, int32_t* n_good, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- Explicit unit durations: a hidden semi-Markov decoder over that model's units (csrc/hmm_hsmm.hip) -------------------
+ * Prefix abnu_; ledger abnet3_amd._lib.NEXT6_SYMBOLS with tests/test_gpu_hmm_hsmm.py.  abnet3_amd/hmm.py states the
+ * definition, tests/hmm_hsmm_np.py restates it.  abnz_hmm_dense_viterbi with lx [K][K] in place of lt and three more
+ * arguments at the end: ld [K][L], ls [K] and L = 2 .. abnu_hmm_hsmm_max_duration() (32).  Unit k has the duration law
+ *     p_k(d) = q[k][d] for d < L,   p_k(d) = q[k][L] (1 - r[k]) r[k]^(d - L) for d >= L
+ * and the tables are float32 logarithms formed on the host (abnet3_amd.hmm.duration_tables, switch_log_transitions; the
+ * kernel takes no logarithm, the caller guarantees finite entries):  ld[k][i-1] = log q[k][i] for i < L,
+ * ld[k][L-1] = log(q[k][L] (1 - r[k])),  ls[k] = log r[k],  lx[j][k] = log(trans[j][k] / (1 - trans[j][j])) for j != k (the
+ * diagonal of lx is never read), li as before.  Good frames only (BAD frames get id -1 and are passed over; durations count
+ * good frames).  A path is a sequence of segments (k_i, n_i), k_i != k_{i+1}, n_i >= 1, and its score is the sum of the frames'
+ * scores + li[k_1] + lx[k_{i-1}][k_i] for each later segment + log p_{k_i}(n_i) for EVERY segment, the last one included (it
+ * is treated as complete).  Recurrence, fp32, every operation one rounded add or a compare; V[k][1 .. L] the normalised
+ * previous values, state i = "the current segment is i frames long", state L = "L or more":
+ *     first good frame:  U[k][1] = s[k] + li[k], every other state -inf
+ *     later good frames: x[j] = max_i (V[j][i] + ld[j][i]),  xi[j] = the lowest i attaining it (strict, ascending i)
+ *                        ent[k] = max over j != k of (x[j] + lx[j][k]),  bp[k] = the lowest such j (strict, ascending j)
+ *                        U[k][1] = s[k] + ent[k];   U[k][i] = s[k] + V[k][i-1] for 1 < i < L
+ *                        a = V[k][L] + ls[k],  st = a > V[k][L-1] (strict),  U[k][L] = s[k] + (st ? a : V[k][L-1])
+ *     every good frame:  N_t = max U,  V = U - N_t,  log_prob += N_t (float64, frame order)
+ *     after the last:    F = max (V[k][i] + ld[k][i]), final = the lowest k, then the lowest i, attaining it;  log_prob += F
+ * Backwards from (k, i) at frame t: i == L and st set -> (k, L); else i > 1 -> (k, i-1); else -> (bp[k], xi[bp[k]] as recorded
+ * at frame t), one switch.  Outputs, limits and the treatment of refused utterances are abnz_hmm_dense_viterbi's.
+ * Workspace: abnu_hmm_hsmm_viterbi_ws_bytes(n_utt, max_len, K, D, L) bytes, the same for every L: min(n_utt, 256) regions of
+ * 128 x 128 x 4 + max_len x (2 K' + 1) bytes rounded up to 256, K' = K rounded up to 16, 32, 64 or 128 (the slab, a
+ * backpointer byte with the stay bit and an xi byte per frame and unit, a BAD byte per frame); 16-byte aligned, -1 with
+ * abn_last_error for refused sizes; it need not be cleared.  Refusals are abnz_hmm_dense_viterbi's, in its order, with L
+ * outside 2 .. abnu_hmm_hsmm_max_duration(): ABN_E_ARG behind the null pointers and ahead of the workspace.
+ *
+ * abnu_hmm_run_stats: from unit ids [T] int32 the statistics that train q and r.  A frame is good if 0 <= ids[t] < K, every
+ * other id is passed over.  For every maximal run, over the good frames of one utterance, of unit k with length n:
+ *     dur[k][min(n, L) - 1] += 1   (int64 [K][L]),    tail[k] += max(n - L, 0)   (int64 [K]).
+ * Nothing connects two utterances; rows outside every utterance count nothing; an utterance outside 0 .. T or longer than
+ * abn_hmm_max_len() adds nothing.  Integer arithmetic only: the same counts for any grid and any order of the utterances.
+ * dur and tail are cleared by the entry (two memsets, one launch).  Refusals, before any launch: T, n_utt or K < 1:
+ * ABN_E_ARG; K beyond abny_hmm_dense_max_k(): ABN_E_UNSUPPORTED; null pointers, L out of range: ABN_E_ARG. */
+int32_t abnu_hmm_hsmm_max_duration(void);  /* host */
+int64_t abnu_hmm_hsmm_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D, int32_t L);   /* host */
+int abnu_hmm_hsmm_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
+                          const float* shift, const float* A, const float* B, const float* c0,
+                          const float* li, const float* lx, int64_t K,
+                          int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good,
+                          void* ws, int64_t ws_bytes, void* stream, const float* ld, const float* ls, int32_t L);
+int abnu_hmm_run_stats(const int32_t* ids, int64_t T, const int64_t* off, const int32_t* len, int64_t n_utt, int64_t K,
+                       int32_t L, int64_t* dur, int64_t* tail, void* stream);
 
 #ifdef __cplusplus
 }
