@@ -429,9 +429,10 @@ __device__ __forceinline__ float packed_inv(const char* __restrict__ image, int 
 // the compiler counts their vmcnt itself, and -- unlike plain loads, which InstCombine sinks through the loop's phi
 // right in front of their MFMAs -- they stay where the pipeline puts them, PL_DEPTH steps ahead.
 // A chain keeps ONE ring through its layers (rs spans the whole packed image, offsets are relative to it): where the
-// next layer gives the wave the same share (two blocks, all steps), the last PL_DEPTH refills of a layer fetch the
-// next layer's first steps instead of repeats nobody reads -- they are in flight through the epilogue, OLDER than its
-// image stores, so the next k-loop starts without a round trip (`filled`).
+// next layer gives the wave the same share (two blocks, all steps), the last PL_DEPTH steps of a layer -- which have
+// nothing of their own layer left to fetch and otherwise issue no load at all -- fetch the next layer's first steps:
+// they are in flight through the epilogue, OLDER than its image stores, so the next k-loop starts without a round
+// trip (`filled`).
 // (measured at C2, fp16 x 2: 0.1851-0.1866 ms / step with the hand-over against 0.1848-0.1850 without -- the k-loops
 // are bound by what the 32 CUs of an XCD pull from its L2, a round trip less per layer changes nothing, and the ring
 // held through the epilogue spills: off unless built with -DPL_HANDOVER_ON)
@@ -459,7 +460,7 @@ __device__ __forceinline__ void ring_open(WeightRing<NP>& ring, const char* base
     ring.filled = false;
 }
 
-// acc[j] += block j x img over my_steps steps (a multiple of PL_DEPTH).  wv[j]: byte offset (from the ring's base) of
+// acc[j] += block j x img over my_steps steps (a multiple of PL_DEPTH, at least PL_DEPTH).  wv[j]: byte offset (from the ring's base) of
 // block j's first step for this lane; dnext[j] (wave-uniform): what to add to reach the block the wave takes in the
 // next layer (chain_next), whose first PL_DEPTH steps the ring holds on return.
 template <int NP, int BPW>
@@ -492,7 +493,11 @@ __device__ __forceinline__ void ring_kloop(f32x16* acc, WeightRing<NP>& ring, co
     __shared__ int pl_prog[PL_WAVES];
     const int my_wave = threadIdx.x >> 6;
 #endif
-    for (int s0 = 0; s0 < my_steps; s0 += PL_DEPTH) {
+    // PL_DEPTH steps from s0 on.  The main groups refill each slot for step s + PL_DEPTH; the layer's last group (TAIL)
+    // has nothing of this layer left to fetch: it refills only for a hand-over (chain_next: the next layer's step i),
+    // and its last step reads no further activation fragment.
+    auto group = [&](int s0, auto tail) {
+        constexpr bool TAIL = decltype(tail)::value;
 #if PL_THROTTLE_LAG > 0
         {
             if (lane == 0) pl_prog[my_wave] = s0;
@@ -515,9 +520,10 @@ __device__ __forceinline__ void ring_kloop(f32x16* acc, WeightRing<NP>& ring, co
             // (the three regions are fenced: left alone, the machine scheduler issues a refill before
             // the slot's last MFMA -- a second register set and copies that wait for the loads at the
             // loop's end -- or gathers all refills there)
-            const int s1 = s + 1 < my_steps ? s + 1 : s;
+            if (!TAIL || i + 1 < PL_DEPTH) {
 #pragma unroll
-            for (int pl = 0; pl < NP; ++pl) af[(i + 1) & 1][pl] = *reinterpret_cast<const bf16x8*>(ab + (s1 * NP + pl) * 1024);
+                for (int pl = 0; pl < NP; ++pl) af[(i + 1) & 1][pl] = *reinterpret_cast<const bf16x8*>(ab + ((s + 1) * NP + pl) * 1024);
+            }
             __builtin_amdgcn_sched_barrier(0);
             const bf16x8* a = af[i & 1];
             // smallest terms first (gemm_f32.h); the blocks alternate so that consecutive MFMAs are independent
@@ -531,18 +537,20 @@ __device__ __forceinline__ void ring_kloop(f32x16* acc, WeightRing<NP>& ring, co
 #pragma unroll
             for (int j = 0; j < BPW; ++j) asm volatile("" : "+v"(acc[j]) :: "memory");
             __builtin_amdgcn_sched_barrier(0);
-            // refill the slot for step s + PL_DEPTH; past this layer's last step: the next layer's step i (chain_next),
-            // else a repeat nobody reads
-            const bool past = s + PL_DEPTH >= my_steps;
+            if (!TAIL || chain_next) {
 #pragma unroll
-            for (int j = 0; j < BPW; ++j) {
-                const int so = past ? (chain_next ? dnext[j] + i * (NP * 1024) : (my_steps - 1) * (NP * 1024)) : (s + PL_DEPTH) * (NP * 1024);
+                for (int j = 0; j < BPW; ++j) {
+                    const int so = TAIL ? dnext[j] + i * (NP * 1024) : (s + PL_DEPTH) * (NP * 1024);
 #pragma unroll
-                for (int pl = 0; pl < NP; ++pl) ring.wq[i][j][pl] = __builtin_amdgcn_raw_buffer_load_b128(rs, wv[j], so + pl * 1024, 0);
+                    for (int pl = 0; pl < NP; ++pl) ring.wq[i][j][pl] = __builtin_amdgcn_raw_buffer_load_b128(rs, wv[j], so + pl * 1024, 0);
+                }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-    }
+    };
+    int s0 = 0;
+    for (; s0 + PL_DEPTH < my_steps; s0 += PL_DEPTH) group(s0, std::false_type{});
+    group(s0, std::true_type{});
 #if PL_THROTTLE_LAG > 0
     if (lane == 0) pl_prog[my_wave] = 1 << 20;          // (done: nobody waits for this wave)
 #endif
