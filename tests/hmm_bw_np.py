@@ -44,7 +44,7 @@ def forward_backward(logn, bad, w32, rho, dtype=np.float64):
     with np.errstate(all='ignore'):
         lg = logn[good]
         m = np.where(w32 > 0, lg, dt(-np.inf)).max(axis=1)
-        bt = np.exp(lg - m[:, None])
+        bt = np.where(w32 > 0, np.exp(lg - m[:, None]), dt(0))
         n = len(good)
         ahat, c = np.zeros((n, K), dtype=dtype), np.zeros(n, dtype=dtype)
         for i in range(n):

@@ -47,7 +47,7 @@ def forward_backward(logn, bad, w32, rho, dtype=np.float64, smooth=True):
             s = dt(0)
             u = np.zeros(K, dtype=dtype)
             for k in range(K):
-                bt[t, k] = np.exp(dt(logn[t, k] - mt))
+                bt[t, k] = np.exp(dt(logn[t, k] - mt)) if live[k] else dt(0)    # (the kernel's rule: no inf x 0 at a far emission)
                 pred = w[k] if prev is None else dt(dt(r * ahat[prev, k]) + dt(omr * w[k]))
                 u[k] = dt(bt[t, k] * pred)
                 s = dt(s + u[k])
@@ -139,7 +139,7 @@ def forward_backward_fast(logn, bad, w32, rho, smooth=True, dtype=np.float64):
     with np.errstate(all='ignore'):
         lg = logn[good]
         m = np.where(w32 > 0, lg, dt(-np.inf)).max(axis=1)
-        bt = np.exp(lg - m[:, None])
+        bt = np.where(w32 > 0, np.exp(lg - m[:, None]), dt(0))    # (0 at weight 0, as in the kernel: no inf x 0 at a far emission)
         n = len(good)
         ahat, c = np.zeros((n, K), dtype=dtype), np.zeros(n, dtype=dtype)
         for i in range(n):
