@@ -1,21 +1,16 @@
 // hmm_dense.hip -- forward-backward of the HMM with a full K x K transition matrix over a mixture's components
 // (abny_hmm_dense_forward_backward) and the expected transition counts of its Baum-Welch step.
-// abnet3_amd/hmm.py states the definition; DESIGN.md section 3.4c6 the shape.  The host side (workspace geometry, checks)
-// is utt_chain.h's, shared with the sticky kernels of hmm.hip and kmeans.hip.
+// abnet3_amd/hmm.py states the definition; DESIGN.md section 3.4c6 the shape.  The launch shape, the score block's logN half,
+// the matrix in LDS and the launcher are hmm_dense.h's, described there; workspace geometry and checks are utt_chain.h's.
 //
-// hmm_fb_kernel's twin (hmm.hip): one launch for the corpus, persistent workgroups that loop over the utterances
-// (u = blockIdx.x, + gridDim.x, ...: a static assignment), a slab of 128 frames x K emission scores from the mixture's own
-// fp32 MFMA tile (gmm_tile.h, c0 as the third table: the sticky kernel's bits), rewritten in place as bt = exp(logN - m_t),
-// then one sequential step per frame and sweep.  `post` is the store of ahat between the sweeps; c_t per frame goes to the
-// workspace.  What is new:
-//   * the transition matrix lives in LDS for the whole launch, behind the operand tiles: [KC][KC + 1] fp32, KC the
-//     capacity the kernel is instantiated with (16, 32, 64, 128), zero past K.  The forward step reads a column slice
-//     trans[j0 .. j0 + SW - 1][k] with the lanes over k: consecutive dwords, conflict-free at any stride.  The backward
-//     step reads a row slice trans[j][k0 .. k0 + SW - 1] with the lanes over j: KC + 1 dwords apart, and KC + 1 is odd, so
-//     the 32 lanes of a ds_read_b32 group fall on 32 different banks.
-//   * the step is a KC x KC product over 256 threads: thread t has `own` = t % KC (k forward, j backward) and the slice
-//     sl = t / KC of SW = KC^2 / 256 indices of the other side; the NS = 256 / KC partial sums go through LDS and are added
-//     slice 0 first.  c_t is ONE sum reduction (DPP inside the wave, one LDS exchange, w0 + w1 + w2 + w3).
+// hmm_fb_kernel's twin (hmm.hip): the slab of a block is rewritten in place as bt = exp(logN - m_t) (the sticky kernel's
+// bits), then one sequential step per frame and sweep.  `post` is the store of ahat between the sweeps; c_t per frame goes
+// to the workspace.  What is new:
+//   * the transition matrix is zero past K.  The forward step reads a column slice trans[j0 .. j0 + SW - 1][k] with the
+//     lanes over k: consecutive dwords.  The backward step reads a row slice trans[j][k0 .. k0 + SW - 1] with the lanes over
+//     j: KC + 1 dwords apart, 32 different banks for the 32 lanes of a ds_read_b32 group.
+//   * own is k forward and j backward; the NS partial sums are added slice 0 first.  c_t is ONE sum reduction (DPP inside
+//     the wave, one LDS exchange, w0 + w1 + w2 + w3).
 //   * G[j][k] += ahat_p[j] e_t[k] is a rank-one update per transition, off the chain: thread t owns the SW cells
 //     (own, sl SW + c) in registers (64 at KC = 128), adds over a block of at most 128 frames in fp32 and then into its own
 //     cells of the workgroup's float64 slab in the workspace (cell c of thread t at [c][t]: a coalesced row per c; behind
@@ -23,15 +18,9 @@
 //     launch (hmm_dense_stats_kernel) adds the workgroups' slabs in workgroup order and applies xi = trans o G once.
 // No floating-point atomic; nothing of an utterance's results depends on the grid or on its neighbours, and the statistics
 // depend on the grid only through min(n_utt, 256).
-#include "common.h"
-#include "gemm_f32.h"
-#include "gmm_tile.h"
 #include "fixed_sum.h"
-#include "utt_chain.h"
 #include "hmm_dense.h"
 #include "../../include/abnet3_hip_next.h"
-
-#include <math.h>
 
 namespace abn {
 
@@ -48,39 +37,15 @@ struct HmmDenseP {
     int ks, cap;                            // slab row stride (floats), frames the region holds
 };
 
-// The block of frames m0 .. m0 + nf - 1: BAD flags, the bt slab and m_t (hmm_block_scores of hmm.hip with every
-// component live: the same tile, the same max, the same expf).  Ends behind a barrier.
+// The block of frames m0 .. m0 + nf - 1: hd_logn_block, then the slab rewritten as bt and m_t (hmm_block_scores of hmm.hip
+// with every component live: the same tile, the same max, the same expf).  Ends behind a barrier.
 __device__ __forceinline__ void hd_block_scores(const HmmDenseP& p, int m0, int nf, float* smem, float* slab, int* bad_s,
                                                 float* mt_s)
 {
-    float* const As = smem;
-    float* const Bs = smem + 2 * GmTile::floats;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ks = p.ks;
     const GmmP& gp = p.g;
-    if (t < GM_B) {
-        bool bad = false;
-        if (t < nf)
-            for (int d = 0; d < gp.D; ++d) {
-                const float xc = gp.x[(int64_t)(m0 + t) * gp.D + d] - gp.shift[d];
-                bad |= !__builtin_isfinite(xc * xc);
-            }
-        bad_s[t] = bad;
-    }
-    {
-        f32x16 acc[2][2];                                             // (K <= 128: one tile of components)
-        gmm_score_tile(gp, m0, 0, As, Bs, acc);
-        const int col_l = lane & 31, rsub = 4 * (lane >> 5);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    slab[(int64_t)(wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + rsub) * ks + wn0 + 32 * j + col_l] = acc[i][j][r];
-    }
-    __syncthreads();                                                  // the slab is this workgroup's own
+    hd_logn_block(gp, m0, nf, smem, slab, ks, bad_s);
     for (int f = wave; f < nf; f += 4) {                              // wave w takes frames w, w + 4, ...: lanes over k
         float* const row = slab + (int64_t)f * ks;
         float m = -INFINITY;
@@ -118,10 +83,7 @@ __global__ __launch_bounds__(256) void hmm_dense_kernel(HmmDenseP p)
     float* const cw = reinterpret_cast<float*>(base + (int64_t)sizeof(float) * GM_B * ks + hd_stats_bytes(KC));
     const bool want_stats = p.want_stats != 0;
 
-    for (int i = t; i < KC * TS; i += 256) {
-        const int j = i / TS, k = i % TS;
-        tr_s[i] = (j < K && k < K) ? p.trans[j * K + k] : 0.0f;
-    }
+    hd_load_matrix<KC>(tr_s, p.trans, K, 0.0f, false);
     if (want_stats) {                                                 // this thread's own cells
 #pragma unroll
         for (int c = 0; c < SW; ++c) gs[c * 256 + t] = 0.0;
@@ -134,7 +96,7 @@ __global__ __launch_bounds__(256) void hmm_dense_kernel(HmmDenseP p)
     for (int u = (int)blockIdx.x; u < p.n_utt; u += (int)gridDim.x) {
         const int64_t o = p.off[u];
         const int L = p.len[u];
-        if (o < 0 || L < 0 || o + L > p.g.T || L > p.cap) {          // (uniform) nothing of this utterance is touched
+        if (hd_out_of_range(o, L, p.g.T, p.cap)) {                    // (uniform) nothing of this utterance is touched
             if (t == 0) {
                 p.loglik[u] = NAN;
                 p.n_good[u] = -1;
@@ -302,14 +264,6 @@ extern "C" int64_t abny_hmm_dense_ws_bytes(int64_t n_utt, int64_t max_len, int64
                           K >= 1 && K <= HD_MAX_K ? hd_stats_bytes(hd_kc_for(K)) : 0);
 }
 
-template <int KC>
-static void hd_launch(const HmmDenseP& p, int grid, hipStream_t st)
-{
-    static bool attr_set[16] = {};
-    if (first_use_on_device(attr_set)) chain_opt_in(reinterpret_cast<const void*>(hmm_dense_kernel<KC>), hd_lds_bytes(KC));
-    hipLaunchKernelGGL(hmm_dense_kernel<KC>, dim3((unsigned)grid), dim3(256), hd_lds_bytes(KC), st, p);
-}
-
 extern "C" int abny_hmm_dense_forward_backward(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len,
                                                int64_t n_utt, const float* shift, const float* A, const float* B,
                                                const float* c0, const float* init, const float* trans, int64_t K, int mode,
@@ -335,10 +289,10 @@ extern "C" int abny_hmm_dense_forward_backward(const float* x, int64_t T, int64_
     p.ws = a.ws; p.per_wg = a.per_wg;
     p.ks = a.ks; p.cap = a.cap;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (kc == 16) hd_launch<16>(p, hw.grid, st);
-    else if (kc == 32) hd_launch<32>(p, hw.grid, st);
-    else if (kc == 64) hd_launch<64>(p, hw.grid, st);
-    else hd_launch<128>(p, hw.grid, st);
+    hd_for_kc(kc, [&](auto c) {
+        constexpr int KC = decltype(c)::value;
+        hd_launch<hmm_dense_kernel<KC>, KC>(p, hw.grid, st);
+    });
     ABN_CHECK_LAUNCH(what);
     if (stats) {
         const int cells = (int)((K + 1) * K);

@@ -1,39 +1,29 @@
 // hmm_dense_vit.hip -- the max-product path of the HMM with a full K x K transition matrix (abnz_hmm_dense_viterbi).
-// abnet3_amd/hmm.py states the definition, tests/hmm_dense_vit_np.py restates it; DESIGN.md section 3.4c7 the shape.  The
-// host side (workspace geometry, checks) is utt_chain.h's.  Behind it the same path with a minimum unit duration
-// (hmm_dense_dur_kernel: abnw_hmm_dense_viterbi_dur), which shares the score phase and the launch shape.
+// abnet3_amd/hmm.py states the definition, tests/hmm_dense_vit_np.py restates it; DESIGN.md section 3.4c7 the shape.  Behind
+// it the same path with a minimum unit duration (hmm_dense_dur_kernel: abnw_hmm_dense_viterbi_dur).  The launch shape, the
+// score block, the matrix load, the refusal, the id and result writes and the host side are hmm_dense.h's, described there;
+// workspace geometry and checks are utt_chain.h's.  The entry maximum, the key reduction and the plane copies stand in
+// both kernels' own text: as shared functions they measured 1 % slower in each kernel at one capacity (the figures are
+// beside the text).
 //
-// hmm_dense_kernel's launch shape (hmm_dense.hip): one launch for the corpus, persistent workgroups that loop over the
-// utterances (u = blockIdx.x, + gridDim.x, ...: a static assignment), a slab of 128 frames x K raw scores logN from the
-// mixture's fp32 MFMA tile (gmm_tile.h, c0 as the third table; no exp, no m_t) in the workgroup's region of the workspace,
-// then one sequential step per good frame.  The log transitions live in LDS for the whole launch behind the operand tiles:
-// [KC][KC + 1] fp32, -inf past K.  What the sticky decoders (hmm.hip) cannot do and this kernel does:
+// hmm_dense_vit_kernel: one sequential step per good frame over the log transitions in LDS (-inf past K).  What the sticky
+// decoders (hmm.hip) cannot do and this kernel does:
 //   * a true argmax over j for every (frame, k): thread t has own = t % KC (k) and the slice sl = t / KC of SW = KC^2 / 256
 //     consecutive j; it takes the max of W[j] + lt[j][own] over its slice with a strict compare in ascending j (the lowest
 //     j on ties), the NS = 256 / KC partial (value, j) pairs go through LDS and the threads t < KC combine them slice 0
 //     first, again strictly: the lowest j of the maximum, and its value.
 //   * W is not stored: the previous frame's u[j] stays in LDS and every reader takes W[j] = u[j] - M itself, M in a
-//     register (the same rounded subtraction, the same bits), which saves the frame a third barrier.  u is kept by
-//     parity, so a frame has two barriers: behind the partial pairs and behind the wave keys.
+//     register, which saves the frame a third barrier.  u is kept by parity, so a frame has two barriers: behind the
+//     partial pairs and behind the wave keys.
 //   * M and its lowest index -- at the last good frame the final state -- are ONE 64-bit key max-reduction (vit_wave.h).
-//   * a backpointer byte per (frame, k).  A block's bytes [128][KC] are collected in LDS over the dead operand tiles and go
-//     to the workspace as whole dwords from all 256 threads when the block is done (the utterance's last block stays in
-//     LDS).  The traceback takes the blocks last to first, stages each one in LDS the same way, lets one lane chase the
-//     bytes there, and writes the block's ids coalesced.  A BAD frame is marked by 0xFF in its first byte (j < 128); the
-//     first good frame's bytes are bp[k] = k, so the walk counts no switch there.
+//   * a backpointer byte per (frame, k): one plane.  A BAD frame is marked by 0xFF in its first byte (j < 128); the first
+//     good frame's bytes are bp[k] = k, so the walk counts no switch there.
 // Padding never wins: lt is -inf outside K x K and u is -inf past K (written once, never by an owner), so a padded
 // candidate is -inf + -inf = -inf and loses every strict compare against slice 0's j = 0; threads with own >= K put no
 // key into the reduction (0 is below every key of a float).  No floating-point atomic, fixed orders throughout; nothing of
 // an utterance's results depends on the grid or on its neighbours.
-#include "common.h"
-#include "gemm_f32.h"
-#include "gmm_tile.h"
-#include "utt_chain.h"
-#include "vit_wave.h"
 #include "hmm_dense.h"
 #include "../../include/abnet3_hip_next.h"
-
-#include <math.h>
 
 namespace abn {
 
@@ -41,53 +31,10 @@ constexpr unsigned char HDV_BAD = 0xFF;    // a BAD frame's first backpointer by
 static_assert(HD_MAX_K <= 128, "a backpointer is one byte and 0xFF marks a BAD frame");
 static_assert((size_t)GM_B * HD_MAX_K <= GM_TILE_BYTES, "a block's backpointers fit over the operand tiles");
 
-struct HmmDenseVitP {
-    GmmP g;                                 // x, shift, A, B, c = c0, T, K, D, tiles_k: a kernel argument, as in hmm.hip
-    const float* li; const float* lt;
-    const int64_t* off; const int* len;
-    int n_utt;
-    int* ids; double* log_prob; int* n_switch; int* n_good;
-    char* ws; int64_t per_wg;               // bytes of a workgroup's region
-    int ks, cap;                            // slab row stride (floats), frames the region holds
-};
-
-// The block of frames m0 .. m0 + nf - 1: BAD flags and the score tile logN into the slab (hmm_vit_scores of hmm.hip with
-// one tile of components).  Ends behind a barrier.
-__device__ __forceinline__ void hdv_block_scores(const GmmP& gp, int m0, int nf, float* smem, float* slab, int ks, int* bad_s)
-{
-    float* const As = smem;
-    float* const Bs = smem + 2 * GmTile::floats;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
-    if (t < GM_B) {
-        bool bad = false;
-        if (t < nf)
-            for (int d = 0; d < gp.D; ++d) {
-                const float xc = gp.x[(int64_t)(m0 + t) * gp.D + d] - gp.shift[d];
-                bad |= !__builtin_isfinite(xc * xc);
-            }
-        bad_s[t] = bad;
-    }
-    {
-        f32x16 acc[2][2];                                             // (K <= 128: one tile of components)
-        gmm_score_tile(gp, m0, 0, As, Bs, acc);
-        const int col_l = lane & 31, rsub = 4 * (lane >> 5);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    slab[(int64_t)(wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + rsub) * ks + wn0 + 32 * j + col_l] = acc[i][j][r];
-    }
-    __syncthreads();                                                  // the slab and bad_s are this workgroup's own
-}
-
 template <int KC>
 __global__ __launch_bounds__(256) void hmm_dense_vit_kernel(HmmDenseVitP p)
 {
-    constexpr int NS = 256 / KC, SW = KC / NS, TS = KC + 1;
-    static_assert(NS * SW == KC && NS * KC == 256, "256 threads cover KC x KC in slices of SW");
+    static_assert(256 % KC == 0 && KC * KC % 256 == 0, "256 threads cover KC x KC in slices");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ int bad_s[GM_B];
     __shared__ int ids_s[GM_B];
@@ -96,20 +43,16 @@ __global__ __launch_bounds__(256) void hmm_dense_vit_kernel(HmmDenseVitP p)
     __shared__ int part_j[256];
     __shared__ float u_s[2][KC];                                      // the previous good frame's u, by parity; -inf past K
 
-    float* const lt_s = smem + 4 * GmTile::floats;                    // [KC][TS], behind the operand tiles
+    float* const lt_s = smem + 4 * GmTile::floats;                    // [KC][KC + 1], behind the operand tiles
     unsigned char* const bp_s = reinterpret_cast<unsigned char*>(smem);      // [128][KC], over the operand tiles
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int own = t % KC, sl = t / KC;
+    const int t = threadIdx.x;
     const int K = p.g.K, ks = p.ks;
     const bool owner = t < K;                                         // state t's chain value is formed by this thread
     char* const base = p.ws + (int64_t)blockIdx.x * p.per_wg;
     float* const slab = reinterpret_cast<float*>(base);
     unsigned char* const bpw = reinterpret_cast<unsigned char*>(base + (int64_t)sizeof(float) * GM_B * ks);
 
-    for (int i = t; i < KC * TS; i += 256) {
-        const int j = i / TS, k = i % TS;
-        lt_s[i] = (j < K && k < K) ? p.lt[j * K + k] : -INFINITY;
-    }
+    hd_load_matrix<KC>(lt_s, p.lt, K, -INFINITY, false);
     if (t < KC) { u_s[0][t] = -INFINITY; u_s[1][t] = -INFINITY; }
     const float li = owner ? p.li[t] : 0.0f;
     __syncthreads();
@@ -117,14 +60,7 @@ __global__ __launch_bounds__(256) void hmm_dense_vit_kernel(HmmDenseVitP p)
     for (int u = (int)blockIdx.x; u < p.n_utt; u += (int)gridDim.x) {
         const int64_t o = p.off[u];
         const int L = p.len[u];
-        if (o < 0 || L < 0 || o + L > p.g.T || L > p.cap) {          // (uniform) nothing of this utterance is touched
-            if (t == 0) {
-                if (p.log_prob) p.log_prob[u] = NAN;
-                if (p.n_switch) p.n_switch[u] = -1;
-                if (p.n_good) p.n_good[u] = -1;
-            }
-            continue;
-        }
+        if (hd_refused(p, u, o, L)) continue;                         // (uniform)
         bool started = false;
         int par = 0, ngood = 0, jlast = -1;
         float M = 0.0f;                                               // the previous good frame's max
@@ -134,7 +70,7 @@ __global__ __launch_bounds__(256) void hmm_dense_vit_kernel(HmmDenseVitP p)
         for (int b = 0; b < nblk; ++b) {
             const int f0 = b * GM_B;
             const int nf = min(GM_B, L - f0);
-            hdv_block_scores(p.g, (int)o + f0, nf, smem, slab, ks, bad_s);
+            hd_logn_block(p.g, (int)o + f0, nf, smem, slab, ks, bad_s);
 
             float sn = owner ? slab[t] : 0.0f;
             for (int f = 0; f < nf; ++f) {
@@ -146,7 +82,13 @@ __global__ __launch_bounds__(256) void hmm_dense_vit_kernel(HmmDenseVitP p)
                 }
                 float c = li;
                 int bj = t;                                           // the first good frame: bp[k] = k
-                if (started) {                                        // (uniform) c[own] = max_j (u[j] - M) + lt[j][own]
+                // (uniform) c[own] = max_j (u[j] - M) + lt[j][own].  This step and the key reduction below are the same text in
+                // hmm_dense_dur_kernel, on purpose: as two shared __forceinline__ functions this kernel measured 1.009 to 1.010 x
+                // the build without them at (D, K) = (40, 128) (16.21 -> 16.37 ms, run-to-run band 0.1 %), with both in its own
+                // text 1.000 to 1.003 x (profiles/hmm_dense_shared_layer.md)
+                if (started) {
+                    constexpr int NS = 256 / KC, SW = KC / NS, TS = KC + 1;
+                    const int own = t % KC, sl = t / KC;
                     const float* const ltc = lt_s + (sl * SW) * TS + own;
                     const float* const uv = u_s[par] + sl * SW;
                     float best = (uv[0] - M) + ltc[0];
@@ -176,18 +118,19 @@ __global__ __launch_bounds__(256) void hmm_dense_vit_kernel(HmmDenseVitP p)
                     bp_s[f * KC + t] = (unsigned char)bj;
                     key = vit_key(uu, t);
                 }
-                key = vit_wave_max(key);
-                if (lane == 0) red_k[par][wave] = key;
-                __syncthreads();
+                {                                                     // the key's max over the workgroup, in every thread
+                    const int lane = t & 63, wave = t >> 6;
+                    key = vit_wave_max(key);
+                    if (lane == 0) red_k[par][wave] = key;
+                    __syncthreads();
 #pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const unsigned long long ok = red_k[par][w];
-                    key = ok > key ? ok : key;
+                    for (int w = 0; w < 4; ++w) {
+                        const unsigned long long ok = red_k[par][w];
+                        key = ok > key ? ok : key;
+                    }
                 }
                 M = vit_key_score(key);
-                int bi = (int)~(unsigned)key;
-                if ((unsigned)bi >= (unsigned)K) bi = 0;              // no score compared greater than -inf: still an id
-                jlast = bi;
+                jlast = hd_key_index(key, K);
                 lp += (double)M;
                 par ^= 1;                                             // (the other sets are not rewritten before the next barrier)
                 started = true;
@@ -229,18 +172,12 @@ __global__ __launch_bounds__(256) void hmm_dense_vit_kernel(HmmDenseVitP p)
                     cur = pj;
                 }
             }
-            __syncthreads();
-            if (t < nf) p.ids[o + f0 + t] = ids_s[t];
+            hd_write_ids(p.ids, o, f0, nf, ids_s);
         }
 #else
         (void)cur;
 #endif
-        if (t == 0) {
-            if (p.log_prob) p.log_prob[u] = lp;
-            if (p.n_switch) p.n_switch[u] = nsw;
-            if (p.n_good) p.n_good[u] = ngood;
-        }
-        __syncthreads();                                              // the traceback's reads before the next utterance's writes
+        hd_write_results(p, u, lp, nsw, ngood);
     }
 }
 
@@ -263,8 +200,7 @@ struct HmmDenseDurP { HmmDenseVitP v; int S; };
 template <int KC, int SC>
 __global__ __launch_bounds__(256) void hmm_dense_dur_kernel(HmmDenseDurP pd)
 {
-    constexpr int NS = 256 / KC, SW = KC / NS, TS = KC + 1;
-    static_assert(NS * SW == KC && NS * KC == 256, "256 threads cover KC x KC in slices of SW");
+    static_assert(256 % KC == 0 && KC * KC % 256 == 0, "256 threads cover KC x KC in slices");
     static_assert(SC >= 2 && SC <= VIT_DUR_MAX, "the chain of a unit is held in SC registers");
     const HmmDenseVitP& p = pd.v;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -276,10 +212,9 @@ __global__ __launch_bounds__(256) void hmm_dense_dur_kernel(HmmDenseDurP pd)
     __shared__ float u_s[2][KC];                                      // the previous good frame's exit U, by parity; -inf past K
     __shared__ int fin_s;                                             // the final unit's chain state
 
-    float* const lt_s = smem + 4 * GmTile::floats;                    // [KC][TS], behind the operand tiles; the diagonal -inf
+    float* const lt_s = smem + 4 * GmTile::floats;                    // [KC][KC + 1], behind the operand tiles; the diagonal -inf
     unsigned char* const bp_s = reinterpret_cast<unsigned char*>(smem);      // [128][KC], over the operand tiles
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int own = t % KC, sl = t / KC;
+    const int t = threadIdx.x;
     const int K = p.g.K, ks = p.ks, S = pd.S;
     const int e0 = SC - S;                                            // state i lives in slot e0 + i
     const bool owner = t < K;                                         // unit t's chain is kept by this thread
@@ -288,10 +223,7 @@ __global__ __launch_bounds__(256) void hmm_dense_dur_kernel(HmmDenseDurP pd)
     unsigned char* const bpw = reinterpret_cast<unsigned char*>(base + (int64_t)sizeof(float) * GM_B * ks);
     unsigned char* const badw = bpw + (int64_t)p.cap * KC;
 
-    for (int i = t; i < KC * TS; i += 256) {
-        const int j = i / TS, k = i % TS;
-        lt_s[i] = (j < K && k < K && j != k) ? p.lt[j * K + k] : -INFINITY;
-    }
+    hd_load_matrix<KC>(lt_s, p.lt, K, -INFINITY, true);
     if (t < KC) { u_s[0][t] = -INFINITY; u_s[1][t] = -INFINITY; }
     const float li = owner ? p.li[t] : 0.0f;
     const float ls = owner ? p.lt[t * K + t] : 0.0f;
@@ -300,14 +232,7 @@ __global__ __launch_bounds__(256) void hmm_dense_dur_kernel(HmmDenseDurP pd)
     for (int u = (int)blockIdx.x; u < p.n_utt; u += (int)gridDim.x) {
         const int64_t o = p.off[u];
         const int L = p.len[u];
-        if (o < 0 || L < 0 || o + L > p.g.T || L > p.cap) {          // (uniform) nothing of this utterance is touched
-            if (t == 0) {
-                if (p.log_prob) p.log_prob[u] = NAN;
-                if (p.n_switch) p.n_switch[u] = -1;
-                if (p.n_good) p.n_good[u] = -1;
-            }
-            continue;
-        }
+        if (hd_refused(p, u, o, L)) continue;                         // (uniform)
         bool started = false;
         int par = 0, ngood = 0, jlast = -1;
         float N = 0.0f;                                               // the previous good frame's max over all states
@@ -320,7 +245,7 @@ __global__ __launch_bounds__(256) void hmm_dense_dur_kernel(HmmDenseDurP pd)
         for (int b = 0; b < nblk; ++b) {
             const int f0 = b * GM_B;
             const int nf = min(GM_B, L - f0);
-            hdv_block_scores(p.g, (int)o + f0, nf, smem, slab, ks, bad_s);
+            hd_logn_block(p.g, (int)o + f0, nf, smem, slab, ks, bad_s);
 
             float sn = owner ? slab[t] : 0.0f;
             for (int f = 0; f < nf; ++f) {
@@ -329,7 +254,15 @@ __global__ __launch_bounds__(256) void hmm_dense_dur_kernel(HmmDenseDurP pd)
                 if (bad_s[f]) continue;                               // (uniform) the chain passes over it
                 float c = li;                                         // what enters state 0
                 int bj = t;                                           // the first good frame: bp[k] = k
-                if (started) {                                        // (uniform) c[own] = max_{j != own} (U[j][S-1] - N) + lt[j][own]
+                // (uniform) c[own] = max_{j != own} (U[j][S-1] - N) + lt[j][own].  This step, the key reduction below and the plane
+                // copies are hmm_dense_vit_kernel's text again, on purpose.  Through shared functions <64, 8> measured 1.010 to
+                // 1.012 x the build without them (9.80 -> 9.91 ms, band 0.3 %); with one more phase in the kernel's own text each
+                // time: the score block 1.010, the plane copies 1.008, this step 1.002 to 1.003, the key reduction 0.998 to
+                // 0.999; these three without the score block 0.996 to 0.998, and with the score block in place of the plane
+                // copies 1.007 (profiles/hmm_dense_shared_layer.md)
+                if (started) {
+                    constexpr int NS = 256 / KC, SW = KC / NS, TS = KC + 1;
+                    const int own = t % KC, sl = t / KC;
                     const float* const ltc = lt_s + (sl * SW) * TS + own;
                     const float* const uv = u_s[par] + sl * SW;
                     float best = (uv[0] - N) + ltc[0];
@@ -360,18 +293,19 @@ __global__ __launch_bounds__(256) void hmm_dense_dur_kernel(HmmDenseDurP pd)
                     bp_s[f * KC + t] = (unsigned char)(bj | (st ? HDD_STAY : 0));
                     key = vit_key(m, t);
                 }
-                key = vit_wave_max(key);
-                if (lane == 0) red_k[par][wave] = key;
-                __syncthreads();
+                {                                                     // the key's max over the workgroup, in every thread
+                    const int lane = t & 63, wave = t >> 6;
+                    key = vit_wave_max(key);
+                    if (lane == 0) red_k[par][wave] = key;
+                    __syncthreads();
 #pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const unsigned long long ok = red_k[par][w];
-                    key = ok > key ? ok : key;
+                    for (int w = 0; w < 4; ++w) {
+                        const unsigned long long ok = red_k[par][w];
+                        key = ok > key ? ok : key;
+                    }
                 }
                 N = vit_key_score(key);
-                int bi = (int)~(unsigned)key;
-                if ((unsigned)bi >= (unsigned)K) bi = 0;              // no score compared greater than -inf: still an id
-                jlast = bi;                                           // the lowest unit whose chain holds the maximum
+                jlast = hd_key_index(key, K);                         // the lowest unit whose chain holds the maximum
 #pragma unroll
                 for (int i = 0; i < SC; ++i) V[i] = V[i] - N;
                 lp += (double)N;
@@ -426,15 +360,9 @@ __global__ __launch_bounds__(256) void hmm_dense_dur_kernel(HmmDenseDurP pd)
                     ci = S - 1;
                 }
             }
-            __syncthreads();
-            if (t < nf) p.ids[o + f0 + t] = ids_s[t];
+            hd_write_ids(p.ids, o, f0, nf, ids_s);
         }
-        if (t == 0) {
-            if (p.log_prob) p.log_prob[u] = lp;
-            if (p.n_switch) p.n_switch[u] = nsw;
-            if (p.n_good) p.n_good[u] = ngood;
-        }
-        __syncthreads();                                              // the traceback's reads before the next utterance's writes
+        hd_write_results(p, u, lp, nsw, ngood);
     }
 }
 
@@ -442,81 +370,53 @@ __global__ __launch_bounds__(256) void hmm_dense_dur_kernel(HmmDenseDurP pd)
 
 using namespace abn;
 
-// A region's bytes per frame: the backpointers of the capacity K rounds up to, and with a minimum duration
-// (abnw_hmm_dense_viterbi_dur, whatever S is) one more for the BAD flag.
-static inline int64_t hdv_frame_bytes(int64_t K, bool dur) { return (K >= 1 && K <= HD_MAX_K ? hd_kc_for(K) : HD_MAX_K) + (dur ? 1 : 0); }
-
+// (abnw_hmm_dense_viterbi_dur's regions have the BAD byte whatever S is)
 extern "C" int64_t abnz_hmm_dense_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D)
 {
-    return chain_ws_bytes("abnz_hmm_dense_viterbi_ws_bytes", n_utt, max_len, K, D, HD_LIMITS, hdv_frame_bytes(K, false), 0);
+    return chain_ws_bytes("abnz_hmm_dense_viterbi_ws_bytes", n_utt, max_len, K, D, HD_LIMITS, hd_frame_bytes(K, 1, false), 0);
 }
 
 extern "C" int64_t abnw_hmm_dense_viterbi_dur_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D)
 {
-    return chain_ws_bytes("abnw_hmm_dense_viterbi_dur_ws_bytes", n_utt, max_len, K, D, HD_LIMITS, hdv_frame_bytes(K, true), 0);
-}
-
-template <int KC>
-static void hdv_launch(const HmmDenseVitP& p, int grid, hipStream_t st)
-{
-    static bool attr_set[16] = {};
-    if (first_use_on_device(attr_set)) chain_opt_in(reinterpret_cast<const void*>(hmm_dense_vit_kernel<KC>), hd_lds_bytes(KC));
-    hipLaunchKernelGGL(hmm_dense_vit_kernel<KC>, dim3((unsigned)grid), dim3(256), hd_lds_bytes(KC), st, p);
-}
-
-template <int KC, int SC>
-static void hdd_launch(const HmmDenseDurP& p, int grid, hipStream_t st)
-{
-    static bool attr_set[16] = {};
-    if (first_use_on_device(attr_set)) chain_opt_in(reinterpret_cast<const void*>(hmm_dense_dur_kernel<KC, SC>), hd_lds_bytes(KC));
-    hipLaunchKernelGGL((hmm_dense_dur_kernel<KC, SC>), dim3((unsigned)grid), dim3(256), hd_lds_bytes(KC), st, p);
+    return chain_ws_bytes("abnw_hmm_dense_viterbi_dur_ws_bytes", n_utt, max_len, K, D, HD_LIMITS, hd_frame_bytes(K, 1, true), 0);
 }
 
 template <int SC>
-static void hdd_launch_kc(const HmmDenseDurP& p, int kc, int grid, hipStream_t st)
+static void hdd_launch(const HmmDenseDurP& pd, int kc, int grid, hipStream_t st)
 {
-    if (kc == 16) hdd_launch<16, SC>(p, grid, st);
-    else if (kc == 32) hdd_launch<32, SC>(p, grid, st);
-    else if (kc == 64) hdd_launch<64, SC>(p, grid, st);
-    else hdd_launch<128, SC>(p, grid, st);
+    hd_for_kc(kc, [&](auto c) {
+        constexpr int KC = decltype(c)::value;
+        hd_launch<hmm_dense_dur_kernel<KC, SC>, KC>(pd, grid, st);
+    });
 }
 
-// Both entries: the checks in their order -- min_duration (null: the entry has none) behind the pointers, as in
-// abnx_hmm_viterbi_dur --, the caller's workspace split into regions of the entry's geometry, and the launch.
-// min_duration = 1 launches hmm_dense_vit_kernel itself (the wider regions hold its backpointers and a spare byte a frame).
+// Both entries: min_duration (null: the entry has none) is checked behind the pointers.  min_duration = 1 launches
+// hmm_dense_vit_kernel itself (the wider regions hold its backpointers and a spare byte a frame).
 static int hdv_run(const char* what, const char* ws_fn, const int32_t* min_duration,
                    const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
                    const float* shift, const float* A, const float* B, const float* c0, const float* li, const float* lt, int64_t K,
                    int32_t* ids, double* log_prob, int32_t* n_switch, int32_t* n_good, void* ws, int64_t ws_bytes, void* stream)
 {
-    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "%s: T = %lld out of range", what, (long long)T);
-    int rc = chain_check_sizes(what, n_utt, K, D, HD_LIMITS);
-    if (rc != ABN_OK) return rc;
-    ABN_REQUIRE(x && off && len && shift && A && B && c0 && li && lt && ids, "%s: null pointer", what);
     const int S = min_duration ? *min_duration : 1;
-    ABN_REQUIRE(S >= 1 && S <= VIT_DUR_MAX, "%s: min_duration = %d, 1 .. %d (abnx_viterbi_dur_max)", what, S, VIT_DUR_MAX);
-    const int kc = hd_kc_for(K);
-    const ChainWs hw = chain_ws(n_utt, 0, K, hdv_frame_bytes(K, min_duration != nullptr), 0);
-    ChainRegion a;
-    rc = chain_region(what, ws_fn, ws, ws_bytes, hw, &a);
-    if (rc != ABN_OK) return rc;
+    const auto check_S = [&]() -> int {
+        ABN_REQUIRE(S >= 1 && S <= VIT_DUR_MAX, "%s: min_duration = %d, 1 .. %d (abnx_viterbi_dur_max)", what, S, VIT_DUR_MAX);
+        return ABN_OK;
+    };
     HmmDenseDurP pd;
-    HmmDenseVitP& p = pd.v;
-    p.g = hmm_score_params(x, T, D, shift, A, B, c0, K);      // (K <= 128: one tile of components)
-    p.li = li; p.lt = lt; p.off = off; p.len = len; p.n_utt = (int)n_utt;
-    p.ids = ids; p.log_prob = log_prob; p.n_switch = n_switch; p.n_good = n_good;
-    p.ws = a.ws; p.per_wg = a.per_wg;
-    p.ks = a.ks; p.cap = a.cap;
+    int grid;
+    const int rc = hd_decode_setup(what, ws_fn, check_S, hd_frame_bytes(K, 1, min_duration != nullptr), x, T, D, off, len, n_utt,
+                                   shift, A, B, c0, li, lt, K, ids, log_prob, n_switch, n_good, ws, ws_bytes, &pd.v, &grid);
+    if (rc != ABN_OK) return rc;
     pd.S = S;
+    const int kc = hd_kc_for(K);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (S == 1) {
-        if (kc == 16) hdv_launch<16>(p, hw.grid, st);
-        else if (kc == 32) hdv_launch<32>(p, hw.grid, st);
-        else if (kc == 64) hdv_launch<64>(p, hw.grid, st);
-        else hdv_launch<128>(p, hw.grid, st);
-    } else if (S == 2) hdd_launch_kc<2>(pd, kc, hw.grid, st);
-    else if (S <= 4) hdd_launch_kc<4>(pd, kc, hw.grid, st);
-    else hdd_launch_kc<8>(pd, kc, hw.grid, st);
+    if (S == 1) hd_for_kc(kc, [&](auto c) {
+        constexpr int KC = decltype(c)::value;
+        hd_launch<hmm_dense_vit_kernel<KC>, KC>(pd.v, grid, st);
+    });
+    else if (S == 2) hdd_launch<2>(pd, kc, grid, st);
+    else if (S <= 4) hdd_launch<4>(pd, kc, grid, st);
+    else hdd_launch<8>(pd, kc, grid, st);
     ABN_CHECK_LAUNCH(what);
     return ABN_OK;
 }

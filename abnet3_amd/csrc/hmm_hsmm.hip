@@ -23,6 +23,13 @@
 //
 // LDS at KC = 128: 72 KiB of operand tiles (the two byte planes, 32 KiB, lie over them) + 64.5 KiB of lx + about 4.6 KiB of
 // static arrays, of the CU's 160 KiB -- hmm_dense_vit.hip's budget, hd_lds_bytes(KC) with its static_assert.
+//
+// Of hmm_dense.h's device layer the kernel takes the score block alone (hd_logn_block: the same function it had as its
+// own), and HsmmP stays flat: its twelve instantiations compile to the instructions they had before that layer existed.
+// Measured against that build at (D, K, L) = (40, 64, 8), 10.53 ms, band 0.3 %: every phase through shared functions
+// 1.016 to 1.019 x; the plane copies in the kernel's own text 1.007; beside them the entry maximum 1.022, the key reduction
+// 1.020, everything else 1.026 (all with HsmmP embedding HmmDenseVitP); the flat HsmmP with the shared phases 1.009: no
+// mixture that was tried met the band (profiles/hmm_dense_shared_layer.md).  The host side below is hmm_dense.h's.
 #include "common.h"
 #include "gemm_f32.h"
 #include "gmm_tile.h"
@@ -50,38 +57,6 @@ struct HsmmP {
     char* ws; int64_t per_wg;               // bytes of a workgroup's region
     int ks, cap;                            // slab row stride (floats), frames the region holds
 };
-
-// The block of frames m0 .. m0 + nf - 1: BAD flags and the score tile logN into the slab (hmm_dense_vit.hip's
-// hdv_block_scores, which lives in that translation unit).  Ends behind a barrier.
-__device__ __forceinline__ void hs_block_scores(const GmmP& gp, int m0, int nf, float* smem, float* slab, int ks, int* bad_s)
-{
-    float* const As = smem;
-    float* const Bs = smem + 2 * GmTile::floats;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
-    if (t < GM_B) {
-        bool bad = false;
-        if (t < nf)
-            for (int d = 0; d < gp.D; ++d) {
-                const float xc = gp.x[(int64_t)(m0 + t) * gp.D + d] - gp.shift[d];
-                bad |= !__builtin_isfinite(xc * xc);
-            }
-        bad_s[t] = bad;
-    }
-    {
-        f32x16 acc[2][2];                                             // (K <= 128: one tile of components)
-        gmm_score_tile(gp, m0, 0, As, Bs, acc);
-        const int col_l = lane & 31, rsub = 4 * (lane >> 5);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    slab[(int64_t)(wm0 + 32 * i + (r & 3) + 8 * (r >> 2) + rsub) * ks + wn0 + 32 * j + col_l] = acc[i][j][r];
-    }
-    __syncthreads();                                                  // the slab and bad_s are this workgroup's own
-}
 
 template <int KC, int LC>
 __global__ __launch_bounds__(256) void hmm_hsmm_kernel(HsmmP p)
@@ -148,7 +123,7 @@ __global__ __launch_bounds__(256) void hmm_hsmm_kernel(HsmmP p)
         for (int b = 0; b < nblk; ++b) {
             const int f0 = b * GM_B;
             const int nf = min(GM_B, n - f0);
-            hs_block_scores(p.g, (int)o + f0, nf, smem, slab, ks, bad_s);
+            hd_logn_block(p.g, (int)o + f0, nf, smem, slab, ks, bad_s);
 
             float sn = owner ? slab[t] : 0.0f;
             for (int f = 0; f < nf; ++f) {
@@ -378,33 +353,22 @@ static int hs_check_L(const char* what, int32_t L)
     return ABN_OK;
 }
 
-// A region's bytes per frame: two bytes per unit of the capacity K rounds up to, and one for the BAD flag.
-static inline int64_t hs_frame_bytes(int64_t K) { return 2 * (K >= 1 && K <= HD_MAX_K ? hd_kc_for(K) : HD_MAX_K) + 1; }
-
 extern "C" int32_t abnu_hmm_hsmm_max_duration(void) { return HS_MAX_L; }
 
 extern "C" int64_t abnu_hmm_hsmm_viterbi_ws_bytes(int64_t n_utt, int64_t max_len, int64_t K, int64_t D, int32_t L)
 {
     const char* what = "abnu_hmm_hsmm_viterbi_ws_bytes";
     if (hs_check_L(what, L) != ABN_OK) return -1;
-    return chain_ws_bytes(what, n_utt, max_len, K, D, HD_LIMITS, hs_frame_bytes(K), 0);
-}
-
-template <int KC, int LC>
-static void hs_launch(const HsmmP& p, int grid, hipStream_t st)
-{
-    static bool attr_set[16] = {};
-    if (first_use_on_device(attr_set)) chain_opt_in(reinterpret_cast<const void*>(hmm_hsmm_kernel<KC, LC>), hd_lds_bytes(KC));
-    hipLaunchKernelGGL((hmm_hsmm_kernel<KC, LC>), dim3((unsigned)grid), dim3(256), hd_lds_bytes(KC), st, p);
+    return chain_ws_bytes(what, n_utt, max_len, K, D, HD_LIMITS, hd_frame_bytes(K, 2, true), 0);
 }
 
 template <int LC>
-static void hs_launch_kc(const HsmmP& p, int kc, int grid, hipStream_t st)
+static void hs_launch(const HsmmP& p, int kc, int grid, hipStream_t st)
 {
-    if (kc == 16) hs_launch<16, LC>(p, grid, st);
-    else if (kc == 32) hs_launch<32, LC>(p, grid, st);
-    else if (kc == 64) hs_launch<64, LC>(p, grid, st);
-    else hs_launch<128, LC>(p, grid, st);
+    hd_for_kc(kc, [&](auto c) {
+        constexpr int KC = decltype(c)::value;
+        hd_launch<hmm_hsmm_kernel<KC, LC>, KC>(p, grid, st);
+    });
 }
 
 extern "C" int abnu_hmm_hsmm_viterbi(const float* x, int64_t T, int64_t D, const int64_t* off, const int32_t* len, int64_t n_utt,
@@ -414,27 +378,24 @@ extern "C" int abnu_hmm_hsmm_viterbi(const float* x, int64_t T, int64_t D, const
                                      void* ws, int64_t ws_bytes, void* stream, const float* ld, const float* ls, int32_t L)
 {
     const char* what = "abnu_hmm_hsmm_viterbi";
-    ABN_REQUIRE(T >= 1 && T < (1LL << 31) - GM_B, "%s: T = %lld out of range", what, (long long)T);
-    int rc = chain_check_sizes(what, n_utt, K, D, HD_LIMITS);
-    if (rc != ABN_OK) return rc;
-    ABN_REQUIRE(x && off && len && shift && A && B && c0 && li && lx && ld && ls && ids, "%s: null pointer", what);
-    rc = hs_check_L(what, L);
-    if (rc != ABN_OK) return rc;
-    const int kc = hd_kc_for(K);
-    const ChainWs hw = chain_ws(n_utt, 0, K, hs_frame_bytes(K), 0);
-    ChainRegion a;
-    rc = chain_region(what, "abnu_hmm_hsmm_viterbi_ws_bytes", ws, ws_bytes, hw, &a);
+    const auto check_L = [&]() -> int {
+        ABN_REQUIRE(ld && ls, "%s: null pointer", what);
+        return hs_check_L(what, L);
+    };
+    HmmDenseVitP v;                                           // the decoders' prologue fills this; the kernel takes its own flat HsmmP
+    int grid;
+    const int rc = hd_decode_setup(what, "abnu_hmm_hsmm_viterbi_ws_bytes", check_L, hd_frame_bytes(K, 2, true), x, T, D, off, len, n_utt,
+                                   shift, A, B, c0, li, lx, K, ids, log_prob, n_switch, n_good, ws, ws_bytes, &v, &grid);
     if (rc != ABN_OK) return rc;
     HsmmP p;
-    p.g = hmm_score_params(x, T, D, shift, A, B, c0, K);      // (K <= 128: one tile of components)
-    p.li = li; p.lx = lx; p.ld = ld; p.ls = ls; p.off = off; p.len = len; p.n_utt = (int)n_utt; p.L = (int)L;
-    p.ids = ids; p.log_prob = log_prob; p.n_switch = n_switch; p.n_good = n_good;
-    p.ws = a.ws; p.per_wg = a.per_wg;
-    p.ks = a.ks; p.cap = a.cap;
+    p.g = v.g; p.li = v.li; p.lx = v.lt; p.ld = ld; p.ls = ls; p.off = v.off; p.len = v.len; p.n_utt = v.n_utt; p.L = (int)L;
+    p.ids = v.ids; p.log_prob = v.log_prob; p.n_switch = v.n_switch; p.n_good = v.n_good;
+    p.ws = v.ws; p.per_wg = v.per_wg; p.ks = v.ks; p.cap = v.cap;
+    const int kc = hd_kc_for(K);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (L <= 8) hs_launch_kc<8>(p, kc, hw.grid, st);
-    else if (L <= 16) hs_launch_kc<16>(p, kc, hw.grid, st);
-    else hs_launch_kc<32>(p, kc, hw.grid, st);
+    if (L <= 8) hs_launch<8>(p, kc, grid, st);
+    else if (L <= 16) hs_launch<16>(p, kc, grid, st);
+    else hs_launch<32>(p, kc, grid, st);
     ABN_CHECK_LAUNCH(what);
     return ABN_OK;
 }

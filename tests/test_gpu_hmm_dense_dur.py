@@ -109,7 +109,7 @@ def test_exact_inputs_equal_the_restatement(K, S, D):
 
 
 # ---- 2: BAD frames ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('K,S', [(K, S) for K in (5, 65) for S in (2, 8)])
+@pytest.mark.parametrize('K,S', [(K, S) for K in (5, 17, 33, 65) for S in (2, 8)])      # every capacity: 16, 32, 64, 128
 def test_bad_frames_with_exact_inputs_equal_the_restatement(K, S):
     lens = (140, 5, 300, 3, 300, 90)
     off, T = layout(lens)
