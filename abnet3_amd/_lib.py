@@ -206,6 +206,12 @@ NEXT6_SYMBOLS = {
     'abnu_hmm_hsmm_viterbi': (C.c_int, NEXT3_SYMBOLS['abnz_hmm_dense_viterbi'][1] + [_vp, _vp, _i32]),
     'abnu_hmm_run_stats': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
 }
+# the seventh section (prefix abnt_: the in-batch contrastive pair loss, csrc/nce.hip)
+NEXT7_SYMBOLS = {
+    'abnt_nce_max_d': (_i64, []),
+    'abnt_nce_ws_bytes': (_i64, [_i64, _i64]),
+    'abnt_nce_loss': (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _i64, _i64, _f32, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
 # abn_sd_count's conditions and the limits of abn_sd_collect / abn_sd_count (include/abnet3_hip.h)
 SD_CONDITION = {'all': 0, 'swdp': 1, 'swsp': 2}
 SD_MAX_N, SD_MAX_THR, SD_MAX_D = 1 << 22, 1 << 30, 4096
@@ -270,7 +276,8 @@ def load():
             '(hipcc, gfx950). There is no CPU fallback.' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SYMBOLS.items()) + list(NEXT_SYMBOLS.items()) + list(NEXT2_SYMBOLS.items()) + \
-            list(NEXT3_SYMBOLS.items()) + list(NEXT4_SYMBOLS.items()) + list(NEXT5_SYMBOLS.items()) + list(NEXT6_SYMBOLS.items()):
+            list(NEXT3_SYMBOLS.items()) + list(NEXT4_SYMBOLS.items()) + list(NEXT5_SYMBOLS.items()) + list(NEXT6_SYMBOLS.items()) + \
+            list(NEXT7_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -9,6 +9,8 @@ Mirrors (file:line relative to the reference checkout)
 forward(input1, input2, y) returns a 0-dim tensor with .backward(); the
 arithmetic (cosine similarity with eps=1e-6 or the two KL divergences, per-label
 transform, sum, /N) and its gradient run fused in one kernel (abn_pair_loss).
+InfoNCELoss (not in the reference) is the in-batch contrastive loss over the same surface: forward(input1, input2, y,
+groups=None); its B x B similarities never reach memory (abnt_nce_loss, csrc/nce.hip).
 """
 import torch
 import torch.nn as nn
@@ -201,6 +203,96 @@ class KLLoss(LossBuilder):
         probability rows act(z)."""
         assert input1.size() == input2.size(), 'Input not the same size'
         return _pair_loss_raw(input1, input2, y, 'KLLoss', self.margin, self.avg, True, act=act, masks=masks)
+
+
+def _nce_raw(e1, e2, y, groups, tau, avg, need_grad):
+    """abnt_nce_loss: (0-dim loss, [2, B, D] gradient of the loss w.r.t. (e1, e2) or None)."""
+    lib = _lib.load()
+    _lib.require_device(e1, e2, y)
+    if e1.dtype != torch.float32 or e2.dtype != torch.float32:
+        raise TypeError('abnet3_amd: embeddings must be float32')
+    if y.dtype not in _lib.Y_DTYPE:
+        raise TypeError('abnet3_amd: unsupported label dtype %s' % y.dtype)
+    if e1.dim() != 2 or e1.size() != e2.size():
+        raise ValueError('abnet3_amd: InfoNCELoss takes two [B, D] inputs of one shape')
+    B, D = e1.shape
+    if y.numel() != B:
+        raise ValueError('abnet3_amd: %d labels for %d pairs' % (y.numel(), B))
+    if D > lib.abnt_nce_max_d():
+        raise ValueError('abnet3_amd: InfoNCELoss takes embeddings of at most %d columns (abnt_nce_max_d), got %d'
+                         % (lib.abnt_nce_max_d(), D))
+    if groups is not None:
+        _lib.require_device(groups)
+        if groups.numel() != B:
+            raise ValueError('abnet3_amd: %d groups for %d pairs' % (groups.numel(), B))
+        groups = groups.to(torch.int32).contiguous()
+    e1, e2, y = e1.contiguous(), e2.contiguous(), y.contiguous()
+    need = lib.abnt_nce_ws_bytes(B, D)
+    if need < 0:
+        _lib.check(_lib.E_UNSUPPORTED, 'abnt_nce_ws_bytes')
+    loss = torch.empty((), dtype=torch.float32, device=e1.device)
+    de = torch.empty(2, B, D, dtype=torch.float32, device=e1.device) if need_grad else None
+    ws = torch.empty(need, dtype=torch.uint8, device=e1.device)          # need not be cleared
+    _lib.check(lib.abnt_nce_loss(
+        _lib.ptr(e1), _lib.ptr(e2), _lib.ptr(y), _lib.Y_DTYPE[y.dtype], _lib.ptr(groups), B, D, float(tau),
+        int(bool(avg)), _lib.ptr(loss), None, _lib.ptr(de[0]) if need_grad else None,
+        _lib.ptr(de[1]) if need_grad else None, _lib.ptr(ws), _lib.stream()), 'abnt_nce_loss')
+    return loss, de
+
+
+class _NceFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, e1, e2, y, groups, tau, avg):
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        loss, ctx.de = _nce_raw(e1, e2, y, groups, tau, avg, need_grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        de = ctx.de
+        if de is None:
+            return None, None, None, None, None, None
+        unit = _UNIT.get(g.device)                    # (the cached unit seed: _PairLossFunction.backward)
+        if unit is None or g.data_ptr() != unit.data_ptr():
+            de = de * g
+        return de[0], de[1], None, None, None, None
+
+
+class InfoNCELoss(LossBuilder):
+    """The in-batch contrastive loss (InfoNCE / NT-Xent) of B pairs: row i of input1 and row i of input2 are a positive, every
+    other row of the batch is a negative -- no 'different' pairs are sampled.  Not part of the reference; for the pair
+    sources that yield positives only (mined pairs, cluster sampling, temporal coherence).
+
+    With a^_i = input1_i / max(|input1_i|, 1e-6), b^_j likewise, s[i][j] = <a^_i, b^_j>, r[i] = (y[i] == 1), n = sum r:
+        la[i] = log sum_j exp(s[i][j] / temperature)      (a^_i against every b^_j)
+        lb[j] = log sum_i exp(s[i][j] / temperature)      (b^_j against every a^_i)
+        loss  = sum_i r[i] ((la[i] + lb[i]) / 2 - s[i][i] / temperature),  divided by n when avg.
+    A row with y != 1 is no anchor, but its two vectors stay among everyone's candidates.  n = 0 gives loss 0 and zero
+    gradients for either avg -- deliberately NOT the NaN an empty batch gives the cosine losses: a batch without a positive
+    is an ordinary event for a sampled loader and must not poison the weights.  `groups` ([B] integers, optional) excludes
+    the cells (i, j), j != i, with groups[i] == groups[j] from both sums: frames of one word pair are near-duplicates and
+    would be false negatives.  No loader delivers groups yet.
+
+    temperature = 0.1 is a common starting point and is NOT tuned on speech.  Loss and both gradients come from one C
+    entry (abnt_nce_loss, csrc/nce.hip): the B x B similarities never reach memory.  Under data parallelism the negatives
+    are those of the rank's own batch; nothing is gathered across ranks.  Trains through autograd (the trainer's direct and
+    planned steps do not know this loss and step aside)."""
+
+    def __init__(self, temperature=0.1, avg=True, *args, **kwargs):
+        super(InfoNCELoss, self).__init__(*args, **kwargs)
+        if not (float(temperature) > 0.0) or float(temperature) == float('inf'):
+            raise ValueError('abnet3_amd: InfoNCELoss temperature = %r must be finite and > 0' % (temperature,))
+        self.temperature = temperature
+        self.avg = avg
+
+    def forward(self, input1, input2, y, groups=None):
+        assert input1.size() == input2.size(), 'Input not the same size'
+        return _NceFunction.apply(input1.contiguous(), input2.contiguous(), y.contiguous(), groups, self.temperature, self.avg)
+
+    def value_and_grad(self, input1, input2, y, groups=None):
+        """(loss, [2, B, D] gradient w.r.t. (input1, input2)) without autograd."""
+        assert input1.size() == input2.size(), 'Input not the same size'
+        return _nce_raw(input1, input2, y, groups, self.temperature, self.avg, True)
 
 
 class weighted_loss_multi(LossBuilder):

@@ -5,6 +5,7 @@ Siamese training -> embedding -> ABX.  The corpus' word labels are used twice on
 mined pairs, and the ABX item file ("phones" = word types).
 
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
+                                     [--infonce] [--temperature T]
                                      [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--hmm-fit N] [--hmm-trans N] [--hmm-decode] [--no-network] [--terms] [--terms-theta T]
                                      [--prefilter] [--alignment FILE]
                                      [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P] [--kmeans-min-duration S]
@@ -13,6 +14,9 @@ mined pairs, and the ABX item file ("phones" = word types).
 
 --softmax runs the same loop with a softmax output layer and KLLoss: the embeddings are posteriorgrams, and their ABX
 error is printed under both frame distances, the angular cosine and the symmetrised Kullback-Leibler divergence.
+--infonce trains with the in-batch contrastive loss (InfoNCELoss, temperature T, default 0.1, untuned) instead of
+coscos2: the 'same' pairs of a batch are the anchors and every other row of the batch is a negative.  It composes with
+--tcl and with the mined-pairs route; it is not combined with --softmax.
 --tcl skips the discovery step altogether: TemporalCoherenceDataLoader trains on temporal-coherence pairs (a frame and
 its neighbour against frames 15-30 steps away, drawn on the GPU), and the dev pairs that early stopping needs are made
 the same way from the last fifth of the files -- a stretch of frames against itself one frame later ("same") and
@@ -72,7 +76,7 @@ from abnet3_amd.features import FeaturesGenerator                 # noqa: E402
 from abnet3_amd.gmm import GmmPosteriorgram                       # noqa: E402
 from abnet3_amd.hmm import StickyHmmPosteriorgram, TransitionHmmPosteriorgram, sticky_transitions      # noqa: E402
 from abnet3_amd.kmeans import KMeansQuantizer, bitrate, unit_sequences   # noqa: E402
-from abnet3_amd.loss import KLLoss, coscos2                       # noqa: E402
+from abnet3_amd.loss import InfoNCELoss, KLLoss, coscos2                       # noqa: E402
 from abnet3_amd.model import SiameseNetwork                       # noqa: E402
 from abnet3_amd.prefilter import TermPrefilter                   # noqa: E402
 from abnet3_amd.samediff import SameDifferentEvaluator            # noqa: E402
@@ -367,6 +371,8 @@ def main():
     ap.add_argument('--out', default='/tmp/abnet3_zr')
     ap.add_argument('--softmax', action='store_true', help='softmax output + KLLoss; ABX under cosine and KL')
     ap.add_argument('--tcl', action='store_true', help='no mined pairs: train on temporal-coherence pairs')
+    ap.add_argument('--infonce', action='store_true', help='train with InfoNCELoss (in-batch negatives) instead of coscos2')
+    ap.add_argument('--temperature', type=float, default=0.1, help='with --infonce: the temperature (untuned)')
     ap.add_argument('--qbe', action='store_true', help='after embedding: search a few planted words by example, print MAP')
     ap.add_argument('--gmm', action='store_true', help='the untrained baseline: GMM posteriorgrams of the filterbanks, ABX (kl)')
     ap.add_argument('--gmm-components', type=int, default=64)
@@ -419,6 +425,8 @@ def main():
         ap.error('--hmm-max-duration belongs to --hmm-trans-viterbi')
     if args.hmm_decode and args.hmm_stay is None and not args.hmm_fit:
         ap.error('--hmm-decode decodes the HMM of --hmm-stay or --hmm-fit')
+    if args.infonce and args.softmax:
+        ap.error('--infonce is a loss over cosine similarities; --softmax trains posteriorgrams with KLLoss')
     esk_k = args.eskmeans_clusters if args.eskmeans else None
     rng = np.random.default_rng(0)
     random.seed(0)
@@ -472,7 +480,7 @@ def main():
     net = SiameseNetwork(input_dim=40, num_hidden_layers=1, hidden_dim=200, output_dim=40, p_dropout=0.0,
                          activation_layer='sigmoid', output_path=args.out + '_network',
                          last_non_linearity='softmax' if args.softmax else 'default')
-    trainer = TrainerSiamese(network=net, loss=KLLoss(avg=False) if args.softmax else coscos2(avg=False),
+    trainer = TrainerSiamese(network=net, loss=KLLoss(avg=False) if args.softmax else InfoNCELoss(args.temperature, avg=False) if args.infonce else coscos2(avg=False),
                              num_epochs=args.epochs, patience=30,
                              optimizer_type='adadelta', lr=0.5, dataloader=dl, log_dir=args.out + '_runs')
     trainer.train()

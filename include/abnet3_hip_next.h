@@ -3,7 +3,8 @@
  * The entries below carry the prefix abnx_ (the minimum unit duration of the max-product decoders), abny_ (the HMM with
  * a full transition matrix), abnz_ (that model's max-product path), abnw_ (that path with a minimum unit duration) or abnv_
  * (the hard statistics of that model's Viterbi training) or abnu_ (explicit unit durations: the semi-Markov decoder and its
- * run statistics, ledger abnet3_amd._lib.NEXT6_SYMBOLS with tests/test_gpu_hmm_hsmm.py) and are
+ * run statistics, ledger abnet3_amd._lib.NEXT6_SYMBOLS with tests/test_gpu_hmm_hsmm.py) or abnt_ (the in-batch contrastive
+ * pair loss, ledger abnet3_amd._lib.NEXT7_SYMBOLS with tests/test_gpu_nce.py) and are
  * exported beside those of abnet3_hip.h, whose conventions they follow (extern "C", plain pointers and sizes, the ABN_E_*
  * return codes, abn_last_error, every refusal before any launch).
  * They do not change ABN_ABI_VERSION.  A later change folds them into abnet3_hip.h under their abn_ names, bumps the
@@ -224,6 +225,37 @@ int abnu_hmm_hsmm_viterbi(const float* x, int64_t T, int64_t D, const int64_t* o
                           void* ws, int64_t ws_bytes, void* stream, const float* ld, const float* ls, int32_t L);
 int abnu_hmm_run_stats(const int32_t* ids, int64_t T, const int64_t* off, const int32_t* len, int64_t n_utt, int64_t K,
                        int32_t L, int64_t* dur, int64_t* tail, void* stream);
+
+/* ---- The in-batch contrastive pair loss, InfoNCE / NT-Xent (csrc/nce.hip) -------------------------------------------------
+ * Prefix abnt_; ledger abnet3_amd._lib.NEXT7_SYMBOLS with tests/test_gpu_nce.py.  abnet3_amd/loss.py (InfoNCELoss) states the
+ * definition, tests/nce_np.py restates it.  e1, e2 [B][D] fp32; y [B] of y_dtype (abn_pair_loss's codes: 0 int8, 1 int32,
+ * 2 int64, 3 float32, 4 float64); groups [B] int32 or null; tau > 0.  With a^_i = e1_i / max(|e1_i|, 1e-6), b^_j likewise
+ * from e2, z[i][j] = <a^_i, b^_j> / tau over the cells that are not excluded ((i, j) is excluded when j != i and
+ * groups[i] == groups[j]; null: none), r[i] = (y[i] == 1), n = sum r:
+ *     la[i] = log sum_j exp z[i][j],   lb[j] = log sum_i exp z[i][j],   l[i] = (la[i] + lb[i]) / 2 - z[i][i]
+ *     loss = sum_i r[i] l[i], divided by n when avg;   n = 0: loss 0 and zero gradients for either avg.
+ * loss [1] fp32; terms [B] fp32 or null: every l[i], anchors or not; de1, de2 [B][D] fp32, both or neither (both null:
+ * forward only, the same loss bits): the gradient of loss with respect to e1 and e2, through the normalisation (the
+ * projection only where the norm is at least 1e-6).  A row with y != 1 is no anchor; its vectors stay candidates.
+ *
+ * The B x B similarities never reach memory: exact-fp32 MFMA tiles folded into running (max, sum) pairs, then recomputed
+ * and fed through LDS into the gradient GEMM.  No floating-point atomics, every sum in a fixed order: two calls on the same
+ * inputs give the same bits, and swapping (e1, de1) with (e2, de2) swaps the outputs' bits (groups symmetric by
+ * construction).  Padding columns and excluded cells have weight exactly 0.  The candidates of a row block are split over
+ * up to 16 workgroups by the grid; ABN_NCE_SPLIT = 1 .. 16 in the environment forces the split (read at every call; the
+ * results stay inside the same error bars, the bits may differ: the split moves the points where partial sums are merged).
+ *
+ * D <= abnt_nce_max_d() (256: the gradient accumulators of a 128-row block stay in registers), B <= 2^20.  Workspace:
+ * abnt_nce_ws_bytes(B, D) bytes under the same ABN_NCE_SPLIT, 16-byte aligned, -1 with abn_last_error for refused sizes:
+ * the unit rows, a handful of [B] vectors, 2 x split (max, sum) pairs per row and 2 x split gradient slabs [B][D'] (D' = D
+ * rounded up to 4) -- O(B D split), split <= 16, never B x B.  It need not be cleared.  Nine launches (seven forward only).
+ * Refusals, all before any launch: B < 1 or D < 1: ABN_E_ARG; D or B beyond the limits: ABN_E_UNSUPPORTED; null e1, e2, y,
+ * loss or ws, a y_dtype outside 0 .. 4, tau not finite or <= 0 (or so small that 1 / tau is not a finite float), only one of
+ * de1 / de2, a misaligned workspace: ABN_E_ARG. */
+int64_t abnt_nce_max_d(void);              /* host */
+int64_t abnt_nce_ws_bytes(int64_t B, int64_t D);      /* host */
+int abnt_nce_loss(const float* e1, const float* e2, const void* y, int y_dtype, const int32_t* groups, int64_t B, int64_t D,
+                  float tau, int avg, float* loss, float* terms, float* de1, float* de2, void* ws, void* stream);
 
 #ifdef __cplusplus
 }
