@@ -365,6 +365,20 @@ def require_device(*tensors):
             raise HipLibraryError('abnet3_amd: tensor must be contiguous')
 
 
+def require_tensor(who, what, t, dtype, rank, width=None):
+    """ValueError naming `who` unless `t` is a torch tensor of `dtype` (one dtype, or a tuple of them) with `rank`
+    dimensions (and, with `width`, that many columns); then require_device(t).  The check of an argument that reaches a
+    kernel as a raw pointer: what require_device alone does not look at."""
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.dim() != rank or \
+            (width is not None and t.shape[-1] != width):
+        got = '%s %s' % (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__
+        want = '%d-d %s' % (rank, ' / '.join(str(d).replace('torch.', '') for d in dtypes))
+        raise ValueError('%s: %s must be a %s tensor%s, not %s' % (
+            who, what, want, '' if width is None else ' of %d columns' % width, got))
+    require_device(t)
+
+
 def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 

@@ -283,7 +283,10 @@ def dtw_cost_batch(feats1, off1, n1, feats2, off2, n2, distance='cosine', parall
         (feats1, L1, bad1), (feats2, L2, bad2) = feats1, feats2
         _kl_triples('dtw_cost_batch', (feats1, L1, bad1), (feats2, L2, bad2))
     else:
-        _lib.require_device(feats1, feats2)
+        _lib.require_tensor('dtw_cost_batch', 'feats1', feats1, torch.float32, 2)
+        _lib.require_tensor('dtw_cost_batch', 'feats2', feats2, torch.float32, 2)
+        if feats1.shape[1] != feats2.shape[1]:
+            raise ValueError('dtw_cost_batch: the two sides have different frame widths')
     (off1, n1, off2, n2), d_tab = _pair_table('dtw_cost_batch', feats1.shape[0], off1, n1, feats2.shape[0], off2, n2)
     P = len(n1)
     cap = lib.abn_dtw_cost_max_n2()
@@ -325,6 +328,11 @@ def abx_score(dist, plan):
     pairs (abn_abx_score)."""
     lib = _lib.load()
     nc = len(plan.cells)
+    if not isinstance(dist, torch.Tensor) or dist.dtype != torch.float64 or dist.dim() != 1 or dist.numel() != len(plan.P):
+        raise ValueError('abx_score: dist must be a float64 [%d] tensor, one distance per pair of the plan, not %s' % (
+            len(plan.P), '%s %s' % (tuple(dist.shape), dist.dtype) if isinstance(dist, torch.Tensor) else type(dist).__name__))
+    if not dist.is_cuda:
+        raise _lib.HipLibraryError('abx_score: dist must be on the MI355X (HIP) device, not %s' % dist.device)
     score2 = torch.empty(nc, dtype=torch.int64, device=dist.device)
     count = torch.empty(nc, dtype=torch.int64, device=dist.device)
     refused = torch.empty(1, dtype=torch.int32, device=dist.device)

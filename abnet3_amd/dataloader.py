@@ -41,8 +41,11 @@ class DataLoader:
 def gather_rows(table, idx):
     """table[idx] on the device (feat[path, :], dataloader.py:204-205)."""
     lib = _lib.load()
+    _lib.require_tensor('gather_rows', 'table', table, torch.float32, 2)
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 1:
+        raise ValueError('gather_rows: idx must be one row of table row numbers (a 1-d tensor)')
     idx = idx.to(torch.int64).contiguous()
-    _lib.require_device(table, idx)
+    _lib.require_device(idx)
     out = torch.empty(idx.numel(), table.shape[1], dtype=torch.float32, device=table.device)
     _lib.check(lib.abn_gather_rows(_lib.ptr(table), _lib.ptr(idx), idx.numel(),
                                    table.shape[1], _lib.ptr(out), _lib.stream()),

@@ -60,9 +60,14 @@ def enumerate_segments(n_frames, lengths=DEFAULT_LENGTHS, shift=5):
 def segment_vectors(table, row0, seg_len, K=10):
     """abn_segment_vectors: ([n, K D] float32 unit rows, [n] bool "not all zero") on table's device for the segments
     that start at table rows `row0` (host int64) and are `seg_len` (host int32) rows long."""
-    _lib.require_device(table)
+    _lib.require_tensor('segment_vectors', 'table', table, torch.float32, 2)
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K < 1:
+        raise ValueError('segment_vectors: K = %r, a positive number of frames is needed' % (K,))
+    K = int(K)
     row0 = np.ascontiguousarray(row0, dtype=np.int64)
     seg_len = np.ascontiguousarray(seg_len, dtype=np.int32)
+    if row0.ndim != 1 or seg_len.shape != row0.shape:
+        raise ValueError('segment_vectors: row0 and seg_len must be two 1-d arrays of one length')
     n, D = len(row0), table.shape[1]
     if n and (row0.min() < 0 or seg_len.min() < 1 or (row0 + seg_len).max() > table.shape[0]):
         raise ValueError('segment_vectors: a segment lies outside the table')
@@ -77,7 +82,13 @@ def segment_vectors(table, row0, seg_len, K=10):
 def knn_topk(Q, C, k, q_meta=None, c_meta=None):
     """abn_knn_topk: (idx int32 [nq, k], sim float32 [nq, k]) on the device.  Q [nq, d], C [nc, d]: unit rows;
     q_meta / c_meta: int32 [n, 3] device tensors (file, begin, end) for the overlap exclusion, or None."""
-    _lib.require_device(Q, C, q_meta, c_meta)
+    _lib.require_tensor('knn_topk', 'Q', Q, torch.float32, 2)
+    _lib.require_tensor('knn_topk', 'C', C, torch.float32, 2)
+    _lib.require_device(q_meta, c_meta)
+    # (k > nc is legal: the places beyond the candidates hold idx = -1, sim = -inf; the upper limit is the library's)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError('knn_topk: k = %r, a positive number of neighbours is needed' % (k,))
+    k = int(k)
     lib = _lib.load()
     nq, nc, d = Q.shape[0], C.shape[0], Q.shape[1]
     if C.shape[1] != d:

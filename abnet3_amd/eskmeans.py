@@ -112,6 +112,16 @@ def _dev_i64(a, device):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(device)
 
 
+def _packed_landmarks(who, lm, lm_off, device):
+    """(lm, lm_off) int64 on the device.  Host arrays are held to what the kernels assume, which pack_landmarks builds:
+    1-d, lm_off running from 0 to len(lm) without a step back (device tensors are the caller's to have packed)."""
+    if not isinstance(lm, torch.Tensor) and not isinstance(lm_off, torch.Tensor):
+        a, o = np.asarray(lm), np.asarray(lm_off)
+        if a.ndim != 1 or o.ndim != 1 or len(o) < 1 or o[0] != 0 or o[-1] != len(a) or (np.diff(o) < 0).any():
+            raise ValueError('%s: lm_off must run from 0 to the %d landmarks of lm (pack_landmarks)' % (who, a.size))
+    return _dev_i64(lm, device), _dev_i64(lm_off, device)
+
+
 def _check_span(who, S):
     S = int(S)
     if S < 1 or S > max_span():
@@ -137,7 +147,7 @@ def candidate_scores(table, lm, lm_off, m, b, frames=10, max_span=6, max_frames=
         raise ValueError('eskmeans.candidate_scores: K = %d, the kernel takes 1 .. %d (abn_kmeans_max_k)' % (K, kmeans.max_k()))
     if m.shape != (K, frames * D) or m.dtype != torch.float32 or b.dtype != torch.float32:
         raise ValueError('eskmeans.candidate_scores: m [K, frames D] and b [K] float32 are needed')
-    lm, lm_off = _dev_i64(lm, table.device), _dev_i64(lm_off, table.device)
+    lm, lm_off = _packed_landmarks('eskmeans.candidate_scores', lm, lm_off, table.device)
     n_lm, n_utt = lm.numel(), lm_off.numel() - 1
     max_frames = (1 << 62) if max_frames is None else int(max_frames)
     if max_frames < 1:
@@ -156,7 +166,7 @@ def segment_dp(cand_best, cand_id, lm, lm_off, max_span=6):
     lib = _lib.load()
     S = _check_span('eskmeans.segment_dp', max_span)
     _lib.require_device(cand_best, cand_id)
-    lm, lm_off = _dev_i64(lm, cand_best.device), _dev_i64(lm_off, cand_best.device)
+    lm, lm_off = _packed_landmarks('eskmeans.segment_dp', lm, lm_off, cand_best.device)
     n_lm, n_utt = lm.numel(), lm_off.numel() - 1
     if cand_best.dtype != torch.float32 or cand_id.dtype != torch.int32 or cand_best.numel() != n_lm * S or cand_id.numel() != n_lm * S:
         raise ValueError('eskmeans.segment_dp: cand_best float32 and cand_id int32 of n_lm x S = %d entries are needed' % (n_lm * S))

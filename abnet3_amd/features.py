@@ -71,6 +71,9 @@ def _samples_batch(waves):
         s, lens = waves[0], np.asarray(waves[1], dtype=np.int64)
         assert int(lens.sum()) == s.numel()
     else:
+        waves = [w if isinstance(w, torch.Tensor) else np.asarray(w) for w in waves]
+        if any(w.ndim != 1 for w in waves):
+            raise ValueError('abnet3_amd: mono samples are needed, one 1-d array per utterance')
         lens = np.array([len(w) for w in waves], dtype=np.int64)
         if isinstance(waves[0], torch.Tensor):
             s = torch.cat([w.reshape(-1) for w in waves]).cuda()
@@ -91,10 +94,30 @@ def _samples_one(sound):
         if sound.dtype != np.int16:
             sound = sound.astype(np.float32)
         s = torch.from_numpy(sound)
+    if s.dim() != 1:
+        raise ValueError('abnet3_amd: mono samples are needed, one 1-d array per utterance, not %s' % (tuple(s.shape),))
     s = s.cuda().contiguous()
     if s.dtype not in (torch.int16, torch.float32):
         s = s.float()
     return s
+
+
+def _device_table(who, table):
+    """The [T, D] float32 device table `who` hands to a kernel, or ValueError; a strided table is copied dense."""
+    if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.dtype != torch.float32:
+        raise ValueError('%s: a [T, D] float32 table is needed, not %s' % (
+            who, '%s %s' % (tuple(table.shape), table.dtype) if isinstance(table, torch.Tensor) else type(table).__name__))
+    table = table.contiguous()
+    _lib.require_device(table)
+    return table
+
+
+def _frame_offsets(who, lengths, T):
+    """Cumulative frame counts [n_utt + 1] int64 (host) of utterances laid end to end in a table of T rows, or ValueError."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    if lengths.ndim != 1 or (lengths < 0).any() or int(lengths.sum()) != T:
+        raise ValueError('%s: the lengths must be one row of frame counts that add up to the table\'s %d rows' % (who, T))
+    return np.concatenate(([0], np.cumsum(lengths)))
 
 
 class FeaturesGenerator:
@@ -167,7 +190,7 @@ class FeaturesGenerator:
         """Regression deltas of a [T, D] device tensor (spectral's do_deltas): slope over +-4
         frames, edges padded with frame 1 / frame T-2 (oracle/features_np.py)."""
         lib = _lib.load()
-        feats = feats.contiguous()
+        feats = _device_table('deltas_of', feats)
         out = torch.empty_like(feats)
         _lib.check(lib.abn_deltas(_lib.ptr(feats), feats.shape[0], feats.shape[1], _lib.ptr(out),
                                   _lib.stream()), 'abn_deltas')
@@ -283,7 +306,9 @@ class FeaturesGenerator:
     def normalize_table(self, table, lengths):
         """mean_variance_normalisation / mean_var_norm_per_file (features.py:205-297) on a device table of
         utterances laid end to end (no VAD here: normalize_features takes one).  Returns (table, stats)."""
+        table = _device_table('normalize_table', table)
         if self.norm_per_file:
+            _frame_offsets('normalize_table', lengths, table.shape[0])
             out, stats, o = torch.empty_like(table), [], 0
             for n in lengths:
                 n = int(n)
@@ -300,10 +325,11 @@ class FeaturesGenerator:
         nframes = self.nframes if nframes is None else nframes
         assert nframes % 2 == 1, 'number of stacked frames must be odd'
         lib = _lib.load()
-        foff = torch.from_numpy(np.concatenate(([0], np.cumsum(np.asarray(lengths, dtype=np.int64))))).cuda()
+        table = _device_table('stack_table', table)
         T, D = table.shape
+        foff = torch.from_numpy(_frame_offsets('stack_table', lengths, T)).cuda()
         out = torch.empty(T, D * nframes, dtype=torch.float32, device=table.device)
-        _lib.check(lib.abn_stack_frames_batched(_lib.ptr(table.contiguous()), _lib.ptr(foff), len(lengths), T, D, nframes,
+        _lib.check(lib.abn_stack_frames_batched(_lib.ptr(table), _lib.ptr(foff), len(lengths), T, D, nframes,
                                                 _lib.ptr(out), _lib.stream()), 'abn_stack_frames_batched')
         return out
 
@@ -401,6 +427,8 @@ class FeaturesGenerator:
         lib = _lib.load()
         is_np = not isinstance(features, torch.Tensor)
         f = torch.from_numpy(np.ascontiguousarray(features)) if is_np else features
+        if f.dim() != 2:
+            raise ValueError('stack_fbanks: [T, D] features are needed, not %s' % (tuple(f.shape),))
         dtype = f.dtype
         f = f.cuda().float().contiguous()
         T, D = f.shape

@@ -96,6 +96,7 @@ def posteriors(table, shift, A, B, c, want_post=True, out=None):
     if want_post:
         g = out if out is not None else torch.empty((T, K), dtype=torch.float32, device=table.device)
         assert g.shape == (T, K) and g.dtype == torch.float32 and g.is_contiguous()
+        _lib.require_device(g)
     if T:
         _lib.check(lib.abn_gmm_posteriors(_lib.ptr(table), T, D, _lib.ptr(shift), _lib.ptr(A), _lib.ptr(B), _lib.ptr(c), K,
                                           _lib.ptr(lse), _lib.ptr(g), _lib.stream()), 'abn_gmm_posteriors')
@@ -121,7 +122,10 @@ def em_iteration(table, shift, st, var_floor=0.01, min_count=1.0, n_ranges=0):
     """One EM iteration on the device, in place in `st` (an EMState): abn_gmm_posteriors (likelihoods only),
     abn_gmm_accumulate, abn_gmm_mstep.  Returns lse [T].  Nothing is read back."""
     lib = _lib.load()
+    table = _check_table('gmm.em_iteration', table)       # (the dense copy of a strided table: all three launches read it)
     T, D = table.shape
+    if D != st.D:
+        raise ValueError('gmm.em_iteration: D = %d, the state was built for D = %d' % (D, st.D))
     lse, _ = posteriors(table, shift, st.A, st.B, st.c, want_post=False)
     need = lib.abn_gmm_ws_bytes(T, st.K, D, n_ranges)
     if need < 0:

@@ -280,6 +280,9 @@ class _IntegrateFunction(torch.autograd.Function):
     def forward(ctx, spec, x1, x2, z1, z2, wparam):
         mode, kind, wf, wc, K, act, slot, holder = spec
         lib = _lib.load()
+        for t in (x1, x2, z1, z2):
+            if t is not None and (t.dim() != 2 or t.dtype != torch.float32):
+                raise ValueError('abnet3_amd: an integration unit takes [rows, d] float32 inputs, not %s %s' % (tuple(t.shape), t.dtype))
         x1, x2 = x1.contiguous(), x2.contiguous()
         z1 = z1.contiguous() if z1 is not None else None
         z2 = z2.contiguous() if z2 is not None else None
@@ -287,6 +290,10 @@ class _IntegrateFunction(torch.autograd.Function):
         rows, d1, d2 = x1.shape[0], x1.shape[1], x2.shape[1]
         if x2.shape[0] != rows:
             raise ValueError('abnet3_amd: the two modalities must have the same number of rows')
+        if mode == 'sum' and d2 != d1:
+            raise ValueError('abnet3_amd: a sum of two modalities needs inputs of one width, not %d and %d' % (d1, d2))
+        if any(z is not None and tuple(z.shape) != (rows, K) for z in (z1, z2)):
+            raise ValueError('abnet3_amd: the attention nets\' outputs must be [%d, %d]' % (rows, K))
         dout = d1 if mode == 'sum' else d1 + d2
         out = torch.empty(rows, dout, dtype=torch.float32, device=x1.device)
         w_out = torch.empty(rows, K, dtype=torch.float32, device=x1.device) if kind == _lib.W_ATTENTION else None

@@ -152,6 +152,7 @@ def assign(table, shift, m, b, prev=None, ids=None, changed=None, want_best=Fals
     if prev is not None:
         assert prev.shape == (T,) and prev.dtype == torch.int32 and prev.is_contiguous()
         assert changed is not None and changed.dtype == torch.int32 and changed.numel() >= 1
+    _lib.require_device(ids, prev, changed)
     best = torch.empty(T, dtype=torch.float32, device=table.device) if want_best else None
     if T:
         _lib.check(lib.abn_kmeans_assign(_lib.ptr(table), T, D, _lib.ptr(shift), _lib.ptr(m), _lib.ptr(b), K, _lib.ptr(prev),
@@ -237,7 +238,12 @@ def accumulate(table, shift, st, n_ranges=0, update=True):
     """abn_kmeans_accumulate and abn_kmeans_update for the ids in `st`; update=False leaves the centroids alone
     (statistics only).  Nothing is read back."""
     lib = _lib.load()
+    table = _check_table('kmeans.accumulate', table)
     T, D = table.shape
+    _lib.require_device(shift)
+    if D != st.D or shift.shape != (D,) or shift.dtype != torch.float32 or st.ids.shape != (T,):
+        raise ValueError('kmeans.accumulate: a [%d, %d] table (the state\'s ids and D) and shift [D] float32 are needed'
+                         % (st.ids.shape[0], st.D))
     need = _ws_bytes(T, st.K, D, n_ranges)
     if st.ws is None or st.ws.numel() < need:
         st.ws = torch.empty(max(need, 16), dtype=torch.uint8, device=table.device)

@@ -510,6 +510,8 @@ class _SoftmaxRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z):
         lib = _lib.load()
+        if z.dim() != 2 or z.dtype != torch.float32:
+            raise TypeError('abnet3_amd: the softmax head takes [n, width] float32 rows, not %s %s' % (tuple(z.shape), z.dtype))
         z = z.contiguous()
         _lib.require_device(z)
         out = torch.empty_like(z)
@@ -522,7 +524,10 @@ class _SoftmaxRows(torch.autograd.Function):
     def backward(ctx, da):
         lib = _lib.load()
         (a,) = ctx.saved_tensors
+        if da.shape != a.shape or da.dtype != torch.float32:
+            raise TypeError('abnet3_amd: the softmax head\'s gradient must be %s float32, not %s %s' % (tuple(a.shape), tuple(da.shape), da.dtype))
         da = da.contiguous()
+        _lib.require_device(da)
         dz = torch.empty_like(da)
         _lib.check(lib.abn_softmax_rows_backward(_lib.ptr(a), _lib.ptr(da), a.shape[0], a.shape[1],
                                                  _lib.ptr(dz), _lib.stream()),

@@ -160,6 +160,7 @@ def cosine_distance(x, y):
     f64 = torch.float64 if isinstance(x, torch.Tensor) else np.float64
     f32 = torch.float32 if isinstance(x, torch.Tensor) else np.float32
     assert (x.dtype == f64 and y.dtype == f64) or (x.dtype == f32 and y.dtype == f32)
+    assert x.ndim == 2 and y.ndim == 2, 'cosine_distance takes two [rows, D] matrices'
     lib = _lib.load()
     if x.dtype == f64:
         xd = (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).cuda().contiguous()
@@ -261,12 +262,17 @@ def dtw_align_batch(feats1, off1, n1, feats2, off2, n2):
     feats1/feats2: [rows, D] float32 device tensors (the same tensor may be
     passed twice).  off*/n*: host int arrays.  Returns DtwBatchResult."""
     lib = _lib.load()
-    _lib.require_device(feats1, feats2)
+    _lib.require_tensor('dtw_align_batch', 'feats1', feats1, torch.float32, 2)
+    _lib.require_tensor('dtw_align_batch', 'feats2', feats2, torch.float32, 2)
+    if feats1.shape[1] != feats2.shape[1]:
+        raise ValueError('dtw_align_batch: the two sides have different frame widths (%d and %d)' % (feats1.shape[1], feats2.shape[1]))
     off1 = np.ascontiguousarray(off1, dtype=np.int64)
     off2 = np.ascontiguousarray(off2, dtype=np.int64)
     n1 = np.ascontiguousarray(n1, dtype=np.int32)
     n2 = np.ascontiguousarray(n2, dtype=np.int32)
     P = len(n1)
+    if any(a.ndim != 1 or len(a) != P for a in (off1, off2, n1, n2)):
+        raise ValueError('dtw_align_batch: the pair table\'s columns must be four 1-d arrays of one length')
     dev = feats1.device
     stride = max(1, int(np.add(n1, n2, dtype=np.int64).max()) - 1) if P else 1
     both = torch.empty(2, P, stride, dtype=torch.int32, device=dev)      # (one allocation: the host's share of a call is wall time)
