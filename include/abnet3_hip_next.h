@@ -4,7 +4,11 @@
  * a full transition matrix), abnz_ (that model's max-product path), abnw_ (that path with a minimum unit duration) or abnv_
  * (the hard statistics of that model's Viterbi training) or abnu_ (explicit unit durations: the semi-Markov decoder and its
  * run statistics, ledger abnet3_amd._lib.NEXT6_SYMBOLS with tests/test_gpu_hmm_hsmm.py) or abnt_ (the in-batch contrastive
- * pair loss, ledger abnet3_amd._lib.NEXT7_SYMBOLS with tests/test_gpu_nce.py) and are
+ * pair loss, ledger abnet3_amd._lib.NEXT7_SYMBOLS with tests/test_gpu_nce.py) or abns_ (the pair-free histogram of
+ * within-cluster edit distances behind the full term scores, ledger abnet3_amd._lib.EVAL_SYMBOLS with
+ * tests/test_tde_full_host.py and tests/test_gpu_tde_full_contract.py -- a ledger of its own, not a NEXT<n>_SYMBOLS: the
+ * main argument-contract ledger enumerates those by name and demands a row in tests/test_gpu_arg_contract.py for each of
+ * their entries; folding this section into that ledger is for a change that may edit those files) and are
  * exported beside those of abnet3_hip.h, whose conventions they follow (extern "C", plain pointers and sizes, the ABN_E_*
  * return codes, abn_last_error, every refusal before any launch).
  * They do not change ABN_ABI_VERSION.  A later change folds them into abnet3_hip.h under their abn_ names, bumps the
@@ -256,6 +260,40 @@ int64_t abnt_nce_max_d(void);              /* host */
 int64_t abnt_nce_ws_bytes(int64_t B, int64_t D);      /* host */
 int abnt_nce_loss(const float* e1, const float* e2, const void* y, int y_dtype, const int32_t* groups, int64_t B, int64_t D,
                   float tau, int avg, float* loss, float* terms, float* de1, float* de2, void* ws, void* stream);
+
+/* ---- The histogram of within-cluster edit distances, without a pair table (csrc/edit_hist.hip) ------------------------------
+ * Prefix abns_; ledger abnet3_amd._lib.EVAL_SYMBOLS with tests/test_tde_full_host.py and tests/test_gpu_tde_full_contract.py
+ * (the top comment says why it is no NEXT<n>_SYMBOLS).  abnet3_amd/tde.py states the definition, tests/tde_full_np.py restates
+ * it.  sym [rows] int32 is the symbol table; token t (n_tokens of them, flat in cluster order) has the transcription
+ * sym[tok_off[t] .. tok_off[t] + tok_n[t]), lies in file tok_file[t] between tok_on[t] and tok_end[t] (float64 seconds) and
+ * belongs to group tok_group[t] (a speaker id; tok_group null: one group).  tok_off int64, tok_n / tok_file / tok_group
+ * int32, all DEVICE arrays.  cl_first [n_clusters + 1] int64 is a HOST array read during the call: cluster c holds the tokens
+ * cl_first[c] .. cl_first[c + 1].  For every unordered pair (a, b) of tokens of one cluster:
+ *     same file and min(tok_end[a], tok_end[b]) > max(tok_on[a], tok_on[b]):  nothing (the pair overlaps itself)
+ *     else counts[0] += 1;   both tok_n == 0:  counts[1] += 1 and nothing more
+ *     else hist[g][d][L] += 1 with d the Levenshtein distance (unit costs; a side of length 0 gives d = L), L = max(tok_n[a],
+ *     tok_n[b]) and g = (tok_group[a] != tok_group[b]).
+ * hist [2][M + 1][M + 1] int64 and counts [2] int64 are OVERWRITTEN: neither they nor the workspace need be cleared.  M,
+ * 1 .. abns_edit_hist_max_len() (256), is the caller's bound on every tok_n.  Integer atomics only (32-bit in LDS, flushed
+ * into 64-bit global ones long before a counter could wrap): the same counts for any grid, any order of the tokens inside a
+ * cluster and any order of the clusters.  ABN_EDIT_HIST_BLOCKS = 1 .. 65536 in the environment forces the number of
+ * workgroups (read at every call; default 4096).
+ *
+ * No array grows with the number of pairs.  Workspace: abns_edit_cluster_hist_ws_bytes(n_tokens, n_clusters, n_pairs) bytes
+ * (16 + 20 bytes per cluster rounded up to 256: the prefix of C(size, 2) over the clusters that hold a pair; n_tokens and
+ * n_pairs only have to be in range), 16-byte aligned, -1 with abn_last_error for negative sizes or more than 2^31 - 1 tokens
+ * or clusters.  Refusals by ABN_E_ARG before any launch: M out of range, a negative size, more than 2^31 - 1 tokens or
+ * clusters, a null pointer (sym may be null when rows == 0, the token columns when n_tokens == 0, tok_group always), a
+ * misaligned workspace, a cl_first that does not start at 0, end at n_tokens or that decreases; a short workspace:
+ * ABN_E_WORKSPACE.  The tokens are then checked by a launch of their own, for whose answer the call WAITS on the stream (the
+ * entry is not for graph capture): a token with tok_n outside 0 .. M or tok_off outside 0 .. rows - tok_n makes the call
+ * return ABN_E_ARG with hist and counts untouched (only the workspace has been written). */
+int64_t abns_edit_hist_max_len(void);      /* host */
+int64_t abns_edit_cluster_hist_ws_bytes(int64_t n_tokens, int64_t n_clusters, int64_t n_pairs);   /* host */
+int abns_edit_cluster_hist(const int32_t* sym, int64_t rows, const int64_t* tok_off, const int32_t* tok_n,
+                           const int32_t* tok_file, const double* tok_on, const double* tok_end, const int32_t* tok_group,
+                           int64_t n_tokens, const int64_t* cl_first, int64_t n_clusters, int64_t M, int64_t* hist,
+                           int64_t* counts, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
