@@ -222,6 +222,13 @@ EVAL_SYMBOLS = {
     'abns_edit_cluster_hist_ws_bytes': (_i64, [_i64, _i64, _i64]),
     'abns_edit_cluster_hist': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
 }
+# the section behind the correspondence autoencoder (prefix abnr_: the reconstruction loss and its gradient, csrc/recon.hip).
+# A ledger of its own for EVAL_SYMBOLS' reason; tests/test_cae_host.py and tests/test_gpu_cae_contract.py hold it to the contract
+CAE_SYMBOLS = {
+    'abnr_recon_max_d': (_i64, []),
+    'abnr_recon_ws_bytes': (_i64, [_i64, _i64]),
+    'abnr_recon_loss': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
 # abn_sd_count's conditions and the limits of abn_sd_collect / abn_sd_count (include/abnet3_hip.h)
 SD_CONDITION = {'all': 0, 'swdp': 1, 'swsp': 2}
 SD_MAX_N, SD_MAX_THR, SD_MAX_D = 1 << 22, 1 << 30, 4096
@@ -287,7 +294,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SYMBOLS.items()) + list(NEXT_SYMBOLS.items()) + list(NEXT2_SYMBOLS.items()) + \
             list(NEXT3_SYMBOLS.items()) + list(NEXT4_SYMBOLS.items()) + list(NEXT5_SYMBOLS.items()) + list(NEXT6_SYMBOLS.items()) + \
-            list(NEXT7_SYMBOLS.items()) + list(EVAL_SYMBOLS.items()):
+            list(NEXT7_SYMBOLS.items()) + list(EVAL_SYMBOLS.items()) + list(CAE_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, 'lib', 'obj')
 LIB = os.path.join(HERE, 'lib', 'libabnet3_hip.so')
-SOURCES = ['tower.hip', 'loss.hip', 'ops.hip', 'dtw.hip', 'fbank.hip', 'oneshot.hip', 'integrate.hip', 'abx.hip', 'knn.hip', 'sampler.hip', 'tcl.hip', 'search.hip', 'gmm.hip', 'local.hip', 'kmeans.hip', 'edit.hip', 'lsh.hip', 'eskmeans.hip', 'samediff.hip', 'hmm.hip', 'hmm_dense.hip', 'hmm_dense_vit.hip', 'hmm_hard.hip', 'hmm_hsmm.hip', 'nce.hip', 'edit_hist.hip']
+SOURCES = ['tower.hip', 'loss.hip', 'ops.hip', 'dtw.hip', 'fbank.hip', 'oneshot.hip', 'integrate.hip', 'abx.hip', 'knn.hip', 'sampler.hip', 'tcl.hip', 'search.hip', 'gmm.hip', 'local.hip', 'kmeans.hip', 'edit.hip', 'lsh.hip', 'eskmeans.hip', 'samediff.hip', 'hmm.hip', 'hmm_dense.hip', 'hmm_dense_vit.hip', 'hmm_hard.hip', 'hmm_hsmm.hip', 'nce.hip', 'edit_hist.hip', 'recon.hip']
 HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith('.h')) + [os.path.join('..', '..', 'include', h) for h in ('abnet3_hip.h', 'abnet3_hip_next.h')]
 FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-Wall',
          '-Wno-unused-function']

@@ -11,6 +11,8 @@ arithmetic (cosine similarity with eps=1e-6 or the two KL divergences, per-label
 transform, sum, /N) and its gradient run fused in one kernel (abn_pair_loss).
 InfoNCELoss (not in the reference) is the in-batch contrastive loss over the same surface: forward(input1, input2, y,
 groups=None); its B x B similarities never reach memory (abnt_nce_loss, csrc/nce.hip).
+CorrespondenceLoss (not in the reference either) is the reconstruction loss of model.CorrespondenceAutoencoder:
+forward(recon1, recon2, input1, input2, y), loss and gradient from one entry (abnr_recon_loss, csrc/recon.hip).
 """
 import torch
 import torch.nn as nn
@@ -293,6 +295,98 @@ class InfoNCELoss(LossBuilder):
         """(loss, [2, B, D] gradient w.r.t. (input1, input2)) without autograd."""
         assert input1.size() == input2.size(), 'Input not the same size'
         return _nce_raw(input1, input2, y, groups, self.temperature, self.avg, True)
+
+
+RECON_MODE = {'correspondence': 0, 'autoencoder': 1}
+
+
+def _recon_raw(r1, r2, x1, x2, y, mode, symmetric, avg, need_grad):
+    """abnr_recon_loss: (0-dim loss, [2, B, D] gradient of the loss w.r.t. (r1, r2) or None)."""
+    if mode not in RECON_MODE:
+        raise ValueError("abnet3_amd: CorrespondenceLoss mode = %r, supported 'correspondence', 'autoencoder'" % (mode,))
+    for what, t in (('recon1', r1), ('recon2', r2), ('input1', x1), ('input2', x2)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('abnet3_amd: CorrespondenceLoss %s must be a tensor, not %s' % (what, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise TypeError('abnet3_amd: CorrespondenceLoss %s must be float32, not %s' % (what, t.dtype))
+        if t.dim() != 2 or t.size() != r1.size():
+            raise ValueError('abnet3_amd: CorrespondenceLoss takes four [B, D] tensors of one shape (%s is %s, recon1 %s)'
+                             % (what, tuple(t.shape), tuple(r1.shape)))
+    if mode == 'autoencoder':
+        y = None                                   # (every row counts: the labels are not read)
+    elif not isinstance(y, torch.Tensor) or y.dtype not in _lib.Y_DTYPE:
+        raise TypeError('abnet3_amd: unsupported label dtype %s' % (y.dtype if isinstance(y, torch.Tensor) else type(y).__name__))
+    B, D = r1.shape
+    if y is not None and (y.dim() != 1 or y.numel() != B):
+        raise ValueError('abnet3_amd: %s labels for %d pairs' % (tuple(y.shape), B))
+    lib = _lib.load()
+    r1, r2, x1, x2 = r1.contiguous(), r2.contiguous(), x1.contiguous(), x2.contiguous()
+    y = y.contiguous() if y is not None else None
+    _lib.require_device(r1, r2, x1, x2, y)
+    if D > lib.abnr_recon_max_d():
+        raise ValueError('abnet3_amd: CorrespondenceLoss takes rows of at most %d columns (abnr_recon_max_d), got %d'
+                         % (lib.abnr_recon_max_d(), D))
+    need = lib.abnr_recon_ws_bytes(B, D)
+    if need < 0:
+        _lib.check(_lib.E_UNSUPPORTED, 'abnr_recon_ws_bytes')
+    loss = torch.empty((), dtype=torch.float32, device=r1.device)
+    dr = torch.empty(2, B, D, dtype=torch.float32, device=r1.device) if need_grad else None
+    ws = torch.empty(need, dtype=torch.uint8, device=r1.device)          # need not be cleared
+    _lib.check(lib.abnr_recon_loss(
+        _lib.ptr(r1), _lib.ptr(r2), _lib.ptr(x1), _lib.ptr(x2), _lib.ptr(y), _lib.Y_DTYPE[y.dtype] if y is not None else 0, B, D,
+        RECON_MODE[mode], int(bool(symmetric)), int(bool(avg)), _lib.ptr(loss), None, _lib.ptr(dr[0]) if need_grad else None,
+        _lib.ptr(dr[1]) if need_grad else None, _lib.ptr(ws), _lib.stream()), 'abnr_recon_loss')
+    return loss, dr
+
+
+class _ReconFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r1, r2, x1, x2, y, mode, symmetric, avg):
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        loss, ctx.dr = _recon_raw(r1, r2, x1, x2, y, mode, symmetric, avg, need_grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dr = ctx.dr
+        if dr is None:
+            return None, None, None, None, None, None, None, None
+        unit = _UNIT.get(g.device)                    # (the cached unit seed: _PairLossFunction.backward)
+        if unit is None or g.data_ptr() != unit.data_ptr():
+            dr = dr * g
+        return dr[0], dr[1], None, None, None, None, None, None
+
+
+class CorrespondenceLoss(LossBuilder):
+    """The reconstruction loss of the correspondence autoencoder (Kamper et al. 2015; not part of the reference):
+    forward(recon1, recon2, input1, input2, y) with recon = network(input1, input2) of a CorrespondenceAutoencoder.
+
+    With s = 1 if symmetric else 0:
+        mode 'correspondence':  R = {i : y[i] == 1},  t[i] = |recon1[i] - input2[i]|^2 + s |recon2[i] - input1[i]|^2
+                                (each tower reconstructs its aligned PARTNER; a 'different' row carries no target and no gradient)
+        mode 'autoencoder':     R = every row, y is ignored,  t[i] = |recon1[i] - input1[i]|^2 + s |recon2[i] - input2[i]|^2
+                                (the pretraining pass: each tower reconstructs its own input)
+        loss = sum over R of t[i], divided by |R| D (1 + s) when avg: the mean squared error per reconstructed element.
+    |R| = 0 gives loss 0 and zero gradients for either avg (InfoNCELoss's decision, for its reason: a batch without a 'same'
+    pair is an ordinary event for a sampled loader).  `mode` may be reassigned between passes (TrainerCorrespondence.pretrain
+    does).  Loss and both gradients come from one C entry (abnr_recon_loss, csrc/recon.hip), float64 inside, the same bits
+    from call to call.  The inputs get no gradient.  Trains through autograd (the trainer's direct and planned steps do not
+    know this loss and step aside).  Nothing here is tuned or measured on real speech."""
+
+    def __init__(self, avg=True, symmetric=True, mode='correspondence', *args, **kwargs):
+        super(CorrespondenceLoss, self).__init__(*args, **kwargs)
+        if mode not in RECON_MODE:
+            raise ValueError("abnet3_amd: CorrespondenceLoss mode = %r, supported 'correspondence', 'autoencoder'" % (mode,))
+        self.avg = avg
+        self.symmetric = symmetric
+        self.mode = mode
+
+    def forward(self, recon1, recon2, input1, input2, y=None):
+        return _ReconFunction.apply(recon1, recon2, input1, input2, y, self.mode, self.symmetric, self.avg)
+
+    def value_and_grad(self, recon1, recon2, input1, input2, y=None):
+        """(loss, [2, B, D] gradient w.r.t. (recon1, recon2)) without autograd."""
+        return _recon_raw(recon1, recon2, input1, input2, y, self.mode, self.symmetric, self.avg, True)
 
 
 class weighted_loss_multi(LossBuilder):

@@ -1182,6 +1182,142 @@ class SiameseMultitaskNetwork(_HipNetwork):
         torch.save(self.state_dict(), self.output_path + epoch + '.pth')
 
 
+class CorrespondenceAutoencoder(_HipNetwork):
+    """The correspondence autoencoder (Kamper et al. 2015; Renshaw et al. 2015; not part of the reference): an MLP
+    autoencoder whose two towers share every weight.  Pretrained to reconstruct its own input (loss.CorrespondenceLoss,
+    mode 'autoencoder'), then trained to reconstruct frame x2 from its DTW-aligned partner x1 (mode 'correspondence');
+    the bottleneck -- forward_once -- is the embedding.
+
+    The encoder IS a SiameseNetwork: the same modules under the same attribute names (input_emb, hidden_layers,
+    output_layer) built in the same order, so its state_dict keys are SiameseNetwork's and save_encoder's file loads into
+    one.  The decoder follows: decoder_layers, `num_decoder_layers` blocks Linear -> Dropout -> [BatchNorm1d] -> act
+    (default num_hidden_layers + 1, the mirror of the encoder), and recon_layer, Linear(hidden_dim, input_dim) with no
+    BatchNorm, no dropout and no activation.  No tied weights, no input corruption, no layer-wise pretraining.
+
+    Three launch sequences per forward, both towers in each (n_calls = 2: BatchNorm statistics per tower call): the encoder,
+    the decoder's hidden blocks, recon_layer.  recon_layer is a sequence of its own because a tower descriptor carries ONE
+    BatchNorm flag and ONE dropout setting for all its layers, and this layer has neither."""
+
+    def __init__(self, input_dim=None, num_hidden_layers=None, hidden_dim=None,
+                 output_dim=None, p_dropout=0.1, batch_norm=False,
+                 type_init='xavier_uni', activation_layer=None,
+                 output_path=None, last_non_linearity="default", num_decoder_layers=None):
+        super(CorrespondenceAutoencoder, self).__init__()
+        assert activation_layer in ('relu', 'sigmoid', 'tanh')
+        assert type_init in ('xavier_uni', 'xavier_normal', 'orthogonal')
+        assert type(input_dim) == int, 'input dim should be int'
+        assert type(hidden_dim) == int, 'hidden dim should be int'
+        assert type(num_hidden_layers) == int, 'num hidden lay should be int'
+        assert type(output_dim) == int, 'output dim should be int'
+        assert last_non_linearity in ('default', None, 'relu', 'sigmoid', 'tanh'), 'the bottleneck takes an elementwise activation'
+        if num_decoder_layers is None:
+            num_decoder_layers = num_hidden_layers + 1
+        assert type(num_decoder_layers) == int and num_decoder_layers >= 1, 'num decoder lay should be int >= 1'
+        assert num_hidden_layers + 2 <= _lib.MAX_LAYERS and num_decoder_layers <= _lib.MAX_LAYERS, 'too many layers'
+
+        self.input_dim = input_dim
+        self.num_hidden_layers = num_hidden_layers
+        self.hidden_dim = hidden_dim
+        self.output_dim = output_dim
+        self.activation_layer = activation_layer
+        self.batch_norm = batch_norm
+        self.type_init = type_init
+        self.last_non_linearity = last_non_linearity
+        self.p_dropout = p_dropout
+        self.num_decoder_layers = num_decoder_layers
+
+        activation = activation_functions[activation_layer]
+
+        def block(n_in, n_out):
+            layers = [nn.Linear(n_in, n_out), nn.Dropout(p=p_dropout)]
+            if self.batch_norm:
+                layers.append(nn.BatchNorm1d(n_out))
+            return layers
+
+        # the encoder: SiameseNetwork's modules in SiameseNetwork's order (the same keys, the same RNG consumption)
+        self.input_emb = nn.Sequential(*(block(input_dim, hidden_dim) + [activation()]))
+        hidden = []
+        for idx in range(self.num_hidden_layers):
+            hidden += block(hidden_dim, hidden_dim) + [activation()]
+        self.hidden_layers = nn.Sequential(*hidden)
+        output_layer = block(hidden_dim, output_dim)
+        if self.last_non_linearity == "default":
+            output_layer.append(activation())
+            self._last_act = activation_layer
+        elif self.last_non_linearity is None:
+            self._last_act = 'none'
+        else:
+            output_layer.append(activation_functions[self.last_non_linearity]())
+            self._last_act = self.last_non_linearity
+        self.output_layer = nn.Sequential(*output_layer)
+        # the decoder
+        decoder = []
+        for idx in range(num_decoder_layers):
+            decoder += block(output_dim if idx == 0 else hidden_dim, hidden_dim) + [activation()]
+        self.decoder_layers = nn.Sequential(*decoder)
+        self.recon_layer = nn.Linear(hidden_dim, input_dim)
+        self.output_path = output_path
+        self.apply(self.init_weight_method)
+        self._init_hip_state()
+
+    ENCODER_PREFIXES = ('input_emb.', 'hidden_layers.', 'output_layer.')
+
+    def init_weight_method(self, layer):
+        if isinstance(layer, nn.Linear):
+            init_func = init_functions[self.type_init]
+            init_func(layer.weight.data,
+                      gain=nn.init.calculate_gain(self.activation_layer))
+            layer.bias.data.fill_(0.0)
+            self._weights_rewritten()
+
+    def _segments(self):
+        act, bn = self.activation_layer, self.batch_norm
+        enc = _blocks_of(self.input_emb, self.hidden_layers, self.output_layer)
+        dec = _blocks_of(self.decoder_layers)
+        return [_Segment(self, enc, 0, act, self._last_act, bn),
+                _Segment(self, dec, len(enc), act, act, bn),
+                _Segment(self, [(self.recon_layer, None)], len(enc) + len(dec), act, 'none', False)]
+
+    def _forward(self, x1, x2, decode):
+        enc, dec, recon = self._segment_list()
+        n_calls = 1 if x2 is None else 2
+        rows = x1.shape[0] * n_calls
+        gp = _GradPass(self)
+        masks = self._draw_dropout_masks(rows, x1.device) if self.training else None
+        code = self._run(enc, gp, masks, x1, x2, n_calls, False)
+        if not decode:
+            return code
+        h = self._run(dec, gp, masks, code, None, n_calls, False)
+        return self._run(recon, gp, None, h, None, n_calls, x2 is not None)      # (no dropout on recon_layer)
+
+    def forward_once(self, x):
+        """The bottleneck code of x: the embedding (what EmbedderSiamese reads)."""
+        return self._forward(x, None, False)
+
+    def reconstruct(self, x):
+        """decoder(encoder(x))."""
+        return self._forward(x, None, True)
+
+    def forward(self, input1, input2):
+        """(recon1, recon2): both towers through each of the three launch sequences at once."""
+        return self._forward(input1, input2, True)
+
+    def encoder_state_dict(self):
+        """The encoder's part of state_dict(), under SiameseNetwork's keys (copies, not views of the flat buffer)."""
+        return type(self.state_dict())((k, v.detach().clone()) for k, v in self.state_dict().items()
+                                       if k.startswith(self.ENCODER_PREFIXES))
+
+    def save_encoder(self, path):
+        """Writes the encoder alone: SiameseNetwork(<the same shape>).load_network(path) takes the file as it is (an ABnet
+        initialised from a cAE)."""
+        torch.save(self.encoder_state_dict(), path)
+
+    def save_network(self, epoch=''):
+        torch.save(self.state_dict(), self.output_path + str(epoch) + '.pth')
+
+    def load_network(self, network_path=None):
+        self.load_state_dict(torch.load(network_path))
+
 
 class _WeightsHolder(object):
     """Where abn_integrate_forward's w [rows, K] of the last forward lands (BiWeightedDeepLearnt.get_weights)."""

@@ -1065,6 +1065,47 @@ class TrainerSiameseMultitask(TrainerSiamese):
         return static, lambda: self.give_batch_to_network(tuple(static))
 
 
+class TrainerCorrespondence(TrainerSiamese):
+    """Trainer of a CorrespondenceAutoencoder with a CorrespondenceLoss (neither is in the reference): batches are the
+    Siamese loaders' (X1, X2, y); the loss sees the reconstructions AND the inputs.  Every step goes through
+    give_batch_to_network and autograd with the flat optimizer (no autograd-free step, no planned pass: _direct_ok() is
+    false for an overridden give_batch_to_network); single process."""
+
+    def __init__(self, *args, **kwargs):
+        super(TrainerCorrespondence, self).__init__(*args, **kwargs)
+        from .model import CorrespondenceAutoencoder
+        assert type(self.network) == CorrespondenceAutoencoder
+
+    def give_batch_to_network(self, batch):
+        X_batch1, X_batch2, y_batch = batch
+        X_batch1 = X_batch1.cuda(non_blocking=True)
+        X_batch2 = X_batch2.cuda(non_blocking=True)
+        y_batch = y_batch.cuda(non_blocking=True)
+        recon1, recon2 = self.network(X_batch1, X_batch2)
+        return self.loss(recon1, recon2, X_batch1, X_batch2, y_batch)
+
+    def _graph_inputs(self, example_batch):
+        self._static_blob = None
+        static = [t.cuda().clone() for t in example_batch]
+        return static, lambda: self.give_batch_to_network(tuple(static))
+
+    def pretrain(self, num_epochs):
+        """`num_epochs` passes of optimize_model(True) with the loss in 'autoencoder' mode (every row reconstructs itself,
+        the labels are ignored), then the loss's own mode again.  Returns the passes' mean training losses."""
+        if not hasattr(self, 'train_losses'):
+            self.train_losses, self.dev_losses = [], []
+        mode, first = self.loss.mode, len(self.train_losses)
+        self.loss.mode = 'autoencoder'
+        self._forget_captured_steps()            # (a captured step holds the mode it was captured in)
+        try:
+            for _ in range(num_epochs):
+                self.optimize_model(True)
+        finally:
+            self.loss.mode = mode
+            self._forget_captured_steps()
+        return self.train_losses[first:]
+
+
 class MultimodalTrainer(TrainerSiamese):
     """Multimodal Trainer class for ABnet3 (abnet3/trainer.py:281-365): batches are ([X1_m for m], [X2_m for m],
     y) and every step goes through give_batch_to_network and autograd (no autograd-free step, planned pass or

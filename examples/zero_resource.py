@@ -5,7 +5,7 @@ Siamese training -> embedding -> ABX.  The corpus' word labels are used twice on
 mined pairs, and the ABX item file ("phones" = word types).
 
     python examples/zero_resource.py [--utts 40] [--epochs 3] [--out /tmp/abnet3_zr] [--softmax] [--tcl] [--qbe]
-                                     [--infonce] [--temperature T]
+                                     [--infonce] [--temperature T] [--cae] [--cae-pretrain N] [--cae-init-abnet]
                                      [--gmm] [--gmm-components 64] [--hmm-stay P|fit] [--hmm-fit N] [--hmm-trans N] [--hmm-decode] [--no-network] [--terms] [--terms-theta T]
                                      [--prefilter] [--alignment FILE] [--word-alignment FILE]
                                      [--kmeans] [--kmeans-clusters 50] [--kmeans-penalty P] [--kmeans-min-duration S]
@@ -17,6 +17,12 @@ error is printed under both frame distances, the angular cosine and the symmetri
 --infonce trains with the in-batch contrastive loss (InfoNCELoss, temperature T, default 0.1, untuned) instead of
 coscos2: the 'same' pairs of a batch are the anchors and every other row of the batch is a negative.  It composes with
 --tcl and with the mined-pairs route; it is not combined with --softmax.
+--cae trains a correspondence autoencoder (CorrespondenceAutoencoder + CorrespondenceLoss through TrainerCorrespondence)
+on the same pairs instead of the Siamese network -- each frame reconstructs its aligned partner -- and embeds its bottleneck;
+--cae-pretrain N first runs N passes in which every frame reconstructs itself; --cae-init-abnet then trains the usual
+Siamese network starting from the cAE's encoder (save_encoder's file) and embeds that one.  Untuned.  Under --cae the ABX of
+the embeddings reads exactly parallel frames as distance 0 (ABXEvaluator(parallel='zero')): a network started from the cAE's
+encoder gave some frames exactly parallel embeddings on this corpus, and the default rule drops every pair that holds two such frames.
 --tcl skips the discovery step altogether: TemporalCoherenceDataLoader trains on temporal-coherence pairs (a frame and
 its neighbour against frames 15-30 steps away, drawn on the GPU), and the dev pairs that early stopping needs are made
 the same way from the last fifth of the files -- a stretch of frames against itself one frame later ("same") and
@@ -78,14 +84,14 @@ from abnet3_amd.features import FeaturesGenerator                 # noqa: E402
 from abnet3_amd.gmm import GmmPosteriorgram                       # noqa: E402
 from abnet3_amd.hmm import StickyHmmPosteriorgram, TransitionHmmPosteriorgram, sticky_transitions      # noqa: E402
 from abnet3_amd.kmeans import KMeansQuantizer, bitrate, unit_sequences   # noqa: E402
-from abnet3_amd.loss import InfoNCELoss, KLLoss, coscos2                       # noqa: E402
-from abnet3_amd.model import SiameseNetwork                       # noqa: E402
+from abnet3_amd.loss import CorrespondenceLoss, InfoNCELoss, KLLoss, coscos2    # noqa: E402
+from abnet3_amd.model import CorrespondenceAutoencoder, SiameseNetwork   # noqa: E402
 from abnet3_amd.prefilter import TermPrefilter                   # noqa: E402
 from abnet3_amd.samediff import SameDifferentEvaluator            # noqa: E402
 from abnet3_amd.sampler import SamplerClusterSiamese              # noqa: E402
 from abnet3_amd.tde import TermEvaluator, full_summary, summary                 # noqa: E402
 from abnet3_amd.terms import TermDiscoverer                       # noqa: E402
-from abnet3_amd.trainer import TrainerSiamese                     # noqa: E402
+from abnet3_amd.trainer import TrainerCorrespondence, TrainerSiamese   # noqa: E402
 from end_to_end import synth_corpus                               # noqa: E402
 
 
@@ -342,7 +348,7 @@ def eskmeans_route(corpus, unit_ids, n_clusters, tokens=None, tolerance=0.03, al
 
 
 def kmeans_route(corpus, items, label, n_clusters, penalty=None, esk_clusters=None, tokens=None, min_duration=1, alignment=None,
-                 word_alignment=None):
+                 word_alignment=None, parallel='drop'):
     """frames -> KMeansQuantizer.fit -> unit ids (bitrate) and quantised frames (ABX) beside the continuous ones; with a
     penalty the same for the penalised segmentation (min_duration: its units last at least that many frames), and with
     esk_clusters ES-KMeans over its landmarks."""
@@ -350,7 +356,7 @@ def kmeans_route(corpus, items, label, n_clusters, penalty=None, esk_clusters=No
     seconds = 0.01 * corpus.total
     rate = bitrate(unit_sequences(q.predict(corpus), collapse=False), seconds)
     merged = bitrate(unit_sequences(q.predict(corpus)), seconds)
-    cont = ABXEvaluator(items, corpus).run('within')
+    cont = ABXEvaluator(items, corpus, parallel=parallel).run('within')
     # (quantised frames are identical by construction: parallel='zero' reads a cosine that rounds above 1 as distance 0
     # where the reference's rule drops the pair)
     quant = 'quantised %.2f %%' % ABXEvaluator(items, q.quantize(corpus), parallel='zero').run('within').error
@@ -380,6 +386,9 @@ def main():
     ap.add_argument('--tcl', action='store_true', help='no mined pairs: train on temporal-coherence pairs')
     ap.add_argument('--infonce', action='store_true', help='train with InfoNCELoss (in-batch negatives) instead of coscos2')
     ap.add_argument('--temperature', type=float, default=0.1, help='with --infonce: the temperature (untuned)')
+    ap.add_argument('--cae', action='store_true', help='train a correspondence autoencoder on the pairs instead of the Siamese network; embed its bottleneck')
+    ap.add_argument('--cae-pretrain', type=int, default=0, metavar='N', help='with --cae: N autoencoder passes first (every frame reconstructs itself)')
+    ap.add_argument('--cae-init-abnet', action='store_true', help='with --cae: then train the Siamese network from the cAE\'s encoder and embed that')
     ap.add_argument('--qbe', action='store_true', help='after embedding: search a few planted words by example, print MAP')
     ap.add_argument('--gmm', action='store_true', help='the untrained baseline: GMM posteriorgrams of the filterbanks, ABX (kl)')
     ap.add_argument('--gmm-components', type=int, default=64)
@@ -439,6 +448,12 @@ def main():
         ap.error('--hmm-decode decodes the HMM of --hmm-stay or --hmm-fit')
     if args.infonce and args.softmax:
         ap.error('--infonce is a loss over cosine similarities; --softmax trains posteriorgrams with KLLoss')
+    if (args.cae_pretrain or args.cae_init_abnet) and not args.cae:
+        ap.error('--cae-pretrain and --cae-init-abnet belong to --cae')
+    if args.cae and args.softmax:
+        ap.error('--cae reconstructs filterbanks; --softmax trains posteriorgrams with KLLoss')
+    if args.cae and args.infonce and not args.cae_init_abnet:
+        ap.error('--infonce is the Siamese network\'s loss: with --cae it needs --cae-init-abnet')
     esk_k = args.eskmeans_clusters if args.eskmeans else None
     rng = np.random.default_rng(0)
     random.seed(0)
@@ -491,24 +506,40 @@ def main():
         dl = PairsDataLoader(pairs_path, None, map_path, batch_size=8, train_iterations=200, test_iterations=50,
                              split_method='files')
         dl.set_data(fb, times)
-    net = SiameseNetwork(input_dim=40, num_hidden_layers=1, hidden_dim=200, output_dim=40, p_dropout=0.0,
-                         activation_layer='sigmoid', output_path=args.out + '_network',
-                         last_non_linearity='softmax' if args.softmax else 'default')
-    trainer = TrainerSiamese(network=net, loss=KLLoss(avg=False) if args.softmax else InfoNCELoss(args.temperature, avg=False) if args.infonce else coscos2(avg=False),
+    shape = dict(input_dim=40, num_hidden_layers=1, hidden_dim=200, output_dim=40, p_dropout=0.0, activation_layer='sigmoid')
+    cae = None
+    if args.cae:
+        cae = CorrespondenceAutoencoder(output_path=args.out + '_cae', **shape)
+        cae_trainer = TrainerCorrespondence(network=cae, loss=CorrespondenceLoss(avg=True), num_epochs=args.epochs, patience=30,
+                                            optimizer_type='adadelta', lr=0.5, dataloader=dl, log_dir=args.out + '_runs')
+        if args.cae_pretrain:
+            print('cAE pretraining losses per pass:', ['%.4f' % v for v in cae_trainer.pretrain(args.cae_pretrain)])
+        cae_trainer.train()
+        print('cAE dev losses per epoch:', ['%.4f' % v for v in cae_trainer.dev_losses])
+    net = SiameseNetwork(output_path=args.out + '_network', last_non_linearity='softmax' if args.softmax else 'default', **shape)
+    if args.cae_init_abnet:
+        cae.save_encoder(args.out + '_cae_encoder.pth')
+        net.load_network(args.out + '_cae_encoder.pth')
+    if cae is not None and not args.cae_init_abnet:
+        net = cae                                        # (EmbedderSiamese reads output_dim and forward_once: the bottleneck)
+    trainer = None if net is cae else TrainerSiamese(network=net, loss=KLLoss(avg=False) if args.softmax else InfoNCELoss(args.temperature, avg=False) if args.infonce else coscos2(avg=False),
                              num_epochs=args.epochs, patience=30,
                              optimizer_type='adadelta', lr=0.5, dataloader=dl, log_dir=args.out + '_runs')
-    trainer.train()
-    print('dev losses per epoch:', ['%.2f' % v for v in trainer.dev_losses])
+    if trainer is not None:
+        trainer.train()
+        print('dev losses per epoch:', ['%.2f' % v for v in trainer.dev_losses])
 
     names = list(fb)
-    emb = EmbedderSiamese(network=net, network_path=args.out + '_network.pth', feature_path=None,
+    emb = EmbedderSiamese(network=net, network_path=net.output_path + '.pth', feature_path=None,
                           output_path=None).embed_features([fb[k] for k in names])
     keep, items = word_items(tokens)
     for label, feats in (('filterbanks', fb), ('embeddings', dict(zip(names, emb)))):
         corpus = DeviceCorpus({k: np.asarray(feats[k], dtype=np.float32) for k in names}, times)
         if args.samediff:
             samediff_lines(corpus, keep, label, vectors=label == 'embeddings')
-        r = ABXEvaluator(items, corpus).run('within')
+        # (--cae: exactly parallel frames are at distance 0 instead of dropping the pair: the docstring says why)
+        parallel = 'zero' if args.cae and label == 'embeddings' else 'drop'
+        r = ABXEvaluator(items, corpus, parallel=parallel).run('within')
         if args.softmax and label == 'embeddings':
             kl = ABXEvaluator(items, corpus, distance='kl').run('within')
             print('ABX error on %s: cosine %.2f %%, kl %.2f %% (%d triplets)' % (label, r.error, kl.error, r.n_triplets))
@@ -518,7 +549,7 @@ def main():
             qbe_search(corpus, keep, names, label, 'kl' if args.softmax and label == 'embeddings' else 'cosine')
         if args.kmeans and label == 'embeddings':
             kmeans_route(corpus, items, label, args.kmeans_clusters, args.kmeans_penalty, esk_k, tokens, args.kmeans_min_duration,
-                         args.alignment, args.word_alignment)
+                         args.alignment, args.word_alignment, parallel=parallel)
     if gmm_line:
         print(gmm_line)
 

@@ -8,7 +8,9 @@
  * within-cluster edit distances behind the full term scores, ledger abnet3_amd._lib.EVAL_SYMBOLS with
  * tests/test_tde_full_host.py and tests/test_gpu_tde_full_contract.py -- a ledger of its own, not a NEXT<n>_SYMBOLS: the
  * main argument-contract ledger enumerates those by name and demands a row in tests/test_gpu_arg_contract.py for each of
- * their entries; folding this section into that ledger is for a change that may edit those files) and are
+ * their entries; folding this section into that ledger is for a change that may edit those files) or abnr_ (the
+ * reconstruction loss of the correspondence autoencoder, ledger abnet3_amd._lib.CAE_SYMBOLS with tests/test_cae_host.py and
+ * tests/test_gpu_cae_contract.py -- a ledger of its own for the same reason) and are
  * exported beside those of abnet3_hip.h, whose conventions they follow (extern "C", plain pointers and sizes, the ABN_E_*
  * return codes, abn_last_error, every refusal before any launch).
  * They do not change ABN_ABI_VERSION.  A later change folds them into abnet3_hip.h under their abn_ names, bumps the
@@ -294,6 +296,39 @@ int abns_edit_cluster_hist(const int32_t* sym, int64_t rows, const int64_t* tok_
                            const int32_t* tok_file, const double* tok_on, const double* tok_end, const int32_t* tok_group,
                            int64_t n_tokens, const int64_t* cl_first, int64_t n_clusters, int64_t M, int64_t* hist,
                            int64_t* counts, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- The reconstruction loss of the correspondence autoencoder and its gradient (csrc/recon.hip) ----------------------------
+ * Prefix abnr_; ledger abnet3_amd._lib.CAE_SYMBOLS with tests/test_cae_host.py and tests/test_gpu_cae_contract.py (the top
+ * comment says why it is no NEXT<n>_SYMBOLS).  abnet3_amd/loss.py (CorrespondenceLoss) states the definition,
+ * tests/cae_np.py restates it.  r1, r2 [B][D] fp32: the decoder's outputs for tower 1 and tower 2; x1, x2 [B][D] fp32: the
+ * network's inputs; y [B] with abn_pair_loss's dtype codes (0 int8, 1 int32, 2 int64, 3 float32, 4 float64), "same" is
+ * y == 1.  With s = (symmetric != 0):
+ *     mode 0 (correspondence): R = {i : y[i] == 1},  t[i] = |r1[i] - x2[i]|^2 + s |r2[i] - x1[i]|^2
+ *     mode 1 (autoencoder):    R = every row, y is not read (it may be null),  t[i] = |r1[i] - x1[i]|^2 + s |r2[i] - x2[i]|^2
+ *     loss = c sum over R of t[i],  c = 1, or with avg 1 / (|R| D (1 + s)): the mean squared error per reconstructed element;
+ *     |R| = 0: loss 0 and zero gradients for either avg.
+ * loss [1] fp32; terms [B] fp32 or null: t[i], exactly 0 for a row outside R; dr1, dr2 [B][D] fp32, both or neither (both
+ * null: value only, the same loss bits): the gradient of loss with respect to r1 and r2 -- 2 c (r - target) on a row of R,
+ * exact zeros elsewhere, dr2 all zeros when symmetric == 0.  EVERY element of loss, terms, dr1 and dr2 is overwritten.
+ *
+ * One half-wave per row; differences, row sums and the total in float64, each rounded to fp32 once.  Under avg in mode 0 the
+ * rows of R are counted on the device by a launch of the call's own: no read-back and no stream wait, the entry can be
+ * captured into a graph.  No floating-point atomics and no ticket counter; every sum has one order that depends on (B, D)
+ * alone: the same bits from call to call, for aligned and misaligned tables, and for any grid.  ABN_RECON_ROWS = 1 .. 4096 in
+ * the environment forces the rows one workgroup walks (read at every call; default 8, a row per half-wave).  Swapping
+ * (r1, x2, dr1) with (r2, x1, dr2) under symmetric != 0 gives the same loss bits and the swapped gradients.  16-byte loads
+ * and stores only where D % 4 == 0 and r1, r2, x1, x2 (and dr1, dr2 when given) are 16-byte aligned.
+ *
+ * D <= abnr_recon_max_d() (16384), B <= 2^22.  Workspace: abnr_recon_ws_bytes(B, D) bytes (16 + 8 B: the scale and one
+ * float64 per row), 16-byte aligned, -1 with abn_last_error for refused sizes.  It need not be cleared.  Two launches, three
+ * under avg in mode 0.  Refusals, all before any launch: B < 1 or D < 1: ABN_E_ARG; D or B beyond the limits:
+ * ABN_E_UNSUPPORTED; null r1, r2, x1, x2, loss or ws, a null y in mode 0, a y_dtype outside 0 .. 4, a mode outside 0 .. 1,
+ * only one of dr1 / dr2, a misaligned workspace: ABN_E_ARG. */
+int64_t abnr_recon_max_d(void);            /* host */
+int64_t abnr_recon_ws_bytes(int64_t B, int64_t D);    /* host */
+int abnr_recon_loss(const float* r1, const float* r2, const float* x1, const float* x2, const void* y, int y_dtype, int64_t B,
+                    int64_t D, int mode, int symmetric, int avg, float* loss, float* terms, float* dr1, float* dr2, void* ws,
+                    void* stream);
 
 #ifdef __cplusplus
 }
