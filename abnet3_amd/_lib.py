@@ -229,6 +229,15 @@ CAE_SYMBOLS = {
     'abnr_recon_ws_bytes': (_i64, [_i64, _i64]),
     'abnr_recon_loss': (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# the section behind soft-DTW word-pair training (prefix abnq_: the batched soft-DTW forward and backward, csrc/softdtw.hip).
+# A ledger of its own for EVAL_SYMBOLS' reason; tests/test_sdtw_host.py and tests/test_gpu_sdtw_contract.py hold it to the contract
+SDTW_SYMBOLS = {
+    'abnq_softdtw_max_len': (_i64, []),
+    'abnq_softdtw_max_d': (_i64, []),
+    'abnq_softdtw_ws_bytes': (_i64, [_vp, _vp, _i64, _i64, C.c_int]),
+    'abnq_softdtw_forward': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _i64, C.c_int, _vp]),
+    'abnq_softdtw_backward': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
+}
 # abn_sd_count's conditions and the limits of abn_sd_collect / abn_sd_count (include/abnet3_hip.h)
 SD_CONDITION = {'all': 0, 'swdp': 1, 'swsp': 2}
 SD_MAX_N, SD_MAX_THR, SD_MAX_D = 1 << 22, 1 << 30, 4096
@@ -294,7 +303,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SYMBOLS.items()) + list(NEXT_SYMBOLS.items()) + list(NEXT2_SYMBOLS.items()) + \
             list(NEXT3_SYMBOLS.items()) + list(NEXT4_SYMBOLS.items()) + list(NEXT5_SYMBOLS.items()) + list(NEXT6_SYMBOLS.items()) + \
-            list(NEXT7_SYMBOLS.items()) + list(EVAL_SYMBOLS.items()) + list(CAE_SYMBOLS.items()):
+            list(NEXT7_SYMBOLS.items()) + list(EVAL_SYMBOLS.items()) + list(CAE_SYMBOLS.items()) + list(SDTW_SYMBOLS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -14,16 +14,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, 'lib', 'obj')
 LIB = os.path.join(HERE, 'lib', 'libabnet3_hip.so')
-SOURCES = ['tower.hip', 'loss.hip', 'ops.hip', 'dtw.hip', 'fbank.hip', 'oneshot.hip', 'integrate.hip', 'abx.hip', 'knn.hip', 'sampler.hip', 'tcl.hip', 'search.hip', 'gmm.hip', 'local.hip', 'kmeans.hip', 'edit.hip', 'lsh.hip', 'eskmeans.hip', 'samediff.hip', 'hmm.hip', 'hmm_dense.hip', 'hmm_dense_vit.hip', 'hmm_hard.hip', 'hmm_hsmm.hip', 'nce.hip', 'edit_hist.hip', 'recon.hip']
+SOURCES = ['tower.hip', 'loss.hip', 'ops.hip', 'dtw.hip', 'fbank.hip', 'oneshot.hip', 'integrate.hip', 'abx.hip', 'knn.hip', 'sampler.hip', 'tcl.hip', 'search.hip', 'gmm.hip', 'local.hip', 'kmeans.hip', 'edit.hip', 'lsh.hip', 'eskmeans.hip', 'samediff.hip', 'hmm.hip', 'hmm_dense.hip', 'hmm_dense_vit.hip', 'hmm_hard.hip', 'hmm_hsmm.hip', 'nce.hip', 'edit_hist.hip', 'recon.hip', 'softdtw.hip']
 HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith('.h')) + [os.path.join('..', '..', 'include', h) for h in ('abnet3_hip.h', 'abnet3_hip_next.h')]
 FLAGS = ['-O3', '-std=c++17', '--offload-arch=gfx950', '-fPIC', '-Wall',
          '-Wno-unused-function']
 # translation units whose float arithmetic must be identical on CPU and GPU
 # (DTW distances, the integration unit's weighted sums, ABX's DTW costs, the search's, the local alignment's, the
 # segmental DP's segment costs: no fused-multiply-add contraction; nce.hip: its two sweeps must form the SAME rounded logit
-# z = s / tau before they subtract a log-sum-exp from it)
+# z = s / tau before they subtract a log-sum-exp from it; softdtw.hip: it includes dtw_wave.h)
 STRICT_FP = {'dtw.hip': ['-ffp-contract=off'], 'integrate.hip': ['-ffp-contract=off'], 'abx.hip': ['-ffp-contract=off'],
-             'search.hip': ['-ffp-contract=off'], 'local.hip': ['-ffp-contract=off'], 'eskmeans.hip': ['-ffp-contract=off'], 'nce.hip': ['-ffp-contract=off']}
+             'search.hip': ['-ffp-contract=off'], 'local.hip': ['-ffp-contract=off'], 'eskmeans.hip': ['-ffp-contract=off'], 'nce.hip': ['-ffp-contract=off'], 'softdtw.hip': ['-ffp-contract=off']}
 
 
 def hipcc():

@@ -1203,6 +1203,72 @@ class PairsDataLoader(OriginalDataLoader):
                 self.align_pairs(self.pairs[mode], frames=True)
 
 
+class WordPairDataLoader(OriginalDataLoader):
+    """Batches of WORD pairs for trainer.TrainerSequencePairs and loss.SoftDTWLoss (not in the reference): the same pairs
+    files, `batch_size` word pairs per batch, and NO alignment pass -- the alignment is soft-DTW's, inside the loss, and
+    moves with the weights.
+
+    A batch is (X, off1, n1, off2, n2, y): X [rows, D] float32 on the device, the frames of all side-1 tokens followed by
+    those of all side-2 tokens, gathered with one gather_rows call (one index upload per batch); off1, n1, off2, n2 host
+    integer arrays into X (word pair p is X[off1[p] : off1[p] + n1[p]] against X[off2[p] : off2[p] + n2[p]]; no two ranges
+    overlap); y [P] int64 on the device, +1 for a 'same' pair and -1 otherwise.  A pair with an empty token, or with a token
+    of more than softdtw.max_len() frames, is dropped (statistics_training: 'DroppedEmpty', 'DroppedLong'; the kept ones
+    count as 'SameType' / 'DiffType'); a batch whose pairs are all dropped is not yielded.  Tokens are not windowed.
+    The loader hands out no BatchPlan: `plan` is not an attribute of it, so the trainer takes the iterator."""
+
+    def __init__(self, pairs_path, features_path, **kwargs):
+        super(WordPairDataLoader, self).__init__(pairs_path, features_path, **kwargs)
+        assert self.tcl == 0, 'WordPairDataLoader: temporal-coherence pairs are frame pairs; tcl must be 0'
+
+    @property
+    def plan(self):
+        raise AttributeError('WordPairDataLoader hands out no BatchPlan')           # hasattr(loader, 'plan') is False
+
+    def prefetch_alignments(self):
+        """Nothing to do: there is no alignment pass."""
+
+    def word_pairs_device(self, pairs):
+        """One batch from [(f1, s1, e1, f2, s2, e2, type), ...], or None when every pair is dropped."""
+        from . import softdtw
+        cap = softdtw.max_len()
+        a0, n1, b0, n2, ys = [], [], [], [], []
+        for f1, s1, e1, f2, s2, e2, kind in pairs:
+            (a, na), (b, nb) = self._token(f1, s1, e1, False), self._token(f2, s2, e2, False)
+            if s1 > e1 or s2 > e2 or na == 0 or nb == 0:
+                self.statistics_training['DroppedEmpty'] += 1
+                continue
+            if na > cap or nb > cap:
+                self.statistics_training['DroppedLong'] += 1
+                continue
+            same = kind == 'same'
+            self.statistics_training['SameType' if same else 'DiffType'] += 1
+            a0.append(a); n1.append(na); b0.append(b); n2.append(nb)
+            ys.append(1 if same else -1)
+        if not ys:
+            return None
+        n1, n2 = np.asarray(n1, dtype=np.int32), np.asarray(n2, dtype=np.int32)
+        off1 = (np.cumsum(n1, dtype=np.int64) - n1).astype(np.int64)
+        off2 = (int(n1.sum()) + np.cumsum(n2, dtype=np.int64) - n2).astype(np.int64)
+        rows = np.concatenate([np.repeat(np.asarray(a0, dtype=np.int64) - off1, n1),
+                               np.repeat(np.asarray(b0, dtype=np.int64) - off2, n2)]) + np.arange(int(n1.sum()) + int(n2.sum()))
+        table = self.features.table
+        both = torch.from_numpy(np.concatenate([rows, np.asarray(ys, dtype=np.int64)])).to(table.device)      # one upload
+        X = gather_rows(table, both[:len(rows)])
+        return X, off1, n1, off2, n2, both[len(rows):]
+
+    def batch_iterator(self, train_mode=True):
+        """Iterator over (X, off1, n1, off2, n2, y) batches of `batch_size` word pairs."""
+        self.load_data()
+        pairs = self.pairs['train' if train_mode else 'dev']
+        if self.shuffle_between_epochs:
+            self._shuffle_pairs(pairs)
+        batches = [pairs[idx:idx + self.batch_size] for idx in range(0, len(pairs), self.batch_size)]
+        for batch_id in self._select_batches(len(batches), train_mode):
+            batch = self.word_pairs_device(batches[batch_id])
+            if batch is not None:
+                yield batch
+
+
 class MultiTaskDataLoader(OriginalDataLoader):
     """Batches (X1, X2, y_spk, y_phn) for the multitask siamese network
     (abnet3/dataloader.py:742-792).  fid2spk_file: lines "<file id> <speaker id>".

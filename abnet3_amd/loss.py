@@ -13,6 +13,9 @@ InfoNCELoss (not in the reference) is the in-batch contrastive loss over the sam
 groups=None); its B x B similarities never reach memory (abnt_nce_loss, csrc/nce.hip).
 CorrespondenceLoss (not in the reference either) is the reconstruction loss of model.CorrespondenceAutoencoder:
 forward(recon1, recon2, input1, input2, y), loss and gradient from one entry (abnr_recon_loss, csrc/recon.hip).
+SoftDTWLoss (not in the reference either) is a loss over word PAIRS, not frame pairs: forward(e, off1, n1, off2, n2, y) over
+the embedded rows of both words of every pair; the alignment is soft-DTW's and moves with the weights (abnq_softdtw_forward /
+abnq_softdtw_backward, csrc/softdtw.hip, through abnet3_amd/softdtw.py).
 """
 import torch
 import torch.nn as nn
@@ -387,6 +390,103 @@ class CorrespondenceLoss(LossBuilder):
     def value_and_grad(self, recon1, recon2, input1, input2, y=None):
         """(loss, [2, B, D] gradient w.r.t. (recon1, recon2)) without autograd."""
         return _recon_raw(recon1, recon2, input1, input2, y, self.mode, self.symmetric, self.avg, True)
+
+
+class SoftDTWLoss(LossBuilder):
+    """A contrastive loss over WORD pairs under a differentiable alignment (soft-DTW, Cuturi & Blondel 2017; not part of the
+    reference): forward(e, off1, n1, off2, n2, y).  e [R, D] holds the embedded frames of a batch; word pair p is the rows
+    e[off1[p] : off1[p] + n1[p]] against e[off2[p] : off2[p] + n2[p]] (off*, n*: host sequences; within a side the pairs'
+    row ranges must not overlap); y [P] on the device, "same" is y == 1.
+
+    With value(x, y) the soft-DTW value over the cells 1 - cos(x_i, y_j) (softdtw.soft_dtw: include/abnet3_hip_next.h states
+    the recurrence, tests/sdtw_np.py restates it):
+        v_p  = value(x, y),  or with divergence:  value(x, y) - (value(x, x) + value(y, y)) / 2   (>= 0, 0 for x == y)
+        s_p  = v_p / (n1[p] + n2[p]) when normalize, else v_p
+        term = s_p where y[p] == 1,  max(0, margin - s_p) elsewhere
+        loss = sum of the terms, divided by P when avg.  P == 0 gives 0.
+    Unlike the frame-pair losses the alignment is not frozen: it is a function of the embeddings and moves with the weights.
+    The sweeps run in the kernels; the arithmetic on the [P] vectors is plain torch, which also supplies the weights the
+    backward kernel takes.  The divergence costs three soft_dtw calls.
+
+    gamma = 0.1 and margin = 0.5 are UNTUNED: nothing has been measured on speech.  gamma -> 0 approaches the hard DTW cost
+    (value <= hard cost <= value + gamma log(3) (n + m - 2)).  Trains through autograd (the trainer's direct and planned
+    steps do not know this loss and step aside); single process."""
+
+    def __init__(self, gamma=0.1, margin=0.5, normalize=True, divergence=False, avg=True, *args, **kwargs):
+        super(SoftDTWLoss, self).__init__(*args, **kwargs)
+        if not (float(gamma) > 0.0) or float(gamma) == float('inf'):
+            raise ValueError('abnet3_amd: SoftDTWLoss gamma = %r must be finite and > 0' % (gamma,))
+        self.gamma = gamma
+        self.margin = margin
+        self.normalize = normalize
+        self.divergence = divergence
+        self.avg = avg
+
+    def check_batch(self, rows, off1, n1, off2, n2, y):
+        """The columns as host arrays, after every check of a batch that needs no embedding: the columns' shapes, the row
+        ranges (inside a table of `rows` rows, at least one row and at most softdtw.max_len() a side, no overlap within a
+        side) and the labels.  A trainer calls it BEFORE the tower runs, so that a bad batch is refused before any launch."""
+        from . import softdtw
+        cols = softdtw.require_disjoint('SoftDTWLoss', off1, n1, off2, n2)
+        softdtw.require_ranges('SoftDTWLoss', rows, *cols)
+        _lib.require_tensor('SoftDTWLoss', 'y', y, tuple(_lib.Y_DTYPE), 1)
+        if y.shape[0] != len(cols[1]):
+            raise ValueError('abnet3_amd: SoftDTWLoss: %d labels for %d word pairs' % (y.shape[0], len(cols[1])))
+        return cols
+
+    def _check(self, e, off1, n1, off2, n2, y):
+        _lib.require_tensor('SoftDTWLoss', 'e', e, torch.float32, 2)
+        return self.check_batch(e.shape[0], off1, n1, off2, n2, y)
+
+    def _terms(self, v, lens, y):
+        """The pairs' terms [P] from their values."""
+        s = v / lens if self.normalize else v
+        same = y == 1
+        return torch.where(same, s, torch.clamp(self.margin - s, min=0.0))
+
+    def forward(self, e, off1, n1, off2, n2, y, checked=False):
+        """checked=True: off1, n1, off2, n2 are what check_batch(e.shape[0], ..., y) returned for this very batch (a trainer
+        that checked before its tower ran): the host checks are not repeated."""
+        from .softdtw import soft_dtw
+        if checked:
+            _lib.require_tensor('SoftDTWLoss', 'e', e, torch.float32, 2)
+        else:
+            off1, n1, off2, n2 = self._check(e, off1, n1, off2, n2, y)
+        v = soft_dtw(e, off1, n1, off2, n2, self.gamma, checked=True)
+        if self.divergence:
+            v = v - 0.5 * (soft_dtw(e, off1, n1, off1, n1, self.gamma, checked=True) +
+                           soft_dtw(e, off2, n2, off2, n2, self.gamma, checked=True))
+        P = len(n1)
+        lens = torch.from_numpy((n1 + n2).astype('float32')).to(e.device) if self.normalize else None
+        loss = self._terms(v, lens, y).sum()
+        return loss / P if (self.avg and P > 0) else loss
+
+    def value_and_grad(self, e, off1, n1, off2, n2, y):
+        """(loss, [R, D] gradient w.r.t. e) without autograd."""
+        from . import softdtw
+        off1, n1, off2, n2 = self._check(e, off1, n1, off2, n2, y)
+        P = len(n1)
+        with torch.no_grad():
+            calls = [(off1, n1, off2, n2, 1.0)]
+            if self.divergence:
+                calls += [(off1, n1, off1, n1, -0.5), (off2, n2, off2, n2, -0.5)]
+            done = [softdtw.soft_dtw_batch(e, a, b, c, d, self.gamma, keep=True) + (f,) for a, b, c, d, f in calls]
+            v = done[0][0]
+            if self.divergence:
+                v = v - 0.5 * (done[1][0] + done[2][0])
+            lens = torch.from_numpy((n1 + n2).astype('float32')).to(e.device) if self.normalize else None
+            s = v / lens if self.normalize else v
+            same = y == 1
+            scale = 1.0 / P if (self.avg and P > 0) else 1.0
+            loss = self._terms(v, lens, y).sum() * scale
+            w = torch.where(same, torch.ones_like(s), -(self.margin - s > 0).to(s.dtype)) * scale
+            if self.normalize:
+                w = w / lens
+            de = None
+            for value, handle, f in done:
+                g1, g2 = softdtw.soft_dtw_backward(handle, (w * f).contiguous())
+                de = softdtw.fold_blocks(handle, g1, g2, de)
+        return loss, de
 
 
 class weighted_loss_multi(LossBuilder):

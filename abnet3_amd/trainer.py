@@ -1106,6 +1106,40 @@ class TrainerCorrespondence(TrainerSiamese):
         return self.train_losses[first:]
 
 
+class TrainerSequencePairs(TrainerSiamese):
+    """Trainer of a plain SiameseNetwork on WORD pairs with a SoftDTWLoss (neither the loss nor the loader is in the
+    reference): batches are dataloader.WordPairDataLoader's (X, off1, n1, off2, n2, y).  give_batch_to_network embeds X -- the
+    frames of all side-1 tokens followed by those of all side-2 tokens -- with ONE tower call, network.forward_once(X), because
+    the two sides have different row counts, and hands the embeddings and the pairs' row ranges to the loss.  With BatchNorm
+    the statistics of a step therefore span the batch's rows of BOTH sides (the Siamese trainers normalise each tower call on
+    its own).  Every step goes through give_batch_to_network and autograd with the flat optimizer, like TrainerCorrespondence:
+    no autograd-free step, no planned pass (_direct_ok() is false for an overridden give_batch_to_network) and no graph capture
+    (the soft-DTW entries wait for the stream).  Single process: NotImplementedError under data parallelism.  The network stays
+    a plain SiameseNetwork, so EmbedderSiamese, ABX, same-different and QbE work on the result unchanged."""
+
+    def __init__(self, *args, **kwargs):
+        super(TrainerSequencePairs, self).__init__(*args, **kwargs)
+        if self.dp or self.world_size > 1:
+            raise NotImplementedError('abnet3_amd: TrainerSequencePairs is single process: word pairs are not sharded and their '
+                                      'gradients are not exchanged')
+        from .model import SiameseNetwork
+        assert type(self.network) == SiameseNetwork
+
+    def give_batch_to_network(self, batch):
+        X, off1, n1, off2, n2, y = batch
+        X = X.cuda(non_blocking=True)
+        y = y.cuda(non_blocking=True)
+        cols = self.loss.check_batch(X.shape[0], off1, n1, off2, n2, y)      # (a bad batch is refused before the tower runs)
+        return self.loss(self.network.forward_once(X), *cols, y, checked=True)
+
+    def train_step_auto(self, batch):
+        return self.train_step(batch, True)                  # (never a captured step)
+
+    def make_graphed_step(self, example_batch, warmup=3):
+        raise NotImplementedError('abnet3_amd: a soft-DTW step reads its problem table back and waits for the stream: it cannot '
+                                  'be captured into a graph')
+
+
 class MultimodalTrainer(TrainerSiamese):
     """Multimodal Trainer class for ABnet3 (abnet3/trainer.py:281-365): batches are ([X1_m for m], [X2_m for m],
     y) and every step goes through give_batch_to_network and autograd (no autograd-free step, planned pass or

@@ -10,7 +10,9 @@
  * main argument-contract ledger enumerates those by name and demands a row in tests/test_gpu_arg_contract.py for each of
  * their entries; folding this section into that ledger is for a change that may edit those files) or abnr_ (the
  * reconstruction loss of the correspondence autoencoder, ledger abnet3_amd._lib.CAE_SYMBOLS with tests/test_cae_host.py and
- * tests/test_gpu_cae_contract.py -- a ledger of its own for the same reason) and are
+ * tests/test_gpu_cae_contract.py -- a ledger of its own for the same reason) or abnq_ (batched soft-DTW over cosine cells and
+ * its gradient, ledger abnet3_amd._lib.SDTW_SYMBOLS with tests/test_sdtw_host.py and tests/test_gpu_sdtw_contract.py -- a
+ * ledger of its own for the same reason) and are
  * exported beside those of abnet3_hip.h, whose conventions they follow (extern "C", plain pointers and sizes, the ABN_E_*
  * return codes, abn_last_error, every refusal before any launch).
  * They do not change ABN_ABI_VERSION.  A later change folds them into abnet3_hip.h under their abn_ names, bumps the
@@ -329,6 +331,61 @@ int64_t abnr_recon_ws_bytes(int64_t B, int64_t D);    /* host */
 int abnr_recon_loss(const float* r1, const float* r2, const float* x1, const float* x2, const void* y, int y_dtype, int64_t B,
                     int64_t D, int mode, int symmetric, int avg, float* loss, float* terms, float* dr1, float* dr2, void* ws,
                     void* stream);
+
+/* ---- Batched soft-DTW over cosine cells and its gradient (csrc/softdtw.hip) ------------------------------------------------
+ * Prefix abnq_; ledger abnet3_amd._lib.SDTW_SYMBOLS with tests/test_sdtw_host.py and tests/test_gpu_sdtw_contract.py (the top
+ * comment says why it is no NEXT<n>_SYMBOLS).  abnet3_amd/softdtw.py and abnet3_amd/loss.py (SoftDTWLoss) are the callers,
+ * tests/sdtw_np.py restates the definition in float64.
+ *
+ * e [R][D] fp32: one table of rows.  Problem p of P is two runs of its rows, x_i = e[off1[p] + i], i < n1[p], and
+ * y_j = e[off2[p] + j], j < n2[p] (the runs of one problem or of different problems may overlap or coincide).  off1, off2
+ * [P] int64 and n1, n2 [P] int32 are DEVICE arrays.  With x^_i = x_i / max(|x_i|, 1e-6), y^_j likewise (the norm in float64),
+ * c[i][j] = <x^_i, y^_j>, d[i][j] = 1 - c[i][j], gamma > 0 and
+ *     softmin(a, b, c) = -gamma log(exp(-a / gamma) + exp(-b / gamma) + exp(-c / gamma))   (about the minimum: +inf adds 0)
+ *     r[0][0] = 0, every other r[0][.] and r[.][0] = +inf,  r[i][j] = d[i-1][j-1] + softmin(r[i-1][j-1], r[i-1][j], r[i][j-1])
+ * abnq_softdtw_forward writes value[p] = r[n1[p]][n2[p]] (fp32, every element).  With keep != 0 it leaves in the workspace
+ * what abnq_softdtw_backward needs; with keep == 0 it does not, and the workspace may be smaller.
+ *
+ * abnq_softdtw_backward takes the same problem arguments, the workspace of a forward with keep != 0 on them, and w [P] fp32,
+ * w[p] = d loss / d value[p].  With E[n][m] = 1 and, i and j descending,
+ *     E[i][j] = E[i+1][j] exp((r[i+1][j] - r[i][j] - d[i+1][j]) / gamma) + E[i][j+1] exp((r[i][j+1] - r[i][j] - d[i][j+1]) / gamma)
+ *             + E[i+1][j+1] exp((r[i+1][j+1] - r[i][j] - d[i+1][j+1]) / gamma)          (terms outside the matrix are 0)
+ * it writes the gradients of sum_p w[p] value[p] with respect to the rows as BLOCKS IN PROBLEM ORDER: g1 [sum n1][D], problem
+ * p's rows at sum of n1[0 .. p-1], and g2 [sum n2][D] likewise:
+ *     g1[i] = -(w / |x_i|) (sum_j E[i][j] y^_j - (sum_j E[i][j] c[i][j]) x^_i)      where |x_i| >= 1e-6,
+ *     g1[i] = -(w 1e6) sum_j E[i][j] y^_j                                             below the clamp,      g2[j] symmetric.
+ * Every element of g1 and g2 is written, no two problems touch one address, nothing needs clearing; w[p] == 0 gives a block
+ * of exact zeros.  Folding the blocks into a gradient of e is the caller's (abnet3_amd/softdtw.py: two ordered index_add_).
+ *
+ * c is fp32: the cosine formed in float64 from the fp32 rows and rounded once.  The recurrences for r and E, the norms, x^, y^ and
+ * every sum of the gradients are float64; r and E are stored as float64.  No floating-point atomics, every sum has one fixed
+ * order: the same bits from call to call, and a problem's bits depend neither on P, nor on its position, nor on its
+ * neighbours, nor on the grid (ABN_SDTW_GRID = 1 .. 2048 in the environment forces the workgroups, read at every call;
+ * default 2048).  One workgroup of four waves per problem; the forward is two launches, the backward one.
+ *
+ * Limits: n1[p], n2[p] in 1 .. abnq_softdtw_max_len() (256), D in 1 .. abnq_softdtw_max_d() (1024), P <= 2^24, R < 2^40.
+ * Workspace: abnq_softdtw_ws_bytes(n1_host, n2_host, P, D, keep) bytes EXACTLY, from HOST copies of the lengths, -1 with
+ * abn_last_error for a refused size.  With N = sum n1 + sum n2, cells = sum n1 n2, and every part rounded up to 16 bytes:
+ *     64 (header) + 24 (P + 1) (prefix sums) + 16 N (1 / max(|x|, 1e-6) and |x|) + 4 cells (c)
+ *     + with keep: 8 cells (r) + 8 cells (E)
+ * (nothing in it is D wide: the rows are read from e, which must therefore be unchanged between a forward and its backward)
+ * 16-byte aligned; it need not be cleared.  The header records P, R, D, the sums, gamma, keep and a 32-bit hash of e's address
+ * and of off1, n1, off2, n2 of the last forward; the backward compares them with its own arguments.
+ * Refusals, all before any launch (the entries copy the four device arrays -- the backward also the header -- to the host,
+ * in one copy when off1, off2, n1, n2 lie end to end in one allocation, and WAIT for the stream: they are not for graph capture): P < 0, D < 1, R out of range, gamma not finite or not > 0: ABN_E_ARG;
+ * D or P beyond the limits: ABN_E_UNSUPPORTED; (P > 0:) a null or misaligned pointer (e, n1, n2, value, w, g1, g2: 4 bytes, off1,
+ * off2: 8, ws: 16): ABN_E_ARG; a length < 1: ABN_E_ARG, > max_len: ABN_E_UNSUPPORTED; off < 0 or off + n > R: ABN_E_ARG;
+ * ws_bytes too small: ABN_E_WORKSPACE; a backward on a workspace without a forward, with a forward of keep == 0 or of another
+ * problem: ABN_E_ARG.  P == 0 is a successful no-op (no pointer is looked at). */
+int64_t abnq_softdtw_max_len(void);        /* host */
+int64_t abnq_softdtw_max_d(void);          /* host */
+int64_t abnq_softdtw_ws_bytes(const int32_t* n1_host, const int32_t* n2_host, int64_t P, int64_t D, int keep);   /* host */
+int abnq_softdtw_forward(const float* e, int64_t R, int64_t D, const int64_t* off1, const int32_t* n1, const int64_t* off2,
+                         const int32_t* n2, int64_t P, float gamma, float* value, void* ws, int64_t ws_bytes, int keep,
+                         void* stream);
+int abnq_softdtw_backward(const float* e, int64_t R, int64_t D, const int64_t* off1, const int32_t* n1, const int64_t* off2,
+                          const int32_t* n2, int64_t P, float gamma, const float* w, float* g1, float* g2, void* ws,
+                          int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
