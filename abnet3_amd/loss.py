@@ -36,7 +36,13 @@ def unit_grad(device):
         key = torch.device('cuda', torch.cuda.current_device())
     t = _UNIT.get(key)
     if t is None:
-        t = _UNIT[key] = torch.ones((), dtype=torch.float32, device=key)
+        if key.type == 'cuda' and not torch.cuda.is_current_stream_capturing():
+            # built once, read by whichever stream calls next: a blocking upload, complete before this returns (a fill
+            # kernel would be ordered on the building stream alone)
+            t = torch.ones((), dtype=torch.float32).to(key)
+        else:
+            t = torch.ones((), dtype=torch.float32, device=key)
+        _UNIT[key] = t
     return t
 
 
